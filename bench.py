@@ -11,7 +11,11 @@ random inputs (r, y and the challenge d) are pre-sampled like the data itself: t
 host RNG and does no ring arithmetic in generate_challenge (src/prove/open.rs:143-158), so no
 sampler is inside the timed region (config.inputs says so; the device samplers are timed by tools/bench_phases.py).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+A plain run sets up, warms up, times the K steps and prints the headline (value, ms_per_step).  --full adds what the
+headline does not need: HIP-event profiling of every 8th timed step (roofline, per-kernel figures), the secondary
+timed regions (randomness drawn in the step; trusted-producer mode), the stand-alone NTT and the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed (rank 0's proofs) as DIR/<name>.npy.
 N > 1 is launched by the driver through torch.distributed.run (one rank per GPU, RCCL only for the
 barrier / key broadcast / result reduction: proofs are independent, the batch is simply split, weak scaling).
 
@@ -33,6 +37,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0        # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
+DUMP_BYTES = 32 << 20        # --dump-outputs: at most this many bytes of .npy data
+DUMP_SEED = 4242             # --dump-outputs: seed of the proof sample
 BUTTERFLY_PEAK = 4.7e12      # measured chip-wide rate of the 32-bit Montgomery butterfly at 4 waves per SIMD
                              # (tools/microbench/valu_rates.cpp, profiles/r01_valu_rates.txt): the VALU ceiling
 
@@ -57,11 +63,17 @@ def parse():
     ap.add_argument("--broadcast-key", type=int, default=1,
                     help="N > 1: rank 0 generates the key and broadcasts the [a1;a2] slab (RCCL) instead of every rank "
                          "regenerating it from the seed")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel / roofline figures from HIP events, "
+                         "the two secondary timed regions, the stand-alone NTT and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float64 coefficients, float32 "
+                         "verdict flags; a fixed, seeded sample of the proofs when all of them exceed 32 MiB)")
     ap.add_argument("--extra-steps", type=int, default=-1,
-                    help="steps of each of the two secondary timed regions (randomness drawn inside the step; trusted-producer "
-                         "mode): -1 = min(steps, 100), 0 = skip them")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=25.0, help="target length of the CPU baseline sample")
+                    help="--full: steps of each of the two secondary timed regions (randomness drawn inside the step; "
+                         "trusted-producer mode): -1 = min(steps, 100), 0 = skip them")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--cpu-seconds", type=float, default=25.0, help="--full: target length of the CPU baseline sample")
     return ap.parse_args()
 
 
@@ -207,6 +219,50 @@ def cpu_baseline(workload, N, n, k, l, V, seconds):
     }
 
 
+class DumpPlan:
+    """--dump-outputs: which proofs of the last timed step are written, fixed by the output shapes and DUMP_SEED alone, so
+    that runs with the same arguments write the same elements.  Every proof's verdict flags are written (float32); the
+    coefficient outputs (float64, exact for centred residues mod q) of a seeded sample of proofs that fits DUMP_BYTES,
+    and of a seeded sample of coefficient positions too if one proof alone does not fit."""
+
+    def __init__(self, outputs, B, Bc, dev):
+        import numpy as np
+        import torch
+
+        self.rows = {nm: t[0].numel() for nm, t in outputs.items() if t.dim() > 1}   # coefficients per proof
+        nflags = len(outputs) - len(self.rows)
+        per_proof = 8 * sum(self.rows.values())
+        budget = DUMP_BYTES - 4 * B * nflags
+        rng = np.random.default_rng(DUMP_SEED)
+        sel = np.sort(rng.choice(B, max(1, min(B, budget // per_proof)), replace=False))
+        self.cols = {nm: np.sort(rng.choice(m, max(1, m * budget // per_proof), replace=False)) if per_proof > budget
+                     else None for nm, m in self.rows.items()}
+        self.sel = [torch.from_numpy(sel[(sel >= c0) & (sel < c0 + Bc)] - c0).to(dev) for c0 in range(0, B, Bc)]
+        self.summary = {"proofs": len(sel), "of": B, "seed": DUMP_SEED,
+                        "coefficients": "all" if per_proof <= budget else "seeded sample per proof"}
+
+    def select(self, ci, outputs):
+        """Chunk ci's share: the sampled proofs' rows of every coefficient output, the flags of every proof."""
+        return {nm: t.index_select(0, self.sel[ci]) if nm in self.rows else t for nm, t in outputs.items()}
+
+    def write(self, path, parts):
+        import numpy as np
+        import torch
+
+        os.makedirs(path, exist_ok=True)
+        for nm in parts[0]:
+            a = torch.cat([p[nm] for p in parts]).cpu().numpy()
+            if nm not in self.rows:
+                a = a.astype(np.float32)
+            elif self.cols[nm] is None:
+                a = a.astype(np.float64)
+            else:
+                a = a.reshape(len(a), -1)[:, self.cols[nm]].astype(np.float64)
+            np.save(os.path.join(path, nm + ".npy"), a)
+        self.summary["dir"] = path
+        self.summary["files"] = sorted(parts[0])
+
+
 def self_launch(ngpus):
     """`python bench.py --gpus N` (N > 1) started WITHOUT torch.distributed.run: this process becomes a plain parent that
     starts the N ranks as a fresh child (`python -m torch.distributed.run ... bench.py <same args>`), relays the
@@ -324,6 +380,7 @@ def main():
             yield "response"
             acc = ctx.open_verify(z, t, c, I["d"])
             yield "verify"
+            out = dict(c=c, t=t, ok=ok, z=z, acc=acc)
         elif args.workload == "linear":
             c, cp, t, tp, u, ok = ctx.linear_commit(I["g"], I["x"], I["r"], I["rp"], I["y"], I["yp"])
             yield "commit"
@@ -331,6 +388,7 @@ def main():
             yield "response"
             acc = ctx.linear_verify(z, zp, c, cp, I["g"], t, tp, u, I["d"])
             yield "verify"
+            out = dict(c=c, cp=cp, t=t, tp=tp, u=u, ok=ok, z=z, zp=zp, acc=acc)
             ok = (ok == 3).to(torch.uint8)
         else:
             cs, cp, ts, tp, u, ok = ctx.sum_commit(I["gs"], I["xs"], I["rs"], I["rp"], I["ys"], I["yp"])
@@ -339,7 +397,9 @@ def main():
             yield "response"
             acc = ctx.sum_verify(zs, zp, cs, cp, I["gs"], ts, tp, u, I["d"])
             yield "verify"
+            out = dict(cs=cs, cp=cp, ts=ts, tp=tp, u=u, ok=ok, zs=zs, zp=zp, acc=acc)
         phases.result = (ok, acc)
+        phases.outputs = out   # what a caller of the three entry points receives
 
     resident = None if chunk else draw(0)
     torch.cuda.synchronize()
@@ -363,10 +423,12 @@ def main():
                 J[key] = ctx.sample_challenge(seed, sid + i, I[key].shape[:-1])
         return J
 
-    def step(marks=None, count=False, sample=False):
+    def step(marks=None, count=False, sample=False, keep=None):
         """One pass over the batch.  marks: list collecting launch-count marks per phase (profiled steps);
         count: also add up the verdict flags of every chunk (done for the last timed step only: two small torch
-        reductions per chunk that are not part of the path); sample: draw the step's randomness inside the step."""
+        reductions per chunk that are not part of the path); sample: draw the step's randomness inside the step;
+        keep: list collecting every chunk's outputs (last timed step, --dump-outputs): a chunked batch keeps only the
+        sampled proofs of each chunk, a resident one keeps the output tensors as they are."""
         tot_ok = tot_acc = None
         for ci in range(nchunks):
             I = resident if resident is not None else draw(ci)
@@ -380,6 +442,8 @@ def main():
             else:
                 for _name in phases(I):
                     pass
+            if keep is not None:
+                keep.append(dump.select(ci, phases.outputs) if nchunks > 1 else phases.outputs)
             if count:
                 ok, acc = phases.result
                 tot_ok = ok.sum() if tot_ok is None else tot_ok + ok.sum()
@@ -394,7 +458,8 @@ def main():
     # launch costs 4 % of throughput (a ~5 us bubble per event pair) without changing the kernel durations
     # (equal to rocprofv3's either way); every 8th step keeps that below 1 %.
     # RZK_BENCH_PROF=0 times the loop without any event and profiles in a separate pass.
-    prof_live = rank == 0 and os.environ.get("RZK_BENCH_PROF", "1") != "0"
+    # A plain run (no --full) brackets nothing and profiles nothing.
+    prof_live = args.full and rank == 0 and os.environ.get("RZK_BENCH_PROF", "1") != "0"
     prof_every = 8
     # the untimed steps also size the library's event pool (hipEventCreate is slow): as many profiled steps as the
     # timed region will hold
@@ -408,6 +473,7 @@ def main():
         ctx.prof_enable(False)
     w_ok, w_acc = step(count=True)
     assert int(w_ok.item()) >= 0 and int(w_acc.item()) >= 0
+    dump = DumpPlan(phases.outputs, B, Bc, dev) if args.dump_outputs and rank == 0 else None
     # (2) ramp
     ramp_info = None
     if args.ramp < 0:
@@ -443,15 +509,16 @@ def main():
     marks = []   # (launch count before the chunk, after commit, after response, after verify)
     if prof_live:
         ctx.prof_reset()
+    kept = [] if dump is not None else None
     t0 = time.perf_counter()
     for i in range(args.steps):
         final = i + 1 == args.steps
         if prof_live and i % prof_every == 0:
             ctx.prof_enable(True)
-            res = step(marks, count=final)
+            res = step(marks, count=final, keep=kept if final else None)
             ctx.prof_enable(False)
         else:
-            res = step(count=final)
+            res = step(count=final, keep=kept if final else None)
         if final:
             ok_s, acc_s = res
     barrier()
@@ -461,16 +528,18 @@ def main():
     # (RZK_BENCH_DIAG=1: timing-only runs of the diagnostic library builds of DESIGN.md §6, whose results are wrong on purpose)
     diag = os.environ.get("RZK_BENCH_DIAG", "0") == "1"
     assert diag or (accepted == B and ok_cnt == B), f"rank {rank}: {accepted}/{B} accepted, {ok_cnt}/{B} commit-ok"
+    if dump is not None:
+        dump.write(args.dump_outputs, kept if nchunks > 1 else [dump.select(0, kept[0])])
 
     elapsed, tot_acc, per_rank = shard.reduce_result(dist, elapsed, accepted, red_dev, gather=True)
     proofs = B * world * args.steps
     value = proofs / elapsed
 
-    # ---- secondary timed regions (same bracket: barrier + synchronize on both sides, max over ranks) ----------------
+    # ---- secondary timed regions (--full; same bracket: barrier + synchronize on both sides, max over ranks) -------
     # (a) the step's randomness drawn INSIDE the step, as the reference's criterion benches do; (b) trusted-producer
     # mode (rzk_ctx_trust_device_outputs): the cycle's operands are the library's own device outputs, the per-
     # coefficient range test is skipped.  `value` stays the checked, pre-sampled number.
-    extra = args.extra_steps if args.extra_steps >= 0 else min(args.steps, 100)
+    extra = (args.extra_steps if args.extra_steps >= 0 else min(args.steps, 100)) if args.full else 0
     secondary = {}
     if extra > 0:
         def timed(nsteps, **kw):
@@ -506,7 +575,7 @@ def main():
     roofline = None
     ntt = None
     units = None
-    if rank == 0:
+    if rank == 0 and args.full:
         if not prof_live:   # same measurement in a separate pass
             ctx.prof_enable(True)
             ctx.prof_reset()
@@ -616,7 +685,9 @@ def main():
 
     cpu = None
     cpu_reason = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if not args.full:
+        cpu_reason = "plain run (--full times it)"
+    elif rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.workload, N, n, k, l, V, args.cpu_seconds)
     elif world > 1:
         cpu_reason = "timed on rank 0 at N=1 only (the host cores are shared by all ranks of a multi-GPU run)"
@@ -639,6 +710,8 @@ def main():
             "vs_baseline": None,
             "dtype": "u32",
             "data": "synthetic" if not diag else "synthetic; DIAGNOSTIC run (RZK_BENCH_DIAG=1): results not checked, not a measurement of the product",
+            "full": args.full,
+            "dump_outputs": dump.summary if dump is not None else None,
             "config": {
                 "workload": f"{args.workload.capitalize()}Proof cycle, N={N}, (n,k,l)=({n},{k},{l}), kappa=36, "
                             + (f"V={V} summands, " if args.workload == "sum" else "") + f"batch={B} proofs per GPU"

@@ -12,6 +12,6 @@ for cfg in "--workload linear --batch 8192 --steps 50 --warmup 10" "--workload s
   echo "== $cfg"
   for rep in 1 2; do
     (cd .ab_r02 && python bench.py $cfg --no-cpu-baseline 2>/dev/null | python -c "$sumline" r02)
-    python bench.py $cfg --no-cpu-baseline --extra-steps 0 2>/dev/null | python -c "$sumline" new
+    python bench.py $cfg --full --no-cpu-baseline --extra-steps 0 2>/dev/null | python -c "$sumline" new
   done
 done

@@ -7,12 +7,12 @@ tag=${1:-cfg}
 cd "$(dirname "$0")/.."
 out=gpurun_out/${tag}_bench_configs.jsonl
 : > $out
-python bench.py --N 512 --steps 200 --warmup 50 --cpu-seconds 8 >> $out 2>/dev/null
-python bench.py --steps 200 --warmup 50 --cpu-seconds 8 >> $out 2>/dev/null
-python bench.py --N 2048 --batch 4096 --steps 100 --warmup 20 --no-cpu-baseline >> $out 2>/dev/null
-python bench.py --workload linear --batch 8192 --steps 50 --warmup 10 --cpu-seconds 8 >> $out 2>/dev/null
-python bench.py --workload sum --shape 4,9,4 --summands 8 --batch 4096 --steps 5 --warmup 2 --cpu-seconds 8 >> $out 2>/dev/null
-python bench.py --workload sum --N 2048 --shape 8,17,8 --summands 32 --batch 4096 --chunk 256 --steps 1 --warmup 0 --ramp 0 --cpu-seconds 20 >> $out 2>/dev/null
+python bench.py --full --N 512 --steps 200 --warmup 50 --cpu-seconds 8 >> $out 2>/dev/null
+python bench.py --full --steps 200 --warmup 50 --cpu-seconds 8 >> $out 2>/dev/null
+python bench.py --full --N 2048 --batch 4096 --steps 100 --warmup 20 --no-cpu-baseline >> $out 2>/dev/null
+python bench.py --full --workload linear --batch 8192 --steps 50 --warmup 10 --cpu-seconds 8 >> $out 2>/dev/null
+python bench.py --full --workload sum --shape 4,9,4 --summands 8 --batch 4096 --steps 5 --warmup 2 --cpu-seconds 8 >> $out 2>/dev/null
+python bench.py --full --workload sum --N 2048 --shape 8,17,8 --summands 32 --batch 4096 --chunk 256 --steps 1 --warmup 0 --ramp 0 --cpu-seconds 20 >> $out 2>/dev/null
 python - <<PY
 import json
 for line in open("$out"):

@@ -6,7 +6,7 @@ chunks=${@:-512}
 cd "$(dirname "$0")/.."
 out=gpurun_out/${tag}_matrix.jsonl
 : > $out
-X="--no-cpu-baseline --extra-steps 0"
+X="--full --no-cpu-baseline --extra-steps 0"
 python bench.py --N 512 --steps 200 --warmup 50 $X >> $out 2>/dev/null
 python bench.py --steps 200 --warmup 50 $X >> $out 2>/dev/null
 python bench.py --N 2048 --steps 100 --warmup 20 $X >> $out 2>/dev/null

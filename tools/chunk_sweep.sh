@@ -8,7 +8,7 @@ out=gpurun_out/${tag}_chunks.jsonl
 : > $out
 for c in $chunks; do
   python bench.py --workload sum --N 2048 --shape 8,17,8 --summands 32 --batch 4096 --chunk $c --steps 1 --warmup 0 --ramp 0 \
-    --no-cpu-baseline --extra-steps 0 >> $out 2>/dev/null || echo "chunk $c failed"
+    --full --no-cpu-baseline --extra-steps 0 >> $out 2>/dev/null || echo "chunk $c failed"
 done
 python - <<PY
 import json

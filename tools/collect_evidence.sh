@@ -8,9 +8,9 @@ root=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 out=$root/gpurun_out
 pre=$out/${tag}_${name}
 cd /tmp && export TMPDIR=/tmp
-python3 $root/bench.py --no-cpu-baseline "$@" > ${pre}_bench.json 2> ${pre}_bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d ${pre}_trace -o t -- python3 $root/bench.py --no-cpu-baseline --extra-steps 0 "$@" > ${pre}_bench_under_rocprof.json 2> ${pre}_trace.log
-small="--steps 3 --warmup 1 --ramp 0 --no-cpu-baseline --extra-steps 0"
+python3 $root/bench.py --full --no-cpu-baseline "$@" > ${pre}_bench.json 2> ${pre}_bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d ${pre}_trace -o t -- python3 $root/bench.py --full --no-cpu-baseline --extra-steps 0 "$@" > ${pre}_bench_under_rocprof.json 2> ${pre}_trace.log
+small="--full --steps 3 --warmup 1 --ramp 0 --no-cpu-baseline --extra-steps 0"
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d ${pre}_pmc_fetch -o f -- python3 $root/bench.py "$@" $small > /dev/null 2> ${pre}_pmc_fetch.log
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d ${pre}_pmc_write -o w -- python3 $root/bench.py "$@" $small > /dev/null 2> ${pre}_pmc_write.log
 i=0
