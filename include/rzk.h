@@ -50,9 +50,9 @@ extern "C" {
 typedef struct rzk_ctx rzk_ctx;
 
 /* Version of this C ABI: bumped whenever an existing signature changes (rzk_wire_mat_decode gained `q` in 2,
- * version 3 added the entry points marked "v3").  A binding checks rzk_abi_version() == RZK_ABI_VERSION after loading
+ * version 3 added the entry points marked "v3", version 4 those marked "v4").  A binding checks rzk_abi_version() == RZK_ABI_VERSION after loading
  * the library, so that a stale or variant .so fails at load time instead of reading shifted arguments. */
-#define RZK_ABI_VERSION 3u
+#define RZK_ABI_VERSION 4u
 uint32_t rzk_abi_version(void);
 
 /* Which block of the commitment key a matrix-vector product uses (src/commit.rs:19-25). */
@@ -269,13 +269,15 @@ int rzk_sample_uniform_dev(rzk_ctx* ctx, uint64_t seed, uint32_t stream, uint64_
 int rzk_sample_gauss_dev(rzk_ctx* ctx, uint64_t seed, uint32_t stream, double sigma, int64_t* out, size_t count);
 int rzk_sample_challenge_dev(rzk_ctx* ctx, uint64_t seed, uint32_t stream, int64_t* out, size_t count);
 
-/* ---- wire format (host only) ---------------------------------------------------------------------------- */
+/* ---- wire format of one Mat (host only) ---------------------------------------------------------------------------- */
 /* bincode layout of the reference's Mat<I,N> (serde derive at src/mat.rs:11-14; bincode default options as in
  * the reference's own test src/mat.rs:424-438: little-endian, u64 length prefixes):
  *     u64 rows ; rows x { u64 cols ; cols x { u64 len ; len x coefficient } }
  * with every polynomial in the crate's trimmed form (no trailing zero coefficients) <-> dense slabs
- * [rows][cols][N] of int64.  The protocol messages (src/commit.rs:134, src/prove/open.rs:180-228, ...) are
- * plain concatenations of their Mat fields in declaration order.  coef_bytes: 8 (i64) or 4 (i32, the width
+ * [rows][cols][N] of int64.  The protocol messages (src/commit.rs:134, src/prove/open.rs:190-228, ...) are NOT
+ * concatenations of Mats: most of their fields are Vec<Polynomial>, Polynomial or Option<Polynomial>, whose bincode
+ * form differs (an n x 1 Mat carries 8 bytes per row more than a Vec<Polynomial> of n).  Whole messages go through
+ * the batched GPU codec below (rzk_wire_decode_batch / rzk_wire_encode_batch).  coef_bytes: 8 (i64) or 4 (i32, the width
  * of the reference's test vector); the width ZqI64 uses on the wire is set by the third-party ring crate and
  * is not pinned by any file of the reference.
  * encode: writes rzk_wire_mat_size() bytes (returned through *written; RZK_E_ARG if cap is too small or a
@@ -289,6 +291,64 @@ int rzk_wire_mat_encode(const int64_t* slab, uint32_t rows, uint32_t cols, uint3
                         uint8_t* out, size_t cap, size_t* written);
 int rzk_wire_mat_decode(const uint8_t* in, size_t len, uint32_t N, uint32_t coef_bytes, int64_t q, uint32_t* rows,
                         uint32_t* cols, int64_t* slab, size_t slab_polys, size_t* consumed);
+
+/* ---- protocol messages on the wire (v4; batched, on the GPU) ----------------------------------------------------------
+ * bincode with the reference's default options (src/mat.rs:424-438): little-endian, a u64 count before every Vec, struct
+ * fields in declaration order without tags, a 1-byte tag (0 None, 1 Some) before an Option value; a Polynomial is its
+ * trimmed coefficient Vec (u64 len ; len x coefficient), a Mat is u64 rows ; rows x { u64 cols ; cols x Polynomial }.
+ * Each kind lists its fields in declaration order; each field is one dense int64 slab in the layout of the entry point
+ * that consumes it (B messages; V = summands of the Sum kinds, ignored by the others):
+ *   RZK_MSG_COMMITMENT         Commitment { c: Mat (n+l)x1 }                         (commit.rs:134)   c [B][n+l][N]
+ *   RZK_MSG_OPENING            Opening { x: Vec<Poly>, r: Mat kx1, f: Option<Poly> } (commit.rs:222)   x [B][l][N], r [B][k][N], f [B][N]
+ *   RZK_MSG_CHALLENGE          {Open,Linear,Sum}ProofChallenge { d: Poly }                             d [B][N]
+ *   RZK_MSG_OPEN_COMMITMENT    OpenProofCommitment { c: Commitment, t: Vec<Poly> }   (open.rs:190)     c [B][n+l][N], t [B][n][N]
+ *   RZK_MSG_OPEN_RESPONSE      OpenProofResponse { z: Mat kx1 }                      (open.rs:222)     z [B][k][N]
+ *   RZK_MSG_LINEAR_COMMITMENT  LinearProofCommitment { c, cp: Commitment, g: Poly, t, tp: Vec<Poly>, u: Mat lx1 }
+ *                              (linear.rs:271)   c, cp [B][n+l][N], g [B][N], t, tp [B][n][N], u [B][l][N]
+ *   RZK_MSG_SUM_COMMITMENT     SumProofCommitment { cp: Commitment, cs: Vec<Commitment>, gs: Vec<Poly>, tp: Vec<Poly>,
+ *                              ts: Vec<Vec<Poly>>, u: Mat lx1 } (sum.rs:342)   cp [B][n+l][N], cs [B][V][n+l][N], gs [B][V][N],
+ *                              tp [B][n][N], ts [B][V][n][N], u [B][l][N]
+ *   RZK_MSG_SUM_RESPONSE       SumProofResponse { zp: Mat kx1, zs: Vec<Mat kx1> }    (sum.rs:385)      zp [B][k][N], zs [B][V][k][N]
+ * (LinearProofResponse has no serde derive, linear.rs:318: its two Mats go through rzk_wire_mat_*.)
+ * Option: decoding None writes the constant polynomial 1 into f (Commitment::verify with Some(1) makes the same
+ * comparison as with None, commit.rs:200-209); encoding with fields[f] == NULL writes None for every message, otherwise
+ * every message gets Some(f).  coef_bytes: 4 or 8, as for the Mat codec.
+ *
+ * rzk_wire_max_bytes: the largest encoding of one message of the kind (every polynomial at full length); 0 = bad
+ * argument.
+ * rzk_wire_decode_batch: message b is bytes[offsets[b] .. offsets[b+1]) (offsets: [B+1]); fields[i] is the slab of the
+ * kind's i-th field.  Returns RZK_OK on a well-formed call; malformed messages are reported per message: ok[b] = 1 only
+ * if every count, row and column count equals the context's n, k, l and V, every len <= N, every Option tag is 0 or 1,
+ * every coefficient is the centred residue mod q, and the message ends exactly at offsets[b+1].  That last rule is
+ * stricter than bincode::deserialize, which ignores trailing bytes: a batch slot holds one message.  A message with
+ * offsets[b] % coef_bytes != 0 (every kind except RZK_MSG_OPENING, whose messages end with the 1-byte tag and may start
+ * anywhere), offsets[b] > offsets[b+1] or offsets[b+1] > total_len gets ok[b] = 0 without any of its bytes being read.
+ * Slabs of a rejected message are unspecified.  RZK_E_ARG only for a bad kind or width, NULL pointers, V == 0 on a Sum
+ * kind or a `bytes` pointer not aligned to coef_bytes; RZK_E_UNSUPPORTED for total_len >= 2^48.
+ * rzk_wire_encode_batch: writes the B messages back to back from bytes[0] and their B+1 boundaries into offsets.
+ * Requires cap >= B * rzk_wire_max_bytes(...) (checked on the host, RZK_E_ARG otherwise).  A non-canonical input
+ * coefficient raises the input-fault condition (see Conventions: RZK_E_ARG at return, or at the next
+ * rzk_ctx_synchronize for the _dev variant).
+ * The _dev variants take device pointers for bytes, offsets, ok and the slabs; `fields` itself is a host array of
+ * device pointers. */
+#define RZK_MSG_COMMITMENT 0
+#define RZK_MSG_OPENING 1
+#define RZK_MSG_CHALLENGE 2
+#define RZK_MSG_OPEN_COMMITMENT 3
+#define RZK_MSG_OPEN_RESPONSE 4
+#define RZK_MSG_LINEAR_COMMITMENT 5
+#define RZK_MSG_SUM_COMMITMENT 6
+#define RZK_MSG_SUM_RESPONSE 7
+size_t rzk_wire_max_bytes(const rzk_ctx* ctx, int kind, uint32_t V, uint32_t coef_bytes);
+int rzk_wire_decode_batch(rzk_ctx* ctx, int kind, uint32_t V, uint32_t coef_bytes, const uint8_t* bytes,
+                          uint64_t total_len, const uint64_t* offsets, int64_t* const* fields, uint8_t* ok, size_t B);
+int rzk_wire_decode_batch_dev(rzk_ctx* ctx, int kind, uint32_t V, uint32_t coef_bytes, const uint8_t* bytes,
+                              uint64_t total_len, const uint64_t* offsets, int64_t* const* fields, uint8_t* ok,
+                              size_t B);
+int rzk_wire_encode_batch(rzk_ctx* ctx, int kind, uint32_t V, uint32_t coef_bytes, const int64_t* const* fields,
+                          uint8_t* bytes, uint64_t cap, uint64_t* offsets, size_t B);
+int rzk_wire_encode_batch_dev(rzk_ctx* ctx, int kind, uint32_t V, uint32_t coef_bytes, const int64_t* const* fields,
+                              uint8_t* bytes, uint64_t cap, uint64_t* offsets, size_t B);
 
 /* HIP-event timing of the last phase call's dominant kernel is exposed through these counters:
  * accumulated microseconds and launch count of the row kernel since the last reset. */

@@ -10,6 +10,9 @@ SO = os.environ.get("RZK_LIB", os.path.join(HERE, "librzk_hip.so"))  # RZK_LIB: 
 
 RZK_OK, RZK_E_ARG, RZK_E_HIP, RZK_E_STATE, RZK_E_UNSUPPORTED = 0, -1, -2, -3, -4
 KEY_A1, KEY_A2, KEY_A = 0, 1, 2
+# message kinds of the batched wire codec (include/rzk.h "protocol messages on the wire", v4)
+(MSG_COMMITMENT, MSG_OPENING, MSG_CHALLENGE, MSG_OPEN_COMMITMENT, MSG_OPEN_RESPONSE, MSG_LINEAR_COMMITMENT,
+ MSG_SUM_COMMITMENT, MSG_SUM_RESPONSE) = range(8)
 
 _lib = None
 
@@ -69,6 +72,12 @@ SIGNATURES = {
                                       C.POINTER(C.c_size_t)]),
     "rzk_wire_mat_decode": (C.c_int, [_U8, _SZ, C.c_uint32, C.c_uint32, C.c_int64, C.POINTER(C.c_uint32),
                                       C.POINTER(C.c_uint32), _I64, _SZ, C.POINTER(C.c_size_t)]),
+    # v4: batched codec of the protocol messages
+    "rzk_wire_max_bytes": (C.c_size_t, [_CTX, C.c_int, C.c_uint32, C.c_uint32]),
+    "rzk_wire_decode_batch": (C.c_int, [_CTX, C.c_int, C.c_uint32, C.c_uint32, _U8, C.c_uint64, C.c_void_p,
+                                        C.c_void_p, _U8, _SZ]),
+    "rzk_wire_encode_batch": (C.c_int, [_CTX, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, _U8, C.c_uint64,
+                                        C.c_void_p, _SZ]),
     "rzk_bench_ntt_forward_dev": (C.c_double, [_CTX, C.c_int, _U32P, _U32P, _SZ, C.c_int]),
     "rzk_debug_read_scratch": (C.c_int, [_CTX, C.c_void_p, _SZ, C.POINTER(C.c_size_t)]),
     "rzk_prof_reset": (C.c_int, [_CTX]),
@@ -78,7 +87,7 @@ SIGNATURES = {
     "rzk_prof_read_all": (C.c_int, [_CTX, C.POINTER(C.c_double), _SZ, C.POINTER(C.c_size_t)]),
     "rzk_prof_read_kernels": (C.c_int, [_CTX, C.c_char_p, _SZ, C.POINTER(C.c_size_t)]),
 }
-ABI_VERSION = 3   # include/rzk.h: RZK_ABI_VERSION
+ABI_VERSION = 4   # include/rzk.h: RZK_ABI_VERSION
 # every batched entry point also exists as a device-pointer variant with the same signature
 for _name in list(SIGNATURES):
     if _name.endswith("_batch"):

@@ -139,6 +139,7 @@ struct rzk_ctx {
   double* d_key_l2 = nullptr;
   std::map<std::pair<int, uint32_t>, DevProg> progs;
   Arena ws, stage, ws_slots;
+  Arena ws_wire;                       // message codec: position table (decode) / lengths, positions, sizes (encode)
   // canonical-input test (rzk_dev.h, Operands::bad): sticky word set by any kernel that loaded a coefficient
   // outside the centred range on behalf of an entry point without per-proof verdicts; read back at every
   // synchronising call (host-pointer variants, rzk_ctx_synchronize, rzk_ctx_check_inputs)
@@ -1342,6 +1343,7 @@ void rzk_ctx_destroy(rzk_ctx* c) {
   if (c->d_key_l2) (void)hipFree(c->d_key_l2);
   if (c->ws.p) (void)hipFree(c->ws.p);
   if (c->ws_slots.p) (void)hipFree(c->ws_slots.p);
+  if (c->ws_wire.p) (void)hipFree(c->ws_wire.p);
   if (c->ws_dkey.p) (void)hipFree(c->ws_dkey.p);
   if (c->ws_oimg.p) (void)hipFree(c->ws_oimg.p);
   if (c->stage.p) (void)hipFree(c->stage.p);
@@ -2327,6 +2329,144 @@ int rzk_prof_read(rzk_ctx* c, double* row_kernel_us, uint64_t* row_kernel_launch
   if (row_kernel_us) *row_kernel_us = c->prof_us;
   if (row_kernel_launches) *row_kernel_launches = c->prof_launches;
   return RZK_OK;
+}
+
+// =================================================================================================
+// v4: batched codec of the serialized protocol messages (rzk_wire_dev.hip, rzk_wire_walk.h)
+// =================================================================================================
+namespace {
+
+bool wire_schema_of(const rzk_ctx* c, int kind, uint32_t V, uint32_t coef_bytes, WireSchema* s) {
+  return c && wire_schema(kind, c->N, c->n, c->k, c->l, V, coef_bytes, s);
+}
+
+// slabs of the fields; only the Option of an Opening may be NULL, and only on encode
+bool wire_slabs(const WireSchema& s, int kind, const int64_t* const* fields, bool allow_none, WireSlabs* sl) {
+  if (!fields) return false;
+  for (int f = 0; f < kWireMaxFields; ++f) sl->ptr[f] = nullptr;
+  for (uint32_t f = 0; f < s.nfields; ++f) {
+    sl->ptr[f] = const_cast<int64_t*>(fields[f]);
+    if (!fields[f] && !(allow_none && kind == WIRE_OPENING && s.f[f].kind == WF_OPT)) return false;
+  }
+  return true;
+}
+
+size_t wire_field_bytes(const rzk_ctx* c, const WireSchema& s, uint32_t f, size_t B) {
+  return polys(c, B * (size_t)(s.first[f + 1] - s.first[f]));
+}
+
+}  // namespace
+
+size_t rzk_wire_max_bytes(const rzk_ctx* c, int kind, uint32_t V, uint32_t coef_bytes) {
+  WireSchema s;
+  if (!wire_schema_of(c, kind, V, coef_bytes, &s)) return 0;
+  return (size_t)wire_max_bytes(s);
+}
+
+int rzk_wire_decode_batch_dev(rzk_ctx* c, int kind, uint32_t V, uint32_t coef_bytes, const uint8_t* bytes,
+                              uint64_t total_len, const uint64_t* offsets, int64_t* const* fields, uint8_t* ok,
+                              size_t B) {
+  WireSchema s;
+  if (!wire_schema_of(c, kind, V, coef_bytes, &s)) return fail(c, RZK_E_ARG, "wire decode: bad kind, width or V");
+  if (B == 0) return RZK_OK;
+  WireSlabs sl;
+  if (!bytes || !offsets || !ok || !wire_slabs(s, kind, (const int64_t* const*)fields, false, &sl))
+    return fail(c, RZK_E_ARG, "wire decode: NULL pointer");
+  if ((uintptr_t)bytes % coef_bytes) return fail(c, RZK_E_ARG, "wire decode: bytes not aligned to coef_bytes");
+  if (total_len >> 48) return fail(c, RZK_E_UNSUPPORTED, "wire decode: total_len must stay below 2^48");
+  int rc = arena_reserve(c, c->ws_wire, (size_t)B * s.polys * sizeof(uint64_t));
+  if (rc != RZK_OK) return rc;
+  uint64_t* tab = (uint64_t*)c->ws_wire.p;
+  const LaunchCfg cfg = cfg_of(c);
+  // an Opening ends with a 1-byte tag, so Openings written back to back start at any byte
+  rc = check_launch(c, launch_wire_walk(cfg, bytes, total_len, offsets, s, kind != WIRE_OPENING, tab, ok, B),
+                    "wire walk kernel");
+  if (rc != RZK_OK) return rc;
+  return check_launch(c, launch_wire_copy(cfg, bytes, tab, s, sl, (c->q - 1) / 2, ok, B), "wire copy kernel");
+}
+
+int rzk_wire_encode_batch_dev(rzk_ctx* c, int kind, uint32_t V, uint32_t coef_bytes, const int64_t* const* fields,
+                              uint8_t* bytes, uint64_t cap, uint64_t* offsets, size_t B) {
+  WireSchema s;
+  if (!wire_schema_of(c, kind, V, coef_bytes, &s)) return fail(c, RZK_E_ARG, "wire encode: bad kind, width or V");
+  if (B == 0) return RZK_OK;
+  WireSlabs sl;
+  if (!bytes || !offsets || !wire_slabs(s, kind, fields, true, &sl)) return fail(c, RZK_E_ARG, "wire encode: NULL pointer");
+  if ((uintptr_t)bytes % coef_bytes) return fail(c, RZK_E_ARG, "wire encode: bytes not aligned to coef_bytes");
+  // every message fits its maximum, so the device never writes past cap
+  const uint64_t mx = wire_max_bytes(s);
+  if (cap / B < mx) return fail(c, RZK_E_ARG, "wire encode: cap < B * rzk_wire_max_bytes");
+  const size_t np = (size_t)B * s.polys;
+  const size_t lens_b = (np * sizeof(uint32_t) + 255) & ~size_t(255), rel_b = (np * sizeof(uint64_t) + 255) & ~size_t(255);
+  int rc = arena_reserve(c, c->ws_wire, lens_b + rel_b + B * sizeof(uint64_t));
+  if (rc != RZK_OK) return rc;
+  char* w = (char*)c->ws_wire.p;
+  return check_launch(c, launch_wire_encode(cfg_of(c), s, sl, (c->q - 1) / 2, (uint32_t*)w, (uint64_t*)(w + lens_b),
+                                            (uint64_t*)(w + lens_b + rel_b), bytes, offsets, c->d_bad, B),
+                      "wire encode kernels");
+}
+
+int rzk_wire_decode_batch(rzk_ctx* c, int kind, uint32_t V, uint32_t coef_bytes, const uint8_t* bytes,
+                          uint64_t total_len, const uint64_t* offsets, int64_t* const* fields, uint8_t* ok, size_t B) {
+  WireSchema s;
+  if (!wire_schema_of(c, kind, V, coef_bytes, &s)) return fail(c, RZK_E_ARG, "wire decode: bad kind, width or V");
+  if (B == 0) return RZK_OK;
+  WireSlabs sl;
+  if (!bytes || !offsets || !ok || !wire_slabs(s, kind, (const int64_t* const*)fields, false, &sl))
+    return fail(c, RZK_E_ARG, "wire decode: NULL pointer");
+  if ((uintptr_t)bytes % coef_bytes) return fail(c, RZK_E_ARG, "wire decode: bytes not aligned to coef_bytes");
+  std::vector<HostBuf> bufs = {IN(bytes, total_len), IN(offsets, (B + 1) * sizeof(uint64_t)), OUT(ok, B)};
+  for (uint32_t f = 0; f < s.nfields; ++f) bufs.push_back(OUT(fields[f], wire_field_bytes(c, s, f, B)));
+  int64_t* dev_fields[kWireMaxFields] = {};
+  HIPCHK(c, hipMemsetAsync(c->d_bad, 0, sizeof(uint32_t), c->stream));
+  int rc = stage_in(c, bufs);
+  if (rc != RZK_OK) return rc;
+  for (uint32_t f = 0; f < s.nfields; ++f) dev_fields[f] = (int64_t*)bufs[3 + f].dev;
+  // the staged copy of `bytes` starts on a 256-byte boundary, so alignment and offsets carry over
+  rc = rzk_wire_decode_batch_dev(c, kind, V, coef_bytes, DEV(0, const uint8_t*), total_len, DEV(1, const uint64_t*),
+                                 dev_fields, DEV(2, uint8_t*), B);
+  if (rc != RZK_OK) {
+    const std::string keep = c->err;
+    (void)take_input_error(c);
+    c->err = keep;
+    return rc;
+  }
+  return stage_out(c, bufs);
+}
+
+int rzk_wire_encode_batch(rzk_ctx* c, int kind, uint32_t V, uint32_t coef_bytes, const int64_t* const* fields,
+                          uint8_t* bytes, uint64_t cap, uint64_t* offsets, size_t B) {
+  WireSchema s;
+  if (!wire_schema_of(c, kind, V, coef_bytes, &s)) return fail(c, RZK_E_ARG, "wire encode: bad kind, width or V");
+  if (B == 0) return RZK_OK;
+  WireSlabs sl;
+  if (!bytes || !offsets || !wire_slabs(s, kind, fields, true, &sl)) return fail(c, RZK_E_ARG, "wire encode: NULL pointer");
+  const uint64_t mx = wire_max_bytes(s);
+  if (cap / B < mx) return fail(c, RZK_E_ARG, "wire encode: cap < B * rzk_wire_max_bytes");
+  const uint64_t dcap = (uint64_t)B * mx;   // device buffer: what the messages can need, not the caller's whole cap
+  std::vector<HostBuf> bufs;
+  for (uint32_t f = 0; f < s.nfields; ++f) bufs.push_back(IN(fields[f], fields[f] ? wire_field_bytes(c, s, f, B) : 0));
+  bufs.push_back(HostBuf{nullptr, nullptr, (size_t)dcap, nullptr});
+  bufs.push_back(OUT(offsets, (B + 1) * sizeof(uint64_t)));
+  HIPCHK(c, hipMemsetAsync(c->d_bad, 0, sizeof(uint32_t), c->stream));
+  int rc = stage_in(c, bufs);
+  if (rc != RZK_OK) return rc;
+  const int64_t* dev_fields[kWireMaxFields] = {};
+  for (uint32_t f = 0; f < s.nfields; ++f) dev_fields[f] = fields[f] ? (const int64_t*)bufs[f].dev : nullptr;
+  uint8_t* dbytes = (uint8_t*)bufs[s.nfields].dev;
+  rc = rzk_wire_encode_batch_dev(c, kind, V, coef_bytes, dev_fields, dbytes, dcap, (uint64_t*)bufs[s.nfields + 1].dev, B);
+  if (rc == RZK_OK) {
+    HIPCHK(c, hipMemcpyAsync(offsets, bufs[s.nfields + 1].dev, (B + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost,
+                             c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (offsets[B] > dcap) return fail(c, RZK_E_HIP, "wire encode: message sizes exceed their maximum");
+    if (offsets[B]) HIPCHK(c, hipMemcpyAsync(bytes, dbytes, offsets[B], hipMemcpyDeviceToHost, c->stream));
+    return take_input_error(c);
+  }
+  const std::string keep = c->err;
+  (void)take_input_error(c);
+  c->err = keep;
+  return rc;
 }
 
 }  // extern "C"

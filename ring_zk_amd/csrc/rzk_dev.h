@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "rzk_core.h"
+#include "rzk_wire_walk.h"
 
 namespace rzk {
 
@@ -271,6 +272,20 @@ int launch_norm(int logn, const LaunchCfg& cfg, const int64_t* v, uint32_t rows,
                 uint32_t* bad_word);
 int launch_eq(int logn, const LaunchCfg& cfg, const int64_t* a, const int64_t* b, uint32_t rows,
               uint8_t* eq, uint64_t B, uint32_t qhalf, uint32_t* bad_word);
+// ---- batched codec of the serialized protocol messages (rzk_wire_dev.hip; schema in rzk_wire_walk.h) ----------------
+struct WireSlabs {
+  int64_t* ptr[kWireMaxFields];   // dense slab of every field ([B][rows of the field][N]); encode: NULL Option = None
+};
+// decode: walk (ok[b], tab[b * polys + j] = (byte position << 16) | len) then copy (widen, range-check, zero-fill)
+int launch_wire_walk(const LaunchCfg& cfg, const uint8_t* bytes, uint64_t total, const uint64_t* offsets,
+                     const WireSchema& s, int need_align, uint64_t* tab, uint8_t* ok, uint64_t B);
+int launch_wire_copy(const LaunchCfg& cfg, const uint8_t* bytes, const uint64_t* tab, const WireSchema& s,
+                     const WireSlabs& sl, int64_t half, uint8_t* ok, uint64_t B);
+// encode: trimmed lengths + canonical test, per-message scan, batch scan of message sizes, write.
+// lens: [B * polys] u32, rel: [B * polys] u64, msize: [B] u64 (scratch); offsets: [B + 1]
+int launch_wire_encode(const LaunchCfg& cfg, const WireSchema& s, const WireSlabs& sl, int64_t half, uint32_t* lens,
+                       uint64_t* rel, uint64_t* msize, uint8_t* bytes, uint64_t* offsets, uint32_t* bad_word,
+                       uint64_t B);
 // small ring degrees (N = 4 .. 256): schoolbook products mod q, same row programs
 int launch_row_program_small(uint32_t N, const LaunchCfg& cfg, const Program* d_prog, uint32_t nrows,
                              const Operands& ops, const uint32_t* d_key_mont, const DevTables* d_T, uint32_t r2q,
