@@ -370,12 +370,13 @@ int rzk_prof_read_kernels(rzk_ctx* ctx, char* buf, size_t cap, size_t* needed);
  * Testing / tuning switches, NOT part of the API contract: every setting computes the same results; they select which
  * kernel evaluates a row program so that the test-suite can reach every kernel at small shapes and so that A/B
  * measurements need no rebuild.  Defaults are what the measurements in DESIGN.md §6 chose.
- *   RZK_SHIFT=0            challenge products through transforms instead of signed rotations (default 1; N <= 1024)
+ *   RZK_SHIFT=0            challenge products through transforms instead of signed rotations (default 1; at N = 2048 only
+ *                          with RZK_PAIR_POLY=1, the default)
  *   RZK_PAIRS=0            unit_kernel: no pairing of rows that share their last operand (default 1)
  *   RZK_UPT=<u>            unit_kernel: units of a proof per wavefront task (default: all once batch >= 16 x CUs, else 1)
  *   RZK_VEC_ROWS=0         programs with vector x vector products through unit_kernel instead of row_kernel (default 1)
  *   RZK_ROW_GROUPS=0       no row groups (row_group_kernel) for key blocks with n > 1 (default 1)
- *   RZK_GROUP_MAX=<g>      rows per group, 1 .. 4 (default 4 at N <= 1024, 1 at N = 2048)
+ *   RZK_GROUP_MAX=<g>      rows per group, 1 .. 4 at N <= 1024, 1 .. 2 at N = 2048 (default 4 at N <= 1024, 1 at N = 2048)
  *   RZK_BLOCK_MIN_LOGN=<L> row blocks (row_block_kernel) from ring degree 2^L on (default 11; 12 = never, 10 = also N = 1024)
  *   RZK_SLOT_SHARE_MIN=<x> shared-operand path when (operand transforms) / (distinct operands) >= x (default 2.0; 0 = never)
  *   RZK_PAIR_POLY=0        N = 2048: one wavefront per polynomial instead of two (default 1)
@@ -391,6 +392,10 @@ int rzk_prof_read_kernels(rzk_ctx* ctx, char* buf, size_t cap, size_t* needed);
  *                          team evaluates a whole batch entry)
  *   RZK_UNIT_IO=0|1        key-product programs without vector operands: unit_io_kernel (operands read once, per-prime sums
  *                          parked on chip) instead of unit_kernel (default 1 at N = 512, 0 otherwise)
+ *   RZK_GRID_CUS=<c>       testing: size every grid cap, and the scratch behind it, for c CUs instead of the device's count
+ *                          (clamped to 1 .. multiProcessorCount; 0 or a non-number gives 1), so that small batches make
+ *                          several grid-stride trips.  The batch at which RZK_UPT's default switches to all units per
+ *                          wavefront (16 x CUs) moves with it, so 1 CU reaches the full-batch path choice at batch >= 16
  * RZK_LIB (ring_zk_amd/_lib.py, Python only) loads another build of the library for A/B runs. */
 
 #ifdef __cplusplus

@@ -1275,6 +1275,12 @@ int rzk_ctx_create(rzk_ctx** out, int64_t q, uint32_t N, uint32_t n, uint32_t k,
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
     c->num_cus = prop.multiProcessorCount;
+  // RZK_GRID_CUS (testing): every grid cap and the scratch sized from it follow this CU count, so that small batches
+  // make several grid-stride trips; set before the first allocation sized by num_cus (the row scratch below)
+  if (const char* e = std::getenv("RZK_GRID_CUS")) {
+    const long v = std::strtol(e, nullptr, 10);
+    c->num_cus = v < 1 ? 1 : (v < c->num_cus ? (int)v : c->num_cus);
+  }
   if ((de = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking)) != hipSuccess) {
     delete c;
     return create_fail(RZK_E_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(de));

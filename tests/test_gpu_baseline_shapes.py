@@ -71,15 +71,16 @@ def sum_inputs(rng, P, B, V):
     return gs, xs, rs, rp, ys, yp, d
 
 
-def check_sum_cycle(torch, ctx, A, B, V, seed, device_too=True):
-    """Every phase of the Sum cycle vs the oracle, one tampered proof; returns nothing, asserts."""
+def check_sum_cycle(torch, ctx, A, B, V, seed, device_too=True, entries=None):
+    """Every phase of the Sum cycle vs the oracle, one tampered proof; returns nothing, asserts.  `entries`: the batch
+    entries compared with the oracle (default all of them)."""
     P = P_of(ctx)
     rng = np.random.default_rng(seed)
     gs, xs, rs, rp, ys, yp, d = sum_inputs(rng, P, B, V)
     cs, cp, ts, tp, u, ok = ctx.sum_commit(gs, xs, rs, rp, ys, yp)
     zs, zp = ctx.sum_response(ys, yp, rs, rp, d)
     acc = ctx.sum_verify(zs, zp, cs, cp, gs, ts, tp, u, d)
-    for b in range(B):
+    for b in range(B) if entries is None else entries:
         ref = O.sum_commit(P, A, gs[b], xs[b], rs[b], rp[b], ys[b], yp[b])      # sum.rs:99-178
         for got, want, name in zip((cs, cp, ts, tp, u), ref[:5], ("cs", "cp", "ts", "tp", "u")):
             assert np.array_equal(got[b], want), (name, b)
@@ -108,9 +109,11 @@ def check_sum_cycle(torch, ctx, A, B, V, seed, device_too=True):
         assert accd.cpu().numpy().tolist() == [1] * last + [0]
 
 
-def check_key_products_and_open(ctx, A, B, seed):
+def check_key_products_and_open(ctx, A, B, seed, entries=None):
     """matvec(A1 / A2 / A), commit, Commitment::verify and the Open cycle vs the oracle (commit.rs:109-125,
-    open.rs:80-174), with full-range and ternary vectors."""
+    open.rs:80-174), with full-range and ternary vectors.  `entries`: the batch entries compared with the oracle
+    (default all of them)."""
+    entries = range(B) if entries is None else entries
     P = P_of(ctx)
     N, n, k, l = ctx.N, ctx.n, ctx.k, ctx.l
     rng = np.random.default_rng(seed)
@@ -118,7 +121,7 @@ def check_key_products_and_open(ctx, A, B, seed):
     v[B - 1] = synth.small(rng, (k, N))
     for which, sl in ((0, slice(0, n)), (1, slice(n, n + l)), (2, slice(0, n + l))):
         out = ctx.matvec(which, v)
-        for b in range(B):
+        for b in entries:
             assert np.array_equal(out[b], O.mat_dot(A[sl], v[b][:, None, :])[:, 0, :]), (which, b)
     x = synth.uniform(rng, (B, l, N))
     r = synth.small(rng, (B, k, N))
@@ -130,7 +133,7 @@ def check_key_products_and_open(ctx, A, B, seed):
     zt = z.copy()
     zt[0, 0, 0] = O.center(int(zt[0, 0, 0]) + 1)
     acc, acct = ctx.open_verify(z, t, c, d), ctx.open_verify(zt, t, c, d)
-    for b in range(B):
+    for b in entries:
         c_ref, t_ref, ok_ref = O.open_commit(P, A, x[b], r[b], y[b])
         assert np.array_equal(c[b], c_ref) and np.array_equal(t[b], t_ref) and bool(ok[b]) == ok_ref
         assert np.array_equal(cm[b], c_ref) and bool(okc[b]) == ok_ref

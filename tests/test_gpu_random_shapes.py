@@ -60,7 +60,8 @@ def draw_case(seed):
     return dict(N=N, n=nl, k=k, l=nl, B=B, V=V, env=env, seed=seed)
 
 
-def check_linear_cycle(ctx, A, B, seed):
+def check_linear_cycle(ctx, A, B, seed, entries=None):
+    """Linear cycle vs the oracle at `entries` (default every batch entry), the last proof tampered."""
     P = P_of(ctx)
     N, k, l = ctx.N, ctx.k, ctx.l
     rng = np.random.default_rng(seed)
@@ -74,7 +75,7 @@ def check_linear_cycle(ctx, A, B, seed):
     zt = z.copy()
     zt[B - 1, k - 1, N - 1] = O.center(int(zt[B - 1, k - 1, N - 1]) + 1)
     acc, acct = ctx.linear_verify(z, zp, c, cp, g, t, tp, u, d), ctx.linear_verify(zt, zp, c, cp, g, t, tp, u, d)
-    for b in range(B):
+    for b in range(B) if entries is None else entries:
         ref = O.linear_commit(P, A, g[b], x[b], r[b], rp[b], y[b], yp[b])          # linear.rs:82-140
         for got, want, name in zip((c, cp, t, tp, u), ref[:5], ("c", "cp", "t", "tp", "u")):
             assert np.array_equal(got[b], want), (name, b)
