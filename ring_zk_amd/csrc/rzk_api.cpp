@@ -127,7 +127,7 @@ struct rzk_ctx {
   bool lin_e = true;                   // Linear verifier: g(.)(a2.z - c2(.)d) - (a2.z' - c2'(.)d) - u == 0 (one product with g; RZK_LIN_E=0: the reference's grouping)
   int sum_d = -1;                      // Sum proof: a2.(sum_i g_i v_i - v') instead of sum_i g_i (a2.v_i) - a2.v' (-1 = by cost, RZK_SUM_D=0|1 forces)
   bool preset_in_kernel = true;        // verdict flags initialised by the unit kernels themselves where one team owns an entry (RZK_PRESET_IN_KERNEL=0: always a fill launch)
-  bool small = false;                  // N < 512: schoolbook kernels (rzk_kernels.hip, "small ring degrees")
+  bool small = false;                  // N < 512: schoolbook kernels (rzk_xform.h, "small ring degrees")
   uint32_t r2q = 0;                    // 2^64 mod q
   uint32_t* d_key_mont = nullptr;      // small N: key entries as Montgomery-form residues mod q
   // key
@@ -902,6 +902,51 @@ struct OpSpec {
 // programs pass false — there the offending proof's verdict flag is cleared and the call succeeds.
 int check_launch(rzk_ctx* c, int lrc, const char* what);
 
+// Which launcher evaluates a row program: decided here, once, for the flag preset and for the launch.
+enum class Path { Small, Shift, Blocks, Groups, Slots, Rows, Units };
+Path path_of(const rzk_ctx* c, const DevProg& dp) {
+  if (c->small) return Path::Small;
+  if (dp.shift) return Path::Shift;
+  if (dp.nblocks) return Path::Blocks;
+  if (dp.ngroups) return Path::Groups;
+  if (dp.d_slots) return Path::Slots;
+  if (dp.has_dkey || (dp.has_vec && c->vec_rows)) return Path::Rows;   // row_kernel: vector x vector products, prepared multiplier images
+  return Path::Units;
+}
+
+// Profiling of one launch (rzk_prof_*): prof_begin records the start event and returns a launch configuration whose
+// `launched` points at the slot's kernel name, which the launcher fills in; prof_end records the stop event and only
+// then counts the slot.  A failed launch returns before prof_end, so rzk_prof_read* never meets a half-recorded slot.
+// A launcher that has nothing to do (empty batch, no rows) starts no kernel and writes no name: prof_end does not count
+// such a slot either.
+int prof_begin(rzk_ctx* c, uint64_t bytes, LaunchCfg& cfg) {
+  cfg = cfg_of(c);
+  if (!c->prof) return RZK_OK;
+  if (c->prof_used == c->prof_events.size()) {
+    hipEvent_t a, b;
+    // no system-scope fence at the events: a default event flushes the caches to make results visible to the
+    // host, which slows the NEXT kernel (measured 138 -> 162 us for the commit rows)
+    HIPCHK(c, hipEventCreateWithFlags(&a, hipEventDisableSystemFence));
+    const hipError_t eb = hipEventCreateWithFlags(&b, hipEventDisableSystemFence);
+    if (eb != hipSuccess) (void)hipEventDestroy(a);
+    HIPCHK(c, eb);
+    c->prof_events.push_back({a, b});
+  }
+  if (c->prof_info.size() <= c->prof_used) c->prof_info.resize(c->prof_used + 1);
+  rzk_ctx::ProfInfo& pi = c->prof_info[c->prof_used];
+  pi.kernel.clear();
+  pi.bytes = bytes;
+  cfg.launched = &pi.kernel;
+  HIPCHK(c, hipEventRecord(c->prof_events[c->prof_used].first, c->stream));
+  return RZK_OK;
+}
+int prof_end(rzk_ctx* c) {
+  if (!c->prof || c->prof_info[c->prof_used].kernel.empty()) return RZK_OK;
+  HIPCHK(c, hipEventRecord(c->prof_events[c->prof_used].second, c->stream));
+  c->prof_used++;
+  return RZK_OK;
+}
+
 // preset_value != 0: every verdict flag (nflags of them) starts at that value — written by the launch itself when one
 // team evaluates all rows of a batch entry (no 5-us fill launch in front of a 75-us kernel), by a fill launch otherwise.
 int run_program(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSpec>& specs, uint8_t* flags,
@@ -915,9 +960,8 @@ int run_program(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSpec>& spe
   // fills the chip's wave slots; one unit per task below that
   uint32_t upt = batch >= (uint64_t)c->num_cus * 16 ? dp.nunits : 1;
   if (c->units_per_task) upt = c->units_per_task;   // RZK_UPT (tuning)
-  const bool row_path = dp.has_dkey || (dp.has_vec && c->vec_rows);   // row_kernel: vector x vector products, prepared multiplier images
-  const bool unit_path = !c->small && !dp.shift && !dp.nblocks && !dp.ngroups && !dp.d_slots && !row_path;
-  const bool preset_in_kernel = preset_value && flags && c->preset_in_kernel && unit_path && upt >= dp.nunits && dp.nunits > 0 &&
+  const Path path = path_of(c, dp);
+  const bool preset_in_kernel = preset_value && flags && c->preset_in_kernel && path == Path::Units && upt >= dp.nunits && dp.nunits > 0 &&
                                 (group ? group : 1) == 1 && nflags == batch;
   if (preset_value && flags && !preset_in_kernel) {
     rc = check_launch(c, launch_fill_u8(cfg_of(c), flags, preset_value, nflags), "flag preset");
@@ -953,99 +997,75 @@ int run_program(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSpec>& spe
     ops.dkey_l2 = c->dkey_l2;
     ops.dkey_n = c->dkey_n;
   }
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (c->prof) {
-    if (c->prof_used == c->prof_events.size()) {
-      hipEvent_t a, b;
-      // no system-scope fence at the events: a default event flushes the caches to make results visible to the
-      // host, which slows the NEXT kernel (measured 138 -> 162 us for the commit rows)
-      HIPCHK(c, hipEventCreateWithFlags(&a, hipEventDisableSystemFence));
-      HIPCHK(c, hipEventCreateWithFlags(&b, hipEventDisableSystemFence));
-      c->prof_events.push_back({a, b});
-    }
-    e0 = c->prof_events[c->prof_used].first;
-    e1 = c->prof_events[c->prof_used].second;
-    if (c->prof_info.size() <= c->prof_used) c->prof_info.resize(c->prof_used + 1);
-    rzk_ctx::ProfInfo& pi = c->prof_info[c->prof_used];
-    const std::string L = std::to_string(c->logn);
-    const bool pairs = c->logn == 11 && c->pair_poly;   // two wavefronts per polynomial
-    const std::string tf = c->trusted ? "true" : "false";
-    if (c->small) pi.kernel = "row_kernel_small";
-    else if (dp.shift) pi.kernel = "shift_row_kernel<" + L + ", " + tf + (pairs ? ", PairTeam>" : ">");
-    else if (dp.nblocks) pi.kernel = "row_block_kernel<" + L + (pairs ? ", BlockPairTeam>" : ">");
-    else if (dp.ngroups) pi.kernel = "row_group_kernel<" + L + ", " + std::to_string(c->logn >= 11 ? 2 : RZK_GROUP_GM) + ">";
-    else if (dp.d_slots) pi.kernel = "fwd_slots_kernel<" + L + "> + row_slots_kernel<" + L + ">";
-    else if (row_path)
-      pi.kernel = "row_kernel<" + L + ", " + (dp.has_shift ? "true" : "false") + (pairs ? ", PairTeam" : ", WaveTeam") +
-                  (dp.has_dd && !dp.has_shift ? ", true>" : ", false>");
-    else if (!dp.has_vec && c->unit_io && !(c->logn == 11 && dp.has_shift))
-      pi.kernel = "unit_io_kernel<" + L + ", " + (dp.has_shift ? "true" : "false") + (pairs ? ", PairTeam>" : ">");
-    else
-      pi.kernel = "unit_kernel<" + L + ", " + (dp.has_vec ? "true" : "false") + ", " + (dp.has_shift ? "true" : "false") +
-                  (pairs ? ", PairTeam>" : ">");
-    pi.bytes = 0;
-    for (size_t i = 0; i < specs.size(); ++i)
-      pi.bytes += (uint64_t)dp.polys_in[i] * (specs[i].outer ? batch / (group ? group : 1) : batch);
-    pi.bytes = (pi.bytes + (uint64_t)dp.polys_out * batch) * 8ull * c->N;
-    c->prof_used++;
-    HIPCHK(c, hipEventRecord(e0, c->stream));
-  }
+  uint64_t bytes = 0;   // what the launch has to move at least: its operands in, its results out
+  for (size_t i = 0; i < specs.size(); ++i)
+    bytes += (uint64_t)dp.polys_in[i] * (specs[i].outer ? batch / (group ? group : 1) : batch);
+  bytes = (bytes + (uint64_t)dp.polys_out * batch) * 8ull * c->N;
+  LaunchCfg cfg;
+  rc = prof_begin(c, bytes, cfg);
+  if (rc != RZK_OK) return rc;
   int lrc = 0;
-  if (c->small) {
-    lrc = launch_row_program_small(c->N, cfg_of(c), dp.d, dp.nrows, ops, c->d_key_mont, c->dT, c->r2q, flags, batch);
-  } else if (dp.shift) {
-    lrc = launch_shift_rows((int)c->logn, cfg_of(c), dp.d, dp.nrows, ops, c->dT, flags, batch);
-  } else if (dp.nblocks) {
-    if (!c->d_block_scratch)
-      HIPCHK(c, hipMalloc((void**)&c->d_block_scratch, block_scratch_words((int)c->logn, c->num_cus) * sizeof(uint32_t)));
-    lrc = launch_row_blocks((int)c->logn, cfg_of(c), dp.d, dp.d_blocks, dp.nblocks, ops, c->d_key_ntt, c->d_key_l2, c->dT,
-                            c->d_tw, c->d_block_scratch, flags, batch);
-  } else if (dp.ngroups) {
-    if (!c->d_group_scratch)
-      HIPCHK(c, hipMalloc((void**)&c->d_group_scratch, group_scratch_words((int)c->logn, c->num_cus) * sizeof(uint32_t)));
-    lrc = launch_row_groups((int)c->logn, cfg_of(c), dp.d, dp.ngroups, ops, c->d_key_ntt, c->d_key_l2, c->dT, c->d_tw,
-                            c->d_group_scratch, flags, batch);
-  } else if (dp.d_slots) {
-    // shared-operand path; the workspace of stored transforms is bounded, so large batches go in chunks
-    const size_t per_item = (size_t)dp.nslots * dp.np_store * c->N * sizeof(uint32_t) + (size_t)dp.nslots * 16;
-    const size_t cap = (size_t)6 << 30;
-    uint64_t chunk = cap / per_item;
-    const uint64_t grp = ops.group;
-    chunk -= chunk % grp;
-    if (chunk < grp) chunk = grp;
-    if (chunk > batch) chunk = batch;
-    int rc2 = arena_reserve(c, c->ws_slots, (size_t)chunk * per_item + 256);
-    if (rc2 != RZK_OK) return rc2;
-    uint32_t* d_ws = (uint32_t*)c->ws_slots.p;
-    double* d_norms = (double*)((char*)c->ws_slots.p + (((size_t)chunk * dp.nslots * dp.np_store * c->N * 4 + 255) & ~(size_t)255));
-    for (uint64_t b0 = 0; b0 < batch && lrc == 0; b0 += chunk) {
-      const uint64_t nb = batch - b0 < chunk ? batch - b0 : chunk;
-      Operands o2 = ops;
-      for (size_t i = 0; i < specs.size(); ++i) {
-        if (!o2.base[i]) continue;
-        const uint64_t first = o2.outer[i] ? b0 / grp : b0;
-        o2.base[i] += first * o2.stride[i] * c->N;
+  switch (path) {
+    case Path::Small:
+      lrc = launch_row_program_small(c->N, cfg, dp.d, dp.nrows, ops, c->d_key_mont, c->dT, c->r2q, flags, batch);
+      break;
+    case Path::Shift:
+      lrc = launch_shift_rows((int)c->logn, cfg, dp.d, dp.nrows, ops, c->dT, flags, batch);
+      break;
+    case Path::Blocks:
+      if (!c->d_block_scratch)
+        HIPCHK(c, hipMalloc((void**)&c->d_block_scratch, block_scratch_words((int)c->logn, c->num_cus) * sizeof(uint32_t)));
+      lrc = launch_row_blocks((int)c->logn, cfg, dp.d, dp.d_blocks, dp.nblocks, ops, c->d_key_ntt, c->d_key_l2, c->dT,
+                              c->d_tw, c->d_block_scratch, flags, batch);
+      break;
+    case Path::Groups:
+      if (!c->d_group_scratch)
+        HIPCHK(c, hipMalloc((void**)&c->d_group_scratch, group_scratch_words((int)c->logn, c->num_cus) * sizeof(uint32_t)));
+      lrc = launch_row_groups((int)c->logn, cfg, dp.d, dp.ngroups, ops, c->d_key_ntt, c->d_key_l2, c->dT, c->d_tw,
+                              c->d_group_scratch, flags, batch);
+      break;
+    case Path::Slots: {
+      // shared-operand path; the workspace of stored transforms is bounded, so large batches go in chunks
+      const size_t per_item = (size_t)dp.nslots * dp.np_store * c->N * sizeof(uint32_t) + (size_t)dp.nslots * 16;
+      const size_t cap = (size_t)6 << 30;
+      uint64_t chunk = cap / per_item;
+      const uint64_t grp = ops.group;
+      chunk -= chunk % grp;
+      if (chunk < grp) chunk = grp;
+      if (chunk > batch) chunk = batch;
+      int rc2 = arena_reserve(c, c->ws_slots, (size_t)chunk * per_item + 256);
+      if (rc2 != RZK_OK) return rc2;
+      uint32_t* d_ws = (uint32_t*)c->ws_slots.p;
+      double* d_norms = (double*)((char*)c->ws_slots.p + (((size_t)chunk * dp.nslots * dp.np_store * c->N * 4 + 255) & ~(size_t)255));
+      for (uint64_t b0 = 0; b0 < batch && lrc == 0; b0 += chunk) {
+        const uint64_t nb = batch - b0 < chunk ? batch - b0 : chunk;
+        Operands o2 = ops;
+        for (size_t i = 0; i < specs.size(); ++i) {
+          if (!o2.base[i]) continue;
+          const uint64_t first = o2.outer[i] ? b0 / grp : b0;
+          o2.base[i] += first * o2.stride[i] * c->N;
+        }
+        lrc = launch_row_program_slots((int)c->logn, cfg, dp.d, dp.d_slots, dp.nslots, o2, c->d_key_ntt,
+                                       c->d_key_l2, c->dT, c->d_tw, d_ws, d_norms, c->d_row_scratch,
+                                       flags ? flags + b0 / grp : nullptr, nb, dp.np_store);
       }
-      lrc = launch_row_program_slots((int)c->logn, cfg_of(c), dp.d, dp.d_slots, dp.nslots, o2, c->d_key_ntt,
-                                     c->d_key_l2, c->dT, c->d_tw, d_ws, d_norms, c->d_row_scratch,
-                                     flags ? flags + b0 / grp : nullptr, nb, dp.np_store);
+      break;
     }
-  } else {
-    if (row_path) {
-      lrc = launch_rows((int)c->logn, cfg_of(c), dp.d, dp.nrows, dp.has_shift, ops, c->d_key_ntt, c->d_key_l2, c->dT, c->d_tw,
+    case Path::Rows:
+      lrc = launch_rows((int)c->logn, cfg, dp.d, dp.nrows, dp.has_shift, ops, c->d_key_ntt, c->d_key_l2, c->dT, c->d_tw,
                         c->d_row_scratch, flags, batch, dp.has_dd);
-    } else {
-      lrc = launch_units((int)c->logn, cfg_of(c), dp.d, dp.d_wp, dp.nunits, upt, 2 * dp.work, dp.has_vec, dp.has_shift, ops,
+      break;
+    case Path::Units:
+      lrc = launch_units((int)c->logn, cfg, dp.d, dp.d_wp, dp.nunits, upt, 2 * dp.work, dp.has_vec, dp.has_shift, ops,
                          c->d_key_ntt, c->d_key_l2, c->dT, c->d_tw, c->d_row_scratch, flags, batch);
-    }
+      break;
   }
   if (lrc == -2) return fail(c, RZK_E_UNSUPPORTED, "batch * rows must stay below 2^32");
   if (lrc != 0) {
     c->err = std::string("row kernel launch: ") + (lrc > 0 ? hipGetErrorString((hipError_t)lrc) : "bad ring degree");
     return RZK_E_HIP;
   }
-  if (c->prof) HIPCHK(c, hipEventRecord(e1, c->stream));
-  return RZK_OK;
+  return prof_end(c);
 }
 
 int check_launch(rzk_ctx* c, int lrc, const char* what) {
@@ -1104,27 +1124,14 @@ int prepare_dkey(rzk_ctx* c, const int64_t* g, uint64_t entries, uint32_t per_en
   if (rc != RZK_OK) return rc;
   uint32_t* img = (uint32_t*)c->ws_dkey.p;
   double* l2 = (double*)((char*)c->ws_dkey.p + img_bytes);
-  hipEvent_t e1 = nullptr;
-  if (c->prof) {
-    if (c->prof_used == c->prof_events.size()) {
-      hipEvent_t a, b;
-      HIPCHK(c, hipEventCreateWithFlags(&a, hipEventDisableSystemFence));
-      HIPCHK(c, hipEventCreateWithFlags(&b, hipEventDisableSystemFence));
-      c->prof_events.push_back({a, b});
-    }
-    hipEvent_t e0 = c->prof_events[c->prof_used].first;
-    e1 = c->prof_events[c->prof_used].second;
-    if (c->prof_info.size() <= c->prof_used) c->prof_info.resize(c->prof_used + 1);
-    rzk_ctx::ProfInfo& pi = c->prof_info[c->prof_used];
-    pi.kernel = "dkey_transform_kernel<" + std::to_string(c->logn) + ">";
-    pi.bytes = count * 8ull * c->N;   // the multipliers it reads; the images are derived data
-    c->prof_used++;
-    HIPCHK(c, hipEventRecord(e0, c->stream));
-  }
-  rc = check_launch(c, launch_dkey_transform((int)c->logn, cfg_of(c), g, count, per_entry, img, l2, c->dT, c->d_tw, flags,
+  LaunchCfg cfg;
+  rc = prof_begin(c, count * 8ull * c->N, cfg);   // the multipliers it reads; the images are derived data
+  if (rc != RZK_OK) return rc;
+  rc = check_launch(c, launch_dkey_transform((int)c->logn, cfg, g, count, per_entry, img, l2, c->dT, c->d_tw, flags,
                                              sticky ? c->d_bad : nullptr, false, c->trusted), "multiplier images");
   if (rc != RZK_OK) return rc;
-  if (e1) HIPCHK(c, hipEventRecord(e1, c->stream));
+  rc = prof_end(c);
+  if (rc != RZK_OK) return rc;
   c->dkey_img = img;
   c->dkey_l2 = l2;
   c->dkey_n = per_entry;
@@ -1291,7 +1298,7 @@ int rzk_ctx_create(rzk_ctx** out, int64_t q, uint32_t N, uint32_t n, uint32_t k,
   c->group_max = group_max_for((int)c->logn);
   if (const char* e = std::getenv("RZK_GROUP_MAX")) {
     const int g = std::atoi(e);
-    if (g >= 1 && g <= (c->logn >= 11 ? 2 : RZK_GROUP_GM)) c->group_max = g;   // bounded by the compiled accumulators
+    if (g >= 1 && g <= group_accumulators(c->logn)) c->group_max = g;   // bounded by the compiled accumulators
   }
   if (const char* e = std::getenv("RZK_SHIFT")) c->use_shift = std::atoi(e) != 0;
   if (const char* e = std::getenv("RZK_SUM_D")) c->sum_d = std::atoi(e) != 0 ? 1 : 0;

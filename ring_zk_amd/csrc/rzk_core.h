@@ -33,22 +33,6 @@
 #define RZK_HD inline
 #endif
 
-// Optional scheduling fence for the device build (tuning knob, off by default): VALU instructions may
-// not be moved across it (loads, LDS reads and scalar instructions may); placed after every
-// RZK_BFLY_GROUP butterflies.
-#ifndef RZK_BFLY_GROUP
-#define RZK_BFLY_GROUP 0   // 0 = no fence (measured: fences do not lower the register count)
-#endif
-#if defined(__HIP_DEVICE_COMPILE__)
-#define RZK_SCHED_GROUP(count)                                                          \
-  do {                                                                                  \
-    if (RZK_BFLY_GROUP > 0 && ((count) % (RZK_BFLY_GROUP > 0 ? RZK_BFLY_GROUP : 1)) == 0) \
-      __builtin_amdgcn_sched_barrier(0x4 | 0x20 | 0x100);                               \
-  } while (0)
-#else
-#define RZK_SCHED_GROUP(count) do { } while (0)
-#endif
-
 namespace rzk {
 
 constexpr int kMaxPrimes = 3;
@@ -82,16 +66,11 @@ RZK_HD uint32_t mont_lazy(uint32_t x, uint32_t w, uint32_t p, uint32_t npinv) {
 }
 // unsigned conditional subtract: v in [0, 2m) -> [0, m)
 RZK_HD uint32_t csub(uint32_t v, uint32_t m) {
-#if !defined(RZK_CSUB_MIN)
   // subtract with borrow-out, then select: v_sub_co_u32 + v_cndmask_b32 (measured 2-4 % faster per launch on gfx950 than
-  // the v_sub_u32 + v_min_u32 form below, whose v_min_u32 issues at ~4.3 cycles against ~2.8 for these two)
+  // min(v - m, v) as v_sub_u32 + v_min_u32, whose v_min_u32 issues at ~4.3 cycles against ~2.8 for these two)
   uint32_t d;
   const bool borrow = __builtin_sub_overflow(v, m, &d);
   return borrow ? v : d;
-#else
-  uint32_t d = v - m;
-  return d < v ? d : v;   // d wraps above v exactly when v < m
-#endif
 }
 
 // Cooley-Tukey butterfly, Harvey lazy: X, Y in [0,4p) -> [0,4p).  w in Montgomery form.
@@ -223,8 +202,6 @@ RZK_HD void lds_get_p3(uint32_t* x, int lane, const uint32_t* lds) {
 template <int LOGN, int LL = 6>
 RZK_HD void fwd_phase1(uint32_t* x, const uint32_t* tw, const PrimeConsts& pc) {
   using G = Geo<LOGN, LL>;
-  int nb = 0;
-  (void)nb;
 #pragma unroll
   for (int s = 0; s < G::LE; ++s) {
     const int half = G::E >> (s + 1);
@@ -233,16 +210,12 @@ RZK_HD void fwd_phase1(uint32_t* x, const uint32_t* tw, const PrimeConsts& pc) {
       if (e & half) continue;
       const uint32_t w = tw[(1 << s) + (e >> (G::LE - s))];   // wave-uniform
       bfly_fwd(x[e], x[e + half], w, pc);
-      ++nb;
-      RZK_SCHED_GROUP(nb);
     }
   }
 }
 template <int LOGN, int LL = 6>
 RZK_HD void fwd_phase2(uint32_t* x, int lane, const uint32_t* tw, const PrimeConsts& pc) {
   using G = Geo<LOGN, LL>;
-  int nb = 0;
-  (void)nb;
   const int hi = G::p2_hi(lane);
 #pragma unroll
   for (int sp = 0; sp < G::LE; ++sp) {
@@ -252,16 +225,12 @@ RZK_HD void fwd_phase2(uint32_t* x, int lane, const uint32_t* tw, const PrimeCon
     for (int r = 0; r < G::E; ++r) {
       if (r & half) continue;
       bfly_fwd(x[r], x[r + half], twl[r >> (G::LE - sp)], pc);
-      ++nb;
-      RZK_SCHED_GROUP(nb);
     }
   }
 }
 template <int LOGN, int LL = 6>
 RZK_HD void fwd_phase3(uint32_t* x, int lane, const uint32_t* tw, const PrimeConsts& pc) {
   using G = Geo<LOGN, LL>;
-  int nb = 0;
-  (void)nb;
 #pragma unroll
   for (int sq = 0; sq < G::R3; ++sq) {
     const int sh = G::R3 - sq;            // idx = 2^s + (j >> sh)
@@ -271,8 +240,6 @@ RZK_HD void fwd_phase3(uint32_t* x, int lane, const uint32_t* tw, const PrimeCon
     for (int c = 0; c < G::E; ++c) {
       if (c & half) continue;
       bfly_fwd(x[c], x[c + half], twl[c >> sh], pc);
-      ++nb;
-      RZK_SCHED_GROUP(nb);
     }
   }
 }
@@ -281,8 +248,6 @@ RZK_HD void fwd_phase3(uint32_t* x, int lane, const uint32_t* tw, const PrimeCon
 template <int LOGN, int LL = 6>
 RZK_HD void inv_phase3(uint32_t* x, int lane, const uint32_t* tw, const PrimeConsts& pc) {
   using G = Geo<LOGN, LL>;
-  int nb = 0;
-  (void)nb;
 #pragma unroll
   for (int sq = G::R3 - 1; sq >= 0; --sq) {
     const int sh = G::R3 - sq;
@@ -292,16 +257,12 @@ RZK_HD void inv_phase3(uint32_t* x, int lane, const uint32_t* tw, const PrimeCon
     for (int c = 0; c < G::E; ++c) {
       if (c & half) continue;
       bfly_inv(x[c], x[c + half], twl[c >> sh], pc);
-      ++nb;
-      RZK_SCHED_GROUP(nb);
     }
   }
 }
 template <int LOGN, int LL = 6>
 RZK_HD void inv_phase2(uint32_t* x, int lane, const uint32_t* tw, const PrimeConsts& pc) {
   using G = Geo<LOGN, LL>;
-  int nb = 0;
-  (void)nb;
   const int hi = G::p2_hi(lane);
 #pragma unroll
   for (int sp = G::LE - 1; sp >= 0; --sp) {
@@ -311,16 +272,12 @@ RZK_HD void inv_phase2(uint32_t* x, int lane, const uint32_t* tw, const PrimeCon
     for (int r = 0; r < G::E; ++r) {
       if (r & half) continue;
       bfly_inv(x[r], x[r + half], twl[r >> (G::LE - sp)], pc);
-      ++nb;
-      RZK_SCHED_GROUP(nb);
     }
   }
 }
 template <int LOGN, int LL = 6>
 RZK_HD void inv_phase1(uint32_t* x, const uint32_t* tw, const PrimeConsts& pc) {
   using G = Geo<LOGN, LL>;
-  int nb = 0;
-  (void)nb;
 #pragma unroll
   for (int s = G::LE - 1; s >= 0; --s) {
     const int half = G::E >> (s + 1);
@@ -329,8 +286,6 @@ RZK_HD void inv_phase1(uint32_t* x, const uint32_t* tw, const PrimeConsts& pc) {
       if (e & half) continue;
       const uint32_t w = tw[(1 << s) + (e >> (G::LE - s))];
       bfly_inv(x[e], x[e + half], w, pc);
-      ++nb;
-      RZK_SCHED_GROUP(nb);
     }
   }
 }

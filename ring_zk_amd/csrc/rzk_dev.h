@@ -1,7 +1,9 @@
-// rzk_dev.h — structures shared by the kernels (rzk_kernels.hip) and the C-ABI host code (rzk_api.cpp).
+// rzk_dev.h — structures shared by the kernels (rzk_kernels.hip and the family headers it includes) and the C-ABI host code (rzk_api.cpp).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+
+#include <string>
 
 #include "rzk_core.h"
 #include "rzk_wire_walk.h"
@@ -36,7 +38,7 @@ struct DevTables {
 #if defined(__HIPCC__)
 template <class Tp>
 __device__ __forceinline__ Tp table_load(const Tp* p) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(RZK_NO_TABLE_SLOAD)
+#if defined(__HIP_DEVICE_COMPILE__)
   typedef const Tp __attribute__((address_space(4))) * cptr_t;
   return *reinterpret_cast<cptr_t>(reinterpret_cast<uintptr_t>(p));
 #else
@@ -209,6 +211,7 @@ struct LaunchCfg {
   int num_cus;
   int pair_poly;  // N = 2048: two wavefronts per polynomial (PairTeam) in unit_kernel / row_kernel / row_block_kernel
   int unit_io;    // key-product programs through unit_io_kernel (operands read once) instead of unit_kernel
+  std::string* launched = nullptr;   // out: the row-program launchers write the name of the instantiation they started here
 };
 
 // units_per_task: how many consecutive units of one batch entry a wavefront evaluates back to back (all of them =
@@ -242,11 +245,14 @@ int launch_dkey_transform(int logn, const LaunchCfg& cfg, const int64_t* g, uint
                           bool trusted);
 int launch_shift_rows(int logn, const LaunchCfg& cfg, const Program* d_prog, uint32_t nrows, const Operands& ops,
                       const DevTables* d_T, uint8_t* d_flags, uint64_t batch);
-// rows per group; 1 = no grouping (at N = 2048 the accumulators cost too many registers: measured slower)
-#ifndef RZK_GROUP_GM
-#define RZK_GROUP_GM 4   // accumulators (= rows per group) of row_group_kernel at N <= 1024; at most kGroupMax
-#endif
-inline int group_max_for(int logn) { return logn >= 11 ? 1 : RZK_GROUP_GM; }
+// Rows per group of row_group_kernel.  Two numbers, on purpose:
+//   group_accumulators  how many accumulators (= rows per group, at most kGroupMax) the instantiation launched for this
+//                       size is COMPILED with: 4 at N <= 1024, 2 at N = 2048;
+//   group_max_for       what the host groups by DEFAULT: the same at N <= 1024, but 1 = no grouping at N = 2048 (the
+//                       accumulators cost too many registers there: measured slower).  The RZK_GROUP_MAX knob of
+//                       rzk_ctx_create may raise it again, up to group_accumulators (the tests do, to reach the kernel).
+constexpr int group_accumulators(int logn) { return logn >= 11 ? 2 : 4; }
+inline int group_max_for(int logn) { return logn >= 11 ? 1 : group_accumulators(logn); }
 // words of per-wave global scratch of unit_kernel: (max blocks) * 4 waves * 4N (Garner words A, B of rows A, B)
 size_t row_scratch_words(int logn, int num_cus);
 int launch_key_transform(int logn, const LaunchCfg& cfg, const int64_t* d_key, uint32_t entries,

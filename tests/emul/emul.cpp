@@ -202,7 +202,7 @@ int emul_polymul(int logn, int np, uint64_t q, const int64_t* a, const int64_t* 
   }
   return -1;
 }
-// CPU statement of what the device-side samplers draw for polynomial `poly` of a call (rzk_kernels.hip: one Philox block
+// CPU statement of what the device-side samplers draw for polynomial `poly` of a call (rzk_sample.h: one Philox block
 // per coefficient pair; Floyd's subset algorithm for the challenge): the kernels must give exactly these values.
 void emul_sample_uniform(uint64_t seed, uint32_t stream, uint64_t poly, uint32_t N, uint32_t bound, int64_t* out) {
   const uint32_t range = 2u * bound + 1u;

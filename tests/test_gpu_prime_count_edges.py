@@ -1,7 +1,7 @@
 """Prime-count edges on the GPU: Cauchy-Schwarz-tight operands at every kernel that picks 1, 2 or 3 auxiliary primes.
 
 Every NTT-path product is reconstructed from as many auxiliary primes as the kernel's bound sum_terms |a|_2 |b|_2
-asks for (primes_for in rzk_kernels.hip).  A bound that drops a term, a row or a factor makes the CRT reconstruct a
+asks for (primes_for in rzk_rowprog.h).  A bound that drops a term, a row or a factor makes the CRT reconstruct a
 value modulo the wrong product of primes: a wrong answer mod q, or a flipped verdict, with no error.  Random
 protocol data sits bits away from a capacity, so these cases build exact results just below and just above
 (P_np - 1) / 2 on purpose (ring_zk_amd/synth.py, tight_terms / conj; tests/test_crt_edges.py checks the identities

@@ -7,9 +7,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from ring_zk_amd import build  # noqa: E402
 
-os.makedirs(os.path.join(ROOT, "ring_zk_amd", "variants"), exist_ok=True)
-for spec in sys.argv[1:]:
+
+def build_variant(spec):
     name, _, defs = spec.partition(":")
+    os.makedirs(os.path.join(ROOT, "ring_zk_amd", "variants"), exist_ok=True)
     out = os.path.join(ROOT, "ring_zk_amd", "variants", f"lib_{name}.so")
-    build.build_library(out=out, defines=[d for d in defs.split(",") if d])
-    print(name, out)
+    return build.build_library(out=out, defines=[d for d in defs.split(",") if d])
+
+
+if __name__ == "__main__":
+    for spec in sys.argv[1:]:
+        print(spec.partition(":")[0], build_variant(spec))

@@ -6,8 +6,11 @@ root=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 out=$root/gpurun_out/asan
 mkdir -p $out
 cd $root
+# the library's source list, read from build.py by path (no import of the package, which would pull in torch)
+sources=$(python3 -c "import runpy; print(' '.join('ring_zk_amd/csrc/' + s for s in runpy.run_path('ring_zk_amd/build.py')['SOURCES']))")
+[ -n "$sources" ] || { echo "could not read SOURCES from ring_zk_amd/build.py" >&2; exit 1; }
 /opt/rocm/bin/hipcc -O1 -g --offload-arch=gfx950 -std=c++17 -fPIC -shared -Xarch_host -fsanitize=address -Xarch_host -fno-omit-frame-pointer \
-  -o $out/librzk_hip_asan.so ring_zk_amd/csrc/rzk_kernels.hip ring_zk_amd/csrc/rzk_api.cpp ring_zk_amd/csrc/rzk_wire.cpp
+  -o $out/librzk_hip_asan.so $sources
 for n in 16 512 1024 2048; do
   /opt/rocm/lib/llvm/bin/clang++ -O1 -g -std=c++17 -fsanitize=address -fno-omit-frame-pointer -DTEST_N=$n tests/cpp/test_ring_zk.cpp \
     -L$out -lrzk_hip_asan -Wl,-rpath,$out -o $out/test_ring_zk_$n
