@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
@@ -17,68 +18,22 @@
 #include "../../include/rzk.h"
 #include "rzk_core.h"
 #include "rzk_dev.h"
+#include "rzk_plan.h"
 #include "rzk_tables.h"
 
 using namespace rzk;
 
-// table_load (rzk_dev.h) reads these records with scalar loads: they must be naturally aligned inside their tables
-static_assert(sizeof(Term) == 8 && sizeof(AddTerm) == 4 && sizeof(Row) == 16 && sizeof(Item) == 16 && sizeof(Unit) == 8,
-              "program record sizes");
-static_assert(offsetof(Program, rows) % 8 == 0 && offsetof(Program, terms) % 8 == 0 && offsetof(Program, adds) % 4 == 0 &&
-                  offsetof(WaveProgram, units) % 8 == 0 && offsetof(WaveProgram, items) % 8 == 0,
-              "program record alignment");
+// plan_program speaks the C ABI's status codes, PG_MATVEC its key selectors
+static_assert(kPlanOk == RZK_OK && kPlanArg == RZK_E_ARG && kPlanUnsupported == RZK_E_UNSUPPORTED, "plan status codes");
+static_assert(RZK_KEY_A1 == 0 && RZK_KEY_A2 == 1 && RZK_KEY_A == 2, "key selectors");
 
 namespace {
 
-enum KeyClass : uint8_t { KC_ZERO = 0, KC_ONE = 1, KC_GENERAL = 2 };
-
-enum ProgId : int {
-  PG_MATVEC = 0,      // variant = which*2 + has_addend
-  PG_POLYMUL,
-  PG_CMUL,            // variant = rows
-  PG_OPEN_COMMIT,
-  PG_RESPONSE,        // variant = number of (y,r,z) triples sharing d (1 = open, 2 = linear)
-  PG_A1_RELATION,     // a1.z - c1(.)d - t == 0   (open / linear / sum verify)
-  PG_LIN_COMMIT2,
-  PG_LIN_U,
-  PG_LIN_V1,
-  PG_LIN_V2,
-  PG_SUM_XP,          // variant = V
-  PG_SUM_U,           // variant = V
-  PG_SUM_W2,          // variant = V
-  PG_SUM_V3,          // variant = V
-  PG_COMMIT,          // c = [a1;a2].r + [0;x]                       (commit.rs:88-128)
-  PG_COMMIT_VERIFY,   // variant bit 1: opening has a scalar f       (commit.rs:173-210)
-  PG_A1Z,             // w = a1.z (n rows), norm predicate on z fused (bit 0)   } the A1 relation in two steps for
-  PG_REL_ROT,         // w - c1(.)d - t == 0, all rotations                      } n >= 2: grouped rows + rotations
-  PG_SUM_D,           // variant = V: D_c = sum_i g_i(.)v_{i,c} - v'_c for the columns c that a2 uses   } sum_i g_i (a2.v_i) - a2.v'
-  PG_SUM_V4,          // a2.D - w2(.)d - u == 0                                                           }   = a2.(sum_i g_i v_i - v')
-  PG_LIN_V1B,         // Linear verifier, rearranged: relation rows, e = a2.z - c2(.)d, e' = a2.z' - c2'(.)d   } (a2.z)(.)g - a2.z' - (c2(.)g - c2')(.)d - u
-  PG_LIN_V2B,         // g(.)e - e' - u == 0                                                                     }   = g(.)e - e' - u
-};
-
-struct DevProg {
+struct DevProg : PlanFacts {   // a plan's facts and its tables on the device
   Program* d = nullptr;
-  uint32_t nrows = 0;
-  WaveProgram* d_wp = nullptr;   // units / items of unit_kernel (the default path)
-  uint32_t nunits = 0;
-  uint32_t work = 0;             // steps (item + inverse trips) of one batch entry per prime pass
-  bool has_vec = false;
-  // shared-operand path (fwd_slots_kernel + row_slots_kernel), chosen when rows share enough operands
-  SlotTable* d_slots = nullptr;
-  uint32_t nslots = 0;
-  uint32_t np_store = 0;
-  uint32_t ngroups = 0;   // > 0: row groups (row_group_kernel)
-  bool has_dkey = false;  // products with prepared multiplier images (TERM_DKEY): row_kernel only
-  bool has_dd = false;    // ... whose other operand may come from the call's operand images (TERM_DD): row_kernel<.., DD>
-  bool shift = false;     // every product has the sparse challenge as multiplier: shift_row_kernel
-  bool has_shift = false; // some rows end with challenge products evaluated by rotations inside row_kernel
-  bool two_bit = false;   // two-bit verdict flags (CHECK2 marks)
-  BlockPlan* d_blocks = nullptr;   // row blocks (row_block_kernel): operands of a block staged once in LDS
-  uint32_t nblocks = 0;
-  // algorithmic traffic of one batch entry (instrumentation): distinct polynomials read per operand index, rows stored
-  uint16_t polys_in[kMaxOperands] = {};
-  uint32_t polys_out = 0;
+  WaveProgram* d_wp = nullptr;     // units / items of unit_kernel (the default path)
+  SlotTable* d_slots = nullptr;    // shared-operand path (fwd_slots_kernel + row_slots_kernel)
+  BlockPlan* d_blocks = nullptr;   // row blocks (row_block_kernel)
 };
 
 struct Arena {   // grow-only device buffer
@@ -208,425 +163,30 @@ int arena_reserve(rzk_ctx* c, Arena& a, size_t bytes) {
   return RZK_OK;
 }
 
-// ---- program builder ------------------------------------------------------------------------------------------
-struct PB {
-  Program p{};
-  bool overflow = false;
-  bool two_bit = false;      // the program carries CHECK2 marks: two-bit verdict flags (row_kernel only)
-  uint32_t sparse_ops = 0;   // bit i: operand i is a challenge (kappa-sparse, +-1): products with it may use shift-add
-  int cur = -1;
-  void begin_row(uint8_t out_op, uint32_t out_off, uint8_t mode) {
-    if (p.nrows >= (uint32_t)kMaxRows) { overflow = true; return; }
-    cur = (int)p.nrows++;
-    Row& r = p.rows[cur];
-    r.term0 = (uint16_t)p.nterms;
-    r.add0 = (uint16_t)p.nadds;
-    r.nterms = r.nadds = 0;
-    r.nshift = r.pad = 0;
-    r.out_op = out_op;
-    r.out_off = (uint16_t)out_off;
-    r.mode = mode;
-    if (out_off > 0xffff) overflow = true;
-  }
-  // total terms of the program so far (transform terms and shift terms share Program::terms)
-  void key_term(int sign, uint32_t entry, uint8_t vop, uint32_t voff) {
-    if (cur < 0 || p.nterms >= (uint32_t)kMaxTerms || entry > 0xffff || voff > 0xffff || p.rows[cur].nshift) { overflow = true; return; }
-    Term& t = p.terms[p.nterms++];
-    t.kind = TERM_KEY;
-    t.sign = (int8_t)sign;
-    t.a_op = 0;
-    t.a_off = (uint16_t)entry;
-    t.b_op = vop;
-    t.b_off = (uint16_t)voff;
-    p.rows[cur].nterms++;
-  }
-  // sign * (image `idx` of the entry's own multipliers) (.) (bop,boff): Operands::dkey_img, row_kernel only
-  void dkey_term(int sign, uint32_t idx, uint8_t bop, uint32_t boff) {
-    if (cur < 0 || p.nterms >= (uint32_t)kMaxTerms || idx > 0xffff || boff > 0xffff || p.rows[cur].nshift) { overflow = true; return; }
-    Term& t = p.terms[p.nterms++];
-    t.kind = TERM_DKEY;
-    t.sign = (int8_t)sign;
-    t.a_op = 0;
-    t.a_off = (uint16_t)idx;
-    t.b_op = bop;
-    t.b_off = (uint16_t)boff;
-    p.rows[cur].nterms++;
-  }
-  // a product with one of the entry's scalar multipliers (operand gop, index idx): its image when the call prepared
-  // them (dk), a vector x vector term otherwise; oi: the other operand's transform may come from the call's operand images
-  void scalar_term(bool dk, int sign, uint8_t gop, uint32_t idx, uint8_t bop, uint32_t boff, bool oi = false) {
-    if (dk) {
-      dkey_term(sign, idx, bop, boff);
-      if (oi && !overflow) p.terms[p.nterms - 1].kind = TERM_DD;
-    } else {
-      vec_term(sign, bop, boff, gop, idx);
-    }
-  }
-  void vec_term(int sign, uint8_t aop, uint32_t aoff, uint8_t bop, uint32_t boff) {
-    if (cur < 0 || p.nterms >= (uint32_t)kMaxTerms || aoff > 0xffff || boff > 0xffff || p.rows[cur].nshift) { overflow = true; return; }
-    Term& t = p.terms[p.nterms++];
-    t.kind = TERM_VEC;
-    t.sign = (int8_t)sign;
-    t.a_op = aop;
-    t.a_off = (uint16_t)aoff;
-    t.b_op = bop;
-    t.b_off = (uint16_t)boff;
-    p.rows[cur].nterms++;
-  }
-  // sign * (aop,aoff) (.) (bop,boff) with a sparse `a` (the challenge), evaluated as signed rotations inside the
-  // row kernel; such terms close a row's term list (stored behind its transform terms)
-  void shift_term(int sign, uint8_t aop, uint32_t aoff, uint8_t bop, uint32_t boff) {
-    if (cur < 0 || p.nterms >= (uint32_t)kMaxTerms || aoff > 0xffff || boff > 0xffff) { overflow = true; return; }
-    Term& t = p.terms[p.nterms++];
-    t.kind = TERM_SHIFT;
-    t.sign = (int8_t)sign;
-    t.a_op = aop;
-    t.a_off = (uint16_t)aoff;
-    t.b_op = bop;
-    t.b_off = (uint16_t)boff;
-    p.rows[cur].nshift++;
-  }
-  // product with the challenge: rotations when enabled, transform product otherwise
-  void challenge_term(bool rotate, int sign, uint8_t dop, uint8_t bop, uint32_t boff) {
-    if (rotate) shift_term(sign, dop, 0, bop, boff);
-    else vec_term(sign, dop, 0, bop, boff);
-  }
-  void add(int sign, uint8_t op, uint32_t off) {
-    if (cur < 0 || p.nadds >= (uint32_t)kMaxAdds || off > 0xffff) { overflow = true; return; }
-    AddTerm& a = p.adds[p.nadds++];
-    a.op = op;
-    a.sign = (int8_t)sign;
-    a.off = (uint16_t)off;
-    p.rows[cur].nadds++;
-  }
-};
-
-// Fused norm predicate: mark, for each polynomial (vop, 0..count-1), the first load in program order
-// (b operand of a product term, or one of the first four additions of a row).  Returns false when some
-// polynomial is never loaded by the program — the caller then keeps the separate norm kernel.
-bool mark_checks(PB& pb, uint8_t vop, uint32_t count, bool second = false) {
-  const uint8_t tmark = second ? TERM_CHECK2 : TERM_CHECK, amark = second ? ADD_CHECK2 : ADD_CHECK;
-  if (second) pb.two_bit = true;
-  for (uint32_t j = 0; j < count; ++j) {
-    bool done = false;
-    for (uint32_t r = 0; r < pb.p.nrows && !done; ++r) {
-      const Row& row = pb.p.rows[r];
-      for (uint32_t t = 0; t < row.nterms && !done; ++t) {
-        Term& tm = pb.p.terms[row.term0 + t];
-        if (tm.b_op == vop && tm.b_off == j && !(tm.kind & (TERM_CHECK | TERM_CHECK2))) {
-          tm.kind |= tmark;
-          done = true;
-        }
-      }
-      for (uint32_t a = 0; a < row.nadds && a < 4 && !done; ++a) {
-        AddTerm& ad = pb.p.adds[row.add0 + a];
-        if ((ad.op & ADD_OP_MASK) == vop && ad.off == j && !(ad.op & (ADD_CHECK | ADD_CHECK2))) {
-          ad.op |= amark;
-          done = true;
-        }
-      }
-    }
-    if (!done) return false;
-  }
-  return true;
-}
-
-// sign * (row `krow` of [a1;a2]) . v, v = operand (vop, voff .. voff+k-1): skips zero entries, turns
-// entries equal to 1 into plain additions (the identity blocks of commit.rs:38-57), products otherwise.
-void key_row(rzk_ctx* c, PB& pb, int sign, uint32_t krow, uint8_t vop, uint32_t voff) {
-  for (uint32_t j = 0; j < c->k; ++j) {
-    const uint32_t idx = krow * c->k + j;
-    switch (c->key_class[idx]) {
-      case KC_ZERO: break;
-      case KC_ONE: pb.add(sign, vop, voff + j); break;
-      default: pb.key_term(sign, (uint32_t)c->key_entry[idx], vop, voff + j); break;
-    }
-  }
-}
-
 // Challenge products as signed rotations (shift-add) instead of transforms.  At N = 2048 only with two wavefronts
 // per polynomial (16 outputs per thread): with one, a lane holds 32 outputs, the rotation kernels need > 200 VGPRs
 // (one or two waves per SIMD) and measured slower than the transform path (round 2).
 bool shift_ok(const rzk_ctx* c) { return c->use_shift && !c->small && (c->logn <= 10 || c->pair_poly); }
 
-// bit of a program variant: products with the entry's scalar multipliers (g, g_i) take their prepared images (TERM_DKEY)
-constexpr uint32_t kDkeyVar = 0x10000u;
-constexpr uint32_t kOimgVar = 0x20000u;   // ... and (PG_SUM_D) the other operand's transform from the call's operand images (TERM_DD)
+// ---- row programs: planned on the host (rzk_plan.h), uploaded once per (program, shape) --------------------------
+PlanEnv plan_env(const rzk_ctx* c) {
+  return PlanEnv{c->n, c->k, c->l, c->logn, c->small, shift_ok(c), c->block_min_logn, c->use_groups, c->group_max,
+                 c->use_pairs, c->slot_share_min, c->key_class.data(), c->key_entry.data()};
+}
 
-int build_program(rzk_ctx* c, int id, uint32_t var_in, PB& pb) {
-  const uint32_t n = c->n, k = c->k, l = c->l;
-  const bool rot = shift_ok(c);   // challenge products inside mixed rows as rotations
-  const bool dk = (var_in & kDkeyVar) != 0, oi = (var_in & kOimgVar) != 0;
-  const uint32_t var = var_in & ~(kDkeyVar | kOimgVar);
-  switch (id) {
-    case PG_MATVEC: {   // ops: 0 = v[k], 1 = addend[rows], 2 = out[rows]
-      const uint32_t which = var >> 1;
-      const bool has_add = var & 1;
-      const uint32_t r0 = which == RZK_KEY_A2 ? n : 0;
-      const uint32_t rows = which == RZK_KEY_A1 ? n : (which == RZK_KEY_A2 ? l : n + l);
-      for (uint32_t i = 0; i < rows; ++i) {
-        pb.begin_row(2, i, MODE_STORE);
-        key_row(c, pb, +1, r0 + i, 0, 0);
-        if (has_add) pb.add(+1, 1, i);
-      }
-      break;
-    }
-    case PG_POLYMUL:   // ops: 0 = a, 1 = b, 2 = out
-      pb.begin_row(2, 0, MODE_STORE);
-      pb.vec_term(+1, 0, 0, 1, 0);
-      break;
-    case PG_CMUL:      // ops: 0 = m[rows], 1 = p, 2 = out[rows]   (mat.rs:168-178)
-      for (uint32_t i = 0; i < var; ++i) {
-        pb.begin_row(2, i, MODE_STORE);
-        pb.scalar_term(dk, +1, 1, 0, 0, i);
-      }
-      break;
-    case PG_OPEN_COMMIT:   // ops: 0 = x[l], 1 = r[k], 2 = y[k], 3 = c[n+l], 4 = t[n]
-      for (uint32_t i = 0; i < n + l; ++i) {   // commit.rs:125: c = [a1;a2].r + [0_n ; x]
-        pb.begin_row(3, i, MODE_STORE);
-        key_row(c, pb, +1, i, 1, 0);
-        if (i >= n) pb.add(+1, 0, i - n);
-      }
-      for (uint32_t i = 0; i < n; ++i) {       // open.rs:97: t = a1.y
-        pb.begin_row(4, i, MODE_STORE);
-        key_row(c, pb, +1, i, 2, 0);
-      }
-      if (var & 1) {   // fused check_commit_constraint(r)  (commit.rs:98-107)
-        if (!mark_checks(pb, 1, k)) return RZK_E_UNSUPPORTED;
-      }
-      break;
-    case PG_COMMIT:   // ops: 0 = x[l], 1 = r[k], 2 = c[n+l]
-      for (uint32_t i = 0; i < n + l; ++i) {   // commit.rs:109-125
-        pb.begin_row(2, i, MODE_STORE);
-        key_row(c, pb, +1, i, 1, 0);
-        if (i >= n) pb.add(+1, 0, i - n);
-      }
-      if (var & 1) {   // fused check_commit_constraint(r)  (commit.rs:98-107)
-        if (!mark_checks(pb, 1, k)) return RZK_E_UNSUPPORTED;
-      }
-      break;
-    case PG_COMMIT_VERIFY:   // ops: 0 = x[l], 1 = r[k], 2 = c[n+l], 3 = f ; flags &= (commit.rs:199-209)
-      for (uint32_t i = 0; i < n + l; ++i) {
-        pb.begin_row(0, 0, MODE_ZERO);
-        key_row(c, pb, +1, i, 1, 0);
-        if (var & 2) {   // a.r + z(.)f - c(.)f == 0
-          if (i >= n) pb.vec_term(+1, 0, i - n, 3, 0);
-          pb.vec_term(-1, 2, i, 3, 0);
-        } else {         // a.r + z - c == 0
-          if (i >= n) pb.add(+1, 0, i - n);
-          pb.add(-1, 2, i);
-        }
-      }
-      if (var & 1) {   // fused check_commit_constraint(r)  (commit.rs:183-185)
-        if (!mark_checks(pb, 1, k)) return RZK_E_UNSUPPORTED;
-      }
-      break;
-    case PG_A1Z:   // ops: 0 = z[k], 1 = w[n]
-      for (uint32_t i = 0; i < n; ++i) {
-        pb.begin_row(1, i, MODE_STORE);
-        key_row(c, pb, +1, i, 0, 0);
-      }
-      if (var & 1) {   // fused check_verify_constraint(z)
-        if (!mark_checks(pb, 0, k)) return RZK_E_UNSUPPORTED;
-      }
-      break;
-    case PG_REL_ROT:   // ops: 0 = w[n] (= a1.z), 1 = t[n], 2 = c[n+l], 3 = d ; flags &= (w == t + c1(.)d)
-      pb.sparse_ops = 1u << 3;
-      for (uint32_t i = 0; i < n; ++i) {
-        pb.begin_row(0, 0, MODE_ZERO);
-        pb.vec_term(-1, 3, 0, 2, i);
-        pb.add(+1, 0, i);
-        pb.add(-1, 1, i);
-      }
-      break;
-    case PG_RESPONSE:   // ops: 0 = d, then per triple s: 1+3s = y[k], 2+3s = r[k], 3+3s = z[k]
-      pb.sparse_ops = 1u << 0;
-      for (uint32_t s = 0; s < var; ++s)
-        for (uint32_t i = 0; i < k; ++i) {      // open.rs:113-115: z = y + r (.) d
-          pb.begin_row((uint8_t)(3 + 3 * s), i, MODE_STORE);
-          pb.vec_term(+1, 0, 0, (uint8_t)(2 + 3 * s), i);
-          pb.add(+1, (uint8_t)(1 + 3 * s), i);
-        }
-      break;
-    case PG_A1_RELATION:   // ops: 0 = z[k], 1 = t[n], 2 = c[n+l], 3 = d ; flags &= (a1.z == t + c1(.)d)
-      // c1 = first l rows of c (Commitment::c1_c2 -> split_rows(n), commit.rs:213-218, mat.rs:203-213);
-      // Mat::add requires it to have n rows, so n == l is checked by the caller.
-      for (uint32_t i = 0; i < n; ++i) {
-        pb.begin_row(0, 0, MODE_ZERO);
-        key_row(c, pb, +1, i, 0, 0);
-        pb.challenge_term(rot, -1, 3, 2, i);
-        pb.add(-1, 1, i);
-      }
-      if (var & 1) {   // fused check_verify_constraint(z)  (open.rs:167-169)
-        if (!mark_checks(pb, 0, k)) return RZK_E_UNSUPPORTED;
-      }
-      break;
-    case PG_LIN_COMMIT2:
-      // ops: 0 = x[l], 1 = gx[l], 2 = r[k], 3 = rp[k], 4 = y[k], 5 = yp[k],
-      //      6 = c[n+l], 7 = cp[n+l], 8 = t[n], 9 = tp[n], 10 = a2y[l]
-      for (uint32_t i = 0; i < n + l; ++i) {   // linear.rs:97: c = commit(x; r)
-        pb.begin_row(6, i, MODE_STORE);
-        key_row(c, pb, +1, i, 2, 0);
-        if (i >= n) pb.add(+1, 0, i - n);
-      }
-      for (uint32_t i = 0; i < n + l; ++i) {   // linear.rs:96: cp = commit(g*x; rp)
-        pb.begin_row(7, i, MODE_STORE);
-        key_row(c, pb, +1, i, 3, 0);
-        if (i >= n) pb.add(+1, 1, i - n);
-      }
-      for (uint32_t i = 0; i < n; ++i) {       // linear.rs:118
-        pb.begin_row(8, i, MODE_STORE);
-        key_row(c, pb, +1, i, 4, 0);
-      }
-      for (uint32_t i = 0; i < l; ++i) {       // a2.y, reduced mod q before it meets g (linear.rs:124-127); placed
-        pb.begin_row(10, i, MODE_STORE);       // next to t = a1.y so that the two rows can share the transform of y
-        key_row(c, pb, +1, n + i, 4, 0);
-      }
-      for (uint32_t i = 0; i < n; ++i) {       // linear.rs:121
-        pb.begin_row(9, i, MODE_STORE);
-        key_row(c, pb, +1, i, 5, 0);
-      }
-      if (var & 1) {   // fused check_commit_constraint: r -> bit 0, rp -> bit 1 of ok (the two commits of linear.rs:96-97)
-        if (!mark_checks(pb, 2, k) || !mark_checks(pb, 3, k, true)) return RZK_E_UNSUPPORTED;
-      }
-      break;
-    case PG_LIN_U:   // ops: 0 = a2y[l], 1 = g, 2 = yp[k], 3 = u[l] : u = a2y(.)g - a2.yp (linear.rs:124-129)
-      for (uint32_t i = 0; i < l; ++i) {
-        pb.begin_row(3, i, MODE_STORE);
-        pb.scalar_term(dk, +1, 1, 0, 0, i);
-        key_row(c, pb, -1, n + i, 2, 0);
-      }
-      break;
-    case PG_LIN_V1:
-      // ops: 0 = z[k], 1 = zp[k], 2 = t[n], 3 = tp[n], 4 = c[n+l], 5 = cp[n+l], 6 = d, 7 = g,
-      //      8 = w1[l] (a2.z), 9 = w2[l] (c2(.)g - c2p)
-      for (uint32_t i = 0; i < n; ++i) {       // linear.rs:225-229
-        pb.begin_row(0, 0, MODE_ZERO);
-        key_row(c, pb, +1, i, 0, 0);
-        pb.challenge_term(rot, -1, 6, 4, i);
-        pb.add(-1, 2, i);
-      }
-      for (uint32_t i = 0; i < n; ++i) {       // linear.rs:231-235
-        pb.begin_row(0, 0, MODE_ZERO);
-        key_row(c, pb, +1, i, 1, 0);
-        pb.challenge_term(rot, -1, 6, 5, i);
-        pb.add(-1, 3, i);
-      }
-      for (uint32_t i = 0; i < l; ++i) {       // a2.z (linear.rs:238-241), reduced before (.)g
-        pb.begin_row(8, i, MODE_STORE);
-        key_row(c, pb, +1, n + i, 0, 0);
-      }
-      for (uint32_t i = 0; i < l; ++i) {       // c2(.)g - c2p (linear.rs:243-246); c2 = last n rows of c
-        pb.begin_row(9, i, MODE_STORE);
-        pb.scalar_term(dk, +1, 7, 0, 4, l + i);
-        pb.add(-1, 5, l + i);
-      }
-      if (var & 1) {   // fused check_verify_constraint(z), (zp)  (linear.rs:218-223)
-        if (!mark_checks(pb, 0, k) || !mark_checks(pb, 1, k)) return RZK_E_UNSUPPORTED;
-      }
-      break;
-    case PG_LIN_V1B:
-      // ops: 0 = z[k], 1 = zp[k], 2 = t[n], 3 = tp[n], 4 = c[n+l], 5 = cp[n+l], 6 = d, 7 = e[l], 8 = ep[l]
-      // linear.rs:237-249 reads (a2.z)(.)g - a2.z' == (c2(.)g - c2')(.)d + u; in a commutative ring that is
-      // g(.)(a2.z - c2(.)d) - (a2.z' - c2'(.)d) - u == 0: one product with g instead of two, and none in this program
-      for (uint32_t i = 0; i < n; ++i) {       // linear.rs:225-229
-        pb.begin_row(0, 0, MODE_ZERO);
-        key_row(c, pb, +1, i, 0, 0);
-        pb.challenge_term(rot, -1, 6, 4, i);
-        pb.add(-1, 2, i);
-      }
-      for (uint32_t i = 0; i < n; ++i) {       // linear.rs:231-235
-        pb.begin_row(0, 0, MODE_ZERO);
-        key_row(c, pb, +1, i, 1, 0);
-        pb.challenge_term(rot, -1, 6, 5, i);
-        pb.add(-1, 3, i);
-      }
-      for (uint32_t i = 0; i < l; ++i) {       // e = a2.z - c2(.)d ; c2 = last n rows of c
-        pb.begin_row(7, i, MODE_STORE);
-        key_row(c, pb, +1, n + i, 0, 0);
-        pb.challenge_term(rot, -1, 6, 4, l + i);
-      }
-      for (uint32_t i = 0; i < l; ++i) {       // e' = a2.z' - c2'(.)d
-        pb.begin_row(8, i, MODE_STORE);
-        key_row(c, pb, +1, n + i, 1, 0);
-        pb.challenge_term(rot, -1, 6, 5, l + i);
-      }
-      if (var & 1) {   // fused check_verify_constraint(z), (zp)  (linear.rs:218-223)
-        if (!mark_checks(pb, 0, k) || !mark_checks(pb, 1, k)) return RZK_E_UNSUPPORTED;
-      }
-      break;
-    case PG_LIN_V2B:   // ops: 0 = e[l], 1 = ep[l], 2 = g, 3 = u[l] : g(.)e - e' - u == 0
-      for (uint32_t i = 0; i < l; ++i) {
-        pb.begin_row(0, 0, MODE_ZERO);
-        pb.scalar_term(dk, +1, 2, 0, 0, i);
-        pb.add(-1, 1, i);
-        pb.add(-1, 3, i);
-      }
-      break;
-    case PG_LIN_V2:
-      // ops: 0 = w1[l], 1 = w2[l], 2 = g, 3 = d, 4 = zp[k], 5 = u[l]
-      // w1(.)g - a2.zp - w2(.)d - u == 0   (linear.rs:237-249)
-      for (uint32_t i = 0; i < l; ++i) {
-        pb.begin_row(0, 0, MODE_ZERO);
-        pb.scalar_term(dk, +1, 2, 0, 0, i);
-        key_row(c, pb, -1, n + i, 4, 0);
-        pb.challenge_term(rot, -1, 3, 1, i);
-        pb.add(-1, 5, i);
-      }
-      break;
-    case PG_SUM_XP:   // ops: 0 = xs[V*l], 1 = gs[V], 2 = xp[l] : xp = sum_i x_i (.) g_i (sum.rs:107-115)
-      for (uint32_t j = 0; j < l; ++j) {
-        pb.begin_row(2, j, MODE_STORE);
-        for (uint32_t i = 0; i < var; ++i) pb.scalar_term(dk, +1, 1, i, 0, i * l + j);
-      }
-      break;
-    case PG_SUM_U:    // ops: 0 = w[V*l] (a2.y_i), 1 = gs[V], 2 = yp[k], 3 = u[l]   (sum.rs:154-160)
-      for (uint32_t j = 0; j < l; ++j) {
-        pb.begin_row(3, j, MODE_STORE);
-        for (uint32_t i = 0; i < var; ++i) pb.scalar_term(dk, +1, 1, i, 0, i * l + j);
-        key_row(c, pb, -1, n + j, 2, 0);
-      }
-      break;
-    case PG_SUM_W2:   // ops: 0 = cs[V*(n+l)], 1 = gs[V], 2 = cp[n+l], 3 = w2[l] : sum_i c2_i(.)g_i - c2p (sum.rs:309-316)
-      for (uint32_t j = 0; j < l; ++j) {
-        pb.begin_row(3, j, MODE_STORE);
-        for (uint32_t i = 0; i < var; ++i) pb.scalar_term(dk, +1, 1, i, 0, i * (n + l) + l + j);
-        pb.add(-1, 2, l + j);
-      }
-      break;
-    case PG_SUM_V3:   // ops: 0 = w1[V*l] (a2.z_i), 1 = gs[V], 2 = zp[k], 3 = w2[l], 4 = d, 5 = u[l]   (sum.rs:301-319)
-      for (uint32_t j = 0; j < l; ++j) {
-        pb.begin_row(0, 0, MODE_ZERO);
-        for (uint32_t i = 0; i < var; ++i) pb.scalar_term(dk, +1, 1, i, 0, i * l + j);
-        key_row(c, pb, -1, n + j, 2, 0);
-        pb.challenge_term(rot, -1, 4, 3, j);
-        pb.add(-1, 5, j);
-      }
-      break;
-    case PG_SUM_D: {  // ops: 0 = vs[V*k] (ys or zs), 1 = gs[V], 2 = vp[k] (yp or zp), 3 = D[k]
-      // a2 is linear and the ring commutative: sum_i g_i (.) (a2.v_i) - a2.v' = a2.(sum_i g_i (.) v_i - v')
-      // (sum.rs:154-160 and 301-308); only the columns a2 has entries in are formed
-      for (uint32_t col = 0; col < k; ++col) {
-        bool used = false;
-        for (uint32_t j = 0; j < l; ++j) used = used || c->key_class[(n + j) * k + col] != KC_ZERO;
-        if (!used) continue;
-        pb.begin_row(3, col, MODE_STORE);
-        for (uint32_t i = 0; i < var; ++i) pb.scalar_term(dk, +1, 1, i, 0, i * k + col, oi);
-        pb.add(-1, 2, col);
-      }
-      break;
-    }
-    case PG_SUM_V4:   // ops: 0 = D[k], 1 = w2[l], 2 = d, 3 = u[l] : a2.D - w2(.)d - u == 0   (sum.rs:301-319)
-      for (uint32_t j = 0; j < l; ++j) {
-        pb.begin_row(0, 0, MODE_ZERO);
-        key_row(c, pb, +1, n + j, 0, 0);
-        pb.challenge_term(rot, -1, 2, 1, j);
-        pb.add(-1, 3, j);
-      }
-      break;
-    default: return RZK_E_ARG;
-  }
+template <class T>
+int upload(rzk_ctx* c, const T* host, T** dev) {
+  HIPCHK(c, hipMalloc((void**)dev, sizeof(T)));
+  HIPCHK(c, hipMemcpyAsync(*dev, host, sizeof(T), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));   // the host table goes away with its plan; one-off per (program, shape)
   return RZK_OK;
+}
+
+void free_program(DevProg& dp) {
+  if (dp.d) (void)hipFree(dp.d);
+  if (dp.d_slots) (void)hipFree(dp.d_slots);
+  if (dp.d_blocks) (void)hipFree(dp.d_blocks);
+  if (dp.d_wp) (void)hipFree(dp.d_wp);
 }
 
 int get_program(rzk_ctx* c, int id, uint32_t var, DevProg& out) {
@@ -638,256 +198,29 @@ int get_program(rzk_ctx* c, int id, uint32_t var, DevProg& out) {
     out = it->second;
     return RZK_OK;
   }
-  PB pb;
-  int rc = build_program(c, id, var, pb);
-  if (rc == RZK_E_UNSUPPORTED) return rc;   // a fused-check variant that cannot cover every polynomial
+  std::unique_ptr<Plan> plan(new Plan);
+  int rc = plan_program(plan_env(c), id, var, *plan);
+  // (without a message: a fused-check variant that cannot cover every polynomial; the caller keeps the separate norm kernel)
+  if (rc == RZK_E_UNSUPPORTED) return plan->overflow ? fail(c, rc, "shape exceeds row-program capacity") : rc;
   if (rc != RZK_OK) return fail(c, rc, "unknown program");
-  if (pb.overflow) return fail(c, RZK_E_UNSUPPORTED, "shape exceeds row-program capacity");
   DevProg dp;
-  // Row groups: consecutive rows that are key products over the same operand list are evaluated by one
-  // wavefront (row_group_kernel).  Used when it at least halves the number of tasks.
-  pb.p.ngroups = 0;
-  if (shift_ok(c) && pb.sparse_ops && pb.p.nterms > 0) {
-    bool all = true;
-    for (uint32_t t = 0; t < pb.p.nterms; ++t) {
-      const Term& tm = pb.p.terms[t];
-      all = all && tm.kind == TERM_VEC && ((pb.sparse_ops >> tm.a_op) & 1u);   // no fused checks either
-    }
-    dp.shift = all;
-  }
-  for (uint32_t r = 0; r < pb.p.nrows; ++r) dp.has_shift = dp.has_shift || pb.p.rows[r].nshift > 0;
-  for (uint32_t t = 0; t < pb.p.nterms; ++t) dp.has_dd = dp.has_dd || (pb.p.terms[t].kind & TERM_KIND_MASK) == TERM_DD;
-  for (uint32_t t = 0; t < pb.p.nterms; ++t)
-    dp.has_dkey = dp.has_dkey || (pb.p.terms[t].kind & TERM_KIND_MASK) == TERM_DKEY || (pb.p.terms[t].kind & TERM_KIND_MASK) == TERM_DD;
-  dp.two_bit = pb.two_bit;
-  // Row blocks: key-only programs whose rows share operands; consecutive rows are packed into blocks of at
-  // most kBlockMaxRows rows and kBlockMaxSlots distinct operands.  Used when every operand is needed by at
-  // least two terms on average (otherwise nothing is shared and the plain row kernel is as good).
-  if (!c->small && c->logn >= 10 && c->logn >= c->block_min_logn && !dp.shift && !dp.has_shift && !dp.two_bit &&
-      !dp.has_dkey && pb.p.nterms > 0) {
-    bool key_only = true;
-    for (uint32_t t = 0; t < pb.p.nterms; ++t) key_only = key_only && (pb.p.terms[t].kind & TERM_KIND_MASK) == TERM_KEY;
-    std::vector<BlockPlan> planv(1);
-    BlockPlan& bp = planv[0];
-    std::memset(&bp, 0, sizeof(bp));
-    bool fits = key_only;
-    std::map<std::pair<uint32_t, uint32_t>, uint32_t> cur;   // (op, off) -> slot of the open block
-    auto open_block = [&](uint32_t row) {
-      bp.blk[bp.nblocks].row0 = (uint16_t)row;
-      bp.blk[bp.nblocks].nrows = 0;
-      bp.blk[bp.nblocks].slot0 = (uint16_t)bp.nslots_total;
-      bp.blk[bp.nblocks].nslots = 0;
-      cur.clear();
-    };
-    if (fits) open_block(0);
-    for (uint32_t r = 0; fits && r < pb.p.nrows; ++r) {
-      const Row& row = pb.p.rows[r];
-      std::map<std::pair<uint32_t, uint32_t>, uint32_t> add;   // operands this row brings that the block lacks
-      for (uint32_t t = 0; t < row.nterms; ++t) {
-        const Term& tm = pb.p.terms[row.term0 + t];
-        if (!cur.count({tm.b_op, tm.b_off})) add[{tm.b_op, tm.b_off}] = 0;
-      }
-      BlockDesc* bd = &bp.blk[bp.nblocks];
-      if (bd->nrows == kBlockMaxRows || bd->nslots + add.size() > (size_t)kBlockMaxSlots) {
-        if (bd->nrows == 0) { fits = false; break; }   // a single row needs more operands than LDS holds
-        ++bp.nblocks;
-        if (bp.nblocks >= (uint32_t)kMaxRows) { fits = false; break; }
-        open_block(r);
-        bd = &bp.blk[bp.nblocks];
-        add.clear();
-        for (uint32_t t = 0; t < row.nterms; ++t) add[{pb.p.terms[row.term0 + t].b_op, pb.p.terms[row.term0 + t].b_off}] = 0;
-        if (add.size() > (size_t)kBlockMaxSlots) { fits = false; break; }
-      }
-      for (auto& kv : add) {
-        if (bp.nslots_total >= (uint32_t)kMaxSlots) { fits = false; break; }
-        const uint32_t sidx = bd->nslots++;
-        cur[kv.first] = sidx;
-        bp.slot_op[bp.nslots_total] = (uint16_t)kv.first.first;
-        bp.slot_off[bp.nslots_total] = (uint16_t)kv.first.second;
-        ++bp.nslots_total;
-      }
-      for (uint32_t t = 0; fits && t < row.nterms; ++t) {
-        const Term& tm = pb.p.terms[row.term0 + t];
-        const uint32_t sidx = cur[{tm.b_op, tm.b_off}];
-        bp.term_slot[row.term0 + t] = (uint16_t)sidx;
-        if (tm.kind & TERM_CHECK) bp.slot_check[bd->slot0 + sidx] = 1;
-      }
-      bd->nrows++;
-    }
-    if (fits) {
-      ++bp.nblocks;
-      if (bp.nslots_total > 0 && (double)pb.p.nterms / bp.nslots_total >= 2.0) {
-        HIPCHK(c, hipMalloc((void**)&dp.d_blocks, sizeof(BlockPlan)));
-        HIPCHK(c, hipMemcpyAsync(dp.d_blocks, &bp, sizeof(BlockPlan), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        dp.nblocks = bp.nblocks;
-      }
-    }
-  }
-  if (!c->small && c->use_groups && !dp.shift && !dp.two_bit && !dp.nblocks && !dp.has_dkey) {
-    bool key_only = pb.p.nterms > 0;
-    for (uint32_t t = 0; t < pb.p.nterms; ++t) key_only = key_only && (pb.p.terms[t].kind & TERM_KIND_MASK) == TERM_KEY;
-    if (key_only) {
-      const uint32_t gmax = (uint32_t)c->group_max;
-      uint32_t ng = 0;
-      for (uint32_t r = 0; r < pb.p.nrows;) {
-        uint32_t cnt = 1;
-        const Row& r0 = pb.p.rows[r];
-        while (cnt < gmax && r + cnt < pb.p.nrows) {
-          const Row& rr = pb.p.rows[r + cnt];
-          bool same = rr.nterms == r0.nterms && r0.nterms > 0;
-          for (uint32_t t = 0; same && t < r0.nterms; ++t) {
-            const Term& a = pb.p.terms[r0.term0 + t];
-            const Term& b2 = pb.p.terms[rr.term0 + t];
-            same = a.b_op == b2.b_op && a.b_off == b2.b_off;
-          }
-          if (!same) break;
-          ++cnt;
-        }
-        pb.p.groups[ng].row0 = (uint16_t)r;
-        pb.p.groups[ng].count = (uint16_t)cnt;
-        ++ng;
-        r += cnt;
-      }
-      if (ng * 2 <= pb.p.nrows) {
-        pb.p.ngroups = ng;
-        dp.ngroups = ng;
-      }
-    }
-  }
-  HIPCHK(c, hipMalloc((void**)&dp.d, sizeof(Program)));
-  HIPCHK(c, hipMemcpyAsync(dp.d, &pb.p, sizeof(Program), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));   // pb.p is a stack object; one-off per (program, shape)
-  dp.nrows = pb.p.nrows;
-  if (!c->small) {
-    // Wave program of unit_kernel: one unit per row; two consecutive rows become a PAIR when the second has exactly
-    // one key product and its operand is the last operand of the first (c0 / c1 of a commitment share r_{k-1};
-    // t = a1.y and a2.y share y_{k-1}): that transform is then computed once for both.
-    std::vector<WaveProgram> wpv(1);
-    WaveProgram& wp = wpv[0];
-    std::memset(&wp, 0, sizeof(wp));
-    auto key_only = [&](const Row& rr) {
-      for (uint32_t t = 0; t < rr.nterms; ++t)
-        if ((pb.p.terms[rr.term0 + t].kind & TERM_KIND_MASK) != TERM_KEY) return false;
-      return true;
-    };
-    for (uint32_t r = 0; r < pb.p.nrows;) {
-      const Row& ra = pb.p.rows[r];
-      Unit& un = wp.units[wp.nunits++];
-      un.rowA = (uint16_t)r;
-      un.rowB = kNoRow;
-      un.item0 = (uint16_t)wp.nitems;
-      un.nitems = ra.nterms;
-      for (uint32_t t = 0; t < ra.nterms; ++t) {
-        const Term& tm = pb.p.terms[ra.term0 + t];
-        Item& im = wp.items[wp.nitems++];
-        im.kind = (tm.kind & TERM_KIND_MASK) == TERM_VEC ? ITEM_VEC : ITEM_KEY;
-        im.flags = tm.kind & (TERM_CHECK | TERM_CHECK2);
-        im.b_op = tm.b_op;
-        im.b_off = tm.b_off;
-        im.a_op = tm.a_op;
-        im.a_off = tm.a_off;
-        im.keyA = im.kind == ITEM_KEY ? tm.a_off : 0;
-        im.keyB = kNoKey;
-        im.signA = tm.sign;
-        im.signB = 0;
-      }
-      uint32_t step = 1;
-      if (c->use_pairs && r + 1 < pb.p.nrows && ra.nterms >= 1 && ra.nshift == 0 && key_only(ra)) {
-        const Row& rb = pb.p.rows[r + 1];
-        if (rb.nterms == 1 && rb.nshift == 0 && key_only(rb)) {
-          const Term& tb = pb.p.terms[rb.term0];
-          const Term& ta = pb.p.terms[ra.term0 + ra.nterms - 1];
-          if (tb.b_op == ta.b_op && tb.b_off == ta.b_off) {
-            Item& im = wp.items[wp.nitems - 1];
-            im.keyB = tb.a_off;
-            im.signB = tb.sign;
-            im.flags |= tb.kind & (TERM_CHECK | TERM_CHECK2);
-            un.rowB = (uint16_t)(r + 1);
-            step = 2;
-          }
-        }
-      }
-      r += step;
-    }
-    HIPCHK(c, hipMalloc((void**)&dp.d_wp, sizeof(WaveProgram)));
-    HIPCHK(c, hipMemcpyAsync(dp.d_wp, &wp, sizeof(WaveProgram), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    dp.nunits = wp.nunits;
-    for (uint32_t u = 0; u < wp.nunits; ++u)
-      dp.work += (wp.units[u].nitems ? wp.units[u].nitems : 1u) + (wp.units[u].rowB != kNoRow ? 2u : 1u);
-  }
-  for (uint32_t t = 0; t < pb.p.nterms; ++t) dp.has_vec = dp.has_vec || (pb.p.terms[t].kind & TERM_KIND_MASK) == TERM_VEC;
-  // distinct operands of the product terms ("slots"); when rows share them often enough, transform each
-  // once per proof (shared-operand path) instead of once per row
-  if (!c->small && c->slot_share_min > 0 && pb.p.nterms > 0 && dp.ngroups == 0 && !dp.shift && !dp.has_shift &&
-      !dp.two_bit && !dp.nblocks && !dp.has_dkey) {
-    std::vector<SlotTable> stv(1);
-    SlotTable& st = stv[0];
-    std::memset(&st, 0, sizeof(st));
-    std::map<std::pair<uint32_t, uint32_t>, uint32_t> index;
-    bool fits = true;
-    uint32_t transforms = 0;
-    auto slot_of = [&](uint8_t op, uint16_t off) -> uint32_t {
-      auto it = index.find({op, off});
-      if (it != index.end()) return it->second;
-      if (st.nslots >= (uint32_t)kMaxSlots) { fits = false; return 0; }
-      const uint32_t sidx = st.nslots++;
-      st.op[sidx] = op;
-      st.off[sidx] = off;
-      index[{op, off}] = sidx;
-      return sidx;
-    };
-    for (uint32_t t = 0; t < pb.p.nterms; ++t) {
-      const Term& tm = pb.p.terms[t];
-      const uint32_t sb = slot_of(tm.b_op, tm.b_off);
-      st.term_b[t] = (uint16_t)sb;
-      ++transforms;
-      if (tm.kind & TERM_CHECK) st.check[sb] = 1;
-      if ((tm.kind & TERM_KIND_MASK) == TERM_VEC) {
-        st.term_a[t] = (uint16_t)slot_of(tm.a_op, tm.a_off);
-        ++transforms;
-      }
-    }
-    if (fits && st.nslots > 0 && (double)transforms / st.nslots >= c->slot_share_min) {
-      HIPCHK(c, hipMalloc((void**)&dp.d_slots, sizeof(SlotTable)));
-      HIPCHK(c, hipMemcpyAsync(dp.d_slots, &st, sizeof(SlotTable), hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      dp.nslots = st.nslots;
-      dp.np_store = dp.has_vec ? 3 : 2;
-    }
-  }
-  {
-    std::map<std::pair<uint32_t, uint32_t>, int> seen;
-    auto touch = [&](uint32_t op, uint32_t off) {
-      if (op < (uint32_t)kMaxOperands && !seen.count({op, off})) {
-        seen[{op, off}] = 1;
-        dp.polys_in[op]++;
-      }
-    };
-    for (uint32_t r = 0; r < pb.p.nrows; ++r) {
-      const Row& row = pb.p.rows[r];
-      for (uint32_t t = 0; t < (uint32_t)row.nterms + row.nshift; ++t) {
-        const Term& tm = pb.p.terms[row.term0 + t];
-        touch(tm.b_op, tm.b_off);
-        if ((tm.kind & TERM_KIND_MASK) != TERM_KEY) touch(tm.a_op, tm.a_off);
-      }
-      for (uint32_t a = 0; a < row.nadds; ++a) touch(pb.p.adds[row.add0 + a].op & ADD_OP_MASK, pb.p.adds[row.add0 + a].off);
-      if (row.mode == MODE_STORE) dp.polys_out++;
-    }
+  static_cast<PlanFacts&>(dp) = plan->f;
+  if (plan->use_blocks) rc = upload(c, &plan->blocks, &dp.d_blocks);
+  if (rc == RZK_OK) rc = upload(c, &plan->prog, &dp.d);
+  if (rc == RZK_OK && plan->use_wave) rc = upload(c, &plan->wave, &dp.d_wp);
+  if (rc == RZK_OK && plan->use_slots) rc = upload(c, &plan->slots, &dp.d_slots);
+  if (rc != RZK_OK) {
+    free_program(dp);
+    return rc;
   }
   c->progs[{id, var}] = dp;
   out = dp;
   return RZK_OK;
 }
 
+
 void drop_programs(rzk_ctx* c) {
-  for (auto& kv : c->progs) {
-    if (kv.second.d) (void)hipFree(kv.second.d);
-    if (kv.second.d_slots) (void)hipFree(kv.second.d_slots);
-    if (kv.second.d_blocks) (void)hipFree(kv.second.d_blocks);
-    if (kv.second.d_wp) (void)hipFree(kv.second.d_wp);
-  }
+  for (auto& kv : c->progs) free_program(kv.second);
   c->progs.clear();
 }
 
@@ -901,18 +234,6 @@ struct OpSpec {
 // sticky: a non-canonical input coefficient fails the CALL (prover-side / Mat-level entry points); verifier-side
 // programs pass false — there the offending proof's verdict flag is cleared and the call succeeds.
 int check_launch(rzk_ctx* c, int lrc, const char* what);
-
-// Which launcher evaluates a row program: decided here, once, for the flag preset and for the launch.
-enum class Path { Small, Shift, Blocks, Groups, Slots, Rows, Units };
-Path path_of(const rzk_ctx* c, const DevProg& dp) {
-  if (c->small) return Path::Small;
-  if (dp.shift) return Path::Shift;
-  if (dp.nblocks) return Path::Blocks;
-  if (dp.ngroups) return Path::Groups;
-  if (dp.d_slots) return Path::Slots;
-  if (dp.has_dkey || (dp.has_vec && c->vec_rows)) return Path::Rows;   // row_kernel: vector x vector products, prepared multiplier images
-  return Path::Units;
-}
 
 // Profiling of one launch (rzk_prof_*): prof_begin records the start event and returns a launch configuration whose
 // `launched` points at the slot's kernel name, which the launcher fills in; prof_end records the stop event and only
@@ -960,7 +281,7 @@ int run_program(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSpec>& spe
   // fills the chip's wave slots; one unit per task below that
   uint32_t upt = batch >= (uint64_t)c->num_cus * 16 ? dp.nunits : 1;
   if (c->units_per_task) upt = c->units_per_task;   // RZK_UPT (tuning)
-  const Path path = path_of(c, dp);
+  const Path path = path_of(dp, c->small, c->vec_rows);
   const bool preset_in_kernel = preset_value && flags && c->preset_in_kernel && path == Path::Units && upt >= dp.nunits && dp.nunits > 0 &&
                                 (group ? group : 1) == 1 && nflags == batch;
   if (preset_value && flags && !preset_in_kernel) {
@@ -1147,14 +468,12 @@ int prepare_oimg(rzk_ctx* c, uint64_t B, uint32_t V, uint32_t uses) {
   c->oimg_state = Operands{};
   c->oimg_producer_op = 0xffu;
   if (!c->use_oimg || !dkey_wanted(c, uses) || c->k > 32u || !sum_uses_d(c, V)) return RZK_OK;
-  const uint32_t n = c->n, k = c->k, l = c->l;
+  const uint32_t k = c->k;
+  const PlanEnv env = plan_env(c);
   uint32_t ncols = 0;
   for (uint32_t col = 0; col < 32u; ++col) c->oimg_state.oimg_col[col] = -1;
-  for (uint32_t col = 0; col < k; ++col) {
-    bool used = false;
-    for (uint32_t j = 0; j < l; ++j) used = used || c->key_class[(n + j) * k + col] != KC_ZERO;
-    if (used) c->oimg_state.oimg_col[col] = (int8_t)ncols++;
-  }
+  for (uint32_t col = 0; col < k; ++col)
+    if (a2_uses_column(env, col)) c->oimg_state.oimg_col[col] = (int8_t)ncols++;
   if (ncols == 0) return RZK_OK;
   const uint64_t slots = B * V * ncols;
   const size_t img_bytes = ((size_t)slots * kKeyImages * c->N * sizeof(uint32_t) + 255) & ~(size_t)255;

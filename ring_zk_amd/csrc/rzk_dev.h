@@ -1,4 +1,4 @@
-// rzk_dev.h — structures shared by the kernels (rzk_kernels.hip and the family headers it includes) and the C-ABI host code (rzk_api.cpp).
+// rzk_dev.h — structures shared by the kernels (rzk_kernels.hip and the family headers it includes), the host planner (rzk_plan.h) and the C-ABI host code (rzk_api.cpp).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -34,7 +34,7 @@ struct DevTables {
 // Program tables (rows, terms, additions, units, items, plans) are written by the host before a launch and never by
 // a kernel, so the kernels may read them through the constant address space: the compiler then uses scalar loads
 // (one s_load per record, no vector-memory latency in the control flow).  The records are 4 / 8 / 16 bytes, naturally
-// aligned inside their tables (static_asserts in rzk_api.cpp).
+// aligned inside their tables (static_asserts in rzk_plan.h).
 #if defined(__HIPCC__)
 template <class Tp>
 __device__ __forceinline__ Tp table_load(const Tp* p) {

@@ -195,7 +195,7 @@ __device__ __forceinline__ void load_lift(uint32_t* x, const int64_t* __restrict
 // at once into the running Garner state (rzk_core.h, crt_fold*), so no state occupies registers during the transforms.
 // The operands' norms are measured while they are loaded for the first prime, which fixes how many primes (1..3) the
 // exact result needs; the same pass proves that every coefficient is canonical.  Which kernel runs a program is
-// decided once per (program, shape) in rzk_api.cpp:
+// decided once per (program, shape) by the planner (rzk_plan.h, plan_program and path_of):
 //
 //   unit_kernel       key-product programs (the default): one wavefront per proof walks the program's units — single
 //                     rows, or pairs of rows that share their last operand; sums parked in LDS, Garner words in
