@@ -50,9 +50,9 @@ extern "C" {
 typedef struct rzk_ctx rzk_ctx;
 
 /* Version of this C ABI: bumped whenever an existing signature changes (rzk_wire_mat_decode gained `q` in 2,
- * version 3 added the entry points marked "v3", version 4 those marked "v4").  A binding checks rzk_abi_version() == RZK_ABI_VERSION after loading
+ * version 3 added the entry points marked "v3", version 4 those marked "v4", version 5 those marked "v5").  A binding checks rzk_abi_version() == RZK_ABI_VERSION after loading
  * the library, so that a stale or variant .so fails at load time instead of reading shifted arguments. */
-#define RZK_ABI_VERSION 4u
+#define RZK_ABI_VERSION 5u
 uint32_t rzk_abi_version(void);
 
 /* Which block of the commitment key a matrix-vector product uses (src/commit.rs:19-25). */
@@ -349,6 +349,35 @@ int rzk_wire_encode_batch(rzk_ctx* ctx, int kind, uint32_t V, uint32_t coef_byte
                           uint8_t* bytes, uint64_t cap, uint64_t* offsets, size_t B);
 int rzk_wire_encode_batch_dev(rzk_ctx* ctx, int kind, uint32_t V, uint32_t coef_bytes, const int64_t* const* fields,
                               uint8_t* bytes, uint64_t cap, uint64_t* offsets, size_t B);
+
+/* ---- Fiat-Shamir: non-interactive challenges (v5) -----------------------------------------------------------------------
+ * The reference's protocols are interactive (the verifier draws d: open.rs:138-145, linear.rs:182-189, sum.rs:226-233).
+ * Here d is derived from the prover's first message by the "FS1" transcript hash (every byte of the
+ * format is restated in ring_zk_amd/csrc/rzk_keccak.h), so that a proof (commitment, response) can be stored, forwarded
+ * and batch-verified: the verifier recomputes d from the commitment message it received.
+ *   LEAF = min(N, 256), C = N / LEAF; a coefficient is hashed as the little-endian int32 of its centred value
+ *   leaf(p,c)  = SHAKE256("RZKFS1\0L" | le32(p) | le32(c) | coefficients c*LEAF .. (c+1)*LEAF-1 of polynomial p)[0:32]
+ *   keydigest  = SHAKE256("RZKFS1\0K" | le64(q) | le32(N) | le32(n) | le32(k) | le32(l) | le32(kappa) | le32(0) | le64(b)
+ *                         | leaf(p,c) of the (n+l)*k key polynomials row-major)[0:32]
+ *   stream     = SHAKE256("RZKFS1\0R" | le32(kind) | le32(V) | keydigest | aux[32] | leaf(p,c) of the message polynomials)
+ * with the message polynomials in the order of the RZK_MSG_* table above (fields in declaration order, slabs row-major)
+ * and V = 0 for the kinds without summands.  stream[0:32] is the transcript digest; d has exactly kappa coefficients
+ * +-1 (uniform over challenge_space.rs:10-33), sampled from stream[32:].
+ * rzk_fs_key_digest: keydigest of the loaded key (computed on the device by rzk_key_load[_dev] / rzk_key_generate);
+ *   RZK_E_STATE without a key.
+ * rzk_fs_challenge_batch: kind is RZK_MSG_OPEN_COMMITMENT, RZK_MSG_LINEAR_COMMITMENT or RZK_MSG_SUM_COMMITMENT
+ *   (RZK_E_ARG otherwise); fields as for the wire codec; aux32: 32 HOST bytes binding the call to a session or
+ *   statement, NULL = zeros; d: [B][N]; digest: [B][32] or NULL; ok: [B] or NULL.  A coefficient outside the centred
+ *   range clears ok[b] of its own proof only, whose d and digest are unspecified; the call succeeds (as in
+ *   rzk_wire_decode_batch).  With ok == NULL there is no per-proof verdict to clear, so such a coefficient is an input
+ *   fault of the call, as in the phase entry points: the host variant returns RZK_E_ARG, the _dev variant raises the
+ *   sticky word that rzk_ctx_check_inputs reports.  It is never hashed as its low 32 bits without a signal.  In
+ *   trusted-producer mode the test is skipped (the caller vouches for the range).  Needs kappa <= N and a loaded key. */
+int rzk_fs_key_digest(rzk_ctx* ctx, uint8_t* out32);
+int rzk_fs_challenge_batch(rzk_ctx* ctx, int kind, uint32_t V, const int64_t* const* fields, const uint8_t* aux32,
+                           int64_t* d, uint8_t* digest, uint8_t* ok, size_t B);
+int rzk_fs_challenge_batch_dev(rzk_ctx* ctx, int kind, uint32_t V, const int64_t* const* fields, const uint8_t* aux32,
+                               int64_t* d, uint8_t* digest, uint8_t* ok, size_t B);
 
 /* HIP-event timing of the last phase call's dominant kernel is exposed through these counters:
  * accumulated microseconds and launch count of the row kernel since the last reset. */

@@ -18,6 +18,7 @@
 #include "../../include/rzk.h"
 #include "rzk_core.h"
 #include "rzk_dev.h"
+#include "rzk_keccak.h"
 #include "rzk_plan.h"
 #include "rzk_tables.h"
 
@@ -95,6 +96,8 @@ struct rzk_ctx {
   std::map<std::pair<int, uint32_t>, DevProg> progs;
   Arena ws, stage, ws_slots;
   Arena ws_wire;                       // message codec: position table (decode) / lengths, positions, sizes (encode)
+  Arena ws_fs;                         // Fiat-Shamir transcript: leaf digests of the call (and the key while it is hashed)
+  uint64_t key_digest[kFsDigestWords] = {};   // FS1 digest of the loaded key and the context's parameters (rzk_fs_key_digest)
   // canonical-input test (rzk_dev.h, Operands::bad): sticky word set by any kernel that loaded a coefficient
   // outside the centred range on behalf of an entry point without per-proof verdicts; read back at every
   // synchronising call (host-pointer variants, rzk_ctx_synchronize, rzk_ctx_check_inputs)
@@ -676,6 +679,7 @@ void rzk_ctx_destroy(rzk_ctx* c) {
   if (c->ws.p) (void)hipFree(c->ws.p);
   if (c->ws_slots.p) (void)hipFree(c->ws_slots.p);
   if (c->ws_wire.p) (void)hipFree(c->ws_wire.p);
+  if (c->ws_fs.p) (void)hipFree(c->ws_fs.p);
   if (c->ws_dkey.p) (void)hipFree(c->ws_dkey.p);
   if (c->ws_oimg.p) (void)hipFree(c->ws_oimg.p);
   if (c->stage.p) (void)hipFree(c->stage.p);
@@ -730,7 +734,10 @@ uint64_t rzk_verify_bound(const rzk_ctx* c) { return c ? c->verify_bound : 0; }
 // =================================================================================================
 // key
 // =================================================================================================
-static int key_load_impl(rzk_ctx* c, const int64_t* a_host) {
+static int fs_key_digest_dev(rzk_ctx* c, const int64_t* a_host, const int64_t* a_dev);
+
+// a_dev: the same key on the device when the caller has it there (rzk_key_load_dev), else NULL
+static int key_load_impl(rzk_ctx* c, const int64_t* a_host, const int64_t* a_dev = nullptr) {
   const uint32_t N = c->N, rows = c->n + c->l, k = c->k;
   const size_t total = (size_t)rows * k;
   const int64_t half = (c->q - 1) / 2;
@@ -792,7 +799,49 @@ static int key_load_impl(rzk_ctx* c, const int64_t* a_host) {
     if (rc != RZK_OK) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));   // `general` / `kinf` are host temporaries
   }
+  c->key_loaded = false;   // until the digest of the new key is in place
+  int frc = fs_key_digest_dev(c, a_host, a_dev);
+  if (frc != RZK_OK) return frc;
   c->key_loaded = true;
+  return RZK_OK;
+}
+
+// FS1 key digest (rzk_keccak.h): leaf digests of the (n+l)*k key polynomials, then one root lane over the parameter
+// header and those digests.  Runs once per key load, on the coefficients the load has at hand.
+static int fs_key_digest_dev(rzk_ctx* c, const int64_t* a_host, const int64_t* a_dev) {
+  const uint32_t kpolys = (c->n + c->l) * c->k;
+  const uint32_t leaves = kpolys * (c->N / fs_leaf_len(c->N));
+  const size_t dig_b = ((size_t)leaves * kFsDigestWords * sizeof(uint64_t) + 255) & ~size_t(255);
+  const size_t key_b = a_dev ? 0 : (size_t)kpolys * c->N * sizeof(int64_t);
+  int rc = arena_reserve(c, c->ws_fs, dig_b + 256 + key_b);
+  if (rc != RZK_OK) return rc;
+  uint64_t* dig = (uint64_t*)c->ws_fs.p;
+  uint8_t* out = (uint8_t*)c->ws_fs.p + dig_b;
+  if (!a_dev) {
+    int64_t* stage = (int64_t*)((char*)c->ws_fs.p + dig_b + 256);
+    HIPCHK(c, hipMemcpyAsync(stage, a_host, key_b, hipMemcpyHostToDevice, c->stream));
+    a_dev = stage;
+  }
+  FsMsg m{};
+  m.nfields = 1;
+  m.N = c->N;
+  m.polys = kpolys;
+  m.first[1] = kpolys;
+  m.ptr[0] = a_dev;
+  const LaunchCfg cfg = cfg_of(c);
+  // (the host loop of the load has range-tested every coefficient)
+  rc = check_launch(c, launch_fs_leaves(cfg, m, (c->q - 1) / 2, 0, dig, nullptr, nullptr, 1), "key leaf hash");
+  if (rc != RZK_OK) return rc;
+  FsRoot r{};
+  fs_key_header(c->q, c->N, c->n, c->k, c->l, c->kappa, c->b, r.hdr);
+  r.nhdr = kFsKeyHeaderWords;
+  r.leaves = leaves;
+  r.N = c->N;
+  r.kappa = c->kappa;
+  rc = check_launch(c, launch_fs_roots(cfg, r, dig, nullptr, out, 1), "key root hash");
+  if (rc != RZK_OK) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->key_digest, out, sizeof c->key_digest, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return RZK_OK;
 }
 
@@ -846,7 +895,7 @@ int rzk_key_load_dev(rzk_ctx* c, const int64_t* a_dev) {
   std::vector<int64_t> h(total);
   HIPCHK(c, hipMemcpyAsync(h.data(), a_dev, total * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  return key_load_impl(c, h.data());
+  return key_load_impl(c, h.data(), a_dev);
 }
 
 // =================================================================================================
@@ -1799,6 +1848,97 @@ int rzk_wire_encode_batch(rzk_ctx* c, int kind, uint32_t V, uint32_t coef_bytes,
   (void)take_input_error(c);
   c->err = keep;
   return rc;
+}
+
+// =================================================================================================
+// v5: Fiat-Shamir challenges from the FS1 transcript (rzk_fs_dev.hip, rzk_keccak.h)
+// =================================================================================================
+int rzk_fs_key_digest(rzk_ctx* c, uint8_t* out) {
+  if (!c || !out) return RZK_E_ARG;
+  if (!c->key_loaded) return fail(c, RZK_E_STATE, "commitment key not loaded");
+  for (uint32_t w = 0; w < kFsDigestWords; ++w)
+    for (int i = 0; i < 8; ++i) out[8 * w + i] = (uint8_t)(c->key_digest[w] >> (8 * i));   // little-endian on any host
+  return RZK_OK;
+}
+
+namespace {
+bool fs_kind_ok(int kind) {
+  return kind == RZK_MSG_OPEN_COMMITMENT || kind == RZK_MSG_LINEAR_COMMITMENT || kind == RZK_MSG_SUM_COMMITMENT;
+}
+}  // namespace
+
+int rzk_fs_challenge_batch_dev(rzk_ctx* c, int kind, uint32_t V, const int64_t* const* fields, const uint8_t* aux32,
+                               int64_t* d, uint8_t* digest, uint8_t* ok, size_t B) {
+  WireSchema s;
+  if (!c) return RZK_E_ARG;
+  HIPCHK(c, hipSetDevice(c->device));   // the memsets below come before the first cfg_of
+  if (!fs_kind_ok(kind) || !wire_schema_of(c, kind, V, 8, &s)) return fail(c, RZK_E_ARG, "fs challenge: bad kind or V");
+  if (c->kappa > c->N) return fail(c, RZK_E_ARG, "fs challenge: kappa exceeds the ring degree");
+  if (!c->key_loaded) return fail(c, RZK_E_STATE, "commitment key not loaded");
+  if (B == 0) return RZK_OK;
+  WireSlabs sl;
+  if (!d || !wire_slabs(s, kind, fields, false, &sl)) return fail(c, RZK_E_ARG, "fs challenge: NULL pointer");
+  FsMsg m{};
+  m.nfields = s.nfields;
+  m.N = c->N;
+  m.polys = s.polys;
+  for (uint32_t f = 0; f <= s.nfields; ++f) m.first[f] = s.first[f];
+  for (uint32_t f = 0; f < s.nfields; ++f) m.ptr[f] = sl.ptr[f];
+  FsRoot r{};
+  uint64_t aux[kFsDigestWords] = {};
+  if (aux32)
+    for (uint32_t w = 0; w < kFsDigestWords; ++w) aux[w] = shake256_load_le(aux32 + 8 * w, 8);
+  fs_root_header((uint32_t)kind, kind == RZK_MSG_SUM_COMMITMENT ? V : 0, c->key_digest, aux, r.hdr);
+  r.nhdr = kFsRootHeaderWords;
+  r.leaves = s.polys * (c->N / fs_leaf_len(c->N));
+  r.N = c->N;
+  r.kappa = c->kappa;
+  int rc = arena_reserve(c, c->ws_fs, (size_t)B * r.leaves * kFsDigestWords * sizeof(uint64_t));
+  if (rc != RZK_OK) return rc;
+  uint64_t* dig = (uint64_t*)c->ws_fs.p;
+  if (ok) HIPCHK(c, hipMemsetAsync(ok, 1, B, c->stream));
+  HIPCHK(c, hipMemsetAsync(d, 0, polys(c, B), c->stream));   // the sampler writes the kappa non-zero coefficients only
+  const uint64_t hashed = (uint64_t)B * s.polys * c->N * sizeof(int64_t);
+  LaunchCfg cfg;
+  rc = prof_begin(c, hashed, cfg);
+  if (rc != RZK_OK) return rc;
+  rc = check_launch(c, launch_fs_leaves(cfg, m, (c->q - 1) / 2, c->trusted ? 0 : 1, dig, ok, c->d_bad, B),
+                    "fs leaf kernel");
+  if (rc != RZK_OK) return rc;
+  rc = prof_end(c);
+  if (rc != RZK_OK) return rc;
+  rc = prof_begin(c, (uint64_t)B * r.leaves * 32, cfg);
+  if (rc != RZK_OK) return rc;
+  rc = check_launch(c, launch_fs_roots(cfg, r, dig, d, digest, B), "fs root kernel");
+  if (rc != RZK_OK) return rc;
+  return prof_end(c);
+}
+
+int rzk_fs_challenge_batch(rzk_ctx* c, int kind, uint32_t V, const int64_t* const* fields, const uint8_t* aux32,
+                           int64_t* d, uint8_t* digest, uint8_t* ok, size_t B) {
+  WireSchema s;
+  if (!c) return RZK_E_ARG;
+  HIPCHK(c, hipSetDevice(c->device));   // the memsets below come before the first cfg_of
+  if (!fs_kind_ok(kind) || !wire_schema_of(c, kind, V, 8, &s)) return fail(c, RZK_E_ARG, "fs challenge: bad kind or V");
+  if (B == 0) return RZK_OK;
+  WireSlabs sl;
+  if (!d || !wire_slabs(s, kind, fields, false, &sl)) return fail(c, RZK_E_ARG, "fs challenge: NULL pointer");
+  std::vector<HostBuf> bufs = {OUT(d, polys(c, B)), OUT(digest, digest ? B * 32 : 0), OUT(ok, ok ? B : 0)};
+  for (uint32_t f = 0; f < s.nfields; ++f) bufs.push_back(IN(fields[f], wire_field_bytes(c, s, f, B)));
+  HIPCHK(c, hipMemsetAsync(c->d_bad, 0, sizeof(uint32_t), c->stream));
+  int rc = stage_in(c, bufs);
+  if (rc != RZK_OK) return rc;
+  const int64_t* dev_fields[kWireMaxFields] = {};
+  for (uint32_t f = 0; f < s.nfields; ++f) dev_fields[f] = (const int64_t*)bufs[3 + f].dev;
+  rc = rzk_fs_challenge_batch_dev(c, kind, V, dev_fields, aux32, DEV(0, int64_t*), digest ? DEV(1, uint8_t*) : nullptr,
+                                  ok ? DEV(2, uint8_t*) : nullptr, B);
+  if (rc != RZK_OK) {
+    const std::string keep = c->err;
+    (void)take_input_error(c);
+    c->err = keep;
+    return rc;
+  }
+  return stage_out(c, bufs);
 }
 
 }  // extern "C"

@@ -292,6 +292,26 @@ int launch_wire_copy(const LaunchCfg& cfg, const uint8_t* bytes, const uint64_t*
 int launch_wire_encode(const LaunchCfg& cfg, const WireSchema& s, const WireSlabs& sl, int64_t half, uint32_t* lens,
                        uint64_t* rel, uint64_t* msize, uint8_t* bytes, uint64_t* offsets, uint32_t* bad_word,
                        uint64_t B);
+// ---- Fiat-Shamir transcript hash (rzk_fs_dev.hip; format and sponge in rzk_keccak.h) ---------------------------------
+struct FsMsg {   // the polynomials P_0 .. P_{polys-1} of one proof: fields in declaration order, slabs row-major
+  uint32_t nfields, N, polys;
+  uint32_t first[kWireMaxFields + 1];      // first polynomial of every field; first[nfields] = polys
+  const int64_t* ptr[kWireMaxFields];      // slab of every field, [B][rows of the field][N]
+};
+struct FsRoot {
+  uint64_t hdr[10];   // header words in front of the leaf digests (rzk_keccak.h: fs_root_header / fs_key_header)
+  uint32_t nhdr;
+  uint32_t leaves;    // leaf digests per proof
+  uint32_t N, kappa;
+};
+// leaf digests of B proofs: word w of leaf j = p * C + c of proof b at dig[(j * 4 + w) * B + b].  check != 0: every
+// coefficient is range-tested while it is loaded; a violation clears ok[b], or with ok == NULL sets *bad_word (the
+// context's sticky bad-input word), so that a non-canonical coefficient is never hashed silently as its low 32 bits.
+int launch_fs_leaves(const LaunchCfg& cfg, const FsMsg& m, int64_t half, int check, uint64_t* dig, uint8_t* ok,
+                     uint32_t* bad_word, uint64_t B);
+// root of every proof: digest [B][32] (may be NULL) and, with d != NULL, the challenge into d [B][N] (zeroed before)
+int launch_fs_roots(const LaunchCfg& cfg, const FsRoot& r, const uint64_t* dig, int64_t* d, uint8_t* digest,
+                    uint64_t B);
 // small ring degrees (N = 4 .. 256): schoolbook products mod q, same row programs
 int launch_row_program_small(uint32_t N, const LaunchCfg& cfg, const Program* d_prog, uint32_t nrows,
                              const Operands& ops, const uint32_t* d_key_mont, const DevTables* d_T, uint32_t r2q,

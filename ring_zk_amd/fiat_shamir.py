@@ -1,0 +1,144 @@
+"""Non-interactive (Fiat-Shamir) form of the three proofs (include/rzk.h "Fiat-Shamir").
+
+The reference's verifier draws the challenge d itself (open.rs:138-145, linear.rs:182-189, sum.rs:226-233), so it has
+to be online.  Here d is the hash of the prover's commitment message under the FS1 transcript (SHAKE256 on the GPU,
+rzk_fs_challenge_batch[_dev]): a proof is (commitment message, response), and anyone holding the key recomputes d.
+
+  * `challenge` / `key_digest`: the transcript hash itself;
+  * `open_prove` / `open_verify`, `linear_*`, `sum_*`: commit -> challenge -> response, and challenge -> verify; with
+    torch CUDA tensors nothing leaves the device between the phases;
+  * `verify_open_wire`: the same verdict from serialized OpenProofCommitment / OpenProofResponse messages.
+
+`aux` (32 bytes, default zeros) binds the proofs of a call to a session or statement; prover and verifier must agree.
+Like the rest of the package every function takes numpy arrays (host entry points) or torch CUDA tensors (device entry
+points on torch's current stream).
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import numpy as np
+
+from . import wire
+from ._lib import MSG_LINEAR_COMMITMENT, MSG_OPEN_COMMITMENT, MSG_OPEN_RESPONSE, MSG_SUM_COMMITMENT
+
+KINDS = (MSG_OPEN_COMMITMENT, MSG_LINEAR_COMMITMENT, MSG_SUM_COMMITMENT)
+
+
+def key_digest(ctx) -> bytes:
+    """FS1 digest of the loaded key and the context's parameters (rzk_fs_key_digest)."""
+    out = (C.c_uint8 * 32)()
+    ctx._check(ctx._L.rzk_fs_key_digest(ctx._h, out))
+    return bytes(out)
+
+
+def _aux(aux) -> Optional[C.Array]:
+    if aux is None:
+        return None
+    aux = bytes(aux)
+    if len(aux) != 32:
+        raise ValueError("aux must be 32 bytes")
+    return (C.c_uint8 * 32).from_buffer_copy(aux)
+
+
+def challenge(ctx, kind: int, *slabs, V: Optional[int] = None, aux=None):
+    """Field slabs of B commitment messages (declaration order, as for wire.encode_batch) -> (d, digest, ok).
+
+    d [B][N] int64: the challenges; digest [B][32] uint8: the transcript digests; ok [B] uint8: 0 where a coefficient
+    of the proof is not a centred residue mod q (its d and digest are then unspecified)."""
+    if kind not in KINDS:
+        raise ValueError("challenge: kind must be MSG_OPEN_COMMITMENT, MSG_LINEAR_COMMITMENT or MSG_SUM_COMMITMENT")
+    shapes = wire.field_shapes(ctx, kind, V)
+    if len(slabs) != len(shapes):
+        raise ValueError(f"{len(shapes)} field slabs expected, got {len(slabs)}")
+    B = int(slabs[0].shape[0])
+    dev = wire._is_torch(slabs[0])
+    for (name, sh), s in zip(shapes, slabs):
+        if wire._is_torch(s) != dev or tuple(s.shape) != (B,) + sh:
+            raise ValueError(f"field {name}: expected {(B,) + sh}, got {tuple(s.shape)}")
+    if dev:
+        import torch
+
+        slabs = [s.contiguous() for s in slabs]
+        if any(s.dtype != torch.int64 or not s.is_cuda for s in slabs):
+            raise ValueError("device slabs must be int64 CUDA tensors")
+        d = torch.empty((B, ctx.N), dtype=torch.int64, device=slabs[0].device)
+        digest = torch.empty((B, 32), dtype=torch.uint8, device=slabs[0].device)
+        ok = torch.empty(B, dtype=torch.uint8, device=slabs[0].device)
+        ctx._bind_torch_stream()
+        fn = ctx._L.rzk_fs_challenge_batch_dev
+    else:
+        slabs = [np.ascontiguousarray(s, dtype=np.int64) for s in slabs]
+        d = np.empty((B, ctx.N), dtype=np.int64)
+        digest = np.empty((B, 32), dtype=np.uint8)
+        ok = np.empty(B, dtype=np.uint8)
+        fn = ctx._L.rzk_fs_challenge_batch
+    fields = (C.c_void_p * len(slabs))(*[wire._ptr(s).value for s in slabs])
+    ctx._check(fn(ctx._h, kind, V or 0, fields, _aux(aux), wire._ptr(d), wire._ptr(digest), wire._ptr(ok), B))
+    return d, digest, ok
+
+
+def _flag(cond):
+    """boolean array / tensor -> uint8 flags"""
+    if wire._is_torch(cond):
+        import torch
+
+        return cond.to(torch.uint8)
+    return cond.astype(np.uint8)
+
+
+# ---- OpenProof (src/prove/open.rs) -------------------------------------------------------------------------------------
+def open_prove(ctx, x, r, y, aux=None):
+    """commit (open.rs:80-103), d = challenge(c, t), response (open.rs:107-117): (c, t, z, ok); ok[b] = 0 where r fails
+    the commit constraint (the caller resamples) or an output is not canonical."""
+    c, t, ok = ctx.open_commit(x, r, y)
+    d, _, okf = challenge(ctx, MSG_OPEN_COMMITMENT, c, t, aux=aux)
+    z = ctx.open_response(y, r, d)
+    return c, t, z, ok & okf
+
+
+def open_verify(ctx, c, t, z, aux=None):
+    """OpenProofVerifier::verify (open.rs:162-174) with the recomputed challenge."""
+    d, _, okf = challenge(ctx, MSG_OPEN_COMMITMENT, c, t, aux=aux)
+    return ctx.open_verify(z, t, c, d) & okf
+
+
+def verify_open_wire(ctx, commitment_msgs, response_msgs, aux=None, coef_bytes: int = 8):
+    """open_verify from serialized OpenProofCommitment and OpenProofResponse messages (lists of bytes or
+    (data, offsets)): decode, recompute d, verify; a message that does not decode rejects its proof."""
+    c, t, ok1 = wire.decode_batch(ctx, MSG_OPEN_COMMITMENT, *wire._msgs(commitment_msgs), coef_bytes=coef_bytes)
+    (z, ok2) = wire.decode_batch(ctx, MSG_OPEN_RESPONSE, *wire._msgs(response_msgs), coef_bytes=coef_bytes)
+    return open_verify(ctx, c, t, z, aux=aux) & ok1 & ok2
+
+
+# ---- LinearProof (src/prove/linear.rs) ---------------------------------------------------------------------------------
+def linear_prove(ctx, g, x, r, rp, y, yp, aux=None):
+    """(c, cp, t, tp, u, z, zp, ok); ok[b] = 1 iff r and rp both pass the commit constraint."""
+    c, cp, t, tp, u, ok = ctx.linear_commit(g, x, r, rp, y, yp)
+    d, _, okf = challenge(ctx, MSG_LINEAR_COMMITMENT, c, cp, g, t, tp, u, aux=aux)
+    z, zp = ctx.linear_response(y, yp, r, rp, d)
+    return c, cp, t, tp, u, z, zp, _flag(ok == 3) & okf
+
+
+def linear_verify(ctx, c, cp, g, t, tp, u, z, zp, aux=None):
+    """LinearProofVerifier::verify (linear.rs:213-250) with the recomputed challenge."""
+    d, _, okf = challenge(ctx, MSG_LINEAR_COMMITMENT, c, cp, g, t, tp, u, aux=aux)
+    return ctx.linear_verify(z, zp, c, cp, g, t, tp, u, d) & okf
+
+
+# ---- SumProof (src/prove/sum.rs) ---------------------------------------------------------------------------------------
+def sum_prove(ctx, gs, xs, rs, rp, ys, yp, aux=None):
+    """(cs, cp, ts, tp, u, zs, zp, ok) for V = gs.shape[-2] summands per proof."""
+    V = int(gs.shape[-2])
+    cs, cp, ts, tp, u, ok = ctx.sum_commit(gs, xs, rs, rp, ys, yp)
+    d, _, okf = challenge(ctx, MSG_SUM_COMMITMENT, cp, cs, gs, tp, ts, u, V=V, aux=aux)
+    zs, zp = ctx.sum_response(ys, yp, rs, rp, d)
+    return cs, cp, ts, tp, u, zs, zp, ok & okf
+
+
+def sum_verify(ctx, cs, cp, gs, ts, tp, u, zs, zp, aux=None):
+    """SumProofVerifier::verify (sum.rs:257-320) with the recomputed challenge."""
+    V = int(gs.shape[-2])
+    d, _, okf = challenge(ctx, MSG_SUM_COMMITMENT, cp, cs, gs, tp, ts, u, V=V, aux=aux)
+    return ctx.sum_verify(zs, zp, cs, cp, gs, ts, tp, u, d) & okf
