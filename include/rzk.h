@@ -50,9 +50,9 @@ extern "C" {
 typedef struct rzk_ctx rzk_ctx;
 
 /* Version of this C ABI: bumped whenever an existing signature changes (rzk_wire_mat_decode gained `q` in 2,
- * version 3 added the entry points marked "v3", version 4 those marked "v4", version 5 those marked "v5").  A binding checks rzk_abi_version() == RZK_ABI_VERSION after loading
+ * version 3 added the entry points marked "v3", version 4 those marked "v4", version 5 those marked "v5", version 6 those marked "v6").  A binding checks rzk_abi_version() == RZK_ABI_VERSION after loading
  * the library, so that a stale or variant .so fails at load time instead of reading shifted arguments. */
-#define RZK_ABI_VERSION 5u
+#define RZK_ABI_VERSION 6u
 uint32_t rzk_abi_version(void);
 
 /* Which block of the commitment key a matrix-vector product uses (src/commit.rs:19-25). */
@@ -268,6 +268,34 @@ double rzk_bench_ntt_forward_dev(rzk_ctx* ctx, int prime, const uint32_t* in, ui
 int rzk_sample_uniform_dev(rzk_ctx* ctx, uint64_t seed, uint32_t stream, uint64_t bound, int64_t* out, size_t count);
 int rzk_sample_gauss_dev(rzk_ctx* ctx, uint64_t seed, uint32_t stream, double sigma, int64_t* out, size_t count);
 int rzk_sample_challenge_dev(rzk_ctx* ctx, uint64_t seed, uint32_t stream, int64_t* out, size_t count);
+
+/* ---- keyed device-side samplers (v6) --------------------------------------------------------------------------------
+ * The samplers above are keyed by a 64-bit seed through Philox4x32-10: a statistical generator, fine for tests and
+ * benchmarks, NOT for proofs anyone relies on (zero knowledge rests on y, hiding on r, interactive soundness on d being
+ * unpredictable; the reference draws them from rand's ChaCha-based CSPRNG).  These draw the same three distributions,
+ * with the same argument rules, from ChaCha20 (RFC 8439, 20 rounds) under a 256-bit key held by the context:
+ *   subkey = HChaCha20(key, nonce)   (XChaCha construction, once per call, on the host)
+ *   block(stream, poly, blk) = ChaCha20_block(subkey, words 12..15 = blk, poly lo, poly hi, stream)
+ * poly = index of the polynomial within the call, blk = 64-byte block within it; one block serves 8 coefficients or 8
+ * steps of the challenge sampler (ring_zk_amd/csrc/rzk_chacha.h restates every map).  Output is a
+ * function of (key, nonce, stream, polynomial index) alone — not of count, the launch shape or the alignment of out.
+ *
+ * A (key, nonce, stream) triple must NEVER be used for two different draws: the second draw repeats the first one's
+ * randomness (two responses z = y + d r, z' = y + d' r over the same y reveal r).  Use a fresh nonce per call — a
+ * counter is enough — and the stream to separate the vectors of one call site.
+ * Not claimed: constant time (Box-Muller runs in floating point, Floyd's walk has data-dependent LDS addresses).
+ * Bias of a uniform coefficient / challenge position: <= range / 2^64.
+ *
+ * rzk_sampler_set_key copies the 32 bytes into the context (host memory; only per-call subkeys travel to the device, as
+ * kernel arguments); NULL clears it.  The copy is wiped when it is replaced, cleared, and in rzk_ctx_destroy.
+ * The draws return RZK_E_ARG when no key is set or nonce is NULL (and for a bad bound / sigma, as above); count == 0
+ * returns RZK_OK.  They are asynchronous on the context's stream; out is a device pointer. */
+int rzk_sampler_set_key(rzk_ctx* ctx, const uint8_t key[32]);
+int rzk_sample_uniform_keyed_dev(rzk_ctx* ctx, const uint8_t nonce[16], uint32_t stream, uint64_t bound, int64_t* out,
+                                 size_t count);
+int rzk_sample_gauss_keyed_dev(rzk_ctx* ctx, const uint8_t nonce[16], uint32_t stream, double sigma, int64_t* out,
+                               size_t count);
+int rzk_sample_challenge_keyed_dev(rzk_ctx* ctx, const uint8_t nonce[16], uint32_t stream, int64_t* out, size_t count);
 
 /* ---- wire format of one Mat (host only) ---------------------------------------------------------------------------- */
 /* bincode layout of the reference's Mat<I,N> (serde derive at src/mat.rs:11-14; bincode default options as in

@@ -67,6 +67,11 @@ SIGNATURES = {
     "rzk_sample_uniform_dev": (C.c_int, [_CTX, C.c_uint64, C.c_uint32, C.c_uint64, _I64, _SZ]),
     "rzk_sample_gauss_dev": (C.c_int, [_CTX, C.c_uint64, C.c_uint32, C.c_double, _I64, _SZ]),
     "rzk_sample_challenge_dev": (C.c_int, [_CTX, C.c_uint64, C.c_uint32, _I64, _SZ]),
+    # v6: keyed (ChaCha20) samplers
+    "rzk_sampler_set_key": (C.c_int, [_CTX, _U8]),
+    "rzk_sample_uniform_keyed_dev": (C.c_int, [_CTX, _U8, C.c_uint32, C.c_uint64, _I64, _SZ]),
+    "rzk_sample_gauss_keyed_dev": (C.c_int, [_CTX, _U8, C.c_uint32, C.c_double, _I64, _SZ]),
+    "rzk_sample_challenge_keyed_dev": (C.c_int, [_CTX, _U8, C.c_uint32, _I64, _SZ]),
     "rzk_wire_mat_size": (C.c_size_t, [_I64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "rzk_wire_mat_encode": (C.c_int, [_I64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _U8, _SZ,
                                       C.POINTER(C.c_size_t)]),
@@ -90,7 +95,7 @@ SIGNATURES = {
     "rzk_prof_read_all": (C.c_int, [_CTX, C.POINTER(C.c_double), _SZ, C.POINTER(C.c_size_t)]),
     "rzk_prof_read_kernels": (C.c_int, [_CTX, C.c_char_p, _SZ, C.POINTER(C.c_size_t)]),
 }
-ABI_VERSION = 5   # include/rzk.h: RZK_ABI_VERSION
+ABI_VERSION = 6   # include/rzk.h: RZK_ABI_VERSION
 # every batched entry point also exists as a device-pointer variant with the same signature
 for _name in list(SIGNATURES):
     if _name.endswith("_batch"):

@@ -317,6 +317,46 @@ class Context:
         self._check(self._L.rzk_sample_challenge_dev(self._h, seed, stream, C.c_void_p(out.data_ptr()), cnt))
         return out
 
+    # ---- keyed samplers: the same distributions from ChaCha20 under a 256-bit key (include/rzk.h "keyed") ----
+    def set_sampler_key(self, key: Optional[bytes]):
+        """Key of the keyed samplers (32 bytes; None clears it).  The context keeps a copy in host memory and wipes it
+        when it is replaced, cleared or the context is closed."""
+        if key is None:
+            self._check(self._L.rzk_sampler_set_key(self._h, None))
+            return
+        key = bytes(key)
+        if len(key) != 32:
+            raise ValueError("the sampler key must be 32 bytes")
+        self._check(self._L.rzk_sampler_set_key(self._h, (C.c_uint8 * 32).from_buffer_copy(key)))
+
+    @staticmethod
+    def _nonce(nonce: bytes):
+        nonce = bytes(nonce)
+        if len(nonce) != 16:
+            raise ValueError("the nonce must be 16 bytes")
+        return (C.c_uint8 * 16).from_buffer_copy(nonce)
+
+    def sample_uniform_keyed(self, nonce: bytes, stream: int, bound: int, lead):
+        """sample_uniform from the keyed generator.  A (key, nonce, stream) triple must never serve two draws."""
+        out, cnt = self._sample_out(lead)
+        self._check(self._L.rzk_sample_uniform_keyed_dev(self._h, self._nonce(nonce), stream, bound,
+                                                         C.c_void_p(out.data_ptr()), cnt))
+        return out
+
+    def sample_gauss_keyed(self, nonce: bytes, stream: int, sigma: float, lead):
+        """sample_gauss from the keyed generator."""
+        out, cnt = self._sample_out(lead)
+        self._check(self._L.rzk_sample_gauss_keyed_dev(self._h, self._nonce(nonce), stream, float(sigma),
+                                                       C.c_void_p(out.data_ptr()), cnt))
+        return out
+
+    def sample_challenge_keyed(self, nonce: bytes, stream: int, lead):
+        """sample_challenge from the keyed generator."""
+        out, cnt = self._sample_out(lead)
+        self._check(self._L.rzk_sample_challenge_keyed_dev(self._h, self._nonce(nonce), stream,
+                                                           C.c_void_p(out.data_ptr()), cnt))
+        return out
+
     # ---- commitment scheme (src/commit.rs) --------------------------------------------------------------------
     def commit(self, x, r):
         """CommitmentKey::commit (commit.rs:88-128) with caller-supplied r: (c, ok)."""
@@ -445,3 +485,39 @@ class Context:
         dev, p = self._prep([zs, zp, cs, cp, gs, ts, tp, u, d, acc], [np.int64] * 9 + [np.uint8])
         self._check(self._fn("rzk_sum_verify_batch", dev)(self._h, V, *p, B))
         return acc
+
+
+class KeyedSampler:
+    """Prover / verifier randomness from the keyed (ChaCha20) device samplers, one fresh nonce per draw.
+
+    The nonce is a 128-bit little-endian counter starting at `nonce0`; `uniform`, `gauss` and `challenge` each consume
+    its next value, so a program cannot use a (key, nonce) pair twice by accident.  key = None takes 32 bytes from
+    os.urandom; a given key plus nonce0 make a run reproducible (tests).  The key is installed in `ctx`: one sampler
+    per context at a time."""
+
+    STREAM = 0
+
+    def __init__(self, ctx: Context, key: Optional[bytes] = None, nonce0: int = 0):
+        import os
+
+        if not 0 <= nonce0 < 1 << 128:
+            raise ValueError("nonce0 must fit 128 bits")
+        self.ctx = ctx
+        self.counter = nonce0
+        ctx.set_sampler_key(os.urandom(32) if key is None else key)
+
+    def _next_nonce(self) -> bytes:
+        if self.counter >= 1 << 128:
+            raise OverflowError("the nonce counter is exhausted: install a new key")
+        nonce = self.counter.to_bytes(16, "little")
+        self.counter += 1
+        return nonce
+
+    def uniform(self, bound: int, lead):
+        return self.ctx.sample_uniform_keyed(self._next_nonce(), self.STREAM, bound, lead)
+
+    def gauss(self, sigma: float, lead):
+        return self.ctx.sample_gauss_keyed(self._next_nonce(), self.STREAM, sigma, lead)
+
+    def challenge(self, lead):
+        return self.ctx.sample_challenge_keyed(self._next_nonce(), self.STREAM, lead)

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/rzk.h"
+#include "rzk_chacha.h"
 #include "rzk_core.h"
 #include "rzk_dev.h"
 #include "rzk_keccak.h"
@@ -98,6 +99,8 @@ struct rzk_ctx {
   Arena ws_wire;                       // message codec: position table (decode) / lengths, positions, sizes (encode)
   Arena ws_fs;                         // Fiat-Shamir transcript: leaf digests of the call (and the key while it is hashed)
   uint64_t key_digest[kFsDigestWords] = {};   // FS1 digest of the loaded key and the context's parameters (rzk_fs_key_digest)
+  bool sampler_key_set = false;                // rzk_sampler_set_key: the key of the keyed (ChaCha20) samplers, host memory only;
+  uint8_t sampler_key[32] = {};                // wiped when it is cleared and in rzk_ctx_destroy
   // canonical-input test (rzk_dev.h, Operands::bad): sticky word set by any kernel that loaded a coefficient
   // outside the centred range on behalf of an entry point without per-proof verdicts; read back at every
   // synchronising call (host-pointer variants, rzk_ctx_synchronize, rzk_ctx_check_inputs)
@@ -134,6 +137,12 @@ std::string g_create_err;   // last rzk_ctx_create failure (no context exists ye
 int create_fail(int code, const std::string& msg) {
   g_create_err = msg;
   return code;
+}
+
+// zeroes secret bytes through a volatile pointer, so that the stores are not removed as dead
+void wipe(void* p, size_t n) {
+  volatile uint8_t* v = (volatile uint8_t*)p;
+  for (size_t i = 0; i < n; ++i) v[i] = 0;
 }
 
 int fail(rzk_ctx* c, int code, const char* msg) {
@@ -692,6 +701,7 @@ void rzk_ctx_destroy(rzk_ctx* c) {
   if (c->d_bad) (void)hipFree(c->d_bad);
   if (c->h_bad) (void)hipHostFree(c->h_bad);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
+  wipe(c->sampler_key, sizeof(c->sampler_key));
   delete c;
 }
 
@@ -1001,6 +1011,62 @@ int rzk_sample_challenge_dev(rzk_ctx* c, uint64_t seed, uint32_t stream, int64_t
   if (c && count == 0) return RZK_OK;
   if (!c || !out) return RZK_E_ARG;
   return check_launch(c, launch_sample_challenge(cfg_of(c), out, count, c->N, seed, stream, c->kappa), "sampler");
+}
+
+// ---- keyed samplers (v6): the same distributions from ChaCha20 blocks (rzk_chacha.h) ------------------
+int rzk_sampler_set_key(rzk_ctx* c, const uint8_t key[32]) {
+  if (!c) return RZK_E_ARG;
+  wipe(c->sampler_key, sizeof(c->sampler_key));
+  c->sampler_key_set = key != nullptr;
+  if (key) std::memcpy(c->sampler_key, key, sizeof(c->sampler_key));
+  return RZK_OK;
+}
+
+namespace {
+// subkey of one call = HChaCha20(key, nonce), and the launch configuration (a profiling slot when profiling is on)
+int keyed_begin(rzk_ctx* c, const uint8_t* nonce, size_t count, uint32_t subkey[8], LaunchCfg& cfg) {
+  if (!c->sampler_key_set) return fail(c, RZK_E_ARG, "keyed sampler: no key set (rzk_sampler_set_key)");
+  if (!nonce) return fail(c, RZK_E_ARG, "keyed sampler: NULL nonce");
+  const int rc = prof_begin(c, (uint64_t)count * c->N * sizeof(int64_t), cfg);
+  if (rc == RZK_OK) chacha_sampler_subkey(c->sampler_key, nonce, subkey);
+  return rc;
+}
+// the launch has copied the subkey into its kernel arguments: wipe the host copy
+int keyed_end(rzk_ctx* c, int launch_rc, uint32_t subkey[8]) {
+  wipe(subkey, 8 * sizeof(uint32_t));
+  const int rc = check_launch(c, launch_rc, "keyed sampler");
+  return rc != RZK_OK ? rc : prof_end(c);
+}
+}  // namespace
+
+int rzk_sample_uniform_keyed_dev(rzk_ctx* c, const uint8_t nonce[16], uint32_t stream, uint64_t bound, int64_t* out,
+                                 size_t count) {
+  if (c && count == 0) return RZK_OK;
+  if (!c || !out || bound == 0 || bound > (uint64_t)(c->q - 1) / 2) return RZK_E_ARG;
+  uint32_t sk[8];
+  LaunchCfg cfg;
+  const int rc = keyed_begin(c, nonce, count, sk, cfg);
+  if (rc != RZK_OK) return rc;
+  return keyed_end(c, launch_sample_uniform_chacha(cfg, out, count, c->N, sk, stream, (uint32_t)bound), sk);
+}
+int rzk_sample_gauss_keyed_dev(rzk_ctx* c, const uint8_t nonce[16], uint32_t stream, double sigma, int64_t* out,
+                               size_t count) {
+  if (c && count == 0) return RZK_OK;
+  if (!c || !out || !(sigma > 0.0) || sigma > 67108864.0) return RZK_E_ARG;   // as rzk_sample_gauss_dev
+  uint32_t sk[8];
+  LaunchCfg cfg;
+  const int rc = keyed_begin(c, nonce, count, sk, cfg);
+  if (rc != RZK_OK) return rc;
+  return keyed_end(c, launch_sample_gauss_chacha(cfg, out, count, c->N, sk, stream, sigma), sk);
+}
+int rzk_sample_challenge_keyed_dev(rzk_ctx* c, const uint8_t nonce[16], uint32_t stream, int64_t* out, size_t count) {
+  if (c && count == 0) return RZK_OK;
+  if (!c || !out) return RZK_E_ARG;
+  uint32_t sk[8];
+  LaunchCfg cfg;
+  const int rc = keyed_begin(c, nonce, count, sk, cfg);
+  if (rc != RZK_OK) return rc;
+  return keyed_end(c, launch_sample_challenge_chacha(cfg, out, count, c->N, sk, stream, c->kappa), sk);
 }
 
 namespace {

@@ -1,0 +1,259 @@
+// rzk_csprng_dev.hip — the keyed device samplers: uniform, Gaussian and challenge polynomials drawn from ChaCha20 blocks
+// (stream definition and word-to-coefficient maps: rzk_chacha.h).  Same distributions, launch shapes and
+// store discipline as the seeded samplers (rzk_sample.h); only the source of the words differs.
+//
+// Layout: a QUAD of lanes computes one ChaCha20 block.  Lane c = lane & 3 holds column c of the 4 x 4 state
+// (a, b, c, d) = (x[c], x[4+c], x[8+c], x[12+c]), so a column round is one quarter round in every lane, and a diagonal
+// round is the same quarter round after rotating the rows b, c, d by 1, 2, 3 lanes inside the quad (DPP quad_perm: no
+// LDS, no memory).  The state is 4 registers per lane (+ 4 for the feed-forward), indexed with constants only: no
+// scratch.  After the rounds the quad transposes its 4 x 4 words, so that lane c holds "quarter" c = words 4c .. 4c+3 —
+// the two coefficients 8 blk + 2c, 8 blk + 2c + 1 — and a wave instruction stores 64 lane-consecutive 16-byte pieces,
+// exactly as store_pair (rzk_sample.h) does for one Philox block per lane.
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "rzk_chacha.h"
+#include "rzk_dev.h"
+
+namespace rzk {
+
+#define RZK_LAUNCH_CHECK()                      \
+  do {                                          \
+    hipError_t e_ = hipGetLastError();          \
+    if (e_ != hipSuccess) return (int)e_;       \
+  } while (0)
+
+namespace {
+
+struct ChaChaKey {   // the call's subkey, passed by value (kernel arguments: scalar registers)
+  uint32_t w[8];
+};
+
+// value of lane quad_perm[lane & 3] of the same quad, CTRL = p0 | p1 << 2 | p2 << 4 | p3 << 6
+template <int CTRL>
+__device__ __forceinline__ uint32_t quad_perm(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xf, 0xf, true);
+}
+constexpr int kQuadFrom1 = 0x39;   // [1, 2, 3, 0]: lane c reads lane c + 1
+constexpr int kQuadFrom2 = 0x4E;   // [2, 3, 0, 1]: lane c reads lane c + 2
+constexpr int kQuadFrom3 = 0x93;   // [3, 0, 1, 2]: lane c reads lane c + 3
+
+__device__ __forceinline__ uint32_t sel4(uint32_t i, uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3) {   // v[i], i in 0 .. 3
+  return (i & 2u) ? ((i & 1u) ? v3 : v2) : ((i & 1u) ? v1 : v0);
+}
+
+struct Quarter {   // words 4c .. 4c+3 of a block, in lane c of its quad
+  uint32_t w0, w1, w2, w3;
+};
+
+// block (w12, w13, w14, w15) under `key`, computed by the four lanes of a quad (all four must be active; c = lane & 3)
+__device__ __forceinline__ Quarter chacha_quad_block(const ChaChaKey& key, uint32_t c, uint32_t w12, uint32_t w13,
+                                                     uint32_t w14, uint32_t w15) {
+  const uint32_t a0 = sel4(c, chacha_sigma(0), chacha_sigma(1), chacha_sigma(2), chacha_sigma(3));
+  const uint32_t b0 = sel4(c, key.w[0], key.w[1], key.w[2], key.w[3]);
+  const uint32_t c0 = sel4(c, key.w[4], key.w[5], key.w[6], key.w[7]);
+  const uint32_t d0 = sel4(c, w12, w13, w14, w15);
+  uint32_t xa = a0, xb = b0, xc = c0, xd = d0;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    chacha_quarter_round(xa, xb, xc, xd);                                                    // columns
+    xb = quad_perm<kQuadFrom1>(xb), xc = quad_perm<kQuadFrom2>(xc), xd = quad_perm<kQuadFrom3>(xd);
+    chacha_quarter_round(xa, xb, xc, xd);                                                    // diagonals
+    xb = quad_perm<kQuadFrom3>(xb), xc = quad_perm<kQuadFrom2>(xc), xd = quad_perm<kQuadFrom1>(xd);
+  }
+  xa += a0, xb += b0, xc += c0, xd += d0;   // lane c: words c, 4 + c, 8 + c, 12 + c
+  // transpose: lane l sends its word of row (l - s) & 3 to the lane s places below it, s = 0 .. 3, so lane c receives
+  // word 4c + ((c + s) & 3) from lane (c + s) & 3; the four words are then put in order
+  const uint32_t q0 = sel4(c, xa, xb, xc, xd);
+  const uint32_t q1 = quad_perm<kQuadFrom1>(sel4((c - 1u) & 3u, xa, xb, xc, xd));
+  const uint32_t q2 = quad_perm<kQuadFrom2>(sel4((c - 2u) & 3u, xa, xb, xc, xd));
+  const uint32_t q3 = quad_perm<kQuadFrom3>(sel4((c - 3u) & 3u, xa, xb, xc, xd));
+  return Quarter{sel4((0u - c) & 3u, q0, q1, q2, q3), sel4((1u - c) & 3u, q0, q1, q2, q3),
+                 sel4((2u - c) & 3u, q0, q1, q2, q3), sel4((3u - c) & 3u, q0, q1, q2, q3)};
+}
+
+// two coefficients at a lane-consecutive address: one non-temporal 16-byte store (full lines per wave instruction)
+// where `out` is 16-byte aligned, two 8-byte stores otherwise
+__device__ __forceinline__ void store_two(int64_t* __restrict__ p, int64_t v0, int64_t v1, bool pair16) {
+  if (pair16) {
+    typedef int v4i __attribute__((ext_vector_type(4)));
+    v4i t;
+    t.x = (int32_t)v0, t.y = (int32_t)(v0 >> 32), t.z = (int32_t)v1, t.w = (int32_t)(v1 >> 32);
+    __builtin_nontemporal_store(t, reinterpret_cast<v4i*>(p));
+  } else {
+    p[0] = v0;
+    p[1] = v1;
+  }
+}
+
+// Work of the uniform and Gaussian kernels: quad g of the call is block g & (Q - 1) of polynomial g >> log_q, Q =
+// max(N / 8, 1) blocks per polynomial; lane c of the quad owns coefficients 8 blk + 2c, 8 blk + 2c + 1 (N = 4: lanes
+// 0 and 1 only — the block is wider than the polynomial, N = 2: lane 0).  Thread u is lane u & 3 of quad u >> 2: the
+// grid strides by multiples of 256, so whole quads enter and leave the loop together.
+struct QuadTask {
+  uint64_t poly;
+  uint32_t blk, c;
+  __device__ __forceinline__ QuadTask(uint64_t u, uint32_t log_q) : poly((u >> 2) >> log_q), blk((uint32_t)(u >> 2) & ((1u << log_q) - 1u)), c((uint32_t)u & 3u) {}
+  __device__ __forceinline__ uint32_t coef() const { return 8u * blk + 2u * c; }
+};
+
+__global__ void __launch_bounds__(256)
+sample_uniform_chacha_kernel(int64_t* __restrict__ out, uint64_t nquads, uint32_t n_ring, uint32_t log_q, ChaChaKey key,
+                             uint32_t stream, uint32_t bound) {
+  const bool pair16 = (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
+  for (uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x; (u >> 2) < nquads; u += (uint64_t)gridDim.x * 256) {
+    const QuadTask t(u, log_q);
+    const Quarter w = chacha_quad_block(key, t.c, t.blk, (uint32_t)t.poly, (uint32_t)(t.poly >> 32), stream);
+    if (t.coef() < n_ring)
+      store_two(out + t.poly * n_ring + t.coef(), chacha_uniform_coef(w.w0, w.w1, bound), chacha_uniform_coef(w.w2, w.w3, bound),
+                pair16);
+  }
+}
+
+template <bool F32>
+__global__ void __launch_bounds__(256)
+sample_gauss_chacha_kernel(int64_t* __restrict__ out, uint64_t nquads, uint32_t n_ring, uint32_t log_q, ChaChaKey key,
+                           uint32_t stream, double sigma) {
+  const bool pair16 = (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
+  const float sigf = (float)sigma;
+  for (uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x; (u >> 2) < nquads; u += (uint64_t)gridDim.x * 256) {
+    const QuadTask t(u, log_q);
+    const Quarter w = chacha_quad_block(key, t.c, t.blk, (uint32_t)t.poly, (uint32_t)(t.poly >> 32), stream);
+    int64_t v0, v1;
+    if (F32) chacha_gauss_pair_f32(w.w0, w.w1, w.w2, sigf, v0, v1);
+    else chacha_gauss_pair_f64(w.w0, w.w1, w.w2, w.w3, sigma, v0, v1);
+    if (t.coef() < n_ring) store_two(out + t.poly * n_ring + t.coef(), v0, v1, pair16);
+  }
+}
+
+__device__ __forceinline__ void wave_sync() {   // orders a wavefront's LDS accesses (as in rzk_wave.h)
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// One wavefront per polynomial, Floyd's kappa-subset walked over an LDS byte map: sample_challenge_kernel (rzk_sample.h)
+// with the candidates of 64 steps drawn from 8 ChaCha20 blocks.  Lane t & 63 needs words 2s, 2s + 1 (s = t & 7) of
+// block t >> 3: the two quads of lanes 8m .. 8m + 7 both compute block (t0 >> 3) + m, and lane s takes its pair from
+// quarter s >> 1, which lane s >> 1 of its own quad holds.
+__global__ void __launch_bounds__(256)
+sample_challenge_chacha_kernel(int64_t* __restrict__ out, uint64_t npoly, uint32_t n_ring, ChaChaKey key, uint32_t stream,
+                               uint32_t kappa) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  int8_t* mark = reinterpret_cast<int8_t*>(smem) + (size_t)wave * n_ring;
+  uint32_t* mark_w = reinterpret_cast<uint32_t*>(mark);   // n_ring is a multiple of 4
+  const uint32_t kap = kappa < n_ring ? kappa : n_ring;
+  const bool pair16 = (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
+  for (uint64_t poly = (uint64_t)blockIdx.x * 4 + wave; poly < npoly; poly += (uint64_t)gridDim.x * 4) {
+    for (uint32_t i = lane; i < n_ring / 4; i += 64) mark_w[i] = 0;
+    wave_sync();
+    for (uint32_t t0 = 0; t0 < kap; t0 += 64) {
+      const uint32_t t = t0 + lane;
+      const Quarter q = chacha_quad_block(key, lane & 3u, t >> 3, (uint32_t)poly, (uint32_t)(poly >> 32), stream);
+      // quarter (t & 7) >> 1: from lane [0, 0, 1, 1] of the quad in the lower half of an 8-lane group, [2, 2, 3, 3] in the upper
+      const bool up = (lane & 4u) != 0;
+      const uint32_t x0 = up ? quad_perm<0xFA>(q.w0) : quad_perm<0x50>(q.w0);
+      const uint32_t x1 = up ? quad_perm<0xFA>(q.w1) : quad_perm<0x50>(q.w1);
+      const uint32_t x2 = up ? quad_perm<0xFA>(q.w2) : quad_perm<0x50>(q.w2);
+      const uint32_t x3 = up ? quad_perm<0xFA>(q.w3) : quad_perm<0x50>(q.w3);
+      const uint32_t w0 = (lane & 1u) ? x2 : x0, w1 = (lane & 1u) ? x3 : x1;
+      const uint32_t j = n_ring - kap + t;                               // (lanes beyond kap: unused)
+      uint32_t pick;
+      int32_t sign;
+      chacha_challenge_step(w0, w1, j, pick, sign);
+      const uint32_t m = kap - t0 < 64u ? kap - t0 : 64u;
+#pragma unroll 1
+      for (uint32_t e = 0; e < m; ++e) {
+        const uint32_t pk = (uint32_t)__builtin_amdgcn_readlane((int)pick, (int)e);
+        const uint32_t jj = (uint32_t)__builtin_amdgcn_readlane((int)j, (int)e);
+        const int32_t sg = __builtin_amdgcn_readlane(sign, (int)e);
+        const uint32_t pos = mark[pk] ? jj : pk;
+        wave_sync();
+        if (lane == 0) mark[pos] = (int8_t)sg;
+        wave_sync();
+      }
+    }
+    int64_t* dst = out + poly * n_ring;
+    if (pair16) {
+      for (uint32_t i = 2 * lane; i < n_ring; i += 128) {
+        const int32_t a0 = mark[i], a1 = mark[i + 1];
+        store_two(dst + i, (int64_t)a0, (int64_t)a1, true);
+      }
+    } else {
+      for (uint32_t i = lane; i < n_ring; i += 64) dst[i] = (int64_t)mark[i];
+    }
+    wave_sync();
+  }
+}
+
+unsigned grid_for(uint64_t tasks, int num_cus, uint32_t per_block, uint32_t blocks_per_cu) {
+  uint64_t blocks = (tasks + per_block - 1) / per_block;
+  const uint64_t cap = (uint64_t)num_cus * blocks_per_cu;
+  if (blocks > cap) blocks = cap;
+  if (blocks < 1) blocks = 1;
+  return (unsigned)blocks;
+}
+
+bool ring_ok(uint32_t n_ring) { return n_ring >= 2 && !(n_ring & (n_ring - 1)); }
+
+uint32_t log_quads(uint32_t n_ring) {   // log2 of the blocks per polynomial, max(N / 8, 1)
+  uint32_t l = 0;
+  while ((8u << l) < n_ring) ++l;
+  return l;
+}
+
+ChaChaKey key_of(const uint32_t subkey[8]) {
+  ChaChaKey k;
+  for (int i = 0; i < 8; ++i) k.w[i] = subkey[i];
+  return k;
+}
+
+}  // namespace
+
+int launch_sample_uniform_chacha(const LaunchCfg& cfg, int64_t* out, uint64_t npoly, uint32_t n_ring, const uint32_t subkey[8],
+                                 uint32_t stream, uint32_t bound) {
+  if (npoly == 0) return 0;
+  if (!ring_ok(n_ring)) return -1;
+  const uint32_t lq = log_quads(n_ring);
+  const uint64_t nquads = npoly << lq;
+  hipLaunchKernelGGL(sample_uniform_chacha_kernel, dim3(grid_for(nquads, cfg.num_cus, 64, 16)), dim3(256), 0,
+                     (hipStream_t)cfg.stream, out, nquads, n_ring, lq, key_of(subkey), stream, bound);
+  RZK_LAUNCH_CHECK();
+  if (cfg.launched) *cfg.launched = "sample_uniform_chacha_kernel";
+  return 0;
+}
+
+int launch_sample_gauss_chacha(const LaunchCfg& cfg, int64_t* out, uint64_t npoly, uint32_t n_ring, const uint32_t subkey[8],
+                               uint32_t stream, double sigma) {
+  if (npoly == 0) return 0;
+  if (!ring_ok(n_ring)) return -1;
+  const uint32_t lq = log_quads(n_ring);
+  const uint64_t nquads = npoly << lq;
+  const dim3 grid(grid_for(nquads, cfg.num_cus, 64, 16));
+  const bool f32 = sigma < 524288.0;   // as launch_sample_gauss: 9.4 sigma < 2^23
+  if (f32)
+    hipLaunchKernelGGL(sample_gauss_chacha_kernel<true>, grid, dim3(256), 0, (hipStream_t)cfg.stream, out, nquads, n_ring, lq,
+                       key_of(subkey), stream, sigma);
+  else
+    hipLaunchKernelGGL(sample_gauss_chacha_kernel<false>, grid, dim3(256), 0, (hipStream_t)cfg.stream, out, nquads, n_ring, lq,
+                       key_of(subkey), stream, sigma);
+  RZK_LAUNCH_CHECK();
+  if (cfg.launched) *cfg.launched = f32 ? "sample_gauss_chacha_kernel<true>" : "sample_gauss_chacha_kernel<false>";
+  return 0;
+}
+
+int launch_sample_challenge_chacha(const LaunchCfg& cfg, int64_t* out, uint64_t npoly, uint32_t n_ring, const uint32_t subkey[8],
+                                   uint32_t stream, uint32_t kappa) {
+  if (npoly == 0) return 0;
+  if (n_ring < 4 || (n_ring & 3u)) return -1;   // the byte map is cleared and read in words
+  hipLaunchKernelGGL(sample_challenge_chacha_kernel, dim3(grid_for(npoly, cfg.num_cus, 4, 16)), dim3(256), 4 * n_ring,
+                     (hipStream_t)cfg.stream, out, npoly, n_ring, key_of(subkey), stream, kappa);
+  RZK_LAUNCH_CHECK();
+  if (cfg.launched) *cfg.launched = "sample_challenge_chacha_kernel";
+  return 0;
+}
+
+}  // namespace rzk

@@ -312,6 +312,14 @@ int launch_fs_leaves(const LaunchCfg& cfg, const FsMsg& m, int64_t half, int che
 // root of every proof: digest [B][32] (may be NULL) and, with d != NULL, the challenge into d [B][N] (zeroed before)
 int launch_fs_roots(const LaunchCfg& cfg, const FsRoot& r, const uint64_t* dig, int64_t* d, uint8_t* digest,
                     uint64_t B);
+// ---- keyed samplers (rzk_csprng_dev.hip; stream and maps in rzk_chacha.h): the distributions of launch_sample_*,
+// drawn from ChaCha20 blocks under the call's subkey = HChaCha20(key, nonce)
+int launch_sample_uniform_chacha(const LaunchCfg& cfg, int64_t* out, uint64_t npoly, uint32_t n_ring, const uint32_t subkey[8],
+                                 uint32_t stream, uint32_t bound);
+int launch_sample_gauss_chacha(const LaunchCfg& cfg, int64_t* out, uint64_t npoly, uint32_t n_ring, const uint32_t subkey[8],
+                               uint32_t stream, double sigma);
+int launch_sample_challenge_chacha(const LaunchCfg& cfg, int64_t* out, uint64_t npoly, uint32_t n_ring, const uint32_t subkey[8],
+                                   uint32_t stream, uint32_t kappa);
 // small ring degrees (N = 4 .. 256): schoolbook products mod q, same row programs
 int launch_row_program_small(uint32_t N, const LaunchCfg& cfg, const Program* d_prog, uint32_t nrows,
                              const Operands& ops, const uint32_t* d_key_mont, const DevTables* d_T, uint32_t r2q,

@@ -7,7 +7,9 @@ rzk_fs_challenge_batch[_dev]): a proof is (commitment message, response), and an
   * `challenge` / `key_digest`: the transcript hash itself;
   * `open_prove` / `open_verify`, `linear_*`, `sum_*`: commit -> challenge -> response, and challenge -> verify; with
     torch CUDA tensors nothing leaves the device between the phases;
-  * `verify_open_wire`: the same verdict from serialized OpenProofCommitment / OpenProofResponse messages.
+  * `verify_open_wire`: the same verdict from serialized OpenProofCommitment / OpenProofResponse messages;
+  * `open_prove_sampled`, `linear_prove_sampled`, `sum_prove_sampled`: the provers with r and y drawn on the device by a
+    `backend.KeyedSampler` (ChaCha20) instead of supplied by the caller.
 
 `aux` (32 bytes, default zeros) binds the proofs of a call to a session or statement; prover and verifier must agree.
 Like the rest of the package every function takes numpy arrays (host entry points) or torch CUDA tensors (device entry
@@ -142,3 +144,42 @@ def sum_verify(ctx, cs, cp, gs, ts, tp, u, zs, zp, aux=None):
     V = int(gs.shape[-2])
     d, _, okf = challenge(ctx, MSG_SUM_COMMITMENT, cp, cs, gs, tp, ts, u, V=V, aux=aux)
     return ctx.sum_verify(zs, zp, cs, cp, gs, ts, tp, u, d) & okf
+
+
+# ---- provers that draw their own randomness (backend.KeyedSampler: ChaCha20 on the device) ---------------
+# r-type vectors are uniform in [-b, b] (commit.rs:101), y-type vectors N(0, sigma) (open.rs:88-91).  x (and g) must be
+# torch CUDA tensors: the draws live on the device.  ok is passed through as from *_prove (0: r failed the commit
+# constraint, the caller draws again); there is no resampling loop here.
+def _lead(x, tail: int):
+    if not wire._is_torch(x):
+        raise ValueError("the sampled provers take torch CUDA tensors")
+    return tuple(x.shape[:-tail])
+
+
+def open_prove_sampled(ctx, x, sampler, aux=None):
+    """open_prove with r, y from `sampler`: (c, t, z, ok, r)."""
+    lead = _lead(x, 2)
+    r = sampler.uniform(ctx.b, lead + (ctx.k,))
+    y = sampler.gauss(ctx.sigma, lead + (ctx.k,))
+    return open_prove(ctx, x, r, y, aux=aux) + (r,)
+
+
+def linear_prove_sampled(ctx, g, x, sampler, aux=None):
+    """linear_prove with r, r', y, y' from `sampler`: (c, cp, t, tp, u, z, zp, ok, r, rp)."""
+    lead = _lead(x, 2)
+    r = sampler.uniform(ctx.b, lead + (ctx.k,))
+    rp = sampler.uniform(ctx.b, lead + (ctx.k,))
+    y = sampler.gauss(ctx.sigma, lead + (ctx.k,))
+    yp = sampler.gauss(ctx.sigma, lead + (ctx.k,))
+    return linear_prove(ctx, g, x, r, rp, y, yp, aux=aux) + (r, rp)
+
+
+def sum_prove_sampled(ctx, gs, xs, sampler, aux=None):
+    """sum_prove with rs, r', ys, y' from `sampler`: (cs, cp, ts, tp, u, zs, zp, ok, rs, rp)."""
+    lead = _lead(xs, 3)
+    V = int(xs.shape[-3])
+    rs = sampler.uniform(ctx.b, lead + (V, ctx.k))
+    rp = sampler.uniform(ctx.b, lead + (ctx.k,))
+    ys = sampler.gauss(ctx.sigma, lead + (V, ctx.k))
+    yp = sampler.gauss(ctx.sigma, lead + (ctx.k,))
+    return sum_prove(ctx, gs, xs, rs, rp, ys, yp, aux=aux) + (rs, rp)
