@@ -429,6 +429,8 @@ int rzk_prof_read_kernels(rzk_ctx* ctx, char* buf, size_t cap, size_t* needed);
  * measurements need no rebuild.  Defaults are what the measurements in DESIGN.md §6 chose.
  *   RZK_SHIFT=0            challenge products through transforms instead of signed rotations (default 1; at N = 2048 only
  *                          with RZK_PAIR_POLY=1, the default)
+ *   RZK_SHIFT_BYTES=0|1    shift_row_kernel at N <= 1024: terms with |multiplier|_1 * 2 |operand|_inf <= 255 (every response row
+ *                          z = y + r (.) d) rotate packed bytes instead of 32-bit words (default 1; 0 = words only)
  *   RZK_PAIRS=0            unit_kernel: no pairing of rows that share their last operand (default 1)
  *   RZK_UPT=<u>            unit_kernel: units of a proof per wavefront task (default: all once batch >= 16 x CUs, else 1)
  *   RZK_VEC_ROWS=0         programs with vector x vector products through unit_kernel instead of row_kernel (default 1)

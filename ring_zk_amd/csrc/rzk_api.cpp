@@ -71,6 +71,7 @@ struct rzk_ctx {
   bool use_pairs = true;               // unit_kernel: pair rows that share their last operand (RZK_PAIRS=0 turns it off, tuning)
   int group_max = 1;                   // rows per group of row_group_kernel (group_max_for; RZK_GROUP_MAX overrides, tuning)
   bool use_shift = true;               // challenge products as signed rotations (shift_row_kernel) instead of transforms
+  bool shift_bytes = true;             // ... of short operands as packed bytes (shift_row_kernel, N <= 1024; RZK_SHIFT_BYTES=0: words only)
   int use_dkey = 1;                    // the scalar multipliers g_i of Linear / Sum transformed once per proof and call (TERM_DKEY): 0 never (every row
                                        // transforms them itself), 1 when at least kDkeyMinUses rows of the call multiply by each, 2 always (RZK_DKEY)
   Arena ws_dkey;                       // their images + norms
@@ -159,7 +160,7 @@ uint64_t isqrt_u64(uint64_t x) {
 
 LaunchCfg cfg_of(rzk_ctx* c) {
   (void)hipSetDevice(c->device);   // the calling thread may have another current device
-  return LaunchCfg{(void*)c->stream, c->num_cus, c->pair_poly ? 1 : 0, c->unit_io ? 1 : 0};
+  return LaunchCfg{(void*)c->stream, c->num_cus, c->pair_poly ? 1 : 0, c->unit_io ? 1 : 0, c->shift_bytes ? 1 : 0};
 }
 
 int arena_reserve(rzk_ctx* c, Arena& a, size_t bytes) {
@@ -632,6 +633,7 @@ int rzk_ctx_create(rzk_ctx** out, int64_t q, uint32_t N, uint32_t n, uint32_t k,
     if (g >= 1 && g <= group_accumulators(c->logn)) c->group_max = g;   // bounded by the compiled accumulators
   }
   if (const char* e = std::getenv("RZK_SHIFT")) c->use_shift = std::atoi(e) != 0;
+  if (const char* e = std::getenv("RZK_SHIFT_BYTES")) c->shift_bytes = std::atoi(e) != 0;
   if (const char* e = std::getenv("RZK_SUM_D")) c->sum_d = std::atoi(e) != 0 ? 1 : 0;
   if (const char* e = std::getenv("RZK_DKEY")) c->use_dkey = std::atoi(e);
   if (const char* e = std::getenv("RZK_LIN_E")) c->lin_e = std::atoi(e) != 0;

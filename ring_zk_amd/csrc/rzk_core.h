@@ -527,4 +527,104 @@ RZK_HD uint32_t zq_from_i64(int64_t a, const CrtConsts& C) {
   return addq(montq_u(zq_from_centered(hi, C.q), C.r2q, C), lo, C.q);
 }
 
+// ---- short operands: the same rotations on packed bytes (one wavefront, N <= 1024) -------------------------------
+// In z = y + r (.) d the rotated operand is ternary and the multiplier has 36 entries +-1: every partial product lies
+// in {-1, 0, 1}.  Whenever |d|_1 * 2 |v|_inf <= 255 (decided per term from the measured norms, team-uniform) the image
+// holds BYTES biased by bias = |v|_inf,
+//     img8[t] = bias - v[t]  (t < N),   bias + v[t - N]  (N <= t < 2N),   bias - v[t - 2N]  (2N <= t < 3N),
+// so that bias + (X^s v)[j] = img8[j - s + N] and bias - (X^s v)[j] = img8[j - s + 2N]: a negative entry of the
+// multiplier is the same read N bytes further on (X^N = -1), no second image and no negation.  Every byte is in
+// [0, 2 bias]; a sum of |d|_1 of them is at most 255, so four of them are added with ONE 32-bit add and no byte ever
+// carries into its neighbour.  After the scan a byte holds |d|_1 bias + (d (*) v)[j].
+// Ownership: lane l holds the dwords l + 64 k (k < W) of the N-byte sum, i.e. outputs 4 (l + 64 k) .. + 3.  The window
+// of dword m under a rotation is the unaligned dword at byte 4 m + off, off = (N or 2N) - s: the aligned dwords
+// m + (off >> 2) and the next one, realigned by the team-uniform off & 3 (v_alignbyte_b32).  Consecutive lanes read
+// consecutive dwords: conflict-free ds_read_b32 (a lane owning 16 CONSECUTIVE outputs would read at a stride of four
+// dwords: five reads, but 4-way conflicts on the 32 banks of ds_read_b32, 40 LDS cycles per rotation against 16 here;
+// tools/lds_conflicts.py bytes).  The image is 3N bytes + one dword that a rotation by a multiple of four reads and
+// ignores: 3/8 of the word image.
+template <int LOGN>
+struct ByteGeo {
+  static constexpr int N = 1 << LOGN;
+  static constexpr int LANES = 64;
+  static constexpr int E = N / LANES;          // outputs per lane
+  static constexpr int W = E / 4;              // dwords of packed sums per lane
+  static constexpr int IMG_WORDS = 3 * N / 4 + 1;
+};
+typedef uint16_t __attribute__((may_alias)) shift_u16;   // 16-bit views of the dword image
+typedef uint32_t __attribute__((may_alias)) shift_u32;
+
+// the condition; suma = |d|_1, maxv = |v|_inf (the bias must fit a byte too, also under a zero multiplier)
+RZK_HD bool shift_bytes_ok(uint64_t suma, uint32_t maxv) { return maxv <= 127u && suma <= 255u && suma * 2u * maxv <= 255u; }
+
+RZK_HD uint32_t align_bytes(uint32_t hi, uint32_t lo, uint32_t sh) {   // bytes sh .. sh+3 of {hi, lo}, sh < 4
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_alignbyte(hi, lo, sh);
+#else
+  return (uint32_t)((((uint64_t)hi << 32) | lo) >> (8u * sh));
+#endif
+}
+
+// The image is built in two steps, because the bias is only known once all of v has been seen: while v is loaded and
+// measured, each pair of coefficients g*128 + 2*lane + {0,1} (the PAIR layout of ShiftGeo) goes to its 16-bit slot of the
+// middle third as two's-complement bytes; garbage if |v|_inf > 127, but then the condition fails and the image is not used.
+template <int LOGN>
+RZK_HD void shift_bytes_put_raw(int32_t v0, int32_t v1, int lane, int g, uint32_t* img) {
+  constexpr int N = 1 << LOGN;
+  reinterpret_cast<shift_u16*>(img)[N / 2 + g * 64 + lane] = (uint16_t)(((uint32_t)v0 & 0xffu) | (((uint32_t)v1 & 0xffu) << 8));
+}
+// ... then every lane biases its own dwords in place and writes the two negated thirds: four bytes per operation, with
+// (x + bias) mod 256 per byte = ((x & 0x7f) + bias) ^ (x & 0x80) for bias <= 127 (no carry leaves a byte).
+template <int LOGN>
+RZK_HD void shift_bytes_bias(int lane, uint32_t bias, uint32_t* img) {
+  using B = ByteGeo<LOGN>;
+  shift_u32* p = reinterpret_cast<shift_u32*>(img) + lane;
+  const uint32_t b4 = bias * 0x01010101u;
+#pragma unroll
+  for (int k = 0; k < B::W; ++k) {
+    const uint32_t x = p[B::N / 4 + 64 * k];
+    const uint32_t pos = ((x & 0x7f7f7f7fu) + b4) ^ (x & 0x80808080u);
+    const uint32_t neg = 2u * b4 - pos;   // bytewise 2 bias - x, no borrow: x <= 2 bias
+    p[64 * k] = neg;
+    p[B::N / 4 + 64 * k] = pos;
+    p[B::N / 2 + 64 * k] = neg;
+  }
+  if (lane == 0) p[3 * B::N / 4] = 0u;
+}
+
+// acc[k] += |coef| times the four bytes bias + sign(coef) (X^s v)[4 (lane + 64 k) .. + 3]
+template <int LOGN>
+RZK_HD void shift_bytes_accum(uint32_t* acc, int lane, int s, int32_t coef, const uint32_t* img) {
+  using B = ByteGeo<LOGN>;
+  const uint32_t off = (uint32_t)((coef < 0 ? 2 * B::N : B::N) - s);   // >= 1
+  const shift_u32* base = reinterpret_cast<const shift_u32*>(img) + (off >> 2) + lane;
+  uint32_t w[B::W];
+#pragma unroll
+  for (int k = 0; k < B::W; ++k) w[k] = align_bytes(base[64 * k + 1], base[64 * k], off & 3u);
+  uint32_t mag = coef < 0 ? 0u - (uint32_t)coef : (uint32_t)coef;   // 1 for a challenge
+  do {
+#pragma unroll
+    for (int k = 0; k < B::W; ++k) acc[k] += w[k];
+  } while (--mag);
+}
+
+// the packed sums go back to the (idle) image in natural order ...
+template <int LOGN>
+RZK_HD void shift_bytes_park(const uint32_t* acc, int lane, uint32_t* img) {
+#pragma unroll
+  for (int k = 0; k < ByteGeo<LOGN>::W; ++k) reinterpret_cast<shift_u32*>(img)[lane + 64 * k] = acc[k];
+}
+// ... and come out in the PAIR layout as exact integers: out[i] = (d (*) v)[ShiftGeo::j(lane, i)], |out| <= 127
+template <int LOGN>
+RZK_HD void shift_bytes_take(int32_t* out, int lane, uint32_t bias_total, const uint32_t* img) {
+  using S = ShiftGeo<LOGN, true>;
+  const shift_u16* p = reinterpret_cast<const shift_u16*>(img) + lane;
+#pragma unroll
+  for (int g = 0; g < S::G; ++g) {
+    const uint32_t two = p[g * 64];
+    out[2 * g] = (int32_t)(two & 0xffu) - (int32_t)bias_total;
+    out[2 * g + 1] = (int32_t)(two >> 8) - (int32_t)bias_total;
+  }
+}
+
 }  // namespace rzk

@@ -211,6 +211,7 @@ struct LaunchCfg {
   int num_cus;
   int pair_poly;  // N = 2048: two wavefronts per polynomial (PairTeam) in unit_kernel / row_kernel / row_block_kernel
   int unit_io;    // key-product programs through unit_io_kernel (operands read once) instead of unit_kernel
+  int shift_bytes;   // shift_row_kernel at N <= 1024: short operands rotate as packed bytes (RZK_SHIFT_BYTES)
   std::string* launched = nullptr;   // out: the row-program launchers write the name of the instantiation they started here
 };
 

@@ -207,32 +207,40 @@ int launch_units(int logn, const LaunchCfg& cfg, const Program* d_prog, const Wa
   return -1;
 }
 
-template <int LOGN, class TM = WaveTeam>
+template <int LOGN, class TM = WaveTeam, bool BYTES = (TM::LL == 6)>
 static int launch_shift_t(const LaunchCfg& cfg, const Program* d_prog, const Operands& ops, const DevTables* T,
                           uint8_t* d_flags, uint32_t ntasks) {
   constexpr int TPB = ShiftCfg<LOGN, TM>::TPB;
+  static_assert(!BYTES || TM::LL == 6, "packed-byte rotations: one wavefront per polynomial");
   // One team's image is 8 N bytes.  The workgroup asks for at least 40 KiB so that a CU holds four workgroups = 4 waves per
   // SIMD: with the 79 VGPRs the kernel needs, five or six would fit, and measured slower (response rows at N = 1024:
   // 86.7 us against 77.5 us at four — the kernel is co-bound by the LDS pipe, more waves only add contention).
   // Teams of two (N = 2048): 18 KiB per 128-thread workgroup, eight workgroups = 4 waves per SIMD.
+  // BYTES: the packed image is 3 N bytes, but a term that fails the condition still builds the word image, so the request
+  // stays at 8 N bytes per team.  The floor stays too while the kernel is compiled for four waves per SIMD
+  // (RZK_SHIFT_BYTES_WAVES, rzk_row.h: at five it needs 96 VGPRs and spills; measured no gain).
   size_t lds = (size_t)TPB * ShiftCfg<LOGN, TM>::WORDS * sizeof(uint32_t);
-  if (TM::LL == 6 && LOGN >= 10 && lds < 40 * 1024) lds = 40 * 1024;   // (N = 512 keeps its 6 waves per SIMD: 4-KiB images, measured fine in round 2)
+  if ((!BYTES || RZK_SHIFT_BYTES_WAVES < 5) && TM::LL == 6 && LOGN >= 10 && lds < 40 * 1024) lds = 40 * 1024;   // (N = 512 keeps its 6 waves per SIMD: 4-KiB images, measured fine in round 2)
+  const void* fn = ops.trusted ? reinterpret_cast<const void*>(&shift_row_kernel<LOGN, true, TM, BYTES>)
+                               : reinterpret_cast<const void*>(&shift_row_kernel<LOGN, false, TM, BYTES>);
   if (lds > 48 * 1024) {
-    hipError_t e = ops.trusted ? hipFuncSetAttribute(reinterpret_cast<const void*>(&shift_row_kernel<LOGN, true, TM>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                               : hipFuncSetAttribute(reinterpret_cast<const void*>(&shift_row_kernel<LOGN, false, TM>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
   }
   const unsigned grid = grid_for(ntasks, cfg.num_cus, TPB, TM::LL == 6 ? 16 : 64);
   if (ops.trusted)
-    hipLaunchKernelGGL((shift_row_kernel<LOGN, true, TM>), dim3(grid), dim3(TPB << TM::LL), lds, (hipStream_t)cfg.stream, d_prog, ops,
-                       T, d_flags, ntasks);
+    hipLaunchKernelGGL((shift_row_kernel<LOGN, true, TM, BYTES>), dim3(grid), dim3(TPB << TM::LL), lds, (hipStream_t)cfg.stream, d_prog,
+                       ops, T, d_flags, ntasks);
   else
-    hipLaunchKernelGGL((shift_row_kernel<LOGN, false, TM>), dim3(grid), dim3(TPB << TM::LL), lds, (hipStream_t)cfg.stream, d_prog, ops,
-                       T, d_flags, ntasks);
+    hipLaunchKernelGGL((shift_row_kernel<LOGN, false, TM, BYTES>), dim3(grid), dim3(TPB << TM::LL), lds, (hipStream_t)cfg.stream, d_prog,
+                       ops, T, d_flags, ntasks);
   RZK_LAUNCH_CHECK();
-  if (cfg.launched) *cfg.launched = "shift_row_kernel<" + std::to_string(LOGN) + ", " + tf(ops.trusted) + team_arg<TM>() + ">";
+  // template defaults are left out, as everywhere: BYTES defaults to "one wavefront per polynomial", so the short name is
+  // the packed-byte kernel at N <= 1024 and the word kernel of the two-wavefront teams; RZK_SHIFT_BYTES=0 spells it out
+  constexpr bool kDefault = BYTES == (TM::LL == 6);
+  if (cfg.launched)
+    *cfg.launched = "shift_row_kernel<" + std::to_string(LOGN) + ", " + tf(ops.trusted) +
+                    (kDefault ? team_arg<TM>() : std::string(", ") + TM::kName + ", " + tf(BYTES)) + ">";
   return 0;
 }
 
@@ -261,8 +269,12 @@ int launch_shift_rows(int logn, const LaunchCfg& cfg, const Program* d_prog, uin
   if (batch * nrows >= (1ull << 32)) return -2;
   const uint32_t ntasks = (uint32_t)(batch * nrows);
   switch (logn) {
-    case 9: return launch_shift_t<9>(cfg, d_prog, ops, T, d_flags, ntasks);
-    case 10: return launch_shift_t<10>(cfg, d_prog, ops, T, d_flags, ntasks);
+    case 9:
+      return cfg.shift_bytes ? launch_shift_t<9>(cfg, d_prog, ops, T, d_flags, ntasks)
+                             : launch_shift_t<9, WaveTeam, false>(cfg, d_prog, ops, T, d_flags, ntasks);
+    case 10:
+      return cfg.shift_bytes ? launch_shift_t<10>(cfg, d_prog, ops, T, d_flags, ntasks)
+                             : launch_shift_t<10, WaveTeam, false>(cfg, d_prog, ops, T, d_flags, ntasks);
     case 11: return cfg.pair_poly ? launch_shift_t<11, PairTeam>(cfg, d_prog, ops, T, d_flags, ntasks) : -1;   // (rzk_api.cpp, shift_ok)
   }
   return -1;

@@ -112,15 +112,22 @@ row_kernel(const Program* __restrict__ prog, const Operands ops, const uint32_t*
 // is +-1-valued and |d|_1 |v|_inf < 2^30, in 64 bits (v_mad_i64_i32) below 2^62, and in two 16-bit passes
 // beyond that.
 // =============================================================================================
+#ifndef RZK_SHIFT_BYTES_WAVES
+#define RZK_SHIFT_BYTES_WAVES 4   // waves per SIMD the packed-byte instantiations of shift_row_kernel are compiled and launched for (5: 96 VGPRs, spills, measured no gain)
+#endif
 template <int LOGN, class TM = WaveTeam>
 struct ShiftCfg {   // teams per workgroup: one team's image is 8 * N bytes of LDS, 32 KiB per workgroup at most
   static constexpr int TPB = TM::LL == 6 ? 4 : 1;
   static constexpr int WORDS = ShiftGeo<LOGN, true, TM::LL>::WORDS + (TM::LL == 6 ? 0 : kShiftListWords);   // per team
 };
 
-template <int LOGN, bool TRUSTED, class TM = WaveTeam>   // TRUSTED (Operands::trusted) is a template flag here: as a run-time branch around the loads
+// BYTES: terms whose operands are short enough (shift_bytes_ok: the response rows z = y + r (.) d of every parameter set)
+// rotate packed bytes instead of words (shift_product_bytes); every other term takes shift_product as before.  One
+// wavefront only, and the default there (so `shift_row_kernel<10, false>` IS the packed-byte kernel, in C++ as in the names
+// the launcher reports); RZK_SHIFT_BYTES=0 launches shift_row_kernel<., ., WaveTeam, false>.
+template <int LOGN, bool TRUSTED, class TM = WaveTeam, bool BYTES = (TM::LL == 6)>   // TRUSTED (Operands::trusted) is a template flag here: as a run-time branch around the loads
                                                          // it changed the compiler's load scheduling (79 instead of 116 VGPRs, 86 us instead of 77)
-__global__ void __launch_bounds__((ShiftCfg<LOGN, TM>::TPB << TM::LL), (TM::LL == 6 ? 1 : 4))
+__global__ void __launch_bounds__((ShiftCfg<LOGN, TM>::TPB << TM::LL), (BYTES ? RZK_SHIFT_BYTES_WAVES : TM::LL == 6 ? 1 : 4))   // BYTES: the register budget of the waves per SIMD the LDS request allows
 shift_row_kernel(const Program* __restrict__ prog, const Operands ops, const DevTables* __restrict__ Tp,
                  uint8_t* __restrict__ flags, const uint32_t ntasks) {
   using S = ShiftGeo<LOGN, true, TM::LL>;
@@ -157,8 +164,10 @@ shift_row_kernel(const Program* __restrict__ prog, const Operands ops, const Dev
         uint32_t abad = 0, amx = 0;
         load_pairs<LOGN, TM::LL>(a, operand_ptr(ops, tm.a_op, tm.a_off, b, bo, N), lane, qhalf, abad, amx, trusted);
         if (!trusted) fault = fault || canon_fail(abad, amx, qhalf);
-        shift_product<LOGN, true, false, TM>(res, false, tm.sign < 0, a, operand_ptr(ops, tm.b_op, tm.b_off, b, bo, N), lane,
-                                             slab, T, fault, trusted);
+        const int64_t* __restrict__ pv = operand_ptr(ops, tm.b_op, tm.b_off, b, bo, N);
+        bool done = false;
+        if constexpr (BYTES) done = shift_product_bytes<LOGN>(res, tm.sign < 0, a, pv, lane, slab, T, fault, trusted);
+        if (!done) shift_product<LOGN, true, false, TM>(res, false, tm.sign < 0, a, pv, lane, slab, T, fault, trusted);
       }
       // The sums move to the (now idle) image, each thread's pairs in its own 8-byte slots, so that the additions and
       // the store can run as a rolled loop with few registers and four 16-byte loads in flight per addition.

@@ -450,6 +450,85 @@ __device__ __forceinline__ void shift_product(uint32_t* res, bool fresh, bool mi
   }
 }
 
+// The same product on packed bytes (ByteGeo, rzk_core.h) when the operands are short enough; one wavefront, res in
+// registers.  Returns false, with nothing but `fault` touched, when they are not: the caller then runs shift_product.
+// The multiplier's non-zeros are walked as in shift_scan.  The sums leave through the image to get from the scan's dword ownership back to the
+// PAIR layout of res[] and of the global accesses.
+template <int LOGN>
+__device__ __forceinline__ bool shift_product_bytes(uint32_t* res, bool minus, const int32_t* a, const int64_t* __restrict__ pv,
+                                                    int lane, int32_t* slab, const DevTables& T, bool& fault, bool trusted) {
+  using S = ShiftGeo<LOGN, true>;
+  using B = ByteGeo<LOGN>;
+  constexpr int E = S::E;
+  const uint32_t q = T.crt.q, qhalf = T.crt.qhalf;
+  uint32_t* img = reinterpret_cast<uint32_t*>(slab);
+  uint32_t vbad = 0, vmx = 0, maxv = 0, suma = 0;
+#pragma unroll
+  for (int i = 0; i < E; ++i) {
+    const uint32_t ua = (uint32_t)a[i], aa = a[i] < 0 ? 0u - ua : ua;
+    suma += aa < 256u ? aa : 256u;   // saturated: 64 * 16 * 256 fits, and one entry above 255 already fails the condition
+  }
+  const uint32_t norm1 = wave_sum_u32(suma);
+  if (norm1 > 255u) return false;   // (before v is touched: the word path loads it itself)
+  wave_sync();   // earlier reads of the image are done before it is overwritten
+  constexpr int GH = S::G / 2;   // pairs per half: two rolled halves, as shift_fill_from, to keep few 16-byte loads' registers live
+  const longlong2* __restrict__ p = reinterpret_cast<const longlong2*>(pv) + lane;
+#pragma unroll 1
+  for (int h = 0; h < 2; ++h) {
+    int32_t vh[2 * GH];
+#pragma unroll
+    for (int g = 0; g < GH; ++g) {
+      const longlong2 t = ld_stream(p + (h * GH + g) * 64);   // coefficients (h*GH + g)*128 + 2*lane, +1
+      if (trusted) vh[2 * g] = (int32_t)t.x, vh[2 * g + 1] = (int32_t)t.y;
+      else canon_pair(t, qhalf, vbad, vmx, vh[2 * g], vh[2 * g + 1]);
+    }
+#pragma unroll
+    for (int g = 0; g < GH; ++g) {
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const uint32_t uv = (uint32_t)vh[2 * g + c], av = vh[2 * g + c] < 0 ? 0u - uv : uv;
+        maxv = av > maxv ? av : maxv;
+      }
+      shift_bytes_put_raw<LOGN>(vh[2 * g], vh[2 * g + 1], lane, h * GH + g, img);
+    }
+    // A wide operand usually shows in its first half: stop there.  The word path then loads v itself, so such a term
+    // reads half of v (at worst all of it) a second time, mostly from L2; no response row of the protocols is one.
+    if (h == 0 && wave_max_u32(maxv) > 127u) return false;
+  }
+  const uint32_t bias = wave_max_u32(maxv);
+  if (!shift_bytes_ok(norm1, bias)) return false;
+  if (!trusted) fault = fault || canon_fail(vbad, vmx, qhalf);
+  wave_sync();
+  shift_bytes_bias<LOGN>(lane, bias, img);
+  wave_sync();
+  uint32_t acc[B::W];
+#pragma unroll
+  for (int k = 0; k < B::W; ++k) acc[k] = 0;
+#pragma unroll
+  for (int i = 0; i < E; ++i) {
+    uint64_t mask = __ballot(a[i] != 0);
+    while (mask) {
+      const int l = __builtin_ctzll(mask);
+      mask &= mask - 1;
+      const int32_t coef = __builtin_amdgcn_readlane(a[i], l);
+      int ln = lane;
+      asm volatile("" : "+v"(ln));   // (as shift_scan: one address register, not one per i)
+      shift_bytes_accum<LOGN>(acc, ln, S::off(i) + 2 * l, coef, img);
+    }
+  }
+  wave_sync();   // every lane's reads are over: the sums take the image's place
+  shift_bytes_park<LOGN>(acc, lane, img);
+  wave_sync();
+  int32_t prod[E];
+  shift_bytes_take<LOGN>(prod, lane, norm1 * bias, img);
+#pragma unroll
+  for (int i = 0; i < E; ++i) {
+    const uint32_t u = zq_from_centered(prod[i], q);
+    res[i] = minus ? subq(res[i], u, q) : addq(res[i], u, q);
+  }
+  return true;
+}
+
 // Producer side of Operands::oimg: the transform x (prime pi) of operand (op, off) of batch entry b, as it leaves wave_fwd
 template <int LOGN, class TM>
 __device__ __forceinline__ void store_operand_image(const uint32_t* x, const Operands& ops, uint32_t op, uint32_t off, uint32_t b,

@@ -7,6 +7,7 @@ ring degree and each of the three register layouts the script prints the worst m
 indices, for the padded addressing  word(j) = j + (j >> 5)  the kernels use and for the unpadded  word(j) = j.
 
 usage: tools/lds_conflicts.py [pad_shift ...]      (default pad shift 5)
+       tools/lds_conflicts.py bytes                (window reads of the packed-byte rotations, ByteGeo)
 """
 import sys
 
@@ -41,7 +42,37 @@ def worst(E, index, word):
     return w
 
 
+def byte_windows():
+    """ds_read_b32 of the aligned dwords that cover a lane's window of the byte image, for every dword offset c of the
+    rotation: a lane that owns E consecutive outputs (dwords lane*W + c + i, i <= W) against one that owns the dwords
+    lane + 64*k (dwords lane + 64*k + c and the next one).  LDS cycles per rotation = sum over the reads of 2 groups x
+    the worst multiplicity."""
+    for logn in (9, 10):
+        N = 1 << logn
+        W = N // 64 // 4
+
+        def cycles(reads):
+            tot = 0
+            for c in range(0, 2 * N // 4):
+                for rd in reads:
+                    for group in (range(0, 32), range(32, 64)):
+                        banks = {}
+                        for lane in group:
+                            a = rd(lane) + c
+                            banks.setdefault(a % 32, set()).add(a)
+                        tot += max(len(v) for v in banks.values())
+            return tot / (2 * N // 4)
+
+        contiguous = [lambda lane, i=i: lane * W + i for i in range(W + 1)]
+        interleaved = [lambda lane, k=k, o=o: lane + 64 * k + o for k in range(W) for o in (0, 1)]
+        print(f"N = {N}: lane owns {4 * W} consecutive outputs: {W + 1} reads, {cycles(contiguous):.0f} LDS cycles per rotation;"
+              f"   lane owns dwords lane + 64 k: {2 * W} reads, {cycles(interleaved):.0f} cycles"
+              f"   (word image: {4 * W} reads, {8 * W} cycles)")
+
+
 def main():
+    if sys.argv[1:] == ["bytes"]:
+        return byte_windows()
     shifts = [int(a) for a in sys.argv[1:]] or [5]
     for logn in (9, 10, 11):
         N, E, pats = layouts(logn)
