@@ -50,9 +50,9 @@ extern "C" {
 typedef struct rzk_ctx rzk_ctx;
 
 /* Version of this C ABI: bumped whenever an existing signature changes (rzk_wire_mat_decode gained `q` in 2,
- * version 3 added the entry points marked "v3", version 4 those marked "v4", version 5 those marked "v5", version 6 those marked "v6").  A binding checks rzk_abi_version() == RZK_ABI_VERSION after loading
+ * version 3 added the entry points marked "v3", version 4 those marked "v4", version 5 those marked "v5", version 6 those marked "v6", version 7 those marked "v7").  A binding checks rzk_abi_version() == RZK_ABI_VERSION after loading
  * the library, so that a stale or variant .so fails at load time instead of reading shifted arguments. */
-#define RZK_ABI_VERSION 6u
+#define RZK_ABI_VERSION 7u
 uint32_t rzk_abi_version(void);
 
 /* Which block of the commitment key a matrix-vector product uses (src/commit.rs:19-25). */
@@ -406,6 +406,35 @@ int rzk_fs_challenge_batch(rzk_ctx* ctx, int kind, uint32_t V, const int64_t* co
                            int64_t* d, uint8_t* digest, uint8_t* ok, size_t B);
 int rzk_fs_challenge_batch_dev(rzk_ctx* ctx, int kind, uint32_t V, const int64_t* const* fields, const uint8_t* aux32,
                                int64_t* d, uint8_t* digest, uint8_t* ok, size_t B);
+
+/* ---- rejection sampling: the step that makes a response independent of the secret (v7) ----------------------------------
+ * The scheme (BDLOP, eprint 2016/997, Fig. 2; Lyubashevsky 2012, Thm 4.6) releases z = y + d r only with probability
+ * min(1, D_sigma(z) / (M D_{v,sigma}(z))), v = d r, and otherwise starts again with a fresh y; the reference's
+ * create_response (open.rs:107-117, linear.rs:144-158, sum.rs:182-200) leaves that out, so every z it releases is a
+ * Gaussian centred at d r.  This entry point is the test (ring_zk_amd/csrc/rzk_reject.h restates it):
+ * a proof's `rows` response polynomials (Open: k, Linear: 2k, Sum: (V+1) k) are given as nparts (1 .. 4) pairs of slabs
+ * z[p], y[p]: [B][rows[p]][N], an array of field pointers as for rzk_fs_challenge_batch (a HOST array; the _dev variant's
+ * slabs, coin, accept and E are device pointers, the slabs 16-byte aligned).
+ *   per coefficient  v = centred((z - y) mod q)
+ *   per proof        S1 = sum z v, S2 = sum v^2, E = S2 - 2 S1 in exact integers over all rows and coefficients
+ *   fail             a z or y coefficient is not canonical (skipped in trusted-producer mode) | some |v| > kappa b |
+ *                    a z polynomial fails check_verify_constraint (sum c^2 < (verify_bound + 1)^2) | coin[b] outside [0, R)
+ *   accept[b]        !fail && (double)E >= 2 sigma^2 (lnM + log((coin[b] + 1) / R)), in double precision, sigma = rzk_sigma:
+ *                    coin / R < min(1, exp(E / 2 sigma^2) / M) in the log domain; coin[b]: caller-supplied, uniform in [0, R)
+ * E (may be NULL) receives E per proof: exact whenever no fail flag is set and for the norm / kappa b failures short of
+ * |E| >= 2^63 (then it is E mod 2^64); unspecified for non-canonical input.  A non-canonical coefficient clears accept[b]
+ * and is an input fault of the call as in the phase entry points: RZK_E_ARG from the host variant, the sticky word
+ * (rzk_ctx_check_inputs) from the _dev variant.  RZK_E_ARG also for nparts outside 1 .. 4, R outside [2, 2^62], lnM < 0 or
+ * not finite, NULL pointers, and unless rows N 2^24 kappa b < 2^52 and verify_bound < 2^24 (which keep |E| < 2^53 for
+ * every unflagged proof).  B == 0 is a no-op.
+ * rzk_reject_lnm(alpha) = 12 / alpha + 1 / (2 alpha^2): ln M for sigma = alpha |v|_2 (Thm 4.6).  sigma = 11 kappa b sqrt(k N)
+ * (params.rs:94-98) is alpha = 11 for ONE vector d r of k polynomials; a proof with m such vectors uses alpha = 11 / sqrt(m).
+ * Not claimed: constant time. */
+double rzk_reject_lnm(double alpha);
+int rzk_reject_batch(rzk_ctx* ctx, uint32_t nparts, const int64_t* const* z, const int64_t* const* y, const uint32_t* rows,
+                     const int64_t* coin, uint64_t R, double lnM, uint8_t* accept, int64_t* E, size_t B);
+int rzk_reject_batch_dev(rzk_ctx* ctx, uint32_t nparts, const int64_t* const* z, const int64_t* const* y, const uint32_t* rows,
+                         const int64_t* coin, uint64_t R, double lnM, uint8_t* accept, int64_t* E, size_t B);
 
 /* HIP-event timing of the last phase call's dominant kernel is exposed through these counters:
  * accumulated microseconds and launch count of the row kernel since the last reset. */

@@ -86,6 +86,10 @@ SIGNATURES = {
     # v5: Fiat-Shamir challenges from the FS1 transcript
     "rzk_fs_key_digest": (C.c_int, [_CTX, _U8]),
     "rzk_fs_challenge_batch": (C.c_int, [_CTX, C.c_int, C.c_uint32, C.c_void_p, _U8, _I64, _U8, _U8, _SZ]),
+    # v7: rejection sampling of the provers
+    "rzk_reject_lnm": (C.c_double, [C.c_double]),
+    "rzk_reject_batch": (C.c_int, [_CTX, C.c_uint32, C.c_void_p, C.c_void_p, _U32P, _I64, C.c_uint64, C.c_double, _U8, _I64,
+                                   _SZ]),
     "rzk_bench_ntt_forward_dev": (C.c_double, [_CTX, C.c_int, _U32P, _U32P, _SZ, C.c_int]),
     "rzk_debug_read_scratch": (C.c_int, [_CTX, C.c_void_p, _SZ, C.POINTER(C.c_size_t)]),
     "rzk_prof_reset": (C.c_int, [_CTX]),
@@ -95,7 +99,7 @@ SIGNATURES = {
     "rzk_prof_read_all": (C.c_int, [_CTX, C.POINTER(C.c_double), _SZ, C.POINTER(C.c_size_t)]),
     "rzk_prof_read_kernels": (C.c_int, [_CTX, C.c_char_p, _SZ, C.POINTER(C.c_size_t)]),
 }
-ABI_VERSION = 6   # include/rzk.h: RZK_ABI_VERSION
+ABI_VERSION = 7   # include/rzk.h: RZK_ABI_VERSION
 # every batched entry point also exists as a device-pointer variant with the same signature
 for _name in list(SIGNATURES):
     if _name.endswith("_batch"):

@@ -357,6 +357,33 @@ class Context:
                                                            C.c_void_p(out.data_ptr()), cnt))
         return out
 
+    # ---- rejection sampling of the provers (include/rzk.h "rejection sampling") ----------------------------
+    def reject(self, parts, coin, R: int, lnM: float):
+        """The prover's rejection test of B proofs: (accept [B] uint8, E [B] int64).
+
+        parts: 1 .. 4 pairs (z, y) of equally shaped slabs [B][...][N] that together hold every response polynomial of a
+        proof and the y it was made from (Open: [(z, y)]; Linear: [(z, y), (zp, yp)]; Sum: [(zs, ys), (zp, yp)]);
+        coin [B] int64, uniform in [0, R), 2 <= R <= 2^62; lnM = ln M >= 0 (reject_lnm)."""
+        parts = list(parts)
+        B = int(coin.shape[0])
+        if coin.ndim != 1 or not 1 <= len(parts) <= 4:
+            raise ValueError("reject: coin must be [B] and parts 1 .. 4 pairs (z, y)")
+        rows = []
+        for z, y in parts:
+            if tuple(z.shape) != tuple(y.shape) or z.ndim < 2 or int(z.shape[0]) != B or int(z.shape[-1]) != self.N:
+                raise ValueError("reject: every pair is two slabs [B][...][N] of one shape")
+            rows.append(int(np.prod(z.shape[1:-1], dtype=np.int64)))
+        accept = self._empty(coin, (B,), np.uint8)
+        E = self._empty(coin, (B,), np.int64)
+        zs, ys = [z for z, _ in parts], [y for _, y in parts]
+        dev, p = self._prep(zs + ys + [coin, accept, E], [np.int64] * (2 * len(parts) + 1) + [np.uint8, np.int64])
+        n = len(parts)
+        zp = (C.c_void_p * n)(*[q.value for q in p[:n]])
+        yp = (C.c_void_p * n)(*[q.value for q in p[n:2 * n]])
+        self._check(self._fn("rzk_reject_batch", dev)(self._h, n, zp, yp, (C.c_uint32 * n)(*rows), p[2 * n], R, float(lnM),
+                                                      p[2 * n + 1], p[2 * n + 2], B))
+        return accept, E
+
     # ---- commitment scheme (src/commit.rs) --------------------------------------------------------------------
     def commit(self, x, r):
         """CommitmentKey::commit (commit.rs:88-128) with caller-supplied r: (c, ok)."""
@@ -485,6 +512,37 @@ class Context:
         dev, p = self._prep([zs, zp, cs, cp, gs, ts, tp, u, d, acc], [np.int64] * 9 + [np.uint8])
         self._check(self._fn("rzk_sum_verify_batch", dev)(self._h, V, *p, B))
         return acc
+
+
+def reject_lnm(alpha: float) -> float:
+    """ln M = 12 / alpha + 1 / (2 alpha^2) of the rejection step for sigma = alpha |d r|_2 (rzk_reject_lnm)."""
+    return float(_lib.lib().rzk_reject_lnm(float(alpha)))
+
+
+class SeededSampler:
+    """The interface of KeyedSampler over the seeded (Philox) samplers: for tests and benchmarks, NOT for proofs anyone
+    relies on.  Every draw takes the next stream id under `seed`, so a sampler made again from the same seed repeats
+    the same sequence of draws."""
+
+    def __init__(self, ctx: Context, seed: int, stream0: int = 0):
+        self.ctx = ctx
+        self.seed = int(seed)
+        self.stream = int(stream0)
+
+    def _next_stream(self) -> int:
+        if self.stream >= 1 << 32:
+            raise OverflowError("the stream counter is exhausted: use another seed")
+        self.stream += 1
+        return self.stream - 1
+
+    def uniform(self, bound: int, lead):
+        return self.ctx.sample_uniform(self.seed, self._next_stream(), bound, lead)
+
+    def gauss(self, sigma: float, lead):
+        return self.ctx.sample_gauss(self.seed, self._next_stream(), sigma, lead)
+
+    def challenge(self, lead):
+        return self.ctx.sample_challenge(self.seed, self._next_stream(), lead)
 
 
 class KeyedSampler:

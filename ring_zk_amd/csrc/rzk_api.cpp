@@ -21,6 +21,7 @@
 #include "rzk_dev.h"
 #include "rzk_keccak.h"
 #include "rzk_plan.h"
+#include "rzk_reject.h"
 #include "rzk_tables.h"
 
 using namespace rzk;
@@ -99,6 +100,7 @@ struct rzk_ctx {
   Arena ws, stage, ws_slots;
   Arena ws_wire;                       // message codec: position table (decode) / lengths, positions, sizes (encode)
   Arena ws_fs;                         // Fiat-Shamir transcript: leaf digests of the call (and the key while it is hashed)
+  Arena ws_reject;                     // rejection sampling: one RejectPartial per response polynomial of the call
   uint64_t key_digest[kFsDigestWords] = {};   // FS1 digest of the loaded key and the context's parameters (rzk_fs_key_digest)
   bool sampler_key_set = false;                // rzk_sampler_set_key: the key of the keyed (ChaCha20) samplers, host memory only;
   uint8_t sampler_key[32] = {};                // wiped when it is cleared and in rzk_ctx_destroy
@@ -691,6 +693,7 @@ void rzk_ctx_destroy(rzk_ctx* c) {
   if (c->ws_slots.p) (void)hipFree(c->ws_slots.p);
   if (c->ws_wire.p) (void)hipFree(c->ws_wire.p);
   if (c->ws_fs.p) (void)hipFree(c->ws_fs.p);
+  if (c->ws_reject.p) (void)hipFree(c->ws_reject.p);
   if (c->ws_dkey.p) (void)hipFree(c->ws_dkey.p);
   if (c->ws_oimg.p) (void)hipFree(c->ws_oimg.p);
   if (c->stage.p) (void)hipFree(c->stage.p);
@@ -2000,6 +2003,101 @@ int rzk_fs_challenge_batch(rzk_ctx* c, int kind, uint32_t V, const int64_t* cons
   for (uint32_t f = 0; f < s.nfields; ++f) dev_fields[f] = (const int64_t*)bufs[3 + f].dev;
   rc = rzk_fs_challenge_batch_dev(c, kind, V, dev_fields, aux32, DEV(0, int64_t*), digest ? DEV(1, uint8_t*) : nullptr,
                                   ok ? DEV(2, uint8_t*) : nullptr, B);
+  if (rc != RZK_OK) {
+    const std::string keep = c->err;
+    (void)take_input_error(c);
+    c->err = keep;
+    return rc;
+  }
+  return stage_out(c, bufs);
+}
+
+// =================================================================================================
+// v7: the prover's rejection-sampling step (rzk_reject_dev.hip, rzk_reject.h)
+// =================================================================================================
+double rzk_reject_lnm(double alpha) { return reject_lnm(alpha); }
+
+namespace {
+// argument rules shared by both variants; *total = response polynomials per proof
+int reject_args(rzk_ctx* c, uint32_t nparts, const int64_t* const* z, const int64_t* const* y, const uint32_t* rows,
+                const int64_t* coin, uint64_t R, double lnM, const uint8_t* accept, uint64_t* total) {
+  if (nparts < 1 || nparts > (uint32_t)kRejectMaxParts || !z || !y || !rows || !coin || !accept)
+    return fail(c, RZK_E_ARG, "reject: 1 .. 4 parts and non-NULL z, y, rows, coin, accept expected");
+  if (R < 2 || R > kRejectMaxR) return fail(c, RZK_E_ARG, "reject: R must lie in [2, 2^62]");
+  if (!(lnM >= 0.0) || !std::isfinite(lnM)) return fail(c, RZK_E_ARG, "reject: lnM must be a finite number >= 0");
+  uint64_t t = 0;
+  for (uint32_t f = 0; f < nparts; ++f) {
+    if (!z[f] || !y[f] || rows[f] == 0) return fail(c, RZK_E_ARG, "reject: NULL slab or empty part");
+    t += rows[f];
+  }
+  const uint64_t vmax = c->b < (1ull << 28) ? c->b * c->kappa : ~0ull;
+  if (!reject_args_ok(t, c->N, vmax, c->verify_bound))
+    return fail(c, RZK_E_ARG, "reject: rows * N * 2^24 * kappa * b must stay below 2^52 (and verify_bound below 2^24)");
+  *total = t;
+  return RZK_OK;
+}
+}  // namespace
+
+int rzk_reject_batch_dev(rzk_ctx* c, uint32_t nparts, const int64_t* const* z, const int64_t* const* y, const uint32_t* rows,
+                         const int64_t* coin, uint64_t R, double lnM, uint8_t* accept, int64_t* E, size_t B) {
+  if (!c) return RZK_E_ARG;
+  if (B == 0) return RZK_OK;
+  uint64_t total = 0;
+  int rc = reject_args(c, nparts, z, y, rows, coin, R, lnM, accept, &total);
+  if (rc != RZK_OK) return rc;
+  RejectParts m{};
+  m.nparts = nparts;
+  m.N = c->N;
+  m.rows = (uint32_t)total;
+  for (uint32_t f = 0; f < nparts; ++f) {
+    if (((uintptr_t)z[f] | (uintptr_t)y[f]) & 15u) return fail(c, RZK_E_ARG, "reject: slabs must be 16-byte aligned");
+    m.first[f + 1] = m.first[f] + rows[f];
+    m.z[f] = z[f];
+    m.y[f] = y[f];
+  }
+  rc = arena_reserve(c, c->ws_reject, (size_t)B * total * sizeof(RejectPartial));
+  if (rc != RZK_OK) return rc;
+  RejectPartial* part = (RejectPartial*)c->ws_reject.p;
+  const uint64_t limit = (c->verify_bound + 1) * (c->verify_bound + 1);   // <= 2^48 (reject_args_ok)
+  LaunchCfg cfg;
+  rc = prof_begin(c, (uint64_t)B * total * c->N * 2 * sizeof(int64_t), cfg);
+  if (rc != RZK_OK) return rc;
+  rc = check_launch(c, launch_reject_stat(cfg, m, c->q, c->b * c->kappa, limit, c->trusted, part, B), "reject stat kernel");
+  if (rc != RZK_OK) return rc;
+  rc = prof_end(c);
+  if (rc != RZK_OK) return rc;
+  rc = prof_begin(c, (uint64_t)B * total * sizeof(RejectPartial), cfg);
+  if (rc != RZK_OK) return rc;
+  const double sg = (double)c->sigma;
+  rc = check_launch(c, launch_reject_decide(cfg, part, m.rows, coin, R, lnM, 2.0 * sg * sg, accept, E, c->d_bad, B),
+                    "reject decide kernel");
+  if (rc != RZK_OK) return rc;
+  return prof_end(c);
+}
+
+int rzk_reject_batch(rzk_ctx* c, uint32_t nparts, const int64_t* const* z, const int64_t* const* y, const uint32_t* rows,
+                     const int64_t* coin, uint64_t R, double lnM, uint8_t* accept, int64_t* E, size_t B) {
+  if (!c) return RZK_E_ARG;
+  if (B == 0) return RZK_OK;
+  uint64_t total = 0;
+  int rc = reject_args(c, nparts, z, y, rows, coin, R, lnM, accept, &total);
+  if (rc != RZK_OK) return rc;
+  HIPCHK(c, hipSetDevice(c->device));   // the memset below comes before the first cfg_of
+  std::vector<HostBuf> bufs = {IN(coin, B * sizeof(int64_t)), OUT(accept, B), OUT(E, E ? B * sizeof(int64_t) : 0)};
+  for (uint32_t f = 0; f < nparts; ++f) {
+    bufs.push_back(IN(z[f], polys(c, B * rows[f])));
+    bufs.push_back(IN(y[f], polys(c, B * rows[f])));
+  }
+  HIPCHK(c, hipMemsetAsync(c->d_bad, 0, sizeof(uint32_t), c->stream));
+  rc = stage_in(c, bufs);
+  if (rc != RZK_OK) return rc;
+  const int64_t *dz[kRejectMaxParts] = {}, *dy[kRejectMaxParts] = {};
+  for (uint32_t f = 0; f < nparts; ++f) {
+    dz[f] = (const int64_t*)bufs[3 + 2 * f].dev;
+    dy[f] = (const int64_t*)bufs[4 + 2 * f].dev;
+  }
+  rc = rzk_reject_batch_dev(c, nparts, dz, dy, rows, DEV(0, const int64_t*), R, lnM, DEV(1, uint8_t*),
+                            E ? DEV(2, int64_t*) : nullptr, B);
   if (rc != RZK_OK) {
     const std::string keep = c->err;
     (void)take_input_error(c);

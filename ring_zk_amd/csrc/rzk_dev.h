@@ -321,6 +321,20 @@ int launch_sample_gauss_chacha(const LaunchCfg& cfg, int64_t* out, uint64_t npol
                                uint32_t stream, double sigma);
 int launch_sample_challenge_chacha(const LaunchCfg& cfg, int64_t* out, uint64_t npoly, uint32_t n_ring, const uint32_t subkey[8],
                                    uint32_t stream, uint32_t kappa);
+// ---- rejection sampling of the provers (rzk_reject_dev.hip; definition in rzk_reject.h) --------------------------------
+struct RejectPartial;
+struct RejectParts {   // the rows response polynomials of one proof as nparts pairs of slabs (z_f, y_f), each [B][rows of f][N]
+  uint32_t nparts, N, rows;
+  uint32_t first[4 + 1];   // first polynomial of every part; first[nparts] = rows
+  const int64_t* z[4];
+  const int64_t* y[4];
+};
+// part[b * rows + j] = (S2 - 2 S1, flags) of polynomial j of proof b; slabs must be 16-byte aligned
+int launch_reject_stat(const LaunchCfg& cfg, const RejectParts& m, int64_t q, uint64_t vmax, uint64_t norm_limit, bool trusted,
+                       RejectPartial* part, uint64_t B);
+// accept[b], E[b] (may be NULL) from the partials and coin[b]; a non-canonical coefficient also sets *bad_word
+int launch_reject_decide(const LaunchCfg& cfg, const RejectPartial* part, uint32_t rows, const int64_t* coin, uint64_t R,
+                         double lnM, double two_sigma_sq, uint8_t* accept, int64_t* E, uint32_t* bad_word, uint64_t B);
 // small ring degrees (N = 4 .. 256): schoolbook products mod q, same row programs
 int launch_row_program_small(uint32_t N, const LaunchCfg& cfg, const Program* d_prog, uint32_t nrows,
                              const Operands& ops, const uint32_t* d_key_mont, const DevTables* d_T, uint32_t r2q,

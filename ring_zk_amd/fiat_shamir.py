@@ -9,7 +9,9 @@ rzk_fs_challenge_batch[_dev]): a proof is (commitment message, response), and an
     torch CUDA tensors nothing leaves the device between the phases;
   * `verify_open_wire`: the same verdict from serialized OpenProofCommitment / OpenProofResponse messages;
   * `open_prove_sampled`, `linear_prove_sampled`, `sum_prove_sampled`: the provers with r and y drawn on the device by a
-    `backend.KeyedSampler` (ChaCha20) instead of supplied by the caller.
+    `backend.KeyedSampler` (ChaCha20, DESIGN.md §11) instead of supplied by the caller;
+  * `open_prove_zk`, `linear_prove_zk`, `sum_prove_zk`: the sampled provers with the scheme's rejection step
+    (Context.reject): a response is released only once it passed, with a fresh y per attempt.
 
 `aux` (32 bytes, default zeros) binds the proofs of a call to a session or statement; prover and verifier must agree.
 Like the rest of the package every function takes numpy arrays (host entry points) or torch CUDA tensors (device entry
@@ -18,6 +20,7 @@ points on torch's current stream).
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional
 
 import numpy as np
@@ -183,3 +186,121 @@ def sum_prove_sampled(ctx, gs, xs, sampler, aux=None):
     ys = sampler.gauss(ctx.sigma, lead + (V, ctx.k))
     yp = sampler.gauss(ctx.sigma, lead + (ctx.k,))
     return sum_prove(ctx, gs, xs, rs, rp, ys, yp, aux=aux) + (rs, rp)
+
+
+# ---- zero-knowledge provers: the sampled provers plus the rejection step ------------------------------
+# z = y + d r of the provers above is a Gaussian centred at d r: stored proofs under one r average r out.  The scheme
+# releases z only with probability min(1, D_sigma(z) / (M D_{dr,sigma}(z))) and starts again with a fresh y otherwise
+# (BDLOP Fig. 2); Context.reject is that test, these provers loop over it until every proof of the batch has passed.
+COIN_R0 = (1 << 31) - 1
+
+
+def draw_coins(sampler, lead):
+    """(coin, R): one coin per proof, uniform in [0, R), from two uniform(2^30 - 1) draws of one polynomial each:
+    a = coefficient 0 of the first, b = coefficient 1 of the second, R0 = 2^31 - 1 values each,
+    coin = (a + 2^30 - 1) R0 + (b + 2^30 - 1), R = R0^2 (the largest such square below the 2^62 the entry point allows)."""
+    half = (COIN_R0 - 1) // 2
+    a = sampler.uniform(half, tuple(lead))[..., 0]
+    b = sampler.uniform(half, tuple(lead))[..., 1]
+    return ((a + half) * COIN_R0 + (b + half)).contiguous(), COIN_R0 * COIN_R0
+
+
+def zk_lnm(m: int) -> float:
+    """ln M for a proof with m response vectors of k polynomials: sigma = 11 kappa b sqrt(k N) (params.rs:94-98) is
+    alpha = 11 for one vector d r, the m vectors together have up to sqrt(m) times its norm: alpha = 11 / sqrt(m)."""
+    from .backend import reject_lnm
+
+    return reject_lnm(11.0 / math.sqrt(m))
+
+
+def _zk_rounds(ctx, sampler, m: int, max_rounds: int, prove, fresh):
+    """prove(idx) -> (outputs, ok, parts) proves the whole batch (idx None) or the proofs idx with a fresh y; outputs[i]
+    for i in `fresh` depend on y.  Returns (outputs, ok, rounds)."""
+    import torch
+
+    if not 1 <= max_rounds <= 255:
+        raise ValueError("max_rounds must lie in 1 .. 255")
+    lnM = zk_lnm(m)
+    outs, ok, parts = prove(None)
+    outs = list(outs)
+    B = int(ok.shape[0])
+    coin, R = draw_coins(sampler, (B,))
+    acc, _ = ctx.reject(parts, coin, R, lnM)
+    live = ok != 0                      # r passed the commit constraint: worth another y
+    done = live & (acc != 0)
+    rounds = torch.zeros(B, dtype=torch.uint8, device=ok.device)
+    for rnd in range(1, max_rounds):
+        idx = torch.nonzero(live & ~done).flatten()
+        if idx.numel() == 0:
+            break
+        o2, _, parts = prove(idx)
+        coin, R = draw_coins(sampler, (int(idx.numel()),))
+        acc, _ = ctx.reject(parts, coin, R, lnM)
+        a = acc != 0
+        sel = idx[a]
+        for i in fresh:
+            outs[i][sel] = o2[i][a]
+        rounds[sel] = rnd
+        done[sel] = True
+    for i in fresh:                     # a rejected attempt never leaves: what is left of round 0 is overwritten
+        outs[i][~done] = 0
+    return outs, done.to(torch.uint8), rounds
+
+
+def _batch3(x, tail: int, name: str):
+    if not wire._is_torch(x) or x.ndim != tail + 1:
+        raise ValueError(f"{name}: the zero-knowledge provers take torch CUDA tensors with one batch dimension")
+    return int(x.shape[0])
+
+
+def open_prove_zk(ctx, x, sampler, aux=None, max_rounds: int = 64):
+    """open_prove_sampled with the rejection step: (c, t, z, ok, r, rounds).  Round 0 is open_prove_sampled; each later
+    round proves the pending proofs again with the same r and a fresh y.  ok[b] = 1 iff r passed the commit constraint
+    and the proof was accepted within max_rounds, in round rounds[b]; t and z of the other proofs are zero."""
+    B = _batch3(x, 2, "open_prove_zk")
+    r = sampler.uniform(ctx.b, (B, ctx.k))
+
+    def prove(idx):
+        xs, rs = (x, r) if idx is None else (x[idx], r[idx])
+        y = sampler.gauss(ctx.sigma, (int(xs.shape[0]), ctx.k))
+        c, t, z, ok = open_prove(ctx, xs, rs, y, aux=aux)
+        return (c, t, z), ok, [(z, y)]
+
+    (c, t, z), ok, rounds = _zk_rounds(ctx, sampler, 1, max_rounds, prove, fresh=(1, 2))
+    return c, t, z, ok, r, rounds
+
+
+def linear_prove_zk(ctx, g, x, sampler, aux=None, max_rounds: int = 64):
+    """linear_prove_sampled with the rejection step over (z, z'): (c, cp, t, tp, u, z, zp, ok, r, rp, rounds)."""
+    B = _batch3(x, 2, "linear_prove_zk")
+    r = sampler.uniform(ctx.b, (B, ctx.k))
+    rp = sampler.uniform(ctx.b, (B, ctx.k))
+
+    def prove(idx):
+        gs, xs, rs, rps = (g, x, r, rp) if idx is None else (g[idx], x[idx], r[idx], rp[idx])
+        y = sampler.gauss(ctx.sigma, (int(xs.shape[0]), ctx.k))
+        yp = sampler.gauss(ctx.sigma, (int(xs.shape[0]), ctx.k))
+        c, cp, t, tp, u, z, zp, ok = linear_prove(ctx, gs, xs, rs, rps, y, yp, aux=aux)
+        return (c, cp, t, tp, u, z, zp), ok, [(z, y), (zp, yp)]
+
+    outs, ok, rounds = _zk_rounds(ctx, sampler, 2, max_rounds, prove, fresh=(2, 3, 4, 5, 6))
+    return tuple(outs) + (ok, r, rp, rounds)
+
+
+def sum_prove_zk(ctx, gs, xs, sampler, aux=None, max_rounds: int = 64):
+    """sum_prove_sampled with the rejection step over (zs, z'): (cs, cp, ts, tp, u, zs, zp, ok, rs, rp, rounds).  With
+    V summands M = exp(12 sqrt(V+1) / 11 + (V+1) / 242): the acceptance rate 1 / M falls quickly with V."""
+    B = _batch3(xs, 3, "sum_prove_zk")
+    V = int(xs.shape[-3])
+    rs = sampler.uniform(ctx.b, (B, V, ctx.k))
+    rp = sampler.uniform(ctx.b, (B, ctx.k))
+
+    def prove(idx):
+        g_, x_, rs_, rp_ = (gs, xs, rs, rp) if idx is None else (gs[idx], xs[idx], rs[idx], rp[idx])
+        ys = sampler.gauss(ctx.sigma, (int(x_.shape[0]), V, ctx.k))
+        yp = sampler.gauss(ctx.sigma, (int(x_.shape[0]), ctx.k))
+        cs, cp, ts, tp, u, zs, zp, ok = sum_prove(ctx, g_, x_, rs_, rp_, ys, yp, aux=aux)
+        return (cs, cp, ts, tp, u, zs, zp), ok, [(zs, ys), (zp, yp)]
+
+    outs, ok, rounds = _zk_rounds(ctx, sampler, V + 1, max_rounds, prove, fresh=(2, 3, 4, 5, 6))
+    return tuple(outs) + (ok, rs, rp, rounds)
