@@ -50,9 +50,9 @@ extern "C" {
 typedef struct rzk_ctx rzk_ctx;
 
 /* Version of this C ABI: bumped whenever an existing signature changes (rzk_wire_mat_decode gained `q` in 2,
- * version 3 added the entry points marked "v3", version 4 those marked "v4", version 5 those marked "v5", version 6 those marked "v6", version 7 those marked "v7").  A binding checks rzk_abi_version() == RZK_ABI_VERSION after loading
+ * version 3 added the entry points marked "v3", version 4 those marked "v4", version 5 those marked "v5", version 6 those marked "v6", version 7 those marked "v7", version 8 those marked "v8").  A binding checks rzk_abi_version() == RZK_ABI_VERSION after loading
  * the library, so that a stale or variant .so fails at load time instead of reading shifted arguments. */
-#define RZK_ABI_VERSION 7u
+#define RZK_ABI_VERSION 8u
 uint32_t rzk_abi_version(void);
 
 /* Which block of the commitment key a matrix-vector product uses (src/commit.rs:19-25). */
@@ -435,6 +435,48 @@ int rzk_reject_batch(rzk_ctx* ctx, uint32_t nparts, const int64_t* const* z, con
                      const int64_t* coin, uint64_t R, double lnM, uint8_t* accept, int64_t* E, size_t B);
 int rzk_reject_batch_dev(rzk_ctx* ctx, uint32_t nparts, const int64_t* const* z, const int64_t* const* y, const uint32_t* rows,
                          const int64_t* coin, uint64_t R, double lnM, uint8_t* accept, int64_t* E, size_t B);
+
+/* ---- fixed-width packed records "RZKP1" (v8; batched, on the GPU) ----------------------------------------------------------
+ * The bincode form above is the reference's: 8 bytes per coefficient and polynomials of variable length.  For proofs that
+ * are stored and verified later this is the compact form: every record of a kind has the same size, known on the host, and
+ * each coefficient takes the bits its field needs (ring_zk_amd/csrc/rzk_packed.h restates every rule).
+ *   record       8-byte header, then the kind's fields in the declaration order of the RZK_MSG_* table, slabs row-major
+ *   header       'R' 'Z' 'K' 'P', u8 version = 1, u8 kind, u16 V little-endian (0 for the kinds without summands)
+ *   polynomial   of width W: ceil(N W / 64) little-endian 64-bit words; coefficient i is the unsigned value raw = c + bias at
+ *                bits [i W, (i+1) W) of the bit string (bit j = bit j % 64 of word j / 64); bits above N W are zero
+ *   class Q      c cp cs t tp ts u g gs    bias (q-1)/2          largest raw q-1               W = bitlen(q-1) = 32
+ *   class Z      z zp zs                   bias verify_bound     largest raw 2 verify_bound    W = bitlen(2 verify_bound)
+ *   class D      d                         bias 1                largest raw 2                 W = 2
+ * Class Z loses nothing for a proof a verifier could accept: norm_2(z_i) <= verify_bound bounds every coefficient.
+ * Kinds: RZK_MSG_COMMITMENT, CHALLENGE, OPEN_COMMITMENT, OPEN_RESPONSE, LINEAR_COMMITMENT, SUM_COMMITMENT, SUM_RESPONSE as
+ * above, and two that exist here only (the rzk_wire_* entry points reject them):
+ *   RZK_MSG_LINEAR_RESPONSE    { z, zp }       z, zp [B][k][N]
+ *   RZK_MSG_OPEN_SHORT         { c, d, z }     c [B][n+l][N], d [B][N], z [B][k][N]: the signature form of an Open proof, the
+ *                              verifier recomputes t = a1.z - c1 (.) d and accepts iff the transcript of (c, t) gives d again
+ * RZK_MSG_OPENING is not a stored proof and is not supported.
+ * rzk_packed_record_bytes: size of one record; 0 = bad kind or V, or a context with verify_bound > (q-1)/2.
+ * rzk_packed_widths: W of classes Q and Z.
+ * rzk_packed_encode_batch: fields as for the wire codec -> records [B][record_bytes].  A coefficient outside its class's
+ *   range (a non-canonical one included) is written as the all-ones value 2^W - 1, which is above every class's largest raw,
+ *   and clears ok[b] of its message: a per-message verdict, not an input fault of the call, and a failed record never
+ *   decodes as valid.  The test is made in trusted-producer mode too: it decides whether the value fits.
+ * rzk_packed_decode_batch: ok[b] = 0 for a wrong header (magic, version, kind, V), any raw above its class's largest, or a
+ *   set padding bit; slabs of a rejected record are unspecified.  One byte string per message: encoding is canonical.
+ * RZK_E_ARG: bad kind (RZK_MSG_OPENING included), V == 0 or V > 65535 on a Sum kind, NULL pointers (ok included), records not
+ * 8-byte aligned, _dev slabs not 16-byte aligned.  B == 0 is a no-op.  The _dev variants run on the context's stream without
+ * host synchronisation or allocation; `fields` is a host array of device pointers. */
+#define RZK_MSG_LINEAR_RESPONSE 8
+#define RZK_MSG_OPEN_SHORT 9
+size_t rzk_packed_record_bytes(const rzk_ctx* ctx, int kind, uint32_t V);
+int rzk_packed_widths(const rzk_ctx* ctx, uint32_t* wq, uint32_t* wz);
+int rzk_packed_encode_batch(rzk_ctx* ctx, int kind, uint32_t V, const int64_t* const* fields, uint8_t* records, uint8_t* ok,
+                            size_t B);
+int rzk_packed_encode_batch_dev(rzk_ctx* ctx, int kind, uint32_t V, const int64_t* const* fields, uint8_t* records,
+                                uint8_t* ok, size_t B);
+int rzk_packed_decode_batch(rzk_ctx* ctx, int kind, uint32_t V, const uint8_t* records, int64_t* const* fields, uint8_t* ok,
+                            size_t B);
+int rzk_packed_decode_batch_dev(rzk_ctx* ctx, int kind, uint32_t V, const uint8_t* records, int64_t* const* fields,
+                                uint8_t* ok, size_t B);
 
 /* HIP-event timing of the last phase call's dominant kernel is exposed through these counters:
  * accumulated microseconds and launch count of the row kernel since the last reset. */

@@ -13,6 +13,8 @@ KEY_A1, KEY_A2, KEY_A = 0, 1, 2
 # message kinds of the batched wire codec (include/rzk.h "protocol messages on the wire", v4)
 (MSG_COMMITMENT, MSG_OPENING, MSG_CHALLENGE, MSG_OPEN_COMMITMENT, MSG_OPEN_RESPONSE, MSG_LINEAR_COMMITMENT,
  MSG_SUM_COMMITMENT, MSG_SUM_RESPONSE) = range(8)
+# kinds of the packed format only (include/rzk.h "fixed-width packed records", v8)
+MSG_LINEAR_RESPONSE, MSG_OPEN_SHORT = 8, 9
 
 _lib = None
 
@@ -90,6 +92,11 @@ SIGNATURES = {
     "rzk_reject_lnm": (C.c_double, [C.c_double]),
     "rzk_reject_batch": (C.c_int, [_CTX, C.c_uint32, C.c_void_p, C.c_void_p, _U32P, _I64, C.c_uint64, C.c_double, _U8, _I64,
                                    _SZ]),
+    # v8: fixed-width packed records
+    "rzk_packed_record_bytes": (C.c_size_t, [_CTX, C.c_int, C.c_uint32]),
+    "rzk_packed_widths": (C.c_int, [_CTX, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "rzk_packed_encode_batch": (C.c_int, [_CTX, C.c_int, C.c_uint32, C.c_void_p, _U8, _U8, _SZ]),
+    "rzk_packed_decode_batch": (C.c_int, [_CTX, C.c_int, C.c_uint32, _U8, C.c_void_p, _U8, _SZ]),
     "rzk_bench_ntt_forward_dev": (C.c_double, [_CTX, C.c_int, _U32P, _U32P, _SZ, C.c_int]),
     "rzk_debug_read_scratch": (C.c_int, [_CTX, C.c_void_p, _SZ, C.POINTER(C.c_size_t)]),
     "rzk_prof_reset": (C.c_int, [_CTX]),
@@ -99,7 +106,7 @@ SIGNATURES = {
     "rzk_prof_read_all": (C.c_int, [_CTX, C.POINTER(C.c_double), _SZ, C.POINTER(C.c_size_t)]),
     "rzk_prof_read_kernels": (C.c_int, [_CTX, C.c_char_p, _SZ, C.POINTER(C.c_size_t)]),
 }
-ABI_VERSION = 7   # include/rzk.h: RZK_ABI_VERSION
+ABI_VERSION = 8   # include/rzk.h: RZK_ABI_VERSION
 # every batched entry point also exists as a device-pointer variant with the same signature
 for _name in list(SIGNATURES):
     if _name.endswith("_batch"):

@@ -20,6 +20,7 @@
 #include "rzk_core.h"
 #include "rzk_dev.h"
 #include "rzk_keccak.h"
+#include "rzk_packed.h"
 #include "rzk_plan.h"
 #include "rzk_reject.h"
 #include "rzk_tables.h"
@@ -2098,6 +2099,138 @@ int rzk_reject_batch(rzk_ctx* c, uint32_t nparts, const int64_t* const* z, const
   }
   rc = rzk_reject_batch_dev(c, nparts, dz, dy, rows, DEV(0, const int64_t*), R, lnM, DEV(1, uint8_t*),
                             E ? DEV(2, int64_t*) : nullptr, B);
+  if (rc != RZK_OK) {
+    const std::string keep = c->err;
+    (void)take_input_error(c);
+    c->err = keep;
+    return rc;
+  }
+  return stage_out(c, bufs);
+}
+
+// =================================================================================================
+// v8: fixed-width packed records "RZKP1" (rzk_packed_dev.hip, rzk_packed.h)
+// =================================================================================================
+static_assert(RZK_MSG_LINEAR_RESPONSE == PK_LINEAR_RESPONSE && RZK_MSG_OPEN_SHORT == PK_OPEN_SHORT &&
+                  RZK_MSG_OPENING == PK_OPENING && RZK_MSG_SUM_RESPONSE == PK_SUM_RESPONSE,
+              "packed kinds are the RZK_MSG_* values");
+
+namespace {
+
+bool packed_schema_of(const rzk_ctx* c, int kind, uint32_t V, PackedSchema* s) {
+  return c && packed_schema(kind, c->N, c->n, c->k, c->l, V, c->q, c->verify_bound, s);
+}
+
+// argument rules shared by the four entry points; on RZK_OK *s and *sl are filled
+int packed_args(rzk_ctx* c, int kind, uint32_t V, const int64_t* const* fields, const uint8_t* records, const uint8_t* ok,
+                size_t B, PackedSchema* s, PackedSlabs* sl) {
+  if (!packed_schema_of(c, kind, V, s)) return fail(c, RZK_E_ARG, "packed codec: bad kind or V");
+  if (B == 0) return RZK_OK;   // a no-op, whatever the pointers
+  if (!fields || !records || !ok) return fail(c, RZK_E_ARG, "packed codec: NULL pointer");
+  for (int f = 0; f < kPackedMaxFields; ++f) sl->ptr[f] = nullptr;
+  for (uint32_t f = 0; f < s->nfields; ++f) {
+    if (!fields[f]) return fail(c, RZK_E_ARG, "packed codec: NULL slab");
+    sl->ptr[f] = const_cast<int64_t*>(fields[f]);
+  }
+  if ((uintptr_t)records % 8) return fail(c, RZK_E_ARG, "packed codec: records must be 8-byte aligned");
+  return RZK_OK;
+}
+
+size_t packed_field_bytes(const rzk_ctx* c, const PackedSchema& s, uint32_t f, size_t B) { return polys(c, B * (size_t)s.f[f].rows); }
+
+// one launch between preset and profile bookkeeping; decode != 0: records -> slabs
+int packed_run(rzk_ctx* c, const PackedSchema& s, const PackedSlabs& sl, uint8_t* records, uint8_t* ok, size_t B, int decode) {
+  for (uint32_t f = 0; f < s.nfields; ++f)
+    if ((uintptr_t)sl.ptr[f] % 16) return fail(c, RZK_E_ARG, "packed codec: device slabs must be 16-byte aligned");
+  HIPCHK(c, hipSetDevice(c->device));   // the memset below comes before the first cfg_of
+  HIPCHK(c, hipMemsetAsync(ok, 1, B, c->stream));
+  uint64_t slab_bytes = 0;
+  for (uint32_t f = 0; f < s.nfields; ++f) slab_bytes += packed_field_bytes(c, s, f, B);
+  LaunchCfg cfg;
+  int rc = prof_begin(c, slab_bytes + (uint64_t)B * packed_record_bytes(s), cfg);
+  if (rc != RZK_OK) return rc;
+  rc = decode ? check_launch(c, launch_packed_decode(cfg, s, sl, (const uint64_t*)records, ok, B), "packed decode kernel")
+              : check_launch(c, launch_packed_encode(cfg, s, sl, (uint64_t*)records, ok, B), "packed encode kernel");
+  if (rc != RZK_OK) return rc;
+  return prof_end(c);
+}
+
+}  // namespace
+
+size_t rzk_packed_record_bytes(const rzk_ctx* c, int kind, uint32_t V) {
+  PackedSchema s;
+  if (!packed_schema_of(c, kind, V, &s)) return 0;
+  return (size_t)packed_record_bytes(s);
+}
+
+int rzk_packed_widths(const rzk_ctx* c, uint32_t* wq, uint32_t* wz) {
+  PackedWidth w[PK_NCLASSES];
+  if (!c || !wq || !wz) return RZK_E_ARG;
+  if (!packed_widths(c->q, c->verify_bound, w)) return RZK_E_UNSUPPORTED;
+  *wq = w[PK_Q].W;
+  *wz = w[PK_Z].W;
+  return RZK_OK;
+}
+
+int rzk_packed_encode_batch_dev(rzk_ctx* c, int kind, uint32_t V, const int64_t* const* fields, uint8_t* records, uint8_t* ok,
+                                size_t B) {
+  PackedSchema s;
+  PackedSlabs sl;
+  if (!c) return RZK_E_ARG;
+  const int rc = packed_args(c, kind, V, fields, records, ok, B, &s, &sl);
+  if (rc != RZK_OK || B == 0) return rc;
+  return packed_run(c, s, sl, records, ok, B, 0);
+}
+
+int rzk_packed_decode_batch_dev(rzk_ctx* c, int kind, uint32_t V, const uint8_t* records, int64_t* const* fields, uint8_t* ok,
+                                size_t B) {
+  PackedSchema s;
+  PackedSlabs sl;
+  if (!c) return RZK_E_ARG;
+  const int rc = packed_args(c, kind, V, (const int64_t* const*)fields, records, ok, B, &s, &sl);
+  if (rc != RZK_OK || B == 0) return rc;
+  return packed_run(c, s, sl, const_cast<uint8_t*>(records), ok, B, 1);
+}
+
+int rzk_packed_encode_batch(rzk_ctx* c, int kind, uint32_t V, const int64_t* const* fields, uint8_t* records, uint8_t* ok,
+                            size_t B) {
+  PackedSchema s;
+  PackedSlabs sl;
+  if (!c) return RZK_E_ARG;
+  int rc = packed_args(c, kind, V, fields, records, ok, B, &s, &sl);
+  if (rc != RZK_OK || B == 0) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<HostBuf> bufs = {OUT(records, B * (size_t)packed_record_bytes(s)), OUT(ok, B)};
+  for (uint32_t f = 0; f < s.nfields; ++f) bufs.push_back(IN(fields[f], packed_field_bytes(c, s, f, B)));
+  HIPCHK(c, hipMemsetAsync(c->d_bad, 0, sizeof(uint32_t), c->stream));
+  rc = stage_in(c, bufs);
+  if (rc != RZK_OK) return rc;
+  for (uint32_t f = 0; f < s.nfields; ++f) sl.ptr[f] = (int64_t*)bufs[2 + f].dev;   // staged on 256-byte boundaries
+  rc = packed_run(c, s, sl, DEV(0, uint8_t*), DEV(1, uint8_t*), B, 0);
+  if (rc != RZK_OK) {
+    const std::string keep = c->err;
+    (void)take_input_error(c);
+    c->err = keep;
+    return rc;
+  }
+  return stage_out(c, bufs);
+}
+
+int rzk_packed_decode_batch(rzk_ctx* c, int kind, uint32_t V, const uint8_t* records, int64_t* const* fields, uint8_t* ok,
+                            size_t B) {
+  PackedSchema s;
+  PackedSlabs sl;
+  if (!c) return RZK_E_ARG;
+  int rc = packed_args(c, kind, V, (const int64_t* const*)fields, records, ok, B, &s, &sl);
+  if (rc != RZK_OK || B == 0) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<HostBuf> bufs = {IN(records, B * (size_t)packed_record_bytes(s)), OUT(ok, B)};
+  for (uint32_t f = 0; f < s.nfields; ++f) bufs.push_back(OUT(fields[f], packed_field_bytes(c, s, f, B)));
+  HIPCHK(c, hipMemsetAsync(c->d_bad, 0, sizeof(uint32_t), c->stream));
+  rc = stage_in(c, bufs);
+  if (rc != RZK_OK) return rc;
+  for (uint32_t f = 0; f < s.nfields; ++f) sl.ptr[f] = (int64_t*)bufs[2 + f].dev;
+  rc = packed_run(c, s, sl, DEV(0, uint8_t*), DEV(1, uint8_t*), B, 1);
   if (rc != RZK_OK) {
     const std::string keep = c->err;
     (void)take_input_error(c);

@@ -6,6 +6,7 @@
 #include <string>
 
 #include "rzk_core.h"
+#include "rzk_packed.h"
 #include "rzk_wire_walk.h"
 
 namespace rzk {
@@ -335,6 +336,15 @@ int launch_reject_stat(const LaunchCfg& cfg, const RejectParts& m, int64_t q, ui
 // accept[b], E[b] (may be NULL) from the partials and coin[b]; a non-canonical coefficient also sets *bad_word
 int launch_reject_decide(const LaunchCfg& cfg, const RejectPartial* part, uint32_t rows, const int64_t* coin, uint64_t R,
                          double lnM, double two_sigma_sq, uint8_t* accept, int64_t* E, uint32_t* bad_word, uint64_t B);
+// ---- fixed-width packed records (rzk_packed_dev.hip; format in rzk_packed.h) -------------------------------------------
+struct PackedSlabs {
+  int64_t* ptr[kPackedMaxFields];   // dense slab of every field ([B][rows of the field][N]), 16-byte aligned
+};
+// rec: [B][s.rec_words] 64-bit words.  ok[b] must hold 1 before the launch; it is cleared for a message with a coefficient
+// outside its class's range (encode: the marker is written in its place) / a record that does not decode
+int launch_packed_encode(const LaunchCfg& cfg, const PackedSchema& s, const PackedSlabs& sl, uint64_t* rec, uint8_t* ok, uint64_t B);
+int launch_packed_decode(const LaunchCfg& cfg, const PackedSchema& s, const PackedSlabs& sl, const uint64_t* rec, uint8_t* ok,
+                         uint64_t B);
 // small ring degrees (N = 4 .. 256): schoolbook products mod q, same row programs
 int launch_row_program_small(uint32_t N, const LaunchCfg& cfg, const Program* d_prog, uint32_t nrows,
                              const Operands& ops, const uint32_t* d_key_mont, const DevTables* d_T, uint32_t r2q,

@@ -8,6 +8,10 @@ rzk_fs_challenge_batch[_dev]): a proof is (commitment message, response), and an
   * `open_prove` / `open_verify`, `linear_*`, `sum_*`: commit -> challenge -> response, and challenge -> verify; with
     torch CUDA tensors nothing leaves the device between the phases;
   * `verify_open_wire`: the same verdict from serialized OpenProofCommitment / OpenProofResponse messages;
+  * `open_verify_packed`, `linear_verify_packed`, `sum_verify_packed`: the same verdicts from fixed-width packed records
+    (`packed.py`, DESIGN.md §13);
+  * `open_short` / `open_verify_short` / `open_verify_short_packed`: the signature form of an Open proof, (c, d, z): the
+    verifier recomputes t from the verification equation and accepts iff the transcript of (c, t) gives d again;
   * `open_prove_sampled`, `linear_prove_sampled`, `sum_prove_sampled`: the provers with r and y drawn on the device by a
     `backend.KeyedSampler` (ChaCha20, DESIGN.md §11) instead of supplied by the caller;
   * `open_prove_zk`, `linear_prove_zk`, `sum_prove_zk`: the sampled provers with the scheme's rejection step
@@ -25,8 +29,9 @@ from typing import Optional
 
 import numpy as np
 
-from . import wire
-from ._lib import MSG_LINEAR_COMMITMENT, MSG_OPEN_COMMITMENT, MSG_OPEN_RESPONSE, MSG_SUM_COMMITMENT
+from . import packed, wire
+from ._lib import (KEY_A1, MSG_LINEAR_COMMITMENT, MSG_LINEAR_RESPONSE, MSG_OPEN_COMMITMENT, MSG_OPEN_RESPONSE,
+                   MSG_OPEN_SHORT, MSG_SUM_COMMITMENT, MSG_SUM_RESPONSE)
 
 KINDS = (MSG_OPEN_COMMITMENT, MSG_LINEAR_COMMITMENT, MSG_SUM_COMMITMENT)
 
@@ -117,6 +122,42 @@ def verify_open_wire(ctx, commitment_msgs, response_msgs, aux=None, coef_bytes: 
     return open_verify(ctx, c, t, z, aux=aux) & ok1 & ok2
 
 
+def open_verify_packed(ctx, commitment_records, response_records, aux=None):
+    """open_verify from packed MSG_OPEN_COMMITMENT and MSG_OPEN_RESPONSE records (packed.encode_batch): decode,
+    recompute d, verify; a record that does not decode rejects its own proof."""
+    c, t, ok1 = packed.decode_batch(ctx, MSG_OPEN_COMMITMENT, commitment_records)
+    (z, ok2) = packed.decode_batch(ctx, MSG_OPEN_RESPONSE, response_records)
+    return open_verify(ctx, c, t, z, aux=aux) & ok1 & ok2
+
+
+def open_short(ctx, c, t, z, aux=None):
+    """The short form of the Open proof (c, t, z): (c, d, z) with d = challenge(c, t), as a Fiat-Shamir signature sends
+    it.  Returns d; t is dropped, the verifier recomputes it (open_verify_short).  z is left as it is."""
+    d, _, _ = challenge(ctx, MSG_OPEN_COMMITMENT, c, t, aux=aux)
+    return d
+
+
+def open_verify_short(ctx, c, d, z, aux=None):
+    """Verifier of the short form: t' = a1.z - c1 (.) d is the only t that satisfies the verification equation
+    (open.rs:171-173) for (c, d, z); accept iff the transcript of (c, t') gives d again, z passes the norm rule
+    (open_verify on (z, t', c, d), which also rejects non-canonical input) and the transcript hash accepted its input.
+    An honest proof has t' = t.  t' is computed on canonicalized copies, so that foreign data rejects its proof instead
+    of failing the call."""
+    zc, cc, dc = ctx.canonicalize(z), ctx.canonicalize(c), ctx.canonicalize(d)
+    c1 = cc[:, :ctx.n]
+    c1 = c1.contiguous() if wire._is_torch(c1) else np.ascontiguousarray(c1)
+    t = ctx.sub(ctx.matvec(KEY_A1, zc), ctx.cmul(c1, dc))
+    d2, _, okf = challenge(ctx, MSG_OPEN_COMMITMENT, c, t, aux=aux)   # the caller's c: a non-canonical one clears okf
+    same = ctx.eq(d2.reshape(-1, 1, ctx.N), dc.reshape(-1, 1, ctx.N))
+    return ctx.open_verify(z, t, c, d) & same & okf
+
+
+def open_verify_short_packed(ctx, records, aux=None):
+    """open_verify_short from packed MSG_OPEN_SHORT records; a record that does not decode rejects its own proof."""
+    c, d, z, ok = packed.decode_batch(ctx, MSG_OPEN_SHORT, records)
+    return open_verify_short(ctx, c, d, z, aux=aux) & ok
+
+
 # ---- LinearProof (src/prove/linear.rs) ---------------------------------------------------------------------------------
 def linear_prove(ctx, g, x, r, rp, y, yp, aux=None):
     """(c, cp, t, tp, u, z, zp, ok); ok[b] = 1 iff r and rp both pass the commit constraint."""
@@ -130,6 +171,13 @@ def linear_verify(ctx, c, cp, g, t, tp, u, z, zp, aux=None):
     """LinearProofVerifier::verify (linear.rs:213-250) with the recomputed challenge."""
     d, _, okf = challenge(ctx, MSG_LINEAR_COMMITMENT, c, cp, g, t, tp, u, aux=aux)
     return ctx.linear_verify(z, zp, c, cp, g, t, tp, u, d) & okf
+
+
+def linear_verify_packed(ctx, commitment_records, response_records, aux=None):
+    """linear_verify from packed MSG_LINEAR_COMMITMENT and MSG_LINEAR_RESPONSE records."""
+    c, cp, g, t, tp, u, ok1 = packed.decode_batch(ctx, MSG_LINEAR_COMMITMENT, commitment_records)
+    z, zp, ok2 = packed.decode_batch(ctx, MSG_LINEAR_RESPONSE, response_records)
+    return linear_verify(ctx, c, cp, g, t, tp, u, z, zp, aux=aux) & ok1 & ok2
 
 
 # ---- SumProof (src/prove/sum.rs) ---------------------------------------------------------------------------------------
@@ -147,6 +195,13 @@ def sum_verify(ctx, cs, cp, gs, ts, tp, u, zs, zp, aux=None):
     V = int(gs.shape[-2])
     d, _, okf = challenge(ctx, MSG_SUM_COMMITMENT, cp, cs, gs, tp, ts, u, V=V, aux=aux)
     return ctx.sum_verify(zs, zp, cs, cp, gs, ts, tp, u, d) & okf
+
+
+def sum_verify_packed(ctx, commitment_records, response_records, V: int, aux=None):
+    """sum_verify from packed MSG_SUM_COMMITMENT and MSG_SUM_RESPONSE records of V summands."""
+    cp, cs, gs, tp, ts, u, ok1 = packed.decode_batch(ctx, MSG_SUM_COMMITMENT, commitment_records, V=V)
+    zp, zs, ok2 = packed.decode_batch(ctx, MSG_SUM_RESPONSE, response_records, V=V)
+    return sum_verify(ctx, cs, cp, gs, ts, tp, u, zs, zp, aux=aux) & ok1 & ok2
 
 
 # ---- provers that draw their own randomness (backend.KeyedSampler: ChaCha20 on the device, DESIGN.md §11) ---------------
