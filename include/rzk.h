@@ -50,9 +50,9 @@ extern "C" {
 typedef struct rzk_ctx rzk_ctx;
 
 /* Version of this C ABI: bumped whenever an existing signature changes (rzk_wire_mat_decode gained `q` in 2,
- * version 3 added the entry points marked "v3", version 4 those marked "v4", version 5 those marked "v5", version 6 those marked "v6", version 7 those marked "v7", version 8 those marked "v8").  A binding checks rzk_abi_version() == RZK_ABI_VERSION after loading
+ * version 3 added the entry points marked "v3", version 4 those marked "v4", version 5 those marked "v5", version 6 those marked "v6", version 7 those marked "v7", version 8 those marked "v8", version 9 those marked "v9").  A binding checks rzk_abi_version() == RZK_ABI_VERSION after loading
  * the library, so that a stale or variant .so fails at load time instead of reading shifted arguments. */
-#define RZK_ABI_VERSION 8u
+#define RZK_ABI_VERSION 9u
 uint32_t rzk_abi_version(void);
 
 /* Which block of the commitment key a matrix-vector product uses (src/commit.rs:19-25). */
@@ -261,8 +261,10 @@ double rzk_bench_ntt_forward_dev(rzk_ctx* ctx, int prime, const uint32_t* in, ui
  *             1 <= bound <= (q-1)/2  (commit randomness r: bound = b, commit.rs:101; key / message: (q-1)/2)
  *   gauss     random_polynomial_in_normal_distribution (src/polynomial.rs:28-44): (i64) N(0, sigma), truncated
  *             toward zero like I::from_f64; y of the provers: sigma = rzk_sigma(ctx) (open.rs:88-94).  Box-Muller on a
- *             64-bit uniform (tail to 9.4 sigma); evaluated in single precision for sigma < 2^19 (sample error < 0.1
- *             before the truncation: every parameter set of the reference), in double precision up to 2^26
+ *             64-bit uniform (tail to 9.4 sigma); evaluated in single precision for sigma < 2^19 (every parameter set of
+ *             the reference; error of a sample before the truncation < 2^-24 (1.4 sigma^2 / R + 16 R) at radius R: far
+ *             below 1 except for radii below sigma / 1000 or so, where it reaches 0.47 at sigma = 21780 — the word-to-
+ *             pair map and its bound: ring_zk_amd/csrc/rzk_gauss.h), in double precision up to 2^26
  *   challenge random_polynomial_from_challenge_set (src/challenge_space.rs:12-33): exactly kappa coefficients
  *             +-1 (kappa of the context) at a uniformly random subset of positions, zeros elsewhere */
 int rzk_sample_uniform_dev(rzk_ctx* ctx, uint64_t seed, uint32_t stream, uint64_t bound, int64_t* out, size_t count);
@@ -482,6 +484,12 @@ int rzk_packed_decode_batch_dev(rzk_ctx* ctx, int kind, uint32_t V, const uint8_
  * accumulated microseconds and launch count of the row kernel since the last reset. */
 /* diagnostic: copies the row kernels' per-wave scratch lines to the host (tools/wave_timeline.py; *total = its size) */
 int rzk_debug_read_scratch(rzk_ctx* ctx, void* dst, size_t bytes, size_t* total);
+/* v9.  diagnostic: the word-to-pair map of the Gaussian samplers (ring_zk_amd/csrc/rzk_gauss.h) on words the caller
+ * chose, so that a test reaches the edges of the map that no seed or key produces.  words:[pairs][4] and out:[pairs][2] are
+ * device pointers; pair i gets what a sampler draws from a Philox block / ChaCha20 quarter with these four words: the
+ * single-precision form for f32 != 0 (sigma < 2^19; it reads three words of the four), else the double-precision form
+ * (sigma <= 2^26).  Asynchronous on the context's stream; pairs == 0 returns RZK_OK. */
+int rzk_debug_gauss_map_dev(rzk_ctx* ctx, int f32, const uint32_t* words, double sigma, int64_t* out, size_t pairs);
 int rzk_prof_reset(rzk_ctx* ctx);
 int rzk_prof_enable(rzk_ctx* ctx, int on);
 int rzk_prof_read(rzk_ctx* ctx, double* row_kernel_us, uint64_t* row_kernel_launches);

@@ -317,6 +317,22 @@ class Context:
         self._check(self._L.rzk_sample_challenge_dev(self._h, seed, stream, C.c_void_p(out.data_ptr()), cnt))
         return out
 
+    def debug_gauss_map(self, f32: bool, words, sigma: float):
+        """Diagnostic (rzk_debug_gauss_map_dev): the Gaussian samplers' word-to-pair map on chosen words.
+        words: uint32 [pairs][4] (numpy) -> int64 numpy [pairs][2]."""
+        import torch
+
+        self._bind_torch_stream()
+        w = np.ascontiguousarray(words, dtype=np.uint32)
+        if w.ndim != 2 or w.shape[1] != 4:
+            raise ValueError("words must be [pairs][4]")
+        dev = torch.device("cuda", self.device)
+        d_w = torch.from_numpy(w.view(np.int32)).to(dev)
+        out = torch.empty((w.shape[0], 2), dtype=torch.int64, device=dev)
+        self._check(self._L.rzk_debug_gauss_map_dev(self._h, 1 if f32 else 0, C.c_void_p(d_w.data_ptr()), float(sigma),
+                                                    C.c_void_p(out.data_ptr()), w.shape[0]))
+        return out.cpu().numpy()
+
     # ---- keyed samplers: the same distributions from ChaCha20 under a 256-bit key (include/rzk.h "keyed", DESIGN §11) ----
     def set_sampler_key(self, key: Optional[bytes]):
         """Key of the keyed samplers (32 bytes; None clears it).  The context keeps a copy in host memory and wipes it

@@ -1011,7 +1011,11 @@ int rzk_sample_gauss_dev(rzk_ctx* c, uint64_t seed, uint32_t stream, double sigm
   if (c && count == 0) return RZK_OK;
   // |x| stays far below (q-1)/2 for every sigma the parameters produce; 2^26 keeps 12 sigma inside the range
   if (!c || !out || !(sigma > 0.0) || sigma > 67108864.0) return RZK_E_ARG;
-  return check_launch(c, launch_sample_gauss(cfg_of(c), out, count, c->N, seed, stream, sigma), "sampler");
+  LaunchCfg cfg;   // a profiling slot when profiling is on: rzk_prof_read_kernels names the form that ran
+  int rc = prof_begin(c, (uint64_t)count * c->N * sizeof(int64_t), cfg);
+  if (rc != RZK_OK) return rc;
+  rc = check_launch(c, launch_sample_gauss(cfg, out, count, c->N, seed, stream, sigma), "sampler");
+  return rc != RZK_OK ? rc : prof_end(c);
 }
 int rzk_sample_challenge_dev(rzk_ctx* c, uint64_t seed, uint32_t stream, int64_t* out, size_t count) {
   if (c && count == 0) return RZK_OK;
@@ -1722,6 +1726,13 @@ int rzk_debug_read_scratch(rzk_ctx* c, void* dst, size_t bytes, size_t* total) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(dst, c->d_row_scratch, bytes, hipMemcpyDeviceToHost));
   return RZK_OK;
+}
+
+// Diagnostic: the Gaussian samplers' word-to-pair map on the caller's words (one thread per pair).
+int rzk_debug_gauss_map_dev(rzk_ctx* c, int f32, const uint32_t* words, double sigma, int64_t* out, size_t pairs) {
+  if (c && pairs == 0) return RZK_OK;
+  if (!c || !words || !out || !(sigma > 0.0) || sigma > 67108864.0 || (f32 && !(sigma < 524288.0))) return RZK_E_ARG;
+  return check_launch(c, launch_debug_gauss_map(cfg_of(c), f32 != 0, words, sigma, out, pairs), "gauss map kernel");
 }
 
 int rzk_prof_enable(rzk_ctx* c, int on) {

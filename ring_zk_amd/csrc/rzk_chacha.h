@@ -16,9 +16,9 @@
 //   challenge  Floyd step t uses block t >> 3, w0 = w[2 (t & 7)], w1 = w[2 (t & 7) + 1]
 // so "quarter" i of a block (words 4i .. 4i+3) is what one Philox block is to the seeded samplers: two coefficients.
 #pragma once
-#include <math.h>
 #include <stdint.h>
 
+#include "rzk_gauss.h"
 #include "rzk_rng.h"
 
 namespace rzk {
@@ -93,45 +93,8 @@ RZK_HD int64_t chacha_uniform_coef(uint32_t w_even, uint32_t w_odd, uint32_t bou
   return (int64_t)uniform_below(w_even, w_odd, 2u * bound + 1u) - (int64_t)bound;
 }
 
-// Box-Muller in single precision from the quarter (w0, w1, w2, .) = w[4i .. 4i+2] (sigma < 2^19): the radius from the
-// 64-bit uniform w0:w1 through exponent + log2 of the 24-bit mantissa, the angle from w2 — the F32 form of
-// sample_gauss_kernel (rzk_sample.h), word for word.  The conversion truncates toward zero, like I::from_f64.
-RZK_HD void chacha_gauss_pair_f32(uint32_t w0, uint32_t w1, uint32_t w2, float sigf, int64_t& v0, int64_t& v1) {
-  uint64_t X = ((uint64_t)w0 << 32) | w1;   // u0 = X 2^-64 (X = 0, probability 2^-64, is taken as 1)
-  X = X ? X : 1ull;
-  const int lz = __builtin_clzll(X);
-  const uint32_t top = (uint32_t)((X << lz) >> 40);            // 24 bits, top bit set
-  const float m = (float)top * (1.0f / 8388608.0f);            // exact: [1, 2)
-  const float ang = (float)w2 * (2.0f / 4294967296.0f);        // angle 2 pi u1, in half turns
-  float sn, cs;
-#if defined(__HIP_DEVICE_COMPILE__)
-  const float l2 = __log2f(m) - (float)(lz + 1);               // log2 u0 <= -2^-24
-  const float r = sigf * __fsqrt_rn(-1.3862943611198906f * l2);   // sigma sqrt(-2 ln u0)
-  sincospif(ang, &sn, &cs);
-#else
-  const float l2 = log2f(m) - (float)(lz + 1);
-  const float r = sigf * sqrtf(-1.3862943611198906f * l2);
-  sn = sinf(3.14159265358979323846f * ang), cs = cosf(3.14159265358979323846f * ang);
-#endif
-  v0 = (int64_t)(r * cs);
-  v1 = (int64_t)(r * sn);
-}
-
-// the double-precision form (sigma up to 2^26): 53-bit uniforms from w0:w1 and w2:w3 = w[4i .. 4i+3]
-RZK_HD void chacha_gauss_pair_f64(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, double sigma, int64_t& v0, int64_t& v1) {
-  const double k = 1.0 / 9007199254740992.0;   // 2^-53: u0 in (0, 1]
-  const double u0 = ((double)((((uint64_t)w0 << 32) | w1) >> 11) + 1.0) * k;
-  const double u1 = (double)((((uint64_t)w2 << 32) | w3) >> 11) * k;
-  const double r0 = sigma * sqrt(-2.0 * log(u0));
-  double s0, c0;
-#if defined(__HIP_DEVICE_COMPILE__)
-  sincospi(2.0 * u1, &s0, &c0);
-#else
-  s0 = sin(6.283185307179586476925 * u1), c0 = cos(6.283185307179586476925 * u1);
-#endif
-  v0 = (int64_t)(r0 * c0);
-  v1 = (int64_t)(r0 * s0);
-}
+// gauss: quarter i = w[4i .. 4i+3] goes through gauss_pair_f32 (w[4i .. 4i+2]) or gauss_pair_f64 of rzk_gauss.h, the one
+// statement of the Box-Muller map that the seeded kernel (rzk_sample.h) uses on the four words of a Philox block.
 
 // Floyd step t of a kappa-subset of N positions, j = N - kappa + t: the candidate position in [0, j] and the sign
 // (random_bool(0.5): +1 / -1) from the word pair (w0, w1) = (w[2 (t & 7)], w[2 (t & 7) + 1]) of block t >> 3.  The

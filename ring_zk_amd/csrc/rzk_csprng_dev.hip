@@ -121,8 +121,8 @@ sample_gauss_chacha_kernel(int64_t* __restrict__ out, uint64_t nquads, uint32_t 
     const QuadTask t(u, log_q);
     const Quarter w = chacha_quad_block(key, t.c, t.blk, (uint32_t)t.poly, (uint32_t)(t.poly >> 32), stream);
     int64_t v0, v1;
-    if (F32) chacha_gauss_pair_f32(w.w0, w.w1, w.w2, sigf, v0, v1);
-    else chacha_gauss_pair_f64(w.w0, w.w1, w.w2, w.w3, sigma, v0, v1);
+    if (F32) gauss_pair_f32(w.w0, w.w1, w.w2, sigf, v0, v1);
+    else gauss_pair_f64(w.w0, w.w1, w.w2, w.w3, sigma, v0, v1);
     if (t.coef() < n_ring) store_two(out + t.poly * n_ring + t.coef(), v0, v1, pair16);
   }
 }

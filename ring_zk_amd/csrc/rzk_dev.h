@@ -269,6 +269,8 @@ int launch_sample_gauss(const LaunchCfg& cfg, int64_t* out, uint64_t npoly, uint
                         uint32_t stream, double sigma);
 int launch_sample_challenge(const LaunchCfg& cfg, int64_t* out, uint64_t npoly, uint32_t n_ring, uint64_t seed,
                             uint32_t stream, uint32_t kappa);
+// the Gaussian word-to-pair map (rzk_gauss.h) on chosen words: words [pairs][4] -> out [pairs][2]
+int launch_debug_gauss_map(const LaunchCfg& cfg, bool f32, const uint32_t* words, double sigma, int64_t* out, uint64_t pairs);
 int launch_canonicalize(const LaunchCfg& cfg, const int64_t* in, int64_t* out, uint64_t ncoef, int64_t q);
 int launch_addsub(const LaunchCfg& cfg, bool sub, const int64_t* a, const int64_t* b, int64_t* out,
                   uint64_t ncoef, const DevTables* d_T, uint32_t* bad_word);

@@ -459,12 +459,23 @@ int launch_sample_gauss(const LaunchCfg& cfg, int64_t* out, uint64_t npoly, uint
   if (n_ring < 2 || (n_ring & (n_ring - 1))) return -1;
   const uint64_t ncoef = npoly * n_ring;
   const dim3 grid(grid_for((ncoef + 1) / 2, cfg.num_cus, 256, 16));
-  if (sigma < 524288.0)   // 9.4 sigma < 2^23: single precision carries every sample with an error far below 1
+  if (sigma < 524288.0)   // 9.4 sigma < 2^23: single precision carries every sample within the bound of rzk_gauss.h
     hipLaunchKernelGGL(sample_gauss_kernel<true>, grid, dim3(256), 0, (hipStream_t)cfg.stream, out, ncoef, log2_u32(n_ring), seed,
                        stream, sigma);
   else
     hipLaunchKernelGGL(sample_gauss_kernel<false>, grid, dim3(256), 0, (hipStream_t)cfg.stream, out, ncoef, log2_u32(n_ring), seed,
                        stream, sigma);
+  RZK_LAUNCH_CHECK();
+  if (cfg.launched) *cfg.launched = sigma < 524288.0 ? "sample_gauss_kernel<true>" : "sample_gauss_kernel<false>";
+  return 0;
+}
+int launch_debug_gauss_map(const LaunchCfg& cfg, bool f32, const uint32_t* words, double sigma, int64_t* out, uint64_t pairs) {
+  if (pairs == 0) return 0;
+  const dim3 grid(grid_for(pairs, cfg.num_cus, 256, 16));
+  if (f32)
+    hipLaunchKernelGGL(debug_gauss_map_kernel<true>, grid, dim3(256), 0, (hipStream_t)cfg.stream, words, out, pairs, sigma);
+  else
+    hipLaunchKernelGGL(debug_gauss_map_kernel<false>, grid, dim3(256), 0, (hipStream_t)cfg.stream, words, out, pairs, sigma);
   RZK_LAUNCH_CHECK();
   return 0;
 }

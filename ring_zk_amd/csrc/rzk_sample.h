@@ -1,6 +1,7 @@
 // rzk_sample.h - device-side samplers: uniform, Gaussian, challenge.
 // Part of the one translation unit rzk_kernels.hip (device code only; no include guards beyond #pragma once).
 #pragma once
+#include "rzk_gauss.h"
 #include "rzk_rng.h"
 #include "rzk_wave.h"
 
@@ -43,11 +44,13 @@ sample_uniform_kernel(int64_t* __restrict__ out, uint64_t ncoef, uint32_t log_ri
   }
 }
 
-// Box-Muller, one pair per Philox block.  F32 (sigma < 2^19: every sigma the parameter sets produce): the radius from a
-// 64-bit uniform through exponent + v_log_f32 of the 24-bit mantissa (no cancellation: the tail reaches 9.4 sigma), the
-// angle from a 32-bit uniform through sincospif; absolute error of a sample < 0.1 before the truncation toward zero —
-// statistical parity as for the generator itself.  Larger sigma (up to the 2^26 the entry point admits) keeps the
-// double-precision form, whose samples need more than 24 bits.
+// Box-Muller, one pair per Philox block, through the word-to-pair map of rzk_gauss.h (the definition and the error bound
+// of a sample are stated there).  F32 (sigma < 2^19: every sigma the parameter sets produce): the radius from a 64-bit
+// uniform through exponent + v_log_f32 of the 24-bit mantissa (the tail reaches 9.4 sigma), the angle from a 32-bit
+// uniform through sincospif.  The error of a sample before the truncation toward zero is far below 1 except where u0 is
+// within 2^-20 or so of 1 (the logarithm cancels: up to 0.47 at sigma = 21780, probability about 1e-5) — statistical
+// parity as for the generator itself.  Larger sigma (up to the 2^26 the entry point admits) keeps the double-precision
+// form, whose samples need more than 24 bits.
 template <bool F32>
 __global__ void __launch_bounds__(256)
 sample_gauss_kernel(int64_t* __restrict__ out, uint64_t ncoef, uint32_t log_ring, uint64_t seed, uint32_t stream,
@@ -60,30 +63,25 @@ sample_gauss_kernel(int64_t* __restrict__ out, uint64_t ncoef, uint32_t log_ring
     const uint32_t blk = (uint32_t)u & pair_mask;
     const Philox4 a = sampler_block(seed, stream, poly, blk);
     int64_t v0, v1;
-    if (F32) {
-      // u0 = X 2^-64, X = a.v[0]:a.v[1] (X = 0, probability 2^-64, is taken as 1): log2 u0 = log2 m - 1 - lz, m in [1,2)
-      uint64_t X = ((uint64_t)a.v[0] << 32) | a.v[1];
-      X = X ? X : 1ull;
-      const int lz = __builtin_clzll(X);
-      const uint32_t top = (uint32_t)((X << lz) >> 40);                  // 24 bits, top bit set
-      const float m = (float)top * (1.0f / 8388608.0f);                  // exact: [1, 2)
-      const float l2 = __log2f(m) - (float)(lz + 1);                     // <= -2^-24 (m = 2 - 2^-23, lz = 0)
-      const float r = sigf * __fsqrt_rn(-1.3862943611198906f * l2);      // sigma sqrt(-2 ln u0)
-      float sn, cs;
-      sincospif((float)a.v[2] * (2.0f / 4294967296.0f), &sn, &cs);       // angle 2 pi u1
-      v0 = (int64_t)(r * cs);                                            // conversion truncates toward zero, like I::from_f64
-      v1 = (int64_t)(r * sn);
-    } else {
-      const double k = 1.0 / 9007199254740992.0;   // 2^-53: 53-bit uniforms, u0 in (0,1]
-      const double u0 = ((double)((((uint64_t)a.v[0] << 32) | a.v[1]) >> 11) + 1.0) * k;
-      const double u1 = (double)((((uint64_t)a.v[2] << 32) | a.v[3]) >> 11) * k;
-      const double r0 = sigma * sqrt(-2.0 * log(u0));
-      double s0, c0d;
-      sincospi(2.0 * u1, &s0, &c0d);
-      v0 = (int64_t)(r0 * c0d);
-      v1 = (int64_t)(r0 * s0);
-    }
+    if (F32) gauss_pair_f32(a.v[0], a.v[1], a.v[2], sigf, v0, v1);
+    else gauss_pair_f64(a.v[0], a.v[1], a.v[2], a.v[3], sigma, v0, v1);
     store_pair(out, u * 2, ncoef, v0, v1, pair16);
+  }
+}
+
+// Diagnostic (rzk_debug_gauss_map_dev): the same map on words the caller chose, one thread per pair — how the edges of
+// the map (u0 next to 1, a full turn) reach the device's intrinsics, which no seed or key produces in a test-sized draw.
+template <bool F32>
+__global__ void __launch_bounds__(256)
+debug_gauss_map_kernel(const uint32_t* __restrict__ words, int64_t* __restrict__ out, uint64_t pairs, double sigma) {
+  const float sigf = (float)sigma;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < pairs; i += (uint64_t)gridDim.x * 256) {
+    const uint32_t* w = words + 4 * i;
+    int64_t v0, v1;
+    if (F32) gauss_pair_f32(w[0], w[1], w[2], sigf, v0, v1);
+    else gauss_pair_f64(w[0], w[1], w[2], w[3], sigma, v0, v1);
+    out[2 * i] = v0;
+    out[2 * i + 1] = v1;
   }
 }
 

@@ -4,6 +4,8 @@
 //   u32 2, key[32], nonce[16]                                             -> "hchacha <hex of the 32 bytes>"
 //   u32 3, key[32], nonce[16], u32 stream, u32 N, u32 bound, u64 poly     -> "uniform <N coefficients>"
 //   u32 4, key[32], nonce[16], u32 stream, u32 N, u32 kappa, u64 poly     -> "challenge <N coefficients>"
+//   u32 5, u32 f32, f64 sigma, u32 pairs, pairs x u32 w0 w1 w2 w3         -> "gauss <2 pairs coefficients>": the Gaussian
+//          word-to-pair map (rzk_gauss.h) on the given words, gauss_pair_f32 for f32 != 0, else gauss_pair_f64
 // The samplers are the sequential statement of what the kernels draw in parallel: one block per 8 coefficients / 8
 // Floyd steps, through the header's own word-to-coefficient maps.
 #include <cstdint>
@@ -52,6 +54,22 @@ int main(int argc, char** argv) {
   if (!f) return 2;
   uint32_t type;
   while (rd(f, &type, 4)) {
+    if (type == 5) {
+      uint32_t f32, pairs;
+      double sigma;
+      if (!rd(f, &f32, 4) || !rd(f, &sigma, 8) || !rd(f, &pairs, 4) || pairs > (1u << 24)) return 3;
+      std::vector<uint32_t> w(4 * (size_t)pairs);
+      if (!rd(f, w.data(), 4 * w.size())) return 3;
+      printf("gauss");
+      for (size_t i = 0; i < pairs; ++i) {
+        int64_t v0, v1;
+        if (f32) gauss_pair_f32(w[4 * i], w[4 * i + 1], w[4 * i + 2], (float)sigma, v0, v1);
+        else gauss_pair_f64(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3], sigma, v0, v1);
+        printf(" %lld %lld", (long long)v0, (long long)v1);
+      }
+      printf("\n");
+      continue;
+    }
     uint8_t key[32], nonce[16];
     if (!rd(f, key, 32)) return 3;
     if (type == 1) {

@@ -1,13 +1,15 @@
 """Python / numpy restatement of the keyed samplers' generator: the ChaCha20 block function (RFC 8439
-§2.3), HChaCha20 (draft-irtf-cfrg-xchacha §2.2), the counter layout, and the uniform and challenge samplers.  Test
-infrastructure: shares no code with the library; tests/test_chacha.py (CPU) and tests/test_gpu_keyed_samplers.py
-compare against it.
+§2.3), HChaCha20 (draft-irtf-cfrg-xchacha §2.2), the counter layout, the uniform and challenge samplers, and the words
+behind every coefficient pair of the Gaussian sampler (the map from words to a pair is tests/gauss_ref.py).  Test
+infrastructure: shares no code with the library; tests/test_chacha.py (CPU), tests/test_gpu_keyed_samplers.py and
+tests/test_gpu_gauss_pin.py compare against it.
 
     subkey                   = HChaCha20(key[32], nonce[16])
     block(stream, poly, blk) = ChaCha20_block(subkey, w12 = blk, w13 = poly & 0xffffffff, w14 = poly >> 32, w15 = stream)
     uniform    coefficient 8 blk + j = ((w[2j] : w[2j+1]) * (2 bound + 1) >> 64) - bound
     challenge  Floyd step t (block t >> 3, s = t & 7): pick = ((w[2s] : w[2s+1] & ~1) * (j + 1)) >> 64 with
                j = N - kappa + t, sign +1 if w[2s+1] & 1 else -1; position = pick if it is free, else j
+    gauss      coefficients 8 blk + 2i, 8 blk + 2i + 1 from quarter i of the block, w[4i .. 4i+3]
 
 All block arithmetic is vectorised over a leading axis of blocks (uint32 numpy arrays, wrap-around adds).
 """
@@ -104,3 +106,14 @@ def challenge(key: bytes, nonce: bytes, stream: int, N: int, kappa: int, polys):
             pos = j if out[p, pick] else pick
             out[p, pos] = 1 if (w1 & 1) else -1
     return out
+
+
+def gauss_words(key: bytes, nonce: bytes, stream: int, N: int, polys, quarter_xor: int = 0):
+    """uint32 [len(polys), N / 2, 4]: the word quadruple behind every coefficient pair of a Gaussian draw, quarter i of
+    block blk for the pair 4 blk + i.  quarter_xor != 0 exists for the mutation test only (pair i reads quarter
+    i ^ quarter_xor)."""
+    nblk = max(N // 8, 1)
+    w = sampler_blocks(key, nonce, stream, polys, nblk).reshape(len(polys), nblk, 4, 4)
+    if quarter_xor:
+        w = w[:, :, np.arange(4) ^ quarter_xor, :]
+    return w.reshape(len(polys), nblk * 4, 4)[:, :N // 2]

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import chacha_ref
+import gauss_ref
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 Q = 3515337053
@@ -126,3 +127,51 @@ def test_challenge_sampler_matches_reference(driver, tmp_path, N, kappa):
     assert (np.abs(have).sum(axis=-1) == kappa).all() and np.abs(have).max() == 1   # challenge_space.rs:56-82
     if kappa < N:
         assert len({have[i].tobytes() for i in range(len(combos))}) == len(combos)
+
+
+# ---- the Gaussian word-to-pair map on the host (rzk_gauss.h with libm) against tests/gauss_ref.py ---------------------------
+# Assertions and bounds are those of the GPU pin (tests/test_gpu_gauss_pin.py): gauss_ref.check.  The F32 form takes
+# sigma < 2^19, the last one being 2^19 - 1, where almost no truncation is decidable and only |got - ref| < 1 + delta
+# binds; the F64 form is held at every sigma.
+def gauss_record(f32, sigma, words):
+    w = np.ascontiguousarray(words, dtype="<u4")
+    assert w.ndim == 2 and w.shape[1] == 4
+    return struct.pack("<IIdI", 5, 1 if f32 else 0, float(sigma), len(w)) + w.tobytes()
+
+
+def host_gauss(driver, tmp_path, f32, sigma, words):
+    (got,) = run_driver(driver, tmp_path, [gauss_record(f32, sigma, words)])
+    assert got[0] == "gauss" and len(got) == 1 + 2 * len(words)
+    return np.array([int(v) for v in got[1:]], dtype=np.int64).reshape(len(words), 2)
+
+
+GAUSS_CASES = [(True, 3.0, 0.9), (True, 100.0, 0.9), (True, 21780.0, 0.9), (True, float((1 << 19) - 1), None),
+               (False, 3.0, 0.999), (False, 21780.0, 0.999), (False, float(1 << 19), 0.999), (False, float(1 << 26), 0.999)]
+GAUSS_IDS = ["%s-%g" % ("f32" if f else "f64", s) for f, s, _ in GAUSS_CASES]
+
+
+@pytest.mark.parametrize("f32,sigma,least", GAUSS_CASES, ids=GAUSS_IDS)
+def test_host_gauss_map_on_random_words(driver, tmp_path, f32, sigma, least):
+    case = GAUSS_CASES.index((f32, sigma, least))
+    words = gauss_ref.random_words(1000 + case, 100000)
+    v, d = gauss_ref.real(f32, words, sigma)
+    share = gauss_ref.decidable_share(v, d)
+    if least is not None:   # from the reference alone, before the output is looked at
+        assert share >= least, share
+    st = gauss_ref.check(host_gauss(driver, tmp_path, f32, sigma, words), v, d, GAUSS_IDS[case])
+    print("host %s sigma %g: decidable %.5f, differ from trunc(ref) %d of %d, worst (|got - ref| - 1) / delta %.3f"
+          % ("f32" if f32 else "f64", sigma, share, st.differ, st.n, st.worst))
+    assert st.undecidable == round((1 - share) * st.n)
+
+
+@pytest.mark.parametrize("f32,sigma,least", GAUSS_CASES, ids=GAUSS_IDS)
+def test_host_gauss_map_on_edge_words(driver, tmp_path, f32, sigma, least):
+    """The ends of both uniforms and of the angle, and the region where log2 u0 cancels (gauss_ref.x_edges_f32).  No
+    decidable share is asked of these words: they are chosen where the bound is at its widest."""
+    words = gauss_ref.edge_words_f32() if f32 else gauss_ref.edge_words_f64()
+    v, d = gauss_ref.real(f32, words, sigma)
+    got = host_gauss(driver, tmp_path, f32, sigma, words)
+    gauss_ref.check(got, v, d, "edge words")
+    if not f32:
+        zero = (words[:, 0] == 0xFFFFFFFF) & (words[:, 1] >= 0xFFFFF800)    # X >> 11 = 2^53 - 1: u0 = 1
+        assert zero.sum() == 32 and not got[zero].any()
