@@ -50,9 +50,9 @@ extern "C" {
 typedef struct rzk_ctx rzk_ctx;
 
 /* Version of this C ABI: bumped whenever an existing signature changes (rzk_wire_mat_decode gained `q` in 2,
- * version 3 added the entry points marked "v3", version 4 those marked "v4", version 5 those marked "v5", version 6 those marked "v6", version 7 those marked "v7", version 8 those marked "v8", version 9 those marked "v9").  A binding checks rzk_abi_version() == RZK_ABI_VERSION after loading
+ * version 3 added the entry points marked "v3", version 4 those marked "v4", version 5 those marked "v5", version 6 those marked "v6", version 7 those marked "v7", version 8 those marked "v8", version 9 those marked "v9", version 10 those marked "v10").  A binding checks rzk_abi_version() == RZK_ABI_VERSION after loading
  * the library, so that a stale or variant .so fails at load time instead of reading shifted arguments. */
-#define RZK_ABI_VERSION 9u
+#define RZK_ABI_VERSION 10u
 uint32_t rzk_abi_version(void);
 
 /* Which block of the commitment key a matrix-vector product uses (src/commit.rs:19-25). */
@@ -110,6 +110,13 @@ int rzk_key_load_dev(rzk_ctx* ctx, const int64_t* a_dev);
  * U uniform over [-(q-1)/2, (q-1)/2] (src/params.rs:126), drawn from (seed); the key is loaded and, when
  * a_host_out != NULL, also returned ([n+l][k][N], the public key material).  Statistical parity (see samplers). */
 int rzk_key_generate(rzk_ctx* ctx, uint64_t seed, int64_t* a_host_out);
+/* v10.  CommitmentKey::new (src/commit.rs:33-60) as a public function of a 32-byte seed, the way Dilithium and Kyber derive
+ * A = ExpandA(rho): the structure of rzk_key_generate, a1 = [I_n | a1'], a2 = [0 | I_l | a2'], where the general entry at row i,
+ * column j of the (n+l) x k matrix is polynomial p = i*k + j of the "XP1" expansion below under domain RZK_XOF_DOMAIN_KEY and
+ * `seed`.  The index is the position, so a verifier can recompute one entry alone, and the seed is all that has to be stored,
+ * sent or pinned.  The polynomials are produced on the device; the key is loaded through the path of rzk_key_load
+ * (classification, transform, FS1 key digest) and, when a_host_out != NULL, also returned ([n+l][k][N]). */
+int rzk_key_expand(rzk_ctx* ctx, const uint8_t seed[32], int64_t* a_host_out);
 
 /* ---- ring / Mat primitives (the Mat seam) ------------------------------------------------------------ */
 /* Polynomial::mul (src/prove/linear.rs:94; src/mat.rs:110,176): out[i] = a[i] * b[i], count polys */
@@ -479,6 +486,27 @@ int rzk_packed_decode_batch(rzk_ctx* ctx, int kind, uint32_t V, const uint8_t* r
                             size_t B);
 int rzk_packed_decode_batch_dev(rzk_ctx* ctx, int kind, uint32_t V, const uint8_t* records, int64_t* const* fields,
                                 uint8_t* ok, size_t B);
+
+/* ---- seed expansion "XP1": uniform elements of R_q from public seeds with SHAKE256 (v10) ------------------------------------
+ * Hash-to-ring for public data: commitment keys (rzk_key_expand) and the public multipliers g / g_i of Linear and Sum proofs
+ * when they are random-combination coefficients derived from a statement digest (DESIGN.md §14;
+ * ring_zk_amd/csrc/rzk_xof.h restates the format and holds the scalar form).  Never for secrets: those stay with the keyed
+ * samplers.
+ *   CH = min(N, 256), C = N / CH; W = bitlen(q - 1), mask = 2^W - 1
+ *   msg(p, c) = "RZKXP1\0U" | le64(q) | le32(N) | le32(domain) | seed[0:32] | le32(p) | le32(c)                       64 bytes
+ *   stream    = SHAKE256(msg(p, c)) read as little-endian 32-bit words; a word w gives the candidate v = w & mask, accepted
+ *               iff v < q, with the value v - (q-1)/2 (the centred residue)
+ *   chunk c of polynomial p = the first CH accepted values, in order -> coefficients c*CH .. c*CH + CH - 1
+ * Every coefficient is exactly uniform over the q residues (acceptance q / 2^W > 1/2 per word).
+ * rzk_xof_uniform_batch: seeds [B][32], out [B][rows][N]; out[b][r] is polynomial p = r under seeds[b] and `domain`.
+ *   domain RZK_XOF_DOMAIN_KEY (0) is reserved for keys: RZK_E_ARG.  Needs no loaded key.  RZK_E_ARG also for NULL pointers,
+ *   rows == 0, and in the _dev variant seeds not 8-byte aligned or out not 16-byte aligned.  B == 0 is a no-op.  The _dev
+ *   variant runs on the context's stream without host synchronisation or allocation.  There is no per-proof verdict and no
+ *   input fault: every byte string is a valid seed.
+ * Not claimed: constant time (the rejection loop has no fixed trip count; every input is public). */
+#define RZK_XOF_DOMAIN_KEY 0
+int rzk_xof_uniform_batch(rzk_ctx* ctx, const uint8_t* seeds, uint32_t domain, uint32_t rows, int64_t* out, size_t B);
+int rzk_xof_uniform_batch_dev(rzk_ctx* ctx, const uint8_t* seeds, uint32_t domain, uint32_t rows, int64_t* out, size_t B);
 
 /* HIP-event timing of the last phase call's dominant kernel is exposed through these counters:
  * accumulated microseconds and launch count of the row kernel since the last reset. */

@@ -42,6 +42,7 @@ SIGNATURES = {
     "rzk_key_load": (C.c_int, [_CTX, _I64]),
     "rzk_key_load_dev": (C.c_int, [_CTX, _I64]),
     "rzk_key_generate": (C.c_int, [_CTX, C.c_uint64, _I64]),
+    "rzk_key_expand": (C.c_int, [_CTX, _U8, _I64]),   # v10
     "rzk_polymul_batch": (C.c_int, [_CTX, _I64, _I64, _I64, _SZ]),
     "rzk_matvec_batch": (C.c_int, [_CTX, C.c_int, _I64, _I64, _I64, _SZ]),
     "rzk_cmul_batch": (C.c_int, [_CTX, _I64, C.c_uint32, _I64, _I64, _SZ]),
@@ -97,6 +98,8 @@ SIGNATURES = {
     "rzk_packed_widths": (C.c_int, [_CTX, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "rzk_packed_encode_batch": (C.c_int, [_CTX, C.c_int, C.c_uint32, C.c_void_p, _U8, _U8, _SZ]),
     "rzk_packed_decode_batch": (C.c_int, [_CTX, C.c_int, C.c_uint32, _U8, C.c_void_p, _U8, _SZ]),
+    # v10: seed expansion "XP1"
+    "rzk_xof_uniform_batch": (C.c_int, [_CTX, _U8, C.c_uint32, C.c_uint32, _I64, _SZ]),
     "rzk_bench_ntt_forward_dev": (C.c_double, [_CTX, C.c_int, _U32P, _U32P, _SZ, C.c_int]),
     "rzk_debug_read_scratch": (C.c_int, [_CTX, C.c_void_p, _SZ, C.POINTER(C.c_size_t)]),
     "rzk_debug_gauss_map_dev": (C.c_int, [_CTX, C.c_int, C.c_void_p, C.c_double, _I64, _SZ]),
@@ -107,7 +110,7 @@ SIGNATURES = {
     "rzk_prof_read_all": (C.c_int, [_CTX, C.POINTER(C.c_double), _SZ, C.POINTER(C.c_size_t)]),
     "rzk_prof_read_kernels": (C.c_int, [_CTX, C.c_char_p, _SZ, C.POINTER(C.c_size_t)]),
 }
-ABI_VERSION = 9   # include/rzk.h: RZK_ABI_VERSION
+ABI_VERSION = 10   # include/rzk.h: RZK_ABI_VERSION
 # every batched entry point also exists as a device-pointer variant with the same signature
 for _name in list(SIGNATURES):
     if _name.endswith("_batch"):

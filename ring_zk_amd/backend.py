@@ -132,6 +132,16 @@ class Context:
         self._check(self._L.rzk_key_generate(self._h, seed, C.c_void_p(a.ctypes.data)))
         return a
 
+    def expand_key(self, seed: bytes) -> np.ndarray:
+        """CommitmentKey::new as a public function of a 32-byte seed (rzk_key_expand, DESIGN §14): the general entry at
+        row i, column j is polynomial i*k + j of the XP1 expansion under domain 0.  Loads the key and returns it."""
+        seed = bytes(seed)
+        if len(seed) != 32:
+            raise ValueError("the key seed must be 32 bytes")
+        a = np.empty((self.n + self.l, self.k, self.N), dtype=np.int64)
+        self._check(self._L.rzk_key_expand(self._h, (C.c_uint8 * 32).from_buffer_copy(seed), C.c_void_p(a.ctypes.data)))
+        return a
+
     def load_key(self, A):
         """CommitmentKey as the dense matrix [a1;a2] ((n+l) x k polynomials; src/commit.rs:109-114)."""
         self._shape(A, self.n + self.l, self.k, self.N)
@@ -371,6 +381,19 @@ class Context:
         out, cnt = self._sample_out(lead)
         self._check(self._L.rzk_sample_challenge_keyed_dev(self._h, self._nonce(nonce), stream,
                                                            C.c_void_p(out.data_ptr()), cnt))
+        return out
+
+    # ---- seed expansion: uniform ring elements from public seeds with SHAKE256 (include/rzk.h "XP1") ----------
+    def xof_uniform(self, seeds, rows: int, domain: int):
+        """seeds [B, 32] uint8 -> [B, rows, N] int64: out[b][r] is polynomial r of the XP1 expansion under seeds[b] and
+        `domain` (not 0, which is the keys').  numpy seeds go through the host entry point, torch CUDA seeds through the
+        device one on torch's current stream.  For public data only."""
+        if seeds.ndim != 2 or int(seeds.shape[1]) != 32:
+            raise ValueError("xof_uniform: seeds must be [B, 32] uint8")
+        B = int(seeds.shape[0])
+        out = self._empty(seeds, (B, int(rows), self.N))
+        dev, p = self._prep([seeds, out], [np.uint8, np.int64])
+        self._check(self._fn("rzk_xof_uniform_batch", dev)(self._h, p[0], int(domain), int(rows), p[1], B))
         return out
 
     # ---- rejection sampling of the provers (include/rzk.h "rejection sampling", DESIGN §12) ----------------------------

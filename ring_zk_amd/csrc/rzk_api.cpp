@@ -24,6 +24,7 @@
 #include "rzk_plan.h"
 #include "rzk_reject.h"
 #include "rzk_tables.h"
+#include "rzk_xof.h"
 
 using namespace rzk;
 
@@ -2249,6 +2250,79 @@ int rzk_packed_decode_batch(rzk_ctx* c, int kind, uint32_t V, const uint8_t* rec
     return rc;
   }
   return stage_out(c, bufs);
+}
+
+// =================================================================================================
+// v10: commitment keys and public polynomials expanded from 32-byte seeds, "XP1" (rzk_xof_dev.hip, rzk_xof.h)
+// =================================================================================================
+static_assert(RZK_XOF_DOMAIN_KEY == kXofDomainKey, "the key domain of XP1");
+
+namespace {
+// out[b][r] = polynomial p0 + r under seeds[b] and `domain`; seeds and out on the device
+int run_xof(rzk_ctx* c, uint32_t domain, uint32_t p0, uint32_t rows, const uint64_t* seeds, int64_t* out, size_t B) {
+  const XofJob j{(uint64_t)c->q, c->N, domain, p0, rows, c->N / xof_chunk_len(c->N), xof_mask((uint64_t)c->q)};
+  LaunchCfg cfg;
+  int rc = prof_begin(c, (uint64_t)B * rows * c->N * sizeof(int64_t), cfg);
+  if (rc != RZK_OK) return rc;
+  rc = check_launch(c, launch_xof_uniform(cfg, j, seeds, out, B), "xof kernel");
+  return rc != RZK_OK ? rc : prof_end(c);
+}
+}  // namespace
+
+// CommitmentKey::new (commit.rs:33-60) as a public function of the seed: the structure rzk_key_generate builds, with the
+// general entry at row i, column j equal to polynomial i * k + j of XP1 under domain 0 (the index is the position, so
+// one entry can be recomputed alone).  One launch per key row; the key is then loaded like any other.
+int rzk_key_expand(rzk_ctx* c, const uint8_t seed[32], int64_t* a_host_out) {
+  if (!c || !seed) return RZK_E_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  const uint32_t N = c->N, n = c->n, k = c->k, l = c->l;
+  const size_t n_rand = (size_t)n * (k - n) + (size_t)l * (k - n - l);
+  auto first_general = [&](uint32_t i) { return i < n ? n : n + l; };   // a1 = [I_n | a1'], a2 = [0 | I_l | a2']
+  std::vector<int64_t> a((size_t)(n + l) * k * N, 0);
+  for (uint32_t i = 0; i < n + l; ++i) a[((size_t)i * k + i) * N] = 1;
+  if (n_rand) {
+    int rc = arena_reserve(c, c->stage, 256 + polys(c, n_rand));
+    if (rc != RZK_OK) return rc;
+    int64_t* d_out = (int64_t*)((char*)c->stage.p + 256);
+    HIPCHK(c, hipMemcpyAsync(c->stage.p, seed, 32, hipMemcpyHostToDevice, c->stream));
+    size_t next = 0;
+    for (uint32_t i = 0; i < n + l; ++i) {
+      const uint32_t j0 = first_general(i);
+      if (j0 == k) continue;
+      rc = run_xof(c, kXofDomainKey, i * k + j0, k - j0, (const uint64_t*)c->stage.p, d_out + next * N, 1);
+      if (rc != RZK_OK) return rc;
+      next += k - j0;
+    }
+    next = 0;
+    for (uint32_t i = 0; i < n + l; ++i) {   // the rows' general entries are contiguous in the matrix as in the staging slab
+      const uint32_t j0 = first_general(i);
+      if (j0 == k) continue;
+      HIPCHK(c, hipMemcpyAsync(a.data() + ((size_t)i * k + j0) * N, d_out + next * N, polys(c, k - j0), hipMemcpyDeviceToHost,
+                               c->stream));
+      next += k - j0;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  if (a_host_out) std::memcpy(a_host_out, a.data(), a.size() * sizeof(int64_t));
+  return key_load_impl(c, a.data());
+}
+
+int rzk_xof_uniform_batch_dev(rzk_ctx* c, const uint8_t* seeds, uint32_t domain, uint32_t rows, int64_t* out, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !seeds || !out || rows == 0) return RZK_E_ARG;
+  if (domain == RZK_XOF_DOMAIN_KEY) return fail(c, RZK_E_ARG, "xof: domain 0 is reserved for commitment keys (rzk_key_expand)");
+  if (((uintptr_t)seeds & 7u) || ((uintptr_t)out & 15u))
+    return fail(c, RZK_E_ARG, "xof: seeds must be 8-byte aligned and out 16-byte aligned");
+  return run_xof(c, domain, 0, rows, (const uint64_t*)seeds, out, B);
+}
+
+int rzk_xof_uniform_batch(rzk_ctx* c, const uint8_t* seeds, uint32_t domain, uint32_t rows, int64_t* out, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !seeds || !out || rows == 0) return RZK_E_ARG;
+  if (domain == RZK_XOF_DOMAIN_KEY) return fail(c, RZK_E_ARG, "xof: domain 0 is reserved for commitment keys (rzk_key_expand)");
+  HIPCHK(c, hipSetDevice(c->device));   // the memset of HOST_WRAP comes before the first cfg_of
+  std::vector<HostBuf> bufs = {IN(seeds, B * 32), OUT(out, polys(c, B * (size_t)rows))};
+  HOST_WRAP(rzk_xof_uniform_batch_dev(c, DEV(0, const uint8_t*), domain, rows, DEV(1, int64_t*), B));
 }
 
 }  // extern "C"

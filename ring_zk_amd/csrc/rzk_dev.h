@@ -347,6 +347,16 @@ struct PackedSlabs {
 int launch_packed_encode(const LaunchCfg& cfg, const PackedSchema& s, const PackedSlabs& sl, uint64_t* rec, uint8_t* ok, uint64_t B);
 int launch_packed_decode(const LaunchCfg& cfg, const PackedSchema& s, const PackedSlabs& sl, const uint64_t* rec, uint8_t* ok,
                          uint64_t B);
+// ---- seed expansion "XP1" (rzk_xof_dev.hip; format in rzk_xof.h) ---------------------------------------------------------
+struct XofJob {
+  uint64_t q;
+  uint32_t N, domain;
+  uint32_t p0, rows;   // out[b][r] is polynomial p0 + r under seeds[b]
+  uint32_t chunks;     // N / min(N, 256)
+  uint32_t mask;       // 2^bitlen(q - 1) - 1
+};
+// seeds: [B][4] little-endian 64-bit words (8-byte aligned), out: [B][rows][N] (16-byte aligned), both on the device
+int launch_xof_uniform(const LaunchCfg& cfg, const XofJob& j, const uint64_t* seeds, int64_t* out, uint64_t B);
 // small ring degrees (N = 4 .. 256): schoolbook products mod q, same row programs
 int launch_row_program_small(uint32_t N, const LaunchCfg& cfg, const Program* d_prog, uint32_t nrows,
                              const Operands& ops, const uint32_t* d_key_mont, const DevTables* d_T, uint32_t r2q,

@@ -12,6 +12,7 @@ rzk_fs_challenge_batch[_dev]): a proof is (commitment message, response), and an
     (`packed.py`, DESIGN.md §13);
   * `open_short` / `open_verify_short` / `open_verify_short_packed`: the signature form of an Open proof, (c, d, z): the
     verifier recomputes t from the verification equation and accepts iff the transcript of (c, t) gives d again;
+  * `multipliers`: the public multipliers g / g_i of Linear and Sum proofs derived from seeds (DESIGN.md §14);
   * `open_prove_sampled`, `linear_prove_sampled`, `sum_prove_sampled`: the provers with r and y drawn on the device by a
     `backend.KeyedSampler` (ChaCha20, DESIGN.md §11) instead of supplied by the caller;
   * `open_prove_zk`, `linear_prove_zk`, `sum_prove_zk`: the sampled provers with the scheme's rejection step
@@ -87,6 +88,17 @@ def challenge(ctx, kind: int, *slabs, V: Optional[int] = None, aux=None):
     fields = (C.c_void_p * len(slabs))(*[wire._ptr(s).value for s in slabs])
     ctx._check(fn(ctx._h, kind, V or 0, fields, _aux(aux), wire._ptr(d), wire._ptr(digest), wire._ptr(ok), B))
     return d, digest, ok
+
+
+def multipliers(ctx, seeds, V: Optional[int] = None, domain: int = 1):
+    """Public multipliers of Linear / Sum proofs as uniform ring elements derived from seeds [B, 32] uint8 (statement
+    digests, say) by the XP1 expansion (Context.xof_uniform): g [B, N] for V = None, the shape
+    linear_prove takes, or gs [B, V, N] for sum_prove.  Prover and verifier call this with the same seeds and domain."""
+    if V is None:
+        return ctx.xof_uniform(seeds, 1, domain).reshape(-1, ctx.N)
+    if V < 1:
+        raise ValueError("multipliers: V must be at least 1")
+    return ctx.xof_uniform(seeds, V, domain)
 
 
 def _flag(cond):
