@@ -50,9 +50,9 @@ extern "C" {
 typedef struct rzk_ctx rzk_ctx;
 
 /* Version of this C ABI: bumped whenever an existing signature changes (rzk_wire_mat_decode gained `q` in 2,
- * version 3 added the entry points marked "v3", version 4 those marked "v4", version 5 those marked "v5", version 6 those marked "v6", version 7 those marked "v7", version 8 those marked "v8", version 9 those marked "v9", version 10 those marked "v10").  A binding checks rzk_abi_version() == RZK_ABI_VERSION after loading
+ * version 3 added the entry points marked "v3", version 4 those marked "v4", version 5 those marked "v5", version 6 those marked "v6", version 7 those marked "v7", version 8 those marked "v8", version 9 those marked "v9", version 10 those marked "v10", version 11 those marked "v11").  A binding checks rzk_abi_version() == RZK_ABI_VERSION after loading
  * the library, so that a stale or variant .so fails at load time instead of reading shifted arguments. */
-#define RZK_ABI_VERSION 10u
+#define RZK_ABI_VERSION 11u
 uint32_t rzk_abi_version(void);
 
 /* Which block of the commitment key a matrix-vector product uses (src/commit.rs:19-25). */
@@ -306,6 +306,27 @@ int rzk_sample_gauss_keyed_dev(rzk_ctx* ctx, const uint8_t nonce[16], uint32_t s
                                size_t count);
 int rzk_sample_challenge_keyed_dev(rzk_ctx* ctx, const uint8_t nonce[16], uint32_t stream, int64_t* out, size_t count);
 
+/* ---- the exact discrete Gaussian (v11) ------------------------------------------------------------------------------
+ * rzk_sample_gauss_dev / rzk_sample_gauss_keyed_dev truncate a continuous normal toward zero: 0 carries the mass of
+ * (-1, 1), about twice that of +-1, which is not the distribution D_sigma that the provers' rejection step
+ * (rzk_reject_batch) assumes of y.  This sampler draws from D_sigma over the integers itself, P(v) proportional to
+ * exp(-v^2 / 2 sigma^2), for an INTEGER sigma in [1, 2^26], in integer operations alone: the binary-Gaussian rejection
+ * sampler of BLISS (Ducas, Durmus, Lepoint, Lyubashevsky 2013, Alg. 10-12).  The acceptance probability of a trial is
+ * within eps_B = 2^-61 of the exact one, the tail is cut at 8k >= 9.4 sigma (mass < 2^-63), and the sigma realised
+ * differs from the one asked for by less than 2^-73 relative (ring_zk_amd/csrc/rzk_dgauss.h states the sampler and the
+ * error budget, DESIGN.md §15 the argument).  Being integer-only it is the same function of its words on every machine.
+ * Stream: the subkey of the other keyed samplers; trial t of coefficient pair j of polynomial p reads
+ *   ChaCha20_block(subkey, words 12..15 = 0x80000000 | t << 16 | j, p lo, p hi, stream)
+ * (bit 31 of word 12 keeps these blocks apart from the other samplers' under the same key, nonce and stream); a
+ * coefficient takes its first accepted trial, t < 160, and is 0 if there is none (probability < 2^-117).  Output is a
+ * function of (key, nonce, stream, polynomial index, coefficient) alone.
+ * count is the number of COEFFICIENTS written to out and must be a multiple of N (out: [count / N][N]).  RZK_E_ARG for
+ * sigma = 0 or sigma > 2^26, no key set, a NULL nonce or out, a count that is no multiple of N; count == 0 returns RZK_OK.
+ * Not claimed: constant time — the number of trials of a coefficient, and with it the kernel's queue traffic, depends on
+ * the value drawn. */
+int rzk_sample_dgauss_keyed_dev(rzk_ctx* ctx, const uint8_t nonce[16], uint32_t stream, uint32_t sigma, int64_t* out,
+                                size_t count);
+
 /* ---- wire format of one Mat (host only) ---------------------------------------------------------------------------- */
 /* bincode layout of the reference's Mat<I,N> (serde derive at src/mat.rs:11-14; bincode default options as in
  * the reference's own test src/mat.rs:424-438: little-endian, u64 length prefixes):
@@ -518,6 +539,10 @@ int rzk_debug_read_scratch(rzk_ctx* ctx, void* dst, size_t bytes, size_t* total)
  * single-precision form for f32 != 0 (sigma < 2^19; it reads three words of the four), else the double-precision form
  * (sigma <= 2^26).  Asynchronous on the context's stream; pairs == 0 returns RZK_OK. */
 int rzk_debug_gauss_map_dev(rzk_ctx* ctx, int f32, const uint32_t* words, double sigma, int64_t* out, size_t pairs);
+/* v11, diagnostic: one trial of the exact discrete Gaussian sampler (dgauss_trial of rzk_dgauss.h) on words the caller
+ * chose.  words: device, [trials][8] (words 6 and 7 are not used); out: device, [trials][2] = (accepted 0 / 1, the
+ * candidate's signed value).  sigma as rzk_sample_dgauss_keyed_dev. */
+int rzk_debug_dgauss_trial_dev(rzk_ctx* ctx, uint32_t sigma, const uint32_t* words, int64_t* out, size_t trials);
 int rzk_prof_reset(rzk_ctx* ctx);
 int rzk_prof_enable(rzk_ctx* ctx, int on);
 int rzk_prof_read(rzk_ctx* ctx, double* row_kernel_us, uint64_t* row_kernel_launches);

@@ -75,6 +75,8 @@ SIGNATURES = {
     "rzk_sample_uniform_keyed_dev": (C.c_int, [_CTX, _U8, C.c_uint32, C.c_uint64, _I64, _SZ]),
     "rzk_sample_gauss_keyed_dev": (C.c_int, [_CTX, _U8, C.c_uint32, C.c_double, _I64, _SZ]),
     "rzk_sample_challenge_keyed_dev": (C.c_int, [_CTX, _U8, C.c_uint32, _I64, _SZ]),
+    # v11: the exact discrete Gaussian (count in coefficients)
+    "rzk_sample_dgauss_keyed_dev": (C.c_int, [_CTX, _U8, C.c_uint32, C.c_uint32, _I64, _SZ]),
     "rzk_wire_mat_size": (C.c_size_t, [_I64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "rzk_wire_mat_encode": (C.c_int, [_I64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _U8, _SZ,
                                       C.POINTER(C.c_size_t)]),
@@ -103,6 +105,7 @@ SIGNATURES = {
     "rzk_bench_ntt_forward_dev": (C.c_double, [_CTX, C.c_int, _U32P, _U32P, _SZ, C.c_int]),
     "rzk_debug_read_scratch": (C.c_int, [_CTX, C.c_void_p, _SZ, C.POINTER(C.c_size_t)]),
     "rzk_debug_gauss_map_dev": (C.c_int, [_CTX, C.c_int, C.c_void_p, C.c_double, _I64, _SZ]),
+    "rzk_debug_dgauss_trial_dev": (C.c_int, [_CTX, C.c_uint32, C.c_void_p, _I64, _SZ]),   # v11
     "rzk_prof_reset": (C.c_int, [_CTX]),
     "rzk_prof_enable": (C.c_int, [_CTX, C.c_int]),
     "rzk_prof_read": (C.c_int, [_CTX, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
@@ -110,7 +113,7 @@ SIGNATURES = {
     "rzk_prof_read_all": (C.c_int, [_CTX, C.POINTER(C.c_double), _SZ, C.POINTER(C.c_size_t)]),
     "rzk_prof_read_kernels": (C.c_int, [_CTX, C.c_char_p, _SZ, C.POINTER(C.c_size_t)]),
 }
-ABI_VERSION = 10   # include/rzk.h: RZK_ABI_VERSION
+ABI_VERSION = 11   # include/rzk.h: RZK_ABI_VERSION
 # every batched entry point also exists as a device-pointer variant with the same signature
 for _name in list(SIGNATURES):
     if _name.endswith("_batch"):

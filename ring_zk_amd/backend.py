@@ -343,6 +343,22 @@ class Context:
                                                     C.c_void_p(out.data_ptr()), w.shape[0]))
         return out.cpu().numpy()
 
+    def debug_dgauss_trial(self, words, sigma: int):
+        """Diagnostic (rzk_debug_dgauss_trial_dev): one trial of the exact discrete Gaussian sampler on chosen words.
+        words: uint32 [trials][8] (numpy) -> int64 numpy [trials][2] = (accepted, value)."""
+        import torch
+
+        self._bind_torch_stream()
+        w = np.ascontiguousarray(words, dtype=np.uint32)
+        if w.ndim != 2 or w.shape[1] != 8:
+            raise ValueError("words must be [trials][8]")
+        dev = torch.device("cuda", self.device)
+        d_w = torch.from_numpy(w.view(np.int32)).to(dev)
+        out = torch.empty((w.shape[0], 2), dtype=torch.int64, device=dev)
+        self._check(self._L.rzk_debug_dgauss_trial_dev(self._h, int(sigma), C.c_void_p(d_w.data_ptr()),
+                                                       C.c_void_p(out.data_ptr()), w.shape[0]))
+        return out.cpu().numpy()
+
     # ---- keyed samplers: the same distributions from ChaCha20 under a 256-bit key (include/rzk.h "keyed", DESIGN §11) ----
     def set_sampler_key(self, key: Optional[bytes]):
         """Key of the keyed samplers (32 bytes; None clears it).  The context keeps a copy in host memory and wipes it
@@ -374,6 +390,16 @@ class Context:
         out, cnt = self._sample_out(lead)
         self._check(self._L.rzk_sample_gauss_keyed_dev(self._h, self._nonce(nonce), stream, float(sigma),
                                                        C.c_void_p(out.data_ptr()), cnt))
+        return out
+
+    def sample_dgauss_keyed(self, nonce: bytes, stream: int, sigma: int, lead):
+        """[*lead][N] coefficients from the exact discrete Gaussian D_sigma over the integers (integer sigma in
+        [1, 2^26]; rzk_sample_dgauss_keyed_dev), from the keyed generator."""
+        if int(sigma) != sigma:
+            raise ValueError("sample_dgauss_keyed: sigma must be an integer")
+        out, cnt = self._sample_out(lead)
+        self._check(self._L.rzk_sample_dgauss_keyed_dev(self._h, self._nonce(nonce), stream, int(sigma),
+                                                        C.c_void_p(out.data_ptr()), cnt * self.N))
         return out
 
     def sample_challenge_keyed(self, nonce: bytes, stream: int, lead):
@@ -618,3 +644,15 @@ class KeyedSampler:
 
     def challenge(self, lead):
         return self.ctx.sample_challenge_keyed(self._next_nonce(), self.STREAM, lead)
+
+
+class ExactKeyedSampler(KeyedSampler):
+    """KeyedSampler whose `gauss` draws from the exact discrete Gaussian D_sigma (Context.sample_dgauss_keyed, DESIGN
+    §15) instead of the truncated Box-Muller normal: the y that the provers' rejection step assumes.  sigma must be
+    integral (the library's sigma = 11 kappa beta sqrt(kN) is rounded by rzk_sigma).  Nonces, uniform and challenge
+    draws are KeyedSampler's."""
+
+    def gauss(self, sigma, lead):
+        if int(sigma) != sigma:
+            raise ValueError("ExactKeyedSampler.gauss: sigma must be an integer")
+        return self.ctx.sample_dgauss_keyed(self._next_nonce(), self.STREAM, int(sigma), lead)

@@ -19,6 +19,7 @@
 #include "rzk_chacha.h"
 #include "rzk_core.h"
 #include "rzk_dev.h"
+#include "rzk_dgauss.h"
 #include "rzk_keccak.h"
 #include "rzk_packed.h"
 #include "rzk_plan.h"
@@ -1070,6 +1071,18 @@ int rzk_sample_gauss_keyed_dev(rzk_ctx* c, const uint8_t nonce[16], uint32_t str
   if (rc != RZK_OK) return rc;
   return keyed_end(c, launch_sample_gauss_chacha(cfg, out, count, c->N, sk, stream, sigma), sk);
 }
+// v11: the exact discrete Gaussian D_sigma (rzk_dgauss.h); count is in coefficients here
+int rzk_sample_dgauss_keyed_dev(rzk_ctx* c, const uint8_t nonce[16], uint32_t stream, uint32_t sigma, int64_t* out,
+                                size_t count) {
+  if (c && count == 0) return RZK_OK;
+  if (!c || !out || sigma == 0 || sigma > kDgaussSigmaMax || count % c->N != 0) return RZK_E_ARG;
+  const size_t npoly = count / c->N;
+  uint32_t sk[8];
+  LaunchCfg cfg;
+  const int rc = keyed_begin(c, nonce, npoly, sk, cfg);
+  if (rc != RZK_OK) return rc;
+  return keyed_end(c, launch_sample_dgauss_chacha(cfg, out, npoly, c->N, sk, stream, sigma), sk);
+}
 int rzk_sample_challenge_keyed_dev(rzk_ctx* c, const uint8_t nonce[16], uint32_t stream, int64_t* out, size_t count) {
   if (c && count == 0) return RZK_OK;
   if (!c || !out) return RZK_E_ARG;
@@ -1734,6 +1747,13 @@ int rzk_debug_gauss_map_dev(rzk_ctx* c, int f32, const uint32_t* words, double s
   if (c && pairs == 0) return RZK_OK;
   if (!c || !words || !out || !(sigma > 0.0) || sigma > 67108864.0 || (f32 && !(sigma < 524288.0))) return RZK_E_ARG;
   return check_launch(c, launch_debug_gauss_map(cfg_of(c), f32 != 0, words, sigma, out, pairs), "gauss map kernel");
+}
+
+// Diagnostic: one trial of the exact discrete Gaussian sampler on the caller's words (one thread per trial).
+int rzk_debug_dgauss_trial_dev(rzk_ctx* c, uint32_t sigma, const uint32_t* words, int64_t* out, size_t trials) {
+  if (c && trials == 0) return RZK_OK;
+  if (!c || !words || !out || sigma == 0 || sigma > kDgaussSigmaMax) return RZK_E_ARG;
+  return check_launch(c, launch_debug_dgauss_trial(cfg_of(c), sigma, words, out, trials), "dgauss trial kernel");
 }
 
 int rzk_prof_enable(rzk_ctx* c, int on) {

@@ -1,5 +1,6 @@
 // rzk_csprng_dev.hip — the keyed device samplers: uniform, Gaussian and challenge polynomials drawn from ChaCha20 blocks
-// (stream definition and word-to-coefficient maps: rzk_chacha.h).  Same distributions, launch shapes and
+// (stream definition and word-to-coefficient maps: rzk_chacha.h), and the exact discrete Gaussian
+// (rzk_dgauss.h; its kernel is described where it stands).  Same distributions, launch shapes and
 // store discipline as the seeded samplers (rzk_sample.h); only the source of the words differs.
 //
 // Layout: a QUAD of lanes computes one ChaCha20 block.  Lane c = lane & 3 holds column c of the 4 x 4 state
@@ -15,6 +16,7 @@
 
 #include "rzk_chacha.h"
 #include "rzk_dev.h"
+#include "rzk_dgauss.h"
 
 namespace rzk {
 
@@ -189,6 +191,114 @@ sample_challenge_chacha_kernel(int64_t* __restrict__ out, uint64_t npoly, uint32
   }
 }
 
+// ---- the exact discrete Gaussian (rzk_dgauss.h) -----------------------------------------------------------
+// A trial round of one coefficient pair is one block, so one quad computes it; its two trials are one lane each.  A pair g
+// of the call (polynomial g >> log_h, pair g & (N / 2 - 1)) writes out[2g], out[2g + 1], so a TILE of kDgaussTile
+// consecutive pairs is a contiguous piece of the output, whatever N is, and may span polynomials or be cut by the end of
+// the call.
+//
+// A wavefront owns a tile and walks it in generations: generation t is the list of the tile's pairs that still have an
+// open coefficient after t trials — every item of a generation is at the same trial number, so an item is (pair within
+// the tile, 2-bit mask of open coefficients) and the queue is two lists in LDS, the one being read and the one being
+// filled.  A round takes up to 32 items, two per quad: the quad computes block A, then block B, and then every lane
+// runs one trial — lanes 0, 1 the coefficients 2j, 2j + 1 of A (words 0 .. 7, 8 .. 15), lanes 2, 3 those of B.  Accepted
+// values go to the tile in LDS, items with a coefficient still open are appended to the next list at ballot / mbcnt
+// positions.  The loops end by their counters (t < kDgaussTMax, the list length): no exit depends on the random words
+// alone.  The tile leaves as lane-consecutive 16-byte pieces (store_two).
+constexpr uint32_t kDgaussTile = 128;   // pairs per tile: 2 KiB of results + 512 B of lists per wavefront
+
+// Words 8 coef .. 8 coef + 5 of the lane's item, of block A (quarters qa) in lanes 0, 1 of the quad and of block B (qb) in
+// lanes 2, 3: the quarter of lane 2 coef ([0, 2, 0, 2]) and two words of lane 2 coef + 1 ([1, 3, 1, 3]).
+// CALL WITH ALL 64 LANES ACTIVE: a quad permutation reads 0 from a lane that is masked off.  That is why A and B are
+// both permuted in every lane before ?: chooses, and why the choice lives in here and not with the caller.
+struct DgaussWords {
+  uint32_t w0, w1, w2, w3, w4, w5;
+};
+__device__ __forceinline__ DgaussWords dgauss_lane_words(const Quarter& qa, const Quarter& qb, bool second) {
+  const Quarter lo_a = {quad_perm<0x88>(qa.w0), quad_perm<0x88>(qa.w1), quad_perm<0x88>(qa.w2), quad_perm<0x88>(qa.w3)};
+  const Quarter lo_b = {quad_perm<0x88>(qb.w0), quad_perm<0x88>(qb.w1), quad_perm<0x88>(qb.w2), quad_perm<0x88>(qb.w3)};
+  const uint32_t hi_a0 = quad_perm<0xDD>(qa.w0), hi_a1 = quad_perm<0xDD>(qa.w1);
+  const uint32_t hi_b0 = quad_perm<0xDD>(qb.w0), hi_b1 = quad_perm<0xDD>(qb.w1);
+  return {second ? lo_b.w0 : lo_a.w0, second ? lo_b.w1 : lo_a.w1, second ? lo_b.w2 : lo_a.w2,
+          second ? lo_b.w3 : lo_a.w3, second ? hi_b0 : hi_a0,     second ? hi_b1 : hi_a1};
+}
+
+__global__ void __launch_bounds__(256)
+sample_dgauss_chacha_kernel(int64_t* __restrict__ out, uint64_t npairs, uint32_t log_h, ChaChaKey key, uint32_t stream,
+                            DgaussParams P) {
+  __shared__ __attribute__((aligned(16))) int64_t s_tile[4][2 * kDgaussTile];
+  __shared__ uint16_t s_list[4][2][kDgaussTile];
+  const uint32_t lane = threadIdx.x & 63u, c = lane & 3u, quad = lane >> 2, coef = c & 1u;
+  const bool second = (c & 2u) != 0;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  int64_t* tile = s_tile[wave];
+  const bool pair16 = (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
+  const uint64_t ntiles = (npairs + kDgaussTile - 1) / kDgaussTile;
+  for (uint64_t tl = (uint64_t)blockIdx.x * 4 + wave; tl < ntiles; tl += (uint64_t)gridDim.x * 4) {
+    const uint64_t base = tl * kDgaussTile;
+    const uint32_t cnt0 = npairs - base < kDgaussTile ? (uint32_t)(npairs - base) : kDgaussTile;
+    for (uint32_t i = lane; i < kDgaussTile; i += 64) {
+      tile[2 * i] = 0, tile[2 * i + 1] = 0;                     // a coefficient that runs out of trials is 0
+      s_list[wave][0][i] = (uint16_t)(i | (3u << 8));
+    }
+    wave_sync();
+    uint32_t cnt = cnt0, cur = 0;
+    for (uint32_t t = 0; t < kDgaussTMax && cnt != 0; ++t) {
+      const uint16_t* list = s_list[wave][cur];
+      uint16_t* next = s_list[wave][cur ^ 1u];
+      uint32_t ncnt = 0;
+      const auto block_of = [&](uint32_t item) {                 // the block of trial t of the item's pair
+        const uint64_t g = base + (item & 0xffu);
+        const uint64_t poly = g >> log_h;
+        const uint32_t j = (uint32_t)g & ((1u << log_h) - 1u);
+        return chacha_quad_block(key, c, dgauss_w12(t, j), (uint32_t)poly, (uint32_t)(poly >> 32), stream);
+      };
+      for (uint32_t b0 = 0; b0 < cnt; b0 += 32) {
+        const uint32_t idx_a = b0 + quad, idx_b = idx_a + 16;
+        uint32_t item_a = 0, item_b = 0;                         // mask 0: nothing open
+        Quarter qa = {0, 0, 0, 0}, qb = {0, 0, 0, 0};
+        if (idx_a < cnt) item_a = list[idx_a], qa = block_of(item_a);   // whole quads
+        if (idx_b < cnt) item_b = list[idx_b], qb = block_of(item_b);
+        // reconverged: the two fetches above diverge on whole quads only, and every lane of the wavefront is in this loop
+        // (b0 and cnt are uniform), so all 64 lanes are active here, as dgauss_lane_words and the permutations of `still`
+        // below need
+        const uint32_t item = second ? item_b : item_a, pi = item & 0xffu;   // pi < kDgaussTile
+        const DgaussWords w = dgauss_lane_words(qa, qb, second);
+        int64_t v;
+        const bool acc = dgauss_trial(P, w.w0, w.w1, w.w2, w.w3, w.w4, w.w5, v);
+        const bool open = ((item >> (8u + coef)) & 1u) != 0;
+        if (open && acc) tile[2 * pi + coef] = v;
+        const uint32_t still = open && !acc ? 1u : 0u;
+        const uint32_t mask_a = quad_perm<0x00>(still) | (quad_perm<0x55>(still) << 1);   // from lanes 0 and 1
+        const uint32_t mask_b = quad_perm<0xAA>(still) | (quad_perm<0xFF>(still) << 1);   // from lanes 2 and 3
+        const uint32_t mask = second ? mask_b : mask_a;
+        const bool push = coef == 0 && mask != 0;                // lane 0 for A, lane 2 for B
+        const uint64_t bal = __ballot(push);
+        const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+        if (push) next[ncnt + before] = (uint16_t)(pi | (mask << 8));
+        ncnt += (uint32_t)__popcll(bal);                         // <= the items read: the list cannot overflow
+      }
+      wave_sync();
+      cnt = __builtin_amdgcn_readfirstlane(ncnt), cur ^= 1u;
+    }
+    wave_sync();
+    for (uint32_t i = lane; i < cnt0; i += 64) store_two(out + 2 * (base + i), tile[2 * i], tile[2 * i + 1], pair16);
+    wave_sync();
+  }
+}
+
+// Diagnostic (rzk_debug_dgauss_trial_dev): the trial on words the caller chose, one thread per trial
+__global__ void __launch_bounds__(256)
+debug_dgauss_trial_kernel(const uint32_t* __restrict__ words, int64_t* __restrict__ out, uint64_t trials, DgaussParams P) {
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < trials; i += (uint64_t)gridDim.x * 256) {
+    const uint32_t* w = words + 8 * i;
+    int64_t v;
+    const bool acc = dgauss_trial(P, w[0], w[1], w[2], w[3], w[4], w[5], v);
+    out[2 * i] = acc ? 1 : 0;
+    out[2 * i + 1] = v;
+  }
+}
+
 unsigned grid_for(uint64_t tasks, int num_cus, uint32_t per_block, uint32_t blocks_per_cu) {
   uint64_t blocks = (tasks + per_block - 1) / per_block;
   const uint64_t cap = (uint64_t)num_cus * blocks_per_cu;
@@ -242,6 +352,30 @@ int launch_sample_gauss_chacha(const LaunchCfg& cfg, int64_t* out, uint64_t npol
                        key_of(subkey), stream, sigma);
   RZK_LAUNCH_CHECK();
   if (cfg.launched) *cfg.launched = f32 ? "sample_gauss_chacha_kernel<true>" : "sample_gauss_chacha_kernel<false>";
+  return 0;
+}
+
+int launch_sample_dgauss_chacha(const LaunchCfg& cfg, int64_t* out, uint64_t npoly, uint32_t n_ring, const uint32_t subkey[8],
+                                uint32_t stream, uint32_t sigma) {
+  if (npoly == 0) return 0;
+  if (!ring_ok(n_ring) || n_ring > (1u << 16) || sigma == 0 || sigma > kDgaussSigmaMax) return -1;   // the pair index has 16 bits of w12
+  uint32_t log_h = 0;
+  while ((2u << log_h) < n_ring) ++log_h;
+  const uint64_t npairs = npoly << log_h;
+  const uint64_t ntiles = (npairs + kDgaussTile - 1) / kDgaussTile;
+  hipLaunchKernelGGL(sample_dgauss_chacha_kernel, dim3(grid_for(ntiles, cfg.num_cus, 4, 8)), dim3(256), 0, (hipStream_t)cfg.stream,
+                     out, npairs, log_h, key_of(subkey), stream, dgauss_params(sigma));
+  RZK_LAUNCH_CHECK();
+  if (cfg.launched) *cfg.launched = "sample_dgauss_chacha_kernel";
+  return 0;
+}
+
+int launch_debug_dgauss_trial(const LaunchCfg& cfg, uint32_t sigma, const uint32_t* words, int64_t* out, uint64_t trials) {
+  if (trials == 0) return 0;
+  if (sigma == 0 || sigma > kDgaussSigmaMax) return -1;
+  hipLaunchKernelGGL(debug_dgauss_trial_kernel, dim3(grid_for(trials, cfg.num_cus, 256, 16)), dim3(256), 0, (hipStream_t)cfg.stream,
+                     words, out, trials, dgauss_params(sigma));
+  RZK_LAUNCH_CHECK();
   return 0;
 }
 

@@ -324,6 +324,11 @@ int launch_sample_gauss_chacha(const LaunchCfg& cfg, int64_t* out, uint64_t npol
                                uint32_t stream, double sigma);
 int launch_sample_challenge_chacha(const LaunchCfg& cfg, int64_t* out, uint64_t npoly, uint32_t n_ring, const uint32_t subkey[8],
                                    uint32_t stream, uint32_t kappa);
+// the exact discrete Gaussian D_sigma, integer sigma in [1, 2^26] (definition and stream: rzk_dgauss.h), and its trial
+// on chosen words: words [trials][8] -> out [trials][2] = (accepted, value)
+int launch_sample_dgauss_chacha(const LaunchCfg& cfg, int64_t* out, uint64_t npoly, uint32_t n_ring, const uint32_t subkey[8],
+                                uint32_t stream, uint32_t sigma);
+int launch_debug_dgauss_trial(const LaunchCfg& cfg, uint32_t sigma, const uint32_t* words, int64_t* out, uint64_t trials);
 // ---- rejection sampling of the provers (rzk_reject_dev.hip; definition in rzk_reject.h) --------------------------------
 struct RejectPartial;
 struct RejectParts {   // the rows response polynomials of one proof as nparts pairs of slabs (z_f, y_f), each [B][rows of f][N]
