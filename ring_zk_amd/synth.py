@@ -132,6 +132,137 @@ def tight_terms(N: int, target: int, nterms: int, rng, q=Q_DEFAULT, nz=4) -> lis
     return out
 
 
+# ---- norm-predicate edges (verdict edges) ------------------------------------------------------------------------
+# The fused norm predicate sum c^2 < L, L = (bound + 1)^2, is decided by a float total outside the band
+# L (1 +- 2 kNormSlack) = L (1 +- 2^-16) (rzk_wave.h) and by an exact integer sum inside it.  norm_edge builds one
+# polynomial with a chosen exact sum of squares and a chosen placement of the weight over lanes, registers and halves.
+NORM_STYLES = ("point", "spread", "upper", "lower", "lastreg", "wave2")
+NORM_CLAMP = 1 << 24          # lane_sum_sq_exact clamps magnitudes here; norm_edge stays below it
+NORM_BAND_IN = 2.0 ** -17     # |S / L - 1| <= this: inside the band by more than the float total's 2^-18
+NORM_BAND_OUT = 2.0 ** -15    # |S / L - 1| >= this: the float total decides
+
+
+def four_squares(m: int, nonzero: bool = False):
+    """(a, b, c, d), a >= b >= c >= d >= 0, a^2 + b^2 + c^2 + d^2 == m (Lagrange), by search from the largest a; with
+    nonzero every part is positive (None where m has no such split: 1, 3, 5, 9, 11, 17, 29, 41 and 4^j {2, 6, 14})."""
+    if nonzero:
+        odd = m
+        while odd and odd % 4 == 0:
+            odd //= 4
+        if m < 4 or m in (5, 9, 11, 17, 29, 41) or odd in (2, 6, 14):
+            return None
+    a = isqrt(m)
+    while a >= 0 and 4 * a * a >= m:
+        r1 = m - a * a
+        b = min(isqrt(r1), a)
+        while b >= 0 and 3 * b * b >= r1:
+            r2 = r1 - b * b
+            c = min(isqrt(r2), b)
+            while c >= 0 and 2 * c * c >= r2:
+                d = isqrt(r2 - c * c)
+                if d * d == r2 - c * c and (d > 0 or not nonzero):
+                    return a, b, c, d
+                c -= 1
+            b -= 1
+        a -= 1
+    assert nonzero, m
+    return None
+
+
+def _filled(count: int, S: int, rng) -> np.ndarray:
+    """count non-zero coefficients with random signs and sum of squares exactly S: count - 5 of magnitude
+    floor(sqrt(S / count)), the last five absorb the remainder (one free magnitude + a four-squares split with every
+    part positive)."""
+    assert count > 5 and S >= 9 * count
+    base = isqrt(S // count)
+    rest = S - (count - 5) * base * base
+    e = isqrt(rest - 4)
+    while True:
+        assert e > 0
+        four = four_squares(rest - e * e, nonzero=True)
+        if four is not None:
+            break
+        e -= 1
+    mags = np.array([base] * (count - 5) + [e] + list(four), dtype=np.int64)
+    return mags * rng.choice(np.array([-1, 1], dtype=np.int64), count)
+
+
+def norm_edge(N: int, S: int, style: str, pos: int, rng) -> np.ndarray:
+    """One polynomial with sum of squares exactly S and every |c| < 2^24.
+
+      point    [m, a, b, c, d], m = floor(sqrt(S)), a^2 + b^2 + c^2 + d^2 = S - m^2, from coefficient pos on, wrapping
+               past N - 1 (pos is ignored by the other styles)
+      spread   all N coefficients non-zero, random signs: every lane and register carries weight
+      upper    the same over coefficients >= N / 2 only (the second wavefront of a two-wavefront team, the second rolled
+               half of a load)
+      lower    over coefficients < N / 2 only
+      lastreg  over coefficients >= N - 64 only
+      wave2    over coefficients with bit 6 set only: thread t of a team holds coefficients e * LANES + t (Geo::j_p1), so
+               with 128 threads these are exactly the second wavefront's, with 64 the odd registers
+    """
+    out = np.zeros(N, dtype=np.int64)
+    if style == "point":
+        m = isqrt(S)
+        vals = [m] + list(four_squares(S - m * m))
+        for i, v in enumerate(vals):
+            out[(pos + i) % N] = v
+    elif style == "spread":
+        out[:] = _filled(N, S, rng)
+    elif style == "upper":
+        out[N // 2:] = _filled(N // 2, S, rng)
+    elif style == "lower":
+        out[:N // 2] = _filled(N // 2, S, rng)
+    elif style == "lastreg":
+        out[N - 64:] = _filled(64, S, rng)
+    elif style == "wave2":
+        out[(np.arange(N) & 64) != 0] = _filled(N // 2, S, rng)
+    else:
+        raise ValueError(style)
+    assert sq_norm(out) == S and int(np.abs(out).max()) < NORM_CLAMP
+    return out
+
+
+def norm_plan(L: int) -> dict:
+    """Sums of squares around the limit L = (bound + 1)^2 of a norm predicate.  'below' / 'at' / 'above' (L - 1, L,
+    L + 1) lie inside the band, where only the exact sum can decide; lo_in .. hi_out sit ceil(L 2^-19) on either side of
+    the band's own edges L (1 -+ 2^-16), where either path may run; 'far_lo' / 'far_hi' (L (1 -+ 2^-15)) are decided by
+    the float total."""
+    step = -(-L // (1 << 19))
+    lo, hi = L - (L + (1 << 15)) // (1 << 16), L + (L + (1 << 15)) // (1 << 16)
+    return {"below": L - 1, "at": L, "above": L + 1,
+            "lo_out": lo - step, "lo_in": lo + step, "hi_in": hi - step, "hi_out": hi + step,
+            "far_lo": L - -(-L // (1 << 15)), "far_hi": L + -(-L // (1 << 15))}
+
+
+def norm_path(S: int, L: int) -> str:
+    """'exact' / 'float' / 'edge' from exact rational arithmetic: which path must (or, 'edge', may) decide S against L."""
+    dev = abs(S - L)
+    if dev * (1 << 17) <= L:
+        return "exact"
+    if dev * (1 << 15) >= L:
+        return "float"
+    return "edge"
+
+
+def fault_positions(N: int, rows: int, offset: int = 0):
+    """One (row, coefficient) per coefficient position, the row cycling and stepping once more per 64 coefficients:
+    row = (i % 64 + i // 64 + offset) % rows.  A thread of a 64-lane team holds coefficients e * 64 + lane, so every row
+    meets every register index e, and every lane as soon as rows <= N / 64, whatever rows has in common with 64.  In a
+    two-wavefront team (coefficients e * 128 + t) that holds for odd rows; an even number of rows ties the row's parity
+    to the thread, which a second pass with offset 1 undoes."""
+    return [((i % 64 + i // 64 + offset) % rows, i) for i in range(N)]
+
+
+def sweep_faults(N: int, rows: int, pass_: int):
+    """Position sweep over a batch of N entries, pass 0 or 1: entry i carries one fault at fault_positions[i] (offset =
+    pass), except the clean entries, (i + i // 64) % 8 == 4 * pass: one in eight, on other lanes in the next register.
+    Returns (entries, rows, coefficients) of the faulted entries; the two passes together reach every coefficient."""
+    fp = fault_positions(N, rows, pass_)
+    ent = [i for i in range(N) if (i + i // 64) % 8 != 4 * pass_]
+    return (np.array(ent, dtype=np.int64), np.array([fp[i][0] for i in ent], dtype=np.int64),
+            np.array([fp[i][1] for i in ent], dtype=np.int64))
+
+
 def edge_targets(np_: int) -> dict:
     """Exact results around the capacity H = (P_np - 1) / 2 of np_ primes.  'under' (H (1 - 2^-10)), 'below' (H - 1)
     and 'at' (H) fit np_ primes, but only 'under' lies outside the kernels' 2^-12 safety margin, so it is the one that
