@@ -1,5 +1,5 @@
 // rzk_chacha.h — ChaCha20 (RFC 8439) as the generator of the keyed device samplers, shared by the GPU
-// kernels (rzk_csprng_dev.hip), the host side of the entry points (rzk_api.cpp: the subkey) and the CPU test
+// kernels (rzk_csprng_dev.hip), the host side of the entry points (rzk_samplers.cpp: the subkey) and the CPU test
 // (tests/test_chacha.py, g++).  Plain C++.
 //
 // Stream of one call (fixed to the byte):

@@ -1,4 +1,4 @@
-// rzk_dev.h — structures shared by the kernels (rzk_kernels.hip and the family headers it includes), the host planner (rzk_plan.h) and the C-ABI host code (rzk_api.cpp).
+// rzk_dev.h — structures shared by the kernels (rzk_kernels.hip and the family headers it includes), the host planner (rzk_plan.h) and the C-ABI host code (rzk_ctx.h and the rzk_*.cpp files behind it).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -185,7 +185,7 @@ struct Operands {
   uint32_t trusted;
   // != 0: the launch itself initialises every verdict flag to this value before its rows can clear it — only set when
   // one team evaluates ALL rows of a batch entry and flags are per entry (unit kernels with units_per_task = all, group 1);
-  // otherwise the host presets the flags with a fill launch of its own (rzk_api.cpp, run_program)
+  // otherwise the host presets the flags with a fill launch of its own (rzk_run.cpp, run_program)
   uint32_t preset;
   // Per-entry multiplier images (TERM_DKEY, row_kernel only): the scalar polynomials g_i of the Linear / Sum proofs, which
   // every vector x vector row of a proof multiplies by, transformed ONCE per proof and call (dkey_transform_kernel) into

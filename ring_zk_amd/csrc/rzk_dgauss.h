@@ -1,6 +1,6 @@
 // rzk_dgauss.h — the exact discrete Gaussian sampler D_sigma over the integers, in integer operations alone: the one
 // statement of its parameters, of one trial and of its word stream.  Shared by the kernels
-// (rzk_csprng_dev.hip), the host side of the entry point (rzk_api.cpp: the parameters) and the CPU test
+// (rzk_csprng_dev.hip), the host side of the entry point (rzk_samplers.cpp: the parameters) and the CPU test
 // (tests/test_dgauss_host.py, g++).  Host + device, plain C++; the same function of its words on every machine, so
 // tests/dgauss_ref.py (Python integers) is compared with it bit for bit.
 //

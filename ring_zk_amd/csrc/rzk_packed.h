@@ -1,5 +1,5 @@
 // rzk_packed.h — the fixed-width packed proof format "RZKP1" (include/rzk.h "packed records"), shared by
-// the GPU codec (rzk_packed_dev.hip), the entry points (rzk_api.cpp: sizes and argument rules) and the CPU test
+// the GPU codec (rzk_packed_dev.hip), the entry points (rzk_codec.cpp: sizes and argument rules) and the CPU test
 // (tests/test_packed_host.py, g++).  Plain C++.
 //
 // A record of kind K is one 8-byte header followed by the fields of the kind in the declaration order of the RZK_MSG_*

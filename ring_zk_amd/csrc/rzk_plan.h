@@ -1,7 +1,7 @@
 // rzk_plan.h — the row-program planner: writes the rows, terms and additions of every protocol phase (ProgId) and
 // derives what decides the launch path (flags, row blocks, row groups, units / items / pairs, shared-operand slots,
 // traffic counts).  Host-only and pure: a plan is a function of (PlanEnv, id, variant), so it is tested without a GPU
-// (tests/test_plan.py).  rzk_api.cpp uploads the tables of a plan and launches what path_of() names.
+// (tests/test_plan.py).  rzk_run.cpp uploads the tables of a plan and launches what path_of() names.
 #pragma once
 #include <cstring>
 #include <map>

@@ -1,0 +1,346 @@
+// rzk_protocols.cpp — the device-pointer entry points of the ring / Mat primitives, the commitment scheme and the Open,
+// Linear and Sum proofs (include/rzk.h): each is a short sequence of row programs and norm kernels (rzk_run.cpp).
+#include "rzk_ctx.h"
+
+namespace {
+
+// accept &= check_verify_constraint(z) && (a1.z == t + c1 (.) d)      (open.rs:167-173, sum.rs:262-298)
+// specs: z[k], t[n], c[n+l], d.  group / batch / nflags as in run_program; preset: initialise accept.
+// n == 1: one launch, the d-product is a rotation term inside the relation row.  n >= 2 (and rotations +
+// row groups available): a1.z as ONE grouped launch (each z_j transformed once for the n rows, norm predicate
+// fused) into `w`, then the relation rows as pure rotations (shift_row_kernel) — 18 instead of 48 transform
+// units per (4,9,4) relation.
+// Verifier side: non-canonical prover data clears the proof's verdict, the call itself succeeds (sticky = false).
+int run_a1_relation(rzk_ctx* c, const std::vector<OpSpec>& specs, int64_t* w, uint8_t* accept, uint32_t group,
+                    uint64_t batch, uint64_t nflags, bool preset) {
+  // (at N = 2048 the first step runs as row blocks and the second as transform products)
+  const bool blocks = !c->small && c->logn >= 10 && c->logn >= c->block_min_logn;
+  const bool split = w && c->n >= 2 && ((shift_ok(c) && c->use_groups && c->group_max > 1) || blocks);
+  const NormSpec z_norm = {specs[0].base, group * c->k, preset ? 0 : 1, 0};
+  if (!split)
+    return run_checked(c, PG_A1_RELATION, 0, specs, accept, group, batch, nflags, c->verify_bound, preset, false, {z_norm});
+  int rc = run_checked(c, PG_A1Z, 0, {specs[0], {w, c->n, 0}}, accept, group, batch, nflags, c->verify_bound, preset, false,
+                       {z_norm});
+  if (rc != RZK_OK) return rc;
+  return run_program(c, PG_REL_ROT, 0, {{w, c->n, 0}, specs[1], specs[2], specs[3]}, accept, group, batch, 0, false);
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- ring / Mat primitives -----------------------------------------------------------------------------------------
+int rzk_polymul_batch_dev(rzk_ctx* c, const int64_t* a, const int64_t* b, int64_t* out, size_t count) {
+  if (c && count == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !a || !b || !out) return RZK_E_ARG;
+  return run_program(c, PG_POLYMUL, 0, {{a, 1, 0}, {b, 1, 0}, {out, 1, 0}}, nullptr, 1, count);
+}
+
+int rzk_matvec_batch_dev(rzk_ctx* c, int which, const int64_t* v, const int64_t* addend, int64_t* out, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !v || !out || which < 0 || which > 2) return RZK_E_ARG;
+  const uint32_t rows = which == RZK_KEY_A1 ? c->n : (which == RZK_KEY_A2 ? c->l : c->n + c->l);
+  return run_program(c, PG_MATVEC, (uint32_t)which * 2 + (addend ? 1 : 0),
+                     {{v, c->k, 0}, {addend, rows, 0}, {out, rows, 0}}, nullptr, 1, B);
+}
+
+int rzk_cmul_batch_dev(rzk_ctx* c, const int64_t* m, uint32_t rows, const int64_t* p, int64_t* out, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !m || !p || !out || rows == 0) return RZK_E_ARG;
+  if (rows > (uint32_t)kMaxRows) {
+    // more rows than one program holds: treat every row as its own batch entry sharing p
+    return run_program(c, PG_CMUL, 1, {{m, 1, 0}, {p, 1, 1}, {out, 1, 0}}, nullptr, rows, B * rows);
+  }
+  return run_program(c, PG_CMUL, rows, {{m, rows, 0}, {p, 1, 0}, {out, rows, 0}}, nullptr, 1, B);
+}
+
+int rzk_canonicalize_batch_dev(rzk_ctx* c, const int64_t* in, int64_t* out, size_t count) {
+  if (c && count == 0) return RZK_OK;
+  if (!c || !in || !out) return RZK_E_ARG;
+  return check_launch(c, launch_canonicalize(cfg_of(c), in, out, (uint64_t)count * c->N, c->q), "canonicalize kernel");
+}
+
+int rzk_add_batch_dev(rzk_ctx* c, const int64_t* a, const int64_t* b, int64_t* out, size_t count) {
+  if (c && count == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !a || !b || !out) return RZK_E_ARG;
+  return check_launch(c, launch_addsub(cfg_of(c), false, a, b, out, (uint64_t)count * c->N, c->dT, c->d_bad), "add kernel");
+}
+
+int rzk_sub_batch_dev(rzk_ctx* c, const int64_t* a, const int64_t* b, int64_t* out, size_t count) {
+  if (c && count == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !a || !b || !out) return RZK_E_ARG;
+  return check_launch(c, launch_addsub(cfg_of(c), true, a, b, out, (uint64_t)count * c->N, c->dT, c->d_bad), "sub kernel");
+}
+
+int rzk_norm2_le_batch_dev(rzk_ctx* c, const int64_t* v, uint32_t rows, uint64_t bound, uint8_t* ok, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !v || !ok || rows == 0) return RZK_E_ARG;
+  return run_norm(c, v, rows, bound, ok, B, 0, 0);
+}
+
+int rzk_eq_batch_dev(rzk_ctx* c, const int64_t* a, const int64_t* b, uint32_t rows, uint8_t* eq, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !a || !b || !eq || rows == 0) return RZK_E_ARG;
+  const uint32_t qh = c->hT.crt.qhalf;
+  if (c->small) return check_launch(c, launch_eq_small(c->N, cfg_of(c), a, b, rows, eq, B, qh, c->d_bad), "eq kernel");
+  return check_launch(c, launch_eq((int)c->logn, cfg_of(c), a, b, rows, eq, B, qh, c->d_bad), "eq kernel");
+}
+
+int rzk_ntt_forward_batch_dev(rzk_ctx* c, int prime, const uint32_t* in, uint32_t* out, size_t count) {
+  if (c && count == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !in || !out || prime < 0 || prime >= kMaxPrimes) return RZK_E_ARG;
+  if (c->small) return fail(c, RZK_E_UNSUPPORTED, "batched transforms need N >= 512");
+  return check_launch(c, launch_ntt((int)c->logn, false, cfg_of(c), prime, in, out, count, c->dT, c->d_tw), "ntt forward");
+}
+
+int rzk_ntt_inverse_batch_dev(rzk_ctx* c, int prime, const uint32_t* in, uint32_t* out, size_t count) {
+  if (c && count == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !in || !out || prime < 0 || prime >= kMaxPrimes) return RZK_E_ARG;
+  if (c->small) return fail(c, RZK_E_UNSUPPORTED, "batched transforms need N >= 512");
+  return check_launch(c, launch_ntt((int)c->logn, true, cfg_of(c), prime, in, out, count, c->dT, c->d_tw), "ntt inverse");
+}
+
+uint32_t rzk_ntt_prime(int prime) { return prime >= 0 && prime < kMaxPrimes ? kPrimes[prime] : 0; }
+uint32_t rzk_ntt_psi(int prime, uint32_t N) {
+  if (prime < 0 || prime >= kMaxPrimes || N == 0 || (N & (N - 1)) || N > (uint32_t)kTableLen) return 0;
+  return host::psi_for(prime, N);
+}
+uint32_t rzk_ntt_layout_index(uint32_t N, uint32_t j) {
+  if (j >= N || N < 512) return 0xffffffffu;
+  const uint32_t E = N / 64;
+  const uint32_t lane = j / E, c = j % E;
+  return (c >> 2) * 256 + lane * 4 + (c & 3);
+}
+
+// ---- commitment scheme ---------------------------------------------------------------------------------------------
+int rzk_commit_batch_dev(rzk_ctx* c, const int64_t* x, const int64_t* r, int64_t* cm, uint8_t* ok, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !x || !r || !cm) return RZK_E_ARG;
+  // unfused: the exact norm kernel sets ok, then the rows clear it again for proofs with non-canonical inputs
+  return run_checked(c, PG_COMMIT, 0, {{x, c->l, 0}, {r, c->k, 0}, {cm, c->n + c->l, 0}}, ok, 1, B, B, c->commit_bound, true,
+                     true, {{r, c->k, 0, 0}});
+}
+
+int rzk_commitment_verify_batch_dev(rzk_ctx* c, const int64_t* cm, const int64_t* x, const int64_t* r,
+                                    const int64_t* f, uint8_t* ok, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !cm || !x || !r || !ok) return RZK_E_ARG;
+  const uint32_t var = f ? 2u : 0u;
+  // commit.rs:183-185: the norm predicate on r rides on the rows that load r
+  return run_checked(c, PG_COMMIT_VERIFY, var, {{x, c->l, 0}, {r, c->k, 0}, {cm, c->n + c->l, 0}, {f, 1, 0}}, ok, 1, B, B,
+                     c->commit_bound, true, false, {{r, c->k, 0, 0}});
+}
+
+// ---- OpenProof -----------------------------------------------------------------------------------------------------
+int rzk_open_commit_batch_dev(rzk_ctx* c, const int64_t* x, const int64_t* r, const int64_t* y, int64_t* cm,
+                              int64_t* t, uint8_t* ok, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !x || !r || !y || !cm || !t) return RZK_E_ARG;
+  const std::vector<OpSpec> specs = {{x, c->l, 0}, {r, c->k, 0}, {y, c->k, 0}, {cm, c->n + c->l, 0}, {t, c->n, 0}};
+  // check_commit_constraint(r) (params.rs:102-108) rides on the loads of r the commit rows do anyway
+  return run_checked(c, PG_OPEN_COMMIT, 0, specs, ok, 1, B, B, c->commit_bound, true, true, {{r, c->k, 0, 0}});
+}
+
+int rzk_open_response_batch_dev(rzk_ctx* c, const int64_t* y, const int64_t* r, const int64_t* d, int64_t* z,
+                                size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !y || !r || !d || !z) return RZK_E_ARG;
+  return run_program(c, PG_RESPONSE, 1, {{d, 1, 0}, {y, c->k, 0}, {r, c->k, 0}, {z, c->k, 0}}, nullptr, 1, B);
+}
+
+int rzk_open_verify_batch_dev(rzk_ctx* c, const int64_t* z, const int64_t* t, const int64_t* cm, const int64_t* d,
+                              uint8_t* accept, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !z || !t || !cm || !d || !accept) return RZK_E_ARG;
+  if (c->n != c->l) return fail(c, RZK_E_ARG, "c1_c2 split needs n == l (reference panics in Mat::add)");
+  const std::vector<OpSpec> specs = {{z, c->k, 0}, {t, c->n, 0}, {cm, c->n + c->l, 0}, {d, 1, 0}};
+  int rc = arena_reserve(c, c->ws, polys(c, B * c->n));
+  if (rc != RZK_OK) return rc;
+  // open.rs:167-173: the norm predicate on z rides on the rows that load z
+  return run_a1_relation(c, specs, (int64_t*)c->ws.p, accept, 1, B, B, true);
+}
+
+// ---- LinearProof ---------------------------------------------------------------------------------------------------
+int rzk_linear_commit_batch_dev(rzk_ctx* c, const int64_t* g, const int64_t* x, const int64_t* r, const int64_t* rp,
+                                const int64_t* y, const int64_t* yp, int64_t* cm, int64_t* cpm, int64_t* t,
+                                int64_t* tp, int64_t* u, uint8_t* ok, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !g || !x || !r || !rp || !y || !yp || !cm || !cpm || !t || !tp || !u) return RZK_E_ARG;
+  const uint32_t n = c->n, k = c->k, l = c->l;
+  int rc = arena_reserve(c, c->ws, polys(c, 2 * B * l));
+  if (rc != RZK_OK) return rc;
+  int64_t* gx = (int64_t*)c->ws.p;
+  int64_t* a2y = gx + B * l * c->N;
+  // the multiplier g of every proof, transformed once for the rows that multiply by it (gx, u)
+  rc = prepare_dkey(c, g, B, 1, 2 * l, nullptr, true);      // l rows of gx, l rows of u
+  if (rc != RZK_OK) return rc;
+  DkeyScope dkey_scope{c};
+  // linear.rs:91-95: gx = x_i * g
+  rc = run_program(c, PG_CMUL, l | dkv(c), {{x, l, 0}, {g, 1, 0}, {gx, l, 0}}, nullptr, 1, B);
+  if (rc != RZK_OK) return rc;
+  const std::vector<OpSpec> c2 = {{x, l, 0}, {gx, l, 0}, {r, k, 0}, {rp, k, 0}, {y, k, 0}, {yp, k, 0}, {cm, n + l, 0},
+                                  {cpm, n + l, 0}, {t, n, 0}, {tp, n, 0}, {a2y, l, 0}};
+  // the norm predicates on r (bit 0 of ok) and rp (bit 1) ride on the commit rows when the kernel path allows; otherwise
+  // bit 0: constraint(r), bit 1: constraint(rp), and the rows clear the byte on non-canonical inputs
+  rc = run_checked(c, PG_LIN_COMMIT2, 0, c2, ok, 1, B, B, c->commit_bound, true, true, {{r, k, 0, 0}, {rp, k, 2, 1}});
+  if (rc != RZK_OK) return rc;
+  return run_program(c, PG_LIN_U, dkv(c), {{a2y, l, 0}, {g, 1, 0}, {yp, k, 0}, {u, l, 0}}, ok, 1, B);
+}
+
+int rzk_linear_response_batch_dev(rzk_ctx* c, const int64_t* y, const int64_t* yp, const int64_t* r,
+                                  const int64_t* rp, const int64_t* d, int64_t* z, int64_t* zp, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !y || !yp || !r || !rp || !d || !z || !zp) return RZK_E_ARG;
+  const uint32_t k = c->k;
+  return run_program(c, PG_RESPONSE, 2, {{d, 1, 0}, {y, k, 0}, {r, k, 0}, {z, k, 0}, {yp, k, 0}, {rp, k, 0}, {zp, k, 0}},
+                     nullptr, 1, B);
+}
+
+int rzk_linear_verify_batch_dev(rzk_ctx* c, const int64_t* z, const int64_t* zp, const int64_t* cm,
+                                const int64_t* cpm, const int64_t* g, const int64_t* t, const int64_t* tp,
+                                const int64_t* u, const int64_t* d, uint8_t* accept, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !z || !zp || !cm || !cpm || !g || !t || !tp || !u || !d || !accept) return RZK_E_ARG;
+  if (c->n != c->l) return fail(c, RZK_E_ARG, "c1_c2 split needs n == l (reference panics in Mat::add)");
+  const uint32_t n = c->n, k = c->k, l = c->l;
+  int rc = arena_reserve(c, c->ws, polys(c, 2 * B * l));
+  if (rc != RZK_OK) return rc;
+  int64_t* w1 = (int64_t*)c->ws.p;
+  int64_t* w2 = w1 + B * l * c->N;
+  const std::vector<OpSpec> v1 = {{z, k, 0}, {zp, k, 0}, {t, n, 0}, {tp, n, 0}, {cm, n + l, 0}, {cpm, n + l, 0},
+                                  {d, 1, 0}, {g, 1, 0}, {w1, l, 0}, {w2, l, 0}};
+  if (c->lin_e && !c->small) {
+    // rearranged (PG_LIN_V1B / V2B): no product with g in the first program, so it runs on the unit kernel (and
+    // initialises the verdicts itself where one team owns a proof); w1 / w2 hold e / e'
+    const std::vector<OpSpec> v1b = {{z, k, 0}, {zp, k, 0}, {t, n, 0}, {tp, n, 0}, {cm, n + l, 0}, {cpm, n + l, 0},
+                                     {d, 1, 0}, {w1, l, 0}, {w2, l, 0}};
+    rc = run_checked(c, PG_LIN_V1B, 0, v1b, accept, 1, B, B, c->verify_bound, true, false, {{z, k, 0, 0}, {zp, k, 1, 0}});
+    if (rc != RZK_OK) return rc;
+    rc = prepare_dkey(c, g, B, 1, l, accept, false);   // (after the verdicts exist; l rows multiply by g)
+    if (rc != RZK_OK) return rc;
+    DkeyScope dkey_scope{c};
+    return run_program(c, PG_LIN_V2B, dkv(c), {{w1, l, 0}, {w2, l, 0}, {g, 1, 0}, {u, l, 0}}, accept, 1, B, 0, false);
+  }
+  // The verdicts are initialised first, then the multiplier's images are prepared (a non-canonical g clears its proof's
+  // verdict: nothing may preset the flags after that), then the rows.
+  rc = check_launch(c, launch_fill_u8(cfg_of(c), accept, 1, B), "flag preset");
+  if (rc != RZK_OK) return rc;
+  rc = prepare_dkey(c, g, B, 1, 2 * l, accept, false);
+  if (rc != RZK_OK) return rc;
+  DkeyScope dkey_scope{c};
+  // linear.rs:218-223: norm predicates on z and zp, fused into the rows that load them when possible (both AND into the
+  // verdicts the fill above has set)
+  rc = run_checked(c, PG_LIN_V1, dkv(c), v1, accept, 1, B, B, c->verify_bound, false, false, {{z, k, 1, 0}, {zp, k, 1, 0}});
+  if (rc != RZK_OK) return rc;
+  return run_program(c, PG_LIN_V2, dkv(c), {{w1, l, 0}, {w2, l, 0}, {g, 1, 0}, {d, 1, 0}, {zp, k, 0}, {u, l, 0}}, accept, 1, B, 0,
+                     false);
+}
+
+// ---- SumProof ------------------------------------------------------------------------------------------------------
+int rzk_sum_commit_batch_dev(rzk_ctx* c, uint32_t V, const int64_t* gs, const int64_t* xs, const int64_t* rs,
+                             const int64_t* rp, const int64_t* ys, const int64_t* yp, int64_t* cs, int64_t* cpm,
+                             int64_t* ts, int64_t* tp, int64_t* u, uint8_t* ok, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || V == 0 || !gs || !xs || !rs || !rp || !ys || !yp || !cs || !cpm || !ts || !tp || !u) return RZK_E_ARG;
+  const uint32_t n = c->n, k = c->k, l = c->l;
+  const size_t wpolys = (size_t)B * V * l > (size_t)B * k ? (size_t)B * V * l : (size_t)B * k;   // w[B*V][l], or D[B][k]
+  int rc = arena_reserve(c, c->ws, polys(c, B * l + wpolys));
+  if (rc != RZK_OK) return rc;
+  int64_t* xp = (int64_t*)c->ws.p;
+  int64_t* w = xp + B * l * c->N;
+  // sum.rs:107-115: xp = sum_i x_i (.) g_i
+  // (XP runs before ok is preset: a non-canonical x_i / g_i is reported through the sticky word, and again by the
+  //  later rows that load the same polynomials with the flags in place)
+  // the V multipliers g_i of every proof, transformed once for all the rows that multiply by them (XP, D / U)
+  rc = prepare_dkey(c, gs, B, V, 2 * l, nullptr, true);   // l rows of XP, l or (columns of a2) rows of U / D
+  if (rc != RZK_OK) return rc;
+  DkeyScope dkey_scope{c};
+  rc = run_program(c, PG_SUM_XP, V | dkv(c), {{xs, V * l, 0}, {gs, V, 0}, {xp, l, 0}}, nullptr, 1, B);
+  if (rc != RZK_OK) return rc;
+  // the a1.y_i key products below leave the transforms of y_i's a2-columns for the D rows (operand 2 of the summand launch)
+  rc = prepare_oimg(c, B, V, 2 * l);
+  if (rc != RZK_OK) return rc;
+  OimgScope oimg_scope{c};
+  // ok[b] = constraint(rp_b) && all_i constraint(r_{b,i}): fused into the commit rows when possible.  Both launches run
+  // the same program against the same flags, so they take the same side of run_checked; unfused, the norm kernels of
+  // both vectors come in front of the first launch (the second then has none of its own and only ANDs into ok).
+  // sum.rs:116 and 151: cp = commit(xp; rp), tp = a1.yp
+  rc = run_checked(c, PG_OPEN_COMMIT, 0, {{xp, l, 0}, {rp, k, 0}, {yp, k, 0}, {cpm, n + l, 0}, {tp, n, 0}}, ok, 1, B, B,
+                   c->commit_bound, true, true, {{rp, k, 0, 0}, {rs, V * k, 1, 0}});
+  if (rc != RZK_OK) return rc;
+  {   // sum.rs:117-120 and 145-148: c_i = commit(x_i; r_i), t_i = a1.y_i — the V summands are extra batch entries
+    OimgProducer images_of_ys(c, 2);
+    rc = run_checked(c, PG_OPEN_COMMIT, 0, {{xs, l, 0}, {rs, k, 0}, {ys, k, 0}, {cs, n + l, 0}, {ts, n, 0}}, ok, V, B * V, B,
+                     c->commit_bound, false, true, {});
+  }
+  if (rc != RZK_OK) return rc;
+  // sum.rs:154-160: u = sum_i (a2.y_i)(.)g_i - a2.yp
+  if (sum_uses_d(c, V)) {   // = a2.(sum_i g_i(.)y_i - yp): D (k polynomials per proof, the columns a2 uses) lives where w would
+    int64_t* D = w;
+    rc = run_program(c, PG_SUM_D, V | dkv(c) | oiv(c), {{ys, V * k, 0}, {gs, V, 0}, {yp, k, 0}, {D, k, 0}}, ok, 1, B);
+    if (rc != RZK_OK) return rc;
+    return run_program(c, PG_MATVEC, RZK_KEY_A2 * 2, {{D, k, 0}, {nullptr, l, 0}, {u, l, 0}}, ok, 1, B);
+  }
+  rc = run_program(c, PG_MATVEC, RZK_KEY_A2 * 2, {{ys, k, 0}, {nullptr, l, 0}, {w, l, 0}}, nullptr, 1, B * V);
+  if (rc != RZK_OK) return rc;
+  return run_program(c, PG_SUM_U, V | dkv(c), {{w, V * l, 0}, {gs, V, 0}, {yp, k, 0}, {u, l, 0}}, ok, 1, B);
+}
+
+int rzk_sum_response_batch_dev(rzk_ctx* c, uint32_t V, const int64_t* ys, const int64_t* yp, const int64_t* rs,
+                               const int64_t* rp, const int64_t* d, int64_t* zs, int64_t* zp, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || V == 0 || !ys || !yp || !rs || !rp || !d || !zs || !zp) return RZK_E_ARG;
+  const uint32_t k = c->k;
+  // sum.rs:188-193: z_i = y_i + r_i (.) d — summands as batch entries, d shared by the V entries of a proof
+  int rc = run_program(c, PG_RESPONSE, 1, {{d, 1, 1}, {ys, k, 0}, {rs, k, 0}, {zs, k, 0}}, nullptr, V, B * V);
+  if (rc != RZK_OK) return rc;
+  // sum.rs:195-197
+  return run_program(c, PG_RESPONSE, 1, {{d, 1, 0}, {yp, k, 0}, {rp, k, 0}, {zp, k, 0}}, nullptr, 1, B);
+}
+
+int rzk_sum_verify_batch_dev(rzk_ctx* c, uint32_t V, const int64_t* zs, const int64_t* zp, const int64_t* cs,
+                             const int64_t* cpm, const int64_t* gs, const int64_t* ts, const int64_t* tp,
+                             const int64_t* u, const int64_t* d, uint8_t* accept, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || V == 0 || !zs || !zp || !cs || !cpm || !gs || !ts || !tp || !u || !d || !accept) return RZK_E_ARG;
+  if (c->n != c->l) return fail(c, RZK_E_ARG, "c1_c2 split needs n == l (reference panics in Mat::add)");
+  const uint32_t n = c->n, k = c->k, l = c->l;
+  const bool by_d = sum_uses_d(c, V);
+  const size_t w1polys = by_d && (size_t)B * k > (size_t)B * V * l ? (size_t)B * k : (size_t)B * V * l;   // w1[B*V][l], or D[B][k]
+  int rc = arena_reserve(c, c->ws, polys(c, w1polys + B * l + B * V * n));
+  if (rc != RZK_OK) return rc;
+  int64_t* w1 = (int64_t*)c->ws.p;
+  int64_t* w2 = w1 + w1polys * c->N;
+  int64_t* w0 = w2 + B * l * c->N;   // a1.z of the relation checks (n >= 2 only)
+  const std::vector<OpSpec> rel_s = {{zs, k, 0}, {ts, n, 0}, {cs, n + l, 0}, {d, 1, 1}};
+  const std::vector<OpSpec> rel_p = {{zp, k, 0}, {tp, n, 0}, {cpm, n + l, 0}, {d, 1, 0}};
+  // sum.rs:262-271 norm predicates ride on sum.rs:278-291 (every summand; batch entries B*V, flag per proof)
+  // and sum.rs:294-298
+  // (the a1.z_i key products leave the transforms of z_i's a2-columns for the D rows: operand 0 of their launch)
+  rc = prepare_oimg(c, B, V, 2 * l);
+  if (rc != RZK_OK) return rc;
+  OimgScope oimg_scope{c};
+  {
+    OimgProducer images_of_zs(c, 0);
+    rc = run_a1_relation(c, rel_s, w0, accept, V, B * V, B, true);
+  }
+  if (rc != RZK_OK) return rc;
+  rc = run_a1_relation(c, rel_p, w0, accept, 1, B, B, false);
+  if (rc != RZK_OK) return rc;
+  // sum.rs:301-319.  The multipliers' images are prepared AFTER the relation rows above have initialised accept: a
+  // non-canonical g_i must clear the proof's verdict, and nothing presets the flags again from here on.
+  rc = prepare_dkey(c, gs, B, V, 2 * l, accept, false);
+  if (rc != RZK_OK) return rc;
+  DkeyScope dkey_scope{c};
+  // by_d: lhs = a2.(sum_i g_i(.)z_i - zp), D in w1's place, then one relation row per row of a2; else a2.z_i into w1
+  rc = by_d ? run_program(c, PG_SUM_D, V | dkv(c) | oiv(c), {{zs, V * k, 0}, {gs, V, 0}, {zp, k, 0}, {w1, k, 0}}, accept, 1, B, 0, false)
+            : run_program(c, PG_MATVEC, RZK_KEY_A2 * 2, {{zs, k, 0}, {nullptr, l, 0}, {w1, l, 0}}, accept, V, B * V, 0, false);
+  if (rc != RZK_OK) return rc;
+  rc = run_program(c, PG_SUM_W2, V | dkv(c), {{cs, V * (n + l), 0}, {gs, V, 0}, {cpm, n + l, 0}, {w2, l, 0}}, accept, 1, B, 0, false);
+  if (rc != RZK_OK) return rc;
+  if (by_d) return run_program(c, PG_SUM_V4, 0, {{w1, k, 0}, {w2, l, 0}, {d, 1, 0}, {u, l, 0}}, accept, 1, B, 0, false);
+  return run_program(c, PG_SUM_V3, V | dkv(c), {{w1, V * l, 0}, {gs, V, 0}, {zp, k, 0}, {w2, l, 0}, {d, 1, 0}, {u, l, 0}}, accept,
+                     1, B, 0, false);
+}
+
+}  // extern "C"

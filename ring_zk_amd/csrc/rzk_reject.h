@@ -1,5 +1,5 @@
 // rzk_reject.h — the prover's rejection-sampling step (BDLOP, eprint 2016/997, Fig. 2; Lyubashevsky 2012, Thm 4.6;
-// DESIGN.md §12), shared by the GPU kernels (rzk_reject_dev.hip), the entry points (rzk_api.cpp: the argument rules)
+// DESIGN.md §12), shared by the GPU kernels (rzk_reject_dev.hip), the entry points (rzk_codec.cpp: the argument rules)
 // and the CPU test (tests/test_reject_host.py, g++).  Plain C++.
 //
 // A response z = y + v, v = d r, is released only with probability min(1, D_sigma(z) / (M D_{v,sigma}(z))) =

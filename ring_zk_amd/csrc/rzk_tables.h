@@ -1,7 +1,7 @@
 // rzk_tables.h — host-side generation of the constants the kernels consume: per-prime Montgomery
 // constants, bit-reversed twiddle tables, CRT / mod-q constants and the static operand-size bounds
 // that decide how many auxiliary primes a product needs.  Plain C++ (no HIP), header-only, used by
-// the library (rzk_api.hip) and by the CPU lane emulator under tests/emul/.
+// the library (rzk_ctx.cpp) and by the CPU lane emulator under tests/emul/.
 #pragma once
 #include <cstdint>
 #include <vector>
