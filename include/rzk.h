@@ -50,9 +50,9 @@ extern "C" {
 typedef struct rzk_ctx rzk_ctx;
 
 /* Version of this C ABI: bumped whenever an existing signature changes (rzk_wire_mat_decode gained `q` in 2,
- * version 3 added the entry points marked "v3", version 4 those marked "v4", version 5 those marked "v5", version 6 those marked "v6", version 7 those marked "v7", version 8 those marked "v8", version 9 those marked "v9", version 10 those marked "v10", version 11 those marked "v11").  A binding checks rzk_abi_version() == RZK_ABI_VERSION after loading
+ * version 3 added the entry points marked "v3", version 4 those marked "v4", version 5 those marked "v5", version 6 those marked "v6", version 7 those marked "v7", version 8 those marked "v8", version 9 those marked "v9", version 10 those marked "v10", version 11 those marked "v11", version 12 those marked "v12").  A binding checks rzk_abi_version() == RZK_ABI_VERSION after loading
  * the library, so that a stale or variant .so fails at load time instead of reading shifted arguments. */
-#define RZK_ABI_VERSION 11u
+#define RZK_ABI_VERSION 12u
 uint32_t rzk_abi_version(void);
 
 /* Which block of the commitment key a matrix-vector product uses (src/commit.rs:19-25). */
@@ -253,6 +253,40 @@ int rzk_sum_verify_batch_dev(rzk_ctx* ctx, uint32_t V, const int64_t* zs, const 
                              const int64_t* cs, const int64_t* cp, const int64_t* gs, const int64_t* ts,
                              const int64_t* tp, const int64_t* u, const int64_t* d, uint8_t* accept,
                              size_t B);
+
+/* ---- recompute steps of the short proofs (v12) -----------------------------------------------------------------------------
+ * A short proof sends the challenge d in place of the commitment message's t / tp / ts / u (RZK_MSG_OPEN_SHORT,
+ * RZK_MSG_LINEAR_SHORT, RZK_MSG_SUM_SHORT below).  These calls are its verifier's first step: the verifiers' own launches
+ * with the compared operands as outputs, i.e. the unique values for which the reference's verification equations hold,
+ *   open    (open.rs:171-173)     t  = a1.z - c1 (.) d
+ *   linear  (linear.rs:224-249)   t  = a1.z - c1 (.) d,  tp = a1.zp - c1p (.) d,  u = g (.) (a2.z - c2 (.) d) - (a2.zp - c2p (.) d)
+ *   sum     (sum.rs:277-319)      ts_i = a1.zs_i - c1_i (.) d,  tp = a1.zp - c1p (.) d,
+ *                                 u = sum_i g_i (.) (a2.zs_i) - a2.zp - (sum_i c2_i (.) g_i - c2p) (.) d
+ * reduced to centred representatives.  The caller then hashes the full commitment message with the recomputed fields
+ * (rzk_fs_challenge_batch) and accepts iff that gives d again; the equations hold by construction, so no *_verify pass follows.
+ * accept[b] = 1 iff every response vector of proof b passes check_verify_constraint and every coefficient the recompute reads
+ * is canonical.  Verifier-side convention: a non-canonical value clears its own proof's verdict and the call succeeds.  Every
+ * input is read except, for Open, the rows c2 of c (they are range-tested by the transcript hash that follows).  d is foreign
+ * data: the products with it are exact for any canonical d, not only for challenges.  Outputs of a rejected proof are
+ * unspecified (but written inside their own rows).  Requires n == l like the verifiers (RZK_E_ARG); B == 0 is a no-op.
+ * z,zp:[B][k][N] zs:[B][V][k][N] c,cp:[B][n+l][N] cs:[B][V][n+l][N] g,d:[B][N] gs:[B][V][N]
+ * -> t_out,tp_out:[B][n][N] ts_out:[B][V][n][N] u_out:[B][l][N] accept:[B] */
+int rzk_open_recover_batch(rzk_ctx* ctx, const int64_t* z, const int64_t* c, const int64_t* d, int64_t* t_out,
+                           uint8_t* accept, size_t B);
+int rzk_open_recover_batch_dev(rzk_ctx* ctx, const int64_t* z, const int64_t* c, const int64_t* d, int64_t* t_out,
+                               uint8_t* accept, size_t B);
+int rzk_linear_recover_batch(rzk_ctx* ctx, const int64_t* z, const int64_t* zp, const int64_t* c, const int64_t* cp,
+                             const int64_t* g, const int64_t* d, int64_t* t_out, int64_t* tp_out, int64_t* u_out,
+                             uint8_t* accept, size_t B);
+int rzk_linear_recover_batch_dev(rzk_ctx* ctx, const int64_t* z, const int64_t* zp, const int64_t* c, const int64_t* cp,
+                                 const int64_t* g, const int64_t* d, int64_t* t_out, int64_t* tp_out, int64_t* u_out,
+                                 uint8_t* accept, size_t B);
+int rzk_sum_recover_batch(rzk_ctx* ctx, uint32_t V, const int64_t* zs, const int64_t* zp, const int64_t* cs,
+                          const int64_t* cp, const int64_t* gs, const int64_t* d, int64_t* ts_out, int64_t* tp_out,
+                          int64_t* u_out, uint8_t* accept, size_t B);
+int rzk_sum_recover_batch_dev(rzk_ctx* ctx, uint32_t V, const int64_t* zs, const int64_t* zp, const int64_t* cs,
+                              const int64_t* cp, const int64_t* gs, const int64_t* d, int64_t* ts_out, int64_t* tp_out,
+                              int64_t* u_out, uint8_t* accept, size_t B);
 
 /* ---- instrumentation (bench.py) ------------------------------------------------------------------------- */
 /* Times `iters` launches of the batched forward NTT kernel with HIP events on the context stream and
@@ -479,11 +513,14 @@ int rzk_reject_batch_dev(rzk_ctx* ctx, uint32_t nparts, const int64_t* const* z,
  *   class D      d                         bias 1                largest raw 2                 W = 2
  * Class Z loses nothing for a proof a verifier could accept: norm_2(z_i) <= verify_bound bounds every coefficient.
  * Kinds: RZK_MSG_COMMITMENT, CHALLENGE, OPEN_COMMITMENT, OPEN_RESPONSE, LINEAR_COMMITMENT, SUM_COMMITMENT, SUM_RESPONSE as
- * above, and two that exist here only (the rzk_wire_* entry points reject them):
+ * above, and four that exist here only (the rzk_wire_* entry points reject them):
  *   RZK_MSG_LINEAR_RESPONSE    { z, zp }       z, zp [B][k][N]
  *   RZK_MSG_OPEN_SHORT         { c, d, z }     c [B][n+l][N], d [B][N], z [B][k][N]: the signature form of an Open proof, the
  *                              verifier recomputes t = a1.z - c1 (.) d and accepts iff the transcript of (c, t) gives d again
- * RZK_MSG_OPENING is not a stored proof and is not supported.
+ *   RZK_MSG_LINEAR_SHORT (v12) { c, cp, g, d, z, zp }       } the same for Linear and Sum (V summands): the full kinds' fields in
+ *   RZK_MSG_SUM_SHORT    (v12) { cp, cs, gs, d, zp, zs }    } their order without t / tp / ts / u, d behind the commitment fields;
+ *                              the verifier recomputes those (rzk_*_recover_batch) and hashes them under the full kind
+ * RZK_MSG_OPENING is not a stored proof and is not supported; kind 10 is unassigned.
  * rzk_packed_record_bytes: size of one record; 0 = bad kind or V, or a context with verify_bound > (q-1)/2.
  * rzk_packed_widths: W of classes Q and Z.
  * rzk_packed_encode_batch: fields as for the wire codec -> records [B][record_bytes].  A coefficient outside its class's
@@ -497,6 +534,8 @@ int rzk_reject_batch_dev(rzk_ctx* ctx, uint32_t nparts, const int64_t* const* z,
  * host synchronisation or allocation; `fields` is a host array of device pointers. */
 #define RZK_MSG_LINEAR_RESPONSE 8
 #define RZK_MSG_OPEN_SHORT 9
+#define RZK_MSG_LINEAR_SHORT 11
+#define RZK_MSG_SUM_SHORT 12
 size_t rzk_packed_record_bytes(const rzk_ctx* ctx, int kind, uint32_t V);
 int rzk_packed_widths(const rzk_ctx* ctx, uint32_t* wq, uint32_t* wz);
 int rzk_packed_encode_batch(rzk_ctx* ctx, int kind, uint32_t V, const int64_t* const* fields, uint8_t* records, uint8_t* ok,

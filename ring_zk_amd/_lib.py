@@ -15,6 +15,7 @@ KEY_A1, KEY_A2, KEY_A = 0, 1, 2
  MSG_SUM_COMMITMENT, MSG_SUM_RESPONSE) = range(8)
 # kinds of the packed format only (include/rzk.h "fixed-width packed records", v8)
 MSG_LINEAR_RESPONSE, MSG_OPEN_SHORT = 8, 9
+MSG_LINEAR_SHORT, MSG_SUM_SHORT = 11, 12   # v12; 10 is unassigned
 
 _lib = None
 
@@ -67,6 +68,10 @@ SIGNATURES = {
     "rzk_sum_commit_batch": (C.c_int, [_CTX, C.c_uint32] + [_I64] * 11 + [_U8, _SZ]),
     "rzk_sum_response_batch": (C.c_int, [_CTX, C.c_uint32] + [_I64] * 7 + [_SZ]),
     "rzk_sum_verify_batch": (C.c_int, [_CTX, C.c_uint32] + [_I64] * 9 + [_U8, _SZ]),
+    # v12: recompute steps of the short proofs
+    "rzk_open_recover_batch": (C.c_int, [_CTX, _I64, _I64, _I64, _I64, _U8, _SZ]),
+    "rzk_linear_recover_batch": (C.c_int, [_CTX] + [_I64] * 9 + [_U8, _SZ]),
+    "rzk_sum_recover_batch": (C.c_int, [_CTX, C.c_uint32] + [_I64] * 9 + [_U8, _SZ]),
     "rzk_sample_uniform_dev": (C.c_int, [_CTX, C.c_uint64, C.c_uint32, C.c_uint64, _I64, _SZ]),
     "rzk_sample_gauss_dev": (C.c_int, [_CTX, C.c_uint64, C.c_uint32, C.c_double, _I64, _SZ]),
     "rzk_sample_challenge_dev": (C.c_int, [_CTX, C.c_uint64, C.c_uint32, _I64, _SZ]),
@@ -113,7 +118,7 @@ SIGNATURES = {
     "rzk_prof_read_all": (C.c_int, [_CTX, C.POINTER(C.c_double), _SZ, C.POINTER(C.c_size_t)]),
     "rzk_prof_read_kernels": (C.c_int, [_CTX, C.c_char_p, _SZ, C.POINTER(C.c_size_t)]),
 }
-ABI_VERSION = 11   # include/rzk.h: RZK_ABI_VERSION
+ABI_VERSION = 12   # include/rzk.h: RZK_ABI_VERSION
 # every batched entry point also exists as a device-pointer variant with the same signature
 for _name in list(SIGNATURES):
     if _name.endswith("_batch"):

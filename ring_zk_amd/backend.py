@@ -506,6 +506,18 @@ class Context:
         self._check(self._fn("rzk_open_verify_batch", dev)(self._h, *p, B))
         return acc
 
+    def open_recover(self, z, c, d):
+        """The recompute step of a short Open proof (rzk_open_recover_batch): (t, accept) with t = a1.z - c1 (.) d, the
+        only t for which open_verify's equation holds; accept[b] = norm rule on z and every coefficient read canonical."""
+        B = self._shape(z, self.k, self.N)
+        if self._shape(c, self.n + self.l, self.N) != B or self._shape(d, self.N) != B:
+            raise ValueError("open_recover: batch / shape mismatch")
+        t = self._empty(z, tuple(z.shape[:-2]) + (self.n, self.N))
+        acc = self._empty(z, (B,), np.uint8)
+        dev, p = self._prep([z, c, d, t, acc], [np.int64] * 4 + [np.uint8])
+        self._check(self._fn("rzk_open_recover_batch", dev)(self._h, *p, B))
+        return t, acc
+
     # ---- LinearProof (src/prove/linear.rs) ------------------------------------------------------------------------
     def linear_commit(self, g, x, r, rp, y, yp):
         B = self._shape(x, self.l, self.N)
@@ -539,6 +551,21 @@ class Context:
         dev, p = self._prep([z, zp, c, cp, g, t, tp, u, d, acc], [np.int64] * 9 + [np.uint8])
         self._check(self._fn("rzk_linear_verify_batch", dev)(self._h, *p, B))
         return acc
+
+    def linear_recover(self, z, zp, c, cp, g, d):
+        """The recompute step of a short Linear proof (rzk_linear_recover_batch): (t, tp, u, accept)."""
+        B = self._shape(z, self.k, self.N)
+        if (self._shape(zp, self.k, self.N) != B or self._shape(c, self.n + self.l, self.N) != B
+                or self._shape(cp, self.n + self.l, self.N) != B or self._shape(g, self.N) != B or self._shape(d, self.N) != B):
+            raise ValueError("linear_recover: batch / shape mismatch")
+        lead = tuple(z.shape[:-2])
+        t = self._empty(z, lead + (self.n, self.N))
+        tp = self._empty(z, lead + (self.n, self.N))
+        u = self._empty(z, lead + (self.l, self.N))
+        acc = self._empty(z, (B,), np.uint8)
+        dev, p = self._prep([z, zp, c, cp, g, d, t, tp, u, acc], [np.int64] * 9 + [np.uint8])
+        self._check(self._fn("rzk_linear_recover_batch", dev)(self._h, *p, B))
+        return t, tp, u, acc
 
     # ---- SumProof (src/prove/sum.rs) --------------------------------------------------------------------------------
     def sum_commit(self, gs, xs, rs, rp, ys, yp):
@@ -577,6 +604,25 @@ class Context:
         dev, p = self._prep([zs, zp, cs, cp, gs, ts, tp, u, d, acc], [np.int64] * 9 + [np.uint8])
         self._check(self._fn("rzk_sum_verify_batch", dev)(self._h, V, *p, B))
         return acc
+
+    def sum_recover(self, zs, zp, cs, cp, gs, d):
+        """The recompute step of a short Sum proof (rzk_sum_recover_batch): (ts, tp, u, accept)."""
+        V = int(zs.shape[-3])
+        if V == 0:
+            raise ValueError("sum_recover: zs must not be empty")
+        B = self._shape(zs, V, self.k, self.N)
+        if (self._shape(zp, self.k, self.N) != B or self._shape(cs, V, self.n + self.l, self.N) != B
+                or self._shape(cp, self.n + self.l, self.N) != B or self._shape(gs, V, self.N) != B
+                or self._shape(d, self.N) != B):
+            raise ValueError("sum_recover: batch / shape mismatch")
+        lead = tuple(zs.shape[:-3])
+        ts = self._empty(zs, lead + (V, self.n, self.N))
+        tp = self._empty(zs, lead + (self.n, self.N))
+        u = self._empty(zs, lead + (self.l, self.N))
+        acc = self._empty(zs, (B,), np.uint8)
+        dev, p = self._prep([zs, zp, cs, cp, gs, d, ts, tp, u, acc], [np.int64] * 9 + [np.uint8])
+        self._check(self._fn("rzk_sum_recover_batch", dev)(self._h, V, *p, B))
+        return ts, tp, u, acc
 
 
 def reject_lnm(alpha: float) -> float:

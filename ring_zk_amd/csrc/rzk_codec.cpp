@@ -261,7 +261,8 @@ int rzk_reject_batch(rzk_ctx* c, uint32_t nparts, const int64_t* const* z, const
 
 // ---- v8: fixed-width packed records "RZKP1" (rzk_packed_dev.hip, rzk_packed.h) -----------------------------------------
 static_assert(RZK_MSG_LINEAR_RESPONSE == PK_LINEAR_RESPONSE && RZK_MSG_OPEN_SHORT == PK_OPEN_SHORT &&
-                  RZK_MSG_OPENING == PK_OPENING && RZK_MSG_SUM_RESPONSE == PK_SUM_RESPONSE,
+                  RZK_MSG_OPENING == PK_OPENING && RZK_MSG_SUM_RESPONSE == PK_SUM_RESPONSE &&
+                  RZK_MSG_LINEAR_SHORT == PK_LINEAR_SHORT && RZK_MSG_SUM_SHORT == PK_SUM_SHORT,
               "packed kinds are the RZK_MSG_* values");
 
 namespace {

@@ -263,4 +263,44 @@ int rzk_sum_verify_batch(rzk_ctx* c, uint32_t V, const int64_t* zs, const int64_
   return h.run([&] { return rzk_sum_verify_batch_dev(c, V, dzs, dzp, dcs, dcpm, dgs, dts, dtp, du, dd, dacc, B); });
 }
 
+// ---- recompute steps of the short proofs ---------------------------------------------------------------------------
+int rzk_open_recover_batch(rzk_ctx* c, const int64_t* z, const int64_t* cm, const int64_t* d, int64_t* t_out,
+                           uint8_t* accept, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !z || !cm || !d || !t_out || !accept) return RZK_E_ARG;
+  HostCall h(c);
+  const auto dz = h.pin(z, B * c->k), dcm = h.pin(cm, B * (c->n + c->l)), dd = h.pin(d, B);
+  const auto dt = h.pout(t_out, B * c->n);
+  const auto dacc = h.out(accept, B);
+  return h.run([&] { return rzk_open_recover_batch_dev(c, dz, dcm, dd, dt, dacc, B); });
+}
+
+int rzk_linear_recover_batch(rzk_ctx* c, const int64_t* z, const int64_t* zp, const int64_t* cm, const int64_t* cpm,
+                             const int64_t* g, const int64_t* d, int64_t* t_out, int64_t* tp_out, int64_t* u_out,
+                             uint8_t* accept, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !z || !zp || !cm || !cpm || !g || !d || !t_out || !tp_out || !u_out || !accept) return RZK_E_ARG;
+  const size_t k = c->k, n = c->n, l = c->l;
+  HostCall h(c);
+  const auto dz = h.pin(z, B * k), dzp = h.pin(zp, B * k), dcm = h.pin(cm, B * (n + l)), dcpm = h.pin(cpm, B * (n + l)),
+             dg = h.pin(g, B), dd = h.pin(d, B);
+  const auto dt = h.pout(t_out, B * n), dtp = h.pout(tp_out, B * n), du = h.pout(u_out, B * l);
+  const auto dacc = h.out(accept, B);
+  return h.run([&] { return rzk_linear_recover_batch_dev(c, dz, dzp, dcm, dcpm, dg, dd, dt, dtp, du, dacc, B); });
+}
+
+int rzk_sum_recover_batch(rzk_ctx* c, uint32_t V, const int64_t* zs, const int64_t* zp, const int64_t* cs,
+                          const int64_t* cpm, const int64_t* gs, const int64_t* d, int64_t* ts_out, int64_t* tp_out,
+                          int64_t* u_out, uint8_t* accept, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || V == 0 || !zs || !zp || !cs || !cpm || !gs || !d || !ts_out || !tp_out || !u_out || !accept) return RZK_E_ARG;
+  const size_t k = c->k, n = c->n, l = c->l;
+  HostCall h(c);
+  const auto dzs = h.pin(zs, B * V * k), dzp = h.pin(zp, B * k), dcs = h.pin(cs, B * V * (n + l)),
+             dcpm = h.pin(cpm, B * (n + l)), dgs = h.pin(gs, B * V), dd = h.pin(d, B);
+  const auto dts = h.pout(ts_out, B * V * n), dtp = h.pout(tp_out, B * n), du = h.pout(u_out, B * l);
+  const auto dacc = h.out(accept, B);
+  return h.run([&] { return rzk_sum_recover_batch_dev(c, V, dzs, dzp, dcs, dcpm, dgs, dd, dts, dtp, du, dacc, B); });
+}
+
 }  // extern "C"

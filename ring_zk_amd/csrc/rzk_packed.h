@@ -29,7 +29,7 @@
 
 namespace rzk {
 
-// message kinds: the values of RZK_MSG_* (include/rzk.h); 8 and 9 exist in the packed format only
+// message kinds: the values of RZK_MSG_* (include/rzk.h); 8, 9, 11 and 12 exist in the packed format only, 10 is unassigned
 enum PackedKind : int {
   PK_COMMITMENT = 0,         // c
   PK_OPENING = 1,            // a secret, not a stored proof: not supported
@@ -41,6 +41,8 @@ enum PackedKind : int {
   PK_SUM_RESPONSE = 7,       // zp, zs
   PK_LINEAR_RESPONSE = 8,    // z, zp
   PK_OPEN_SHORT = 9,         // c, d, z: the signature form of an Open proof (the verifier recomputes t)
+  PK_LINEAR_SHORT = 11,      // c, cp, g, d, z, zp: the same for Linear (the verifier recomputes t, tp, u)
+  PK_SUM_SHORT = 12,         // cp, cs, gs, d, zp, zs: and for Sum (tp, ts, u)
 };
 
 enum PackedClass : uint8_t { PK_Q = 0, PK_Z = 1, PK_D = 2, PK_NCLASSES = 3 };
@@ -105,7 +107,7 @@ RZK_PK_HD bool packed_widths(int64_t q, uint64_t verify_bound, PackedWidth w[PK_
 
 RZK_PK_HD uint32_t packed_poly_words(uint32_t N, uint32_t W) { return (uint32_t)(((uint64_t)N * W + 63) / 64); }
 
-RZK_PK_HD bool packed_kind_has_v(int kind) { return kind == PK_SUM_COMMITMENT || kind == PK_SUM_RESPONSE; }
+RZK_PK_HD bool packed_kind_has_v(int kind) { return kind == PK_SUM_COMMITMENT || kind == PK_SUM_RESPONSE || kind == PK_SUM_SHORT; }
 
 // Fills *s for a kind over a context (N, n, k, l, q, verify_bound) and V (Sum kinds; ignored elsewhere).  false: bad
 // kind (PK_OPENING included), V == 0 or V > 65535 on a Sum kind, or a context the format does not cover (packed_widths).
@@ -140,6 +142,12 @@ RZK_PK_HD bool packed_schema(int kind, uint32_t N, uint32_t n, uint32_t k, uint3
     case PK_SUM_RESPONSE: add(PK_Z, k); add(PK_Z, V * k); break;
     case PK_LINEAR_RESPONSE: add(PK_Z, k); add(PK_Z, k); break;
     case PK_OPEN_SHORT: add(PK_Q, n + l); add(PK_D, 1); add(PK_Z, k); break;
+    case PK_LINEAR_SHORT:
+      add(PK_Q, n + l); add(PK_Q, n + l); add(PK_Q, 1); add(PK_D, 1); add(PK_Z, k); add(PK_Z, k);
+      break;
+    case PK_SUM_SHORT:
+      add(PK_Q, n + l); add(PK_Q, V * (n + l)); add(PK_Q, V); add(PK_D, 1); add(PK_Z, k); add(PK_Z, V * k);
+      break;
     default: return false;
   }
   for (uint32_t f = s->nfields; f < (uint32_t)kPackedMaxFields; ++f) s->f[f] = PackedField{};

@@ -48,6 +48,15 @@ enum ProgId : int {
 // bit of a program variant: products with the entry's scalar multipliers (g, g_i) take their prepared images (TERM_DKEY)
 constexpr uint32_t kDkeyVar = 0x10000u;
 constexpr uint32_t kOimgVar = 0x20000u;   // ... and (PG_SUM_D) the other operand's transform from the call's operand images (TERM_DD)
+// bit of a program variant: "recover" form of a verifier program.  Every row that tests  lhs - rhs - x == 0  instead stores
+// x' = lhs - rhs into the operand the compare form reads x from (the t / t' / u of a short proof, rzk_*_recover_batch);
+// the fused norm marks and every other row stay as they are.
+constexpr uint32_t kRecoverVar = 0x40000u;
+// the verifier programs that have a recover form; any other id with the bit set is kPlanArg.  The non-rearranged Linear
+// pair (PG_LIN_V1 / PG_LIN_V2) has none: recover calls run PG_LIN_V1B / PG_LIN_V2B on every context.
+inline bool recover_capable(int id) {
+  return id == PG_A1_RELATION || id == PG_REL_ROT || id == PG_LIN_V1B || id == PG_LIN_V2B || id == PG_SUM_V3 || id == PG_SUM_V4;
+}
 
 constexpr int kPlanOk = 0, kPlanArg = -1, kPlanUnsupported = -4;   // plan_program's status: RZK_OK / RZK_E_ARG / RZK_E_UNSUPPORTED (include/rzk.h)
 
@@ -201,13 +210,19 @@ struct PB {
   }
   // a1.z - c1(.)d - t == 0.  c1 = first l rows of c (Commitment::c1_c2 -> split_rows(n), commit.rs:213-218,
   // mat.rs:203-213); Mat::add requires it to have n rows, so n == l is checked by the caller.
-  void relation_rows(uint8_t z_op, uint8_t c_op, uint8_t t_op, uint8_t d_op) {
+  // recover: t_i = (a1.z)_i - (c1(.)d)_i stored instead
+  void relation_rows(uint8_t z_op, uint8_t c_op, uint8_t t_op, uint8_t d_op, bool recover = false) {
     for (uint32_t i = 0; i < e.n; ++i) {
-      begin_row(0, 0, MODE_ZERO);
+      result_row(recover, t_op, i);
       key_row(+1, i, z_op);
       challenge_term(-1, d_op, c_op, i);
-      add(-1, t_op, i);
+      if (!recover) add(-1, t_op, i);
     }
+  }
+  // a row of a verifier's last step: compared with (x_op, i) by the caller's add(-1, x_op, i), or (recover) stored there
+  void result_row(bool recover, uint8_t x_op, uint32_t i) {
+    if (recover) begin_row(x_op, i, MODE_STORE);
+    else begin_row(0, 0, MODE_ZERO);
   }
   // Fused norm predicate: mark, for each polynomial (vop, 0..count-1), the first load in program order
   // (b operand of a product term, or one of the first four additions of a row).  Returns false when some
@@ -242,8 +257,9 @@ struct PB {
 
 inline int build_program(int id, uint32_t var_in, PB& pb) {
   const uint32_t n = pb.e.n, k = pb.e.k, l = pb.e.l;
-  const bool dk = (var_in & kDkeyVar) != 0, oi = (var_in & kOimgVar) != 0;
-  const uint32_t var = var_in & ~(kDkeyVar | kOimgVar);
+  const bool dk = (var_in & kDkeyVar) != 0, oi = (var_in & kOimgVar) != 0, rec = (var_in & kRecoverVar) != 0;
+  const uint32_t var = var_in & ~(kDkeyVar | kOimgVar | kRecoverVar);
+  if (rec && !recover_capable(id)) return kPlanArg;
   bool covered = true;   // a fused-check variant (var & 1) marked every polynomial of its checked vectors
   switch (id) {
     case PG_MATVEC: {   // ops: 0 = v[k], 1 = addend[rows], 2 = out[rows]; which: 0 = a1, 1 = a2, 2 = [a1;a2] (RZK_KEY_*)
@@ -298,10 +314,10 @@ inline int build_program(int id, uint32_t var_in, PB& pb) {
     case PG_REL_ROT:   // ops: 0 = w[n] (= a1.z), 1 = t[n], 2 = c[n+l], 3 = d ; flags &= (w == t + c1(.)d)
       pb.sparse_ops = 1u << 3;
       for (uint32_t i = 0; i < n; ++i) {
-        pb.begin_row(0, 0, MODE_ZERO);
+        pb.result_row(rec, 1, i);
         pb.term(TERM_VEC, -1, 3, 0, 2, i);
         pb.add(+1, 0, i);
-        pb.add(-1, 1, i);
+        if (!rec) pb.add(-1, 1, i);
       }
       break;
     case PG_RESPONSE:   // ops: 0 = d, then per triple s: 1+3s = y[k], 2+3s = r[k], 3+3s = z[k]
@@ -314,7 +330,7 @@ inline int build_program(int id, uint32_t var_in, PB& pb) {
         }
       break;
     case PG_A1_RELATION:   // ops: 0 = z[k], 1 = t[n], 2 = c[n+l], 3 = d ; flags &= (a1.z == t + c1(.)d)
-      pb.relation_rows(0, 2, 1, 3);
+      pb.relation_rows(0, 2, 1, 3, rec);
       if (var & 1) covered = pb.mark_checks(0, k);   // fused check_verify_constraint(z)  (open.rs:167-169)
       break;
     case PG_LIN_COMMIT2:
@@ -351,8 +367,8 @@ inline int build_program(int id, uint32_t var_in, PB& pb) {
       // ops: 0 = z[k], 1 = zp[k], 2 = t[n], 3 = tp[n], 4 = c[n+l], 5 = cp[n+l], 6 = d, 7 = e[l], 8 = ep[l]
       // linear.rs:237-249 reads (a2.z)(.)g - a2.z' == (c2(.)g - c2')(.)d + u; in a commutative ring that is
       // g(.)(a2.z - c2(.)d) - (a2.z' - c2'(.)d) - u == 0: one product with g instead of two, and none in this program
-      pb.relation_rows(0, 4, 2, 6);            // linear.rs:225-229
-      pb.relation_rows(1, 5, 3, 6);            // linear.rs:231-235
+      pb.relation_rows(0, 4, 2, 6, rec);       // linear.rs:225-229
+      pb.relation_rows(1, 5, 3, 6, rec);       // linear.rs:231-235
       for (uint32_t s = 0; s < 2; ++s)         // e = a2.z - c2(.)d, then e' = a2.z' - c2'(.)d ; c2 = last n rows of c
         for (uint32_t i = 0; i < l; ++i) {
           pb.begin_row((uint8_t)(7 + s), i, MODE_STORE);
@@ -363,10 +379,10 @@ inline int build_program(int id, uint32_t var_in, PB& pb) {
       break;
     case PG_LIN_V2B:   // ops: 0 = e[l], 1 = ep[l], 2 = g, 3 = u[l] : g(.)e - e' - u == 0
       for (uint32_t i = 0; i < l; ++i) {
-        pb.begin_row(0, 0, MODE_ZERO);
+        pb.result_row(rec, 3, i);
         pb.scalar_term(dk, +1, 2, 0, 0, i);
         pb.add(-1, 1, i);
-        pb.add(-1, 3, i);
+        if (!rec) pb.add(-1, 3, i);
       }
       break;
     case PG_LIN_V2:
@@ -402,11 +418,11 @@ inline int build_program(int id, uint32_t var_in, PB& pb) {
       break;
     case PG_SUM_V3:   // ops: 0 = w1[V*l] (a2.z_i), 1 = gs[V], 2 = zp[k], 3 = w2[l], 4 = d, 5 = u[l]   (sum.rs:301-319)
       for (uint32_t j = 0; j < l; ++j) {
-        pb.begin_row(0, 0, MODE_ZERO);
+        pb.result_row(rec, 5, j);
         for (uint32_t i = 0; i < var; ++i) pb.scalar_term(dk, +1, 1, i, 0, i * l + j);
         pb.key_row(-1, n + j, 2);
         pb.challenge_term(-1, 4, 3, j);
-        pb.add(-1, 5, j);
+        if (!rec) pb.add(-1, 5, j);
       }
       break;
     case PG_SUM_D:    // ops: 0 = vs[V*k] (ys or zs), 1 = gs[V], 2 = vp[k] (yp or zp), 3 = D[k]
@@ -421,10 +437,10 @@ inline int build_program(int id, uint32_t var_in, PB& pb) {
       break;
     case PG_SUM_V4:   // ops: 0 = D[k], 1 = w2[l], 2 = d, 3 = u[l] : a2.D - w2(.)d - u == 0   (sum.rs:301-319)
       for (uint32_t j = 0; j < l; ++j) {
-        pb.begin_row(0, 0, MODE_ZERO);
+        pb.result_row(rec, 3, j);
         pb.key_row(+1, n + j, 0);
         pb.challenge_term(-1, 2, 1, j);
-        pb.add(-1, 3, j);
+        if (!rec) pb.add(-1, 3, j);
       }
       break;
     default: return kPlanArg;

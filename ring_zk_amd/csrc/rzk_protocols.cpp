@@ -11,18 +11,85 @@ namespace {
 // fused) into `w`, then the relation rows as pure rotations (shift_row_kernel) — 18 instead of 48 transform
 // units per (4,9,4) relation.
 // Verifier side: non-canonical prover data clears the proof's verdict, the call itself succeeds (sticky = false).
+// recover: t is an output, t = a1.z - c1 (.) d (the kRecoverVar forms of the same programs, same launches and paths);
+// accept then only carries the norm predicate and the canonical-input test.
 int run_a1_relation(rzk_ctx* c, const std::vector<OpSpec>& specs, int64_t* w, uint8_t* accept, uint32_t group,
-                    uint64_t batch, uint64_t nflags, bool preset) {
+                    uint64_t batch, uint64_t nflags, bool preset, bool recover = false) {
   // (at N = 2048 the first step runs as row blocks and the second as transform products)
   const bool blocks = !c->small && c->logn >= 10 && c->logn >= c->block_min_logn;
   const bool split = w && c->n >= 2 && ((shift_ok(c) && c->use_groups && c->group_max > 1) || blocks);
   const NormSpec z_norm = {specs[0].base, group * c->k, preset ? 0 : 1, 0};
+  const uint32_t rv = recover ? kRecoverVar : 0u;
   if (!split)
-    return run_checked(c, PG_A1_RELATION, 0, specs, accept, group, batch, nflags, c->verify_bound, preset, false, {z_norm});
+    return run_checked(c, PG_A1_RELATION, rv, specs, accept, group, batch, nflags, c->verify_bound, preset, false, {z_norm});
   int rc = run_checked(c, PG_A1Z, 0, {specs[0], {w, c->n, 0}}, accept, group, batch, nflags, c->verify_bound, preset, false,
                        {z_norm});
   if (rc != RZK_OK) return rc;
-  return run_program(c, PG_REL_ROT, 0, {{w, c->n, 0}, specs[1], specs[2], specs[3]}, accept, group, batch, 0, false);
+  return run_program(c, PG_REL_ROT, rv, {{w, c->n, 0}, specs[1], specs[2], specs[3]}, accept, group, batch, 0, false);
+}
+
+// Linear's verifier, rearranged (PG_LIN_V1B / V2B): no product with g in the first program, so it runs on the unit kernel
+// (and initialises the verdicts itself where one team owns a proof); e / e' live in the workspace.
+// recover: t, tp, u are outputs (linear.rs:224-249 solved for them).
+int linear_rearranged(rzk_ctx* c, const int64_t* z, const int64_t* zp, const int64_t* cm, const int64_t* cpm, const int64_t* g,
+                      const int64_t* t, const int64_t* tp, const int64_t* u, const int64_t* d, uint8_t* accept, size_t B,
+                      bool recover) {
+  const uint32_t n = c->n, k = c->k, l = c->l, rv = recover ? kRecoverVar : 0u;
+  int rc = arena_reserve(c, c->ws, polys(c, 2 * B * l));
+  if (rc != RZK_OK) return rc;
+  int64_t* e = (int64_t*)c->ws.p;
+  int64_t* ep = e + B * l * c->N;
+  const std::vector<OpSpec> v1b = {{z, k, 0}, {zp, k, 0}, {t, n, 0}, {tp, n, 0}, {cm, n + l, 0}, {cpm, n + l, 0},
+                                   {d, 1, 0}, {e, l, 0}, {ep, l, 0}};
+  rc = run_checked(c, PG_LIN_V1B, rv, v1b, accept, 1, B, B, c->verify_bound, true, false, {{z, k, 0, 0}, {zp, k, 1, 0}});
+  if (rc != RZK_OK) return rc;
+  rc = prepare_dkey(c, g, B, 1, l, accept, false);   // (after the verdicts exist; l rows multiply by g)
+  if (rc != RZK_OK) return rc;
+  DkeyScope dkey_scope{c};
+  return run_program(c, PG_LIN_V2B, rv | dkv(c), {{e, l, 0}, {ep, l, 0}, {g, 1, 0}, {u, l, 0}}, accept, 1, B, 0, false);
+}
+
+// Sum's verifier (sum.rs:262-319).  recover: ts, tp, u are outputs.
+int sum_relations(rzk_ctx* c, uint32_t V, const int64_t* zs, const int64_t* zp, const int64_t* cs, const int64_t* cpm,
+                  const int64_t* gs, const int64_t* ts, const int64_t* tp, const int64_t* u, const int64_t* d, uint8_t* accept,
+                  size_t B, bool recover) {
+  const uint32_t n = c->n, k = c->k, l = c->l, rv = recover ? kRecoverVar : 0u;
+  const bool by_d = sum_uses_d(c, V);
+  const size_t w1polys = by_d && (size_t)B * k > (size_t)B * V * l ? (size_t)B * k : (size_t)B * V * l;   // w1[B*V][l], or D[B][k]
+  int rc = arena_reserve(c, c->ws, polys(c, w1polys + B * l + B * V * n));
+  if (rc != RZK_OK) return rc;
+  int64_t* w1 = (int64_t*)c->ws.p;
+  int64_t* w2 = w1 + w1polys * c->N;
+  int64_t* w0 = w2 + B * l * c->N;   // a1.z of the relation checks (n >= 2 only)
+  const std::vector<OpSpec> rel_s = {{zs, k, 0}, {ts, n, 0}, {cs, n + l, 0}, {d, 1, 1}};
+  const std::vector<OpSpec> rel_p = {{zp, k, 0}, {tp, n, 0}, {cpm, n + l, 0}, {d, 1, 0}};
+  // sum.rs:262-271 norm predicates ride on sum.rs:278-291 (every summand; batch entries B*V, flag per proof)
+  // and sum.rs:294-298
+  // (the a1.z_i key products leave the transforms of z_i's a2-columns for the D rows: operand 0 of their launch)
+  rc = prepare_oimg(c, B, V, 2 * l);
+  if (rc != RZK_OK) return rc;
+  OimgScope oimg_scope{c};
+  {
+    OimgProducer images_of_zs(c, 0);
+    rc = run_a1_relation(c, rel_s, w0, accept, V, B * V, B, true, recover);
+  }
+  if (rc != RZK_OK) return rc;
+  rc = run_a1_relation(c, rel_p, w0, accept, 1, B, B, false, recover);
+  if (rc != RZK_OK) return rc;
+  // sum.rs:301-319.  The multipliers' images are prepared AFTER the relation rows above have initialised accept: a
+  // non-canonical g_i must clear the proof's verdict, and nothing presets the flags again from here on.
+  rc = prepare_dkey(c, gs, B, V, 2 * l, accept, false);
+  if (rc != RZK_OK) return rc;
+  DkeyScope dkey_scope{c};
+  // by_d: lhs = a2.(sum_i g_i(.)z_i - zp), D in w1's place, then one relation row per row of a2; else a2.z_i into w1
+  rc = by_d ? run_program(c, PG_SUM_D, V | dkv(c) | oiv(c), {{zs, V * k, 0}, {gs, V, 0}, {zp, k, 0}, {w1, k, 0}}, accept, 1, B, 0, false)
+            : run_program(c, PG_MATVEC, RZK_KEY_A2 * 2, {{zs, k, 0}, {nullptr, l, 0}, {w1, l, 0}}, accept, V, B * V, 0, false);
+  if (rc != RZK_OK) return rc;
+  rc = run_program(c, PG_SUM_W2, V | dkv(c), {{cs, V * (n + l), 0}, {gs, V, 0}, {cpm, n + l, 0}, {w2, l, 0}}, accept, 1, B, 0, false);
+  if (rc != RZK_OK) return rc;
+  if (by_d) return run_program(c, PG_SUM_V4, rv, {{w1, k, 0}, {w2, l, 0}, {d, 1, 0}, {u, l, 0}}, accept, 1, B, 0, false);
+  return run_program(c, PG_SUM_V3, V | rv | dkv(c), {{w1, V * l, 0}, {gs, V, 0}, {zp, k, 0}, {w2, l, 0}, {d, 1, 0}, {u, l, 0}}, accept,
+                     1, B, 0, false);
 }
 
 }  // namespace
@@ -203,24 +270,13 @@ int rzk_linear_verify_batch_dev(rzk_ctx* c, const int64_t* z, const int64_t* zp,
   if (!c || !z || !zp || !cm || !cpm || !g || !t || !tp || !u || !d || !accept) return RZK_E_ARG;
   if (c->n != c->l) return fail(c, RZK_E_ARG, "c1_c2 split needs n == l (reference panics in Mat::add)");
   const uint32_t n = c->n, k = c->k, l = c->l;
+  if (c->lin_e && !c->small) return linear_rearranged(c, z, zp, cm, cpm, g, t, tp, u, d, accept, B, false);
   int rc = arena_reserve(c, c->ws, polys(c, 2 * B * l));
   if (rc != RZK_OK) return rc;
   int64_t* w1 = (int64_t*)c->ws.p;
   int64_t* w2 = w1 + B * l * c->N;
   const std::vector<OpSpec> v1 = {{z, k, 0}, {zp, k, 0}, {t, n, 0}, {tp, n, 0}, {cm, n + l, 0}, {cpm, n + l, 0},
                                   {d, 1, 0}, {g, 1, 0}, {w1, l, 0}, {w2, l, 0}};
-  if (c->lin_e && !c->small) {
-    // rearranged (PG_LIN_V1B / V2B): no product with g in the first program, so it runs on the unit kernel (and
-    // initialises the verdicts itself where one team owns a proof); w1 / w2 hold e / e'
-    const std::vector<OpSpec> v1b = {{z, k, 0}, {zp, k, 0}, {t, n, 0}, {tp, n, 0}, {cm, n + l, 0}, {cpm, n + l, 0},
-                                     {d, 1, 0}, {w1, l, 0}, {w2, l, 0}};
-    rc = run_checked(c, PG_LIN_V1B, 0, v1b, accept, 1, B, B, c->verify_bound, true, false, {{z, k, 0, 0}, {zp, k, 1, 0}});
-    if (rc != RZK_OK) return rc;
-    rc = prepare_dkey(c, g, B, 1, l, accept, false);   // (after the verdicts exist; l rows multiply by g)
-    if (rc != RZK_OK) return rc;
-    DkeyScope dkey_scope{c};
-    return run_program(c, PG_LIN_V2B, dkv(c), {{w1, l, 0}, {w2, l, 0}, {g, 1, 0}, {u, l, 0}}, accept, 1, B, 0, false);
-  }
   // The verdicts are initialised first, then the multiplier's images are prepared (a non-canonical g clears its proof's
   // verdict: nothing may preset the flags after that), then the rows.
   rc = check_launch(c, launch_fill_u8(cfg_of(c), accept, 1, B), "flag preset");
@@ -304,43 +360,39 @@ int rzk_sum_verify_batch_dev(rzk_ctx* c, uint32_t V, const int64_t* zs, const in
   if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
   if (!c || V == 0 || !zs || !zp || !cs || !cpm || !gs || !ts || !tp || !u || !d || !accept) return RZK_E_ARG;
   if (c->n != c->l) return fail(c, RZK_E_ARG, "c1_c2 split needs n == l (reference panics in Mat::add)");
-  const uint32_t n = c->n, k = c->k, l = c->l;
-  const bool by_d = sum_uses_d(c, V);
-  const size_t w1polys = by_d && (size_t)B * k > (size_t)B * V * l ? (size_t)B * k : (size_t)B * V * l;   // w1[B*V][l], or D[B][k]
-  int rc = arena_reserve(c, c->ws, polys(c, w1polys + B * l + B * V * n));
+  return sum_relations(c, V, zs, zp, cs, cpm, gs, ts, tp, u, d, accept, B, false);
+}
+
+// ---- recompute steps of the short proofs: the verifiers' launches with the commitment message as output --------------
+int rzk_open_recover_batch_dev(rzk_ctx* c, const int64_t* z, const int64_t* cm, const int64_t* d, int64_t* t_out,
+                               uint8_t* accept, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !z || !cm || !d || !t_out || !accept) return RZK_E_ARG;
+  if (c->n != c->l) return fail(c, RZK_E_ARG, "c1_c2 split needs n == l (reference panics in Mat::add)");
+  const std::vector<OpSpec> specs = {{z, c->k, 0}, {t_out, c->n, 0}, {cm, c->n + c->l, 0}, {d, 1, 0}};
+  int rc = arena_reserve(c, c->ws, polys(c, B * c->n));
   if (rc != RZK_OK) return rc;
-  int64_t* w1 = (int64_t*)c->ws.p;
-  int64_t* w2 = w1 + w1polys * c->N;
-  int64_t* w0 = w2 + B * l * c->N;   // a1.z of the relation checks (n >= 2 only)
-  const std::vector<OpSpec> rel_s = {{zs, k, 0}, {ts, n, 0}, {cs, n + l, 0}, {d, 1, 1}};
-  const std::vector<OpSpec> rel_p = {{zp, k, 0}, {tp, n, 0}, {cpm, n + l, 0}, {d, 1, 0}};
-  // sum.rs:262-271 norm predicates ride on sum.rs:278-291 (every summand; batch entries B*V, flag per proof)
-  // and sum.rs:294-298
-  // (the a1.z_i key products leave the transforms of z_i's a2-columns for the D rows: operand 0 of their launch)
-  rc = prepare_oimg(c, B, V, 2 * l);
-  if (rc != RZK_OK) return rc;
-  OimgScope oimg_scope{c};
-  {
-    OimgProducer images_of_zs(c, 0);
-    rc = run_a1_relation(c, rel_s, w0, accept, V, B * V, B, true);
-  }
-  if (rc != RZK_OK) return rc;
-  rc = run_a1_relation(c, rel_p, w0, accept, 1, B, B, false);
-  if (rc != RZK_OK) return rc;
-  // sum.rs:301-319.  The multipliers' images are prepared AFTER the relation rows above have initialised accept: a
-  // non-canonical g_i must clear the proof's verdict, and nothing presets the flags again from here on.
-  rc = prepare_dkey(c, gs, B, V, 2 * l, accept, false);
-  if (rc != RZK_OK) return rc;
-  DkeyScope dkey_scope{c};
-  // by_d: lhs = a2.(sum_i g_i(.)z_i - zp), D in w1's place, then one relation row per row of a2; else a2.z_i into w1
-  rc = by_d ? run_program(c, PG_SUM_D, V | dkv(c) | oiv(c), {{zs, V * k, 0}, {gs, V, 0}, {zp, k, 0}, {w1, k, 0}}, accept, 1, B, 0, false)
-            : run_program(c, PG_MATVEC, RZK_KEY_A2 * 2, {{zs, k, 0}, {nullptr, l, 0}, {w1, l, 0}}, accept, V, B * V, 0, false);
-  if (rc != RZK_OK) return rc;
-  rc = run_program(c, PG_SUM_W2, V | dkv(c), {{cs, V * (n + l), 0}, {gs, V, 0}, {cpm, n + l, 0}, {w2, l, 0}}, accept, 1, B, 0, false);
-  if (rc != RZK_OK) return rc;
-  if (by_d) return run_program(c, PG_SUM_V4, 0, {{w1, k, 0}, {w2, l, 0}, {d, 1, 0}, {u, l, 0}}, accept, 1, B, 0, false);
-  return run_program(c, PG_SUM_V3, V | dkv(c), {{w1, V * l, 0}, {gs, V, 0}, {zp, k, 0}, {w2, l, 0}, {d, 1, 0}, {u, l, 0}}, accept,
-                     1, B, 0, false);
+  // open.rs:171-173 solved for t: t = a1.z - c1 (.) d
+  return run_a1_relation(c, specs, (int64_t*)c->ws.p, accept, 1, B, B, true, true);
+}
+
+int rzk_linear_recover_batch_dev(rzk_ctx* c, const int64_t* z, const int64_t* zp, const int64_t* cm, const int64_t* cpm,
+                                 const int64_t* g, const int64_t* d, int64_t* t_out, int64_t* tp_out, int64_t* u_out,
+                                 uint8_t* accept, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !z || !zp || !cm || !cpm || !g || !d || !t_out || !tp_out || !u_out || !accept) return RZK_E_ARG;
+  if (c->n != c->l) return fail(c, RZK_E_ARG, "c1_c2 split needs n == l (reference panics in Mat::add)");
+  // on every context (small rings and RZK_LIN_E=0 included): the non-rearranged pair has no recover form
+  return linear_rearranged(c, z, zp, cm, cpm, g, t_out, tp_out, u_out, d, accept, B, true);
+}
+
+int rzk_sum_recover_batch_dev(rzk_ctx* c, uint32_t V, const int64_t* zs, const int64_t* zp, const int64_t* cs,
+                              const int64_t* cpm, const int64_t* gs, const int64_t* d, int64_t* ts_out, int64_t* tp_out,
+                              int64_t* u_out, uint8_t* accept, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || V == 0 || !zs || !zp || !cs || !cpm || !gs || !d || !ts_out || !tp_out || !u_out || !accept) return RZK_E_ARG;
+  if (c->n != c->l) return fail(c, RZK_E_ARG, "c1_c2 split needs n == l (reference panics in Mat::add)");
+  return sum_relations(c, V, zs, zp, cs, cpm, gs, ts_out, tp_out, u_out, d, accept, B, true);
 }
 
 }  // extern "C"

@@ -12,6 +12,8 @@ rzk_fs_challenge_batch[_dev]): a proof is (commitment message, response), and an
     (`packed.py`, DESIGN.md §13);
   * `open_short` / `open_verify_short` / `open_verify_short_packed`: the signature form of an Open proof, (c, d, z): the
     verifier recomputes t from the verification equation and accepts iff the transcript of (c, t) gives d again;
+  * `linear_short` / `linear_verify_short[_packed]`, `sum_short` / `sum_verify_short[_packed]`: the same for Linear and
+    Sum proofs, which drop t, t', u (DESIGN.md §16).  A short proof and a full proof are one proof in two encodings;
   * `multipliers`: the public multipliers g / g_i of Linear and Sum proofs derived from seeds (DESIGN.md §14);
   * `open_prove_sampled`, `linear_prove_sampled`, `sum_prove_sampled`: the provers with r and y drawn on the device by a
     `backend.KeyedSampler` (ChaCha20, DESIGN.md §11) instead of supplied by the caller;
@@ -31,8 +33,8 @@ from typing import Optional
 import numpy as np
 
 from . import packed, wire
-from ._lib import (KEY_A1, MSG_LINEAR_COMMITMENT, MSG_LINEAR_RESPONSE, MSG_OPEN_COMMITMENT, MSG_OPEN_RESPONSE,
-                   MSG_OPEN_SHORT, MSG_SUM_COMMITMENT, MSG_SUM_RESPONSE)
+from ._lib import (MSG_LINEAR_COMMITMENT, MSG_LINEAR_RESPONSE, MSG_LINEAR_SHORT, MSG_OPEN_COMMITMENT, MSG_OPEN_RESPONSE,
+                   MSG_OPEN_SHORT, MSG_SUM_COMMITMENT, MSG_SUM_RESPONSE, MSG_SUM_SHORT)
 
 KINDS = (MSG_OPEN_COMMITMENT, MSG_LINEAR_COMMITMENT, MSG_SUM_COMMITMENT)
 
@@ -101,6 +103,12 @@ def multipliers(ctx, seeds, V: Optional[int] = None, domain: int = 1):
     return ctx.xof_uniform(seeds, V, domain)
 
 
+def _same_challenge(ctx, d2, d):
+    """d2 (recomputed, canonical) == d per proof; d is foreign, so its canonical copy is compared: a non-canonical d has
+    already cleared the verdict of the recompute step and must not fail the call here."""
+    return ctx.eq(d2.reshape(-1, 1, ctx.N), ctx.canonicalize(d).reshape(-1, 1, ctx.N))
+
+
 def _flag(cond):
     """boolean array / tensor -> uint8 flags"""
     if wire._is_torch(cond):
@@ -151,17 +159,12 @@ def open_short(ctx, c, t, z, aux=None):
 
 def open_verify_short(ctx, c, d, z, aux=None):
     """Verifier of the short form: t' = a1.z - c1 (.) d is the only t that satisfies the verification equation
-    (open.rs:171-173) for (c, d, z); accept iff the transcript of (c, t') gives d again, z passes the norm rule
-    (open_verify on (z, t', c, d), which also rejects non-canonical input) and the transcript hash accepted its input.
-    An honest proof has t' = t.  t' is computed on canonicalized copies, so that foreign data rejects its proof instead
-    of failing the call."""
-    zc, cc, dc = ctx.canonicalize(z), ctx.canonicalize(c), ctx.canonicalize(d)
-    c1 = cc[:, :ctx.n]
-    c1 = c1.contiguous() if wire._is_torch(c1) else np.ascontiguousarray(c1)
-    t = ctx.sub(ctx.matvec(KEY_A1, zc), ctx.cmul(c1, dc))
+    (open.rs:171-173) for (c, d, z), computed by Context.open_recover together with the norm rule on z; accept iff the
+    transcript of (c, t') gives d again, z passes the norm rule and neither step met a non-canonical coefficient
+    (foreign data rejects its proof instead of failing the call).  An honest proof has t' = t."""
+    t, acc = ctx.open_recover(z, c, d)
     d2, _, okf = challenge(ctx, MSG_OPEN_COMMITMENT, c, t, aux=aux)   # the caller's c: a non-canonical one clears okf
-    same = ctx.eq(d2.reshape(-1, 1, ctx.N), dc.reshape(-1, 1, ctx.N))
-    return ctx.open_verify(z, t, c, d) & same & okf
+    return acc & okf & _same_challenge(ctx, d2, d)
 
 
 def open_verify_short_packed(ctx, records, aux=None):
@@ -192,6 +195,28 @@ def linear_verify_packed(ctx, commitment_records, response_records, aux=None):
     return linear_verify(ctx, c, cp, g, t, tp, u, z, zp, aux=aux) & ok1 & ok2
 
 
+def linear_short(ctx, c, cp, g, t, tp, u, z, zp, aux=None):
+    """The short form of the Linear proof: (c, cp, g, d, z, zp) with d = challenge(c, cp, g, t, tp, u).  Returns d; the
+    verifier recomputes t, tp, u (linear_verify_short)."""
+    d, _, _ = challenge(ctx, MSG_LINEAR_COMMITMENT, c, cp, g, t, tp, u, aux=aux)
+    return d
+
+
+def linear_verify_short(ctx, c, cp, g, d, z, zp, aux=None):
+    """Verifier of the short Linear proof: Context.linear_recover gives the only (t', tp', u') that satisfy
+    linear.rs:224-249 for the rest of the proof, with the norm rule on z and zp; accept iff the transcript of the full
+    commitment message with them gives d again."""
+    t, tp, u, acc = ctx.linear_recover(z, zp, c, cp, g, d)
+    d2, _, okf = challenge(ctx, MSG_LINEAR_COMMITMENT, c, cp, g, t, tp, u, aux=aux)
+    return acc & okf & _same_challenge(ctx, d2, d)
+
+
+def linear_verify_short_packed(ctx, records, aux=None):
+    """linear_verify_short from packed MSG_LINEAR_SHORT records; a record that does not decode rejects its own proof."""
+    c, cp, g, d, z, zp, ok = packed.decode_batch(ctx, MSG_LINEAR_SHORT, records)
+    return linear_verify_short(ctx, c, cp, g, d, z, zp, aux=aux) & ok
+
+
 # ---- SumProof (src/prove/sum.rs) ---------------------------------------------------------------------------------------
 def sum_prove(ctx, gs, xs, rs, rp, ys, yp, aux=None):
     """(cs, cp, ts, tp, u, zs, zp, ok) for V = gs.shape[-2] summands per proof."""
@@ -214,6 +239,28 @@ def sum_verify_packed(ctx, commitment_records, response_records, V: int, aux=Non
     cp, cs, gs, tp, ts, u, ok1 = packed.decode_batch(ctx, MSG_SUM_COMMITMENT, commitment_records, V=V)
     zp, zs, ok2 = packed.decode_batch(ctx, MSG_SUM_RESPONSE, response_records, V=V)
     return sum_verify(ctx, cs, cp, gs, ts, tp, u, zs, zp, aux=aux) & ok1 & ok2
+
+
+def sum_short(ctx, cs, cp, gs, ts, tp, u, zs, zp, aux=None):
+    """The short form of the Sum proof: (cp, cs, gs, d, zp, zs) with d = challenge(cp, cs, gs, tp, ts, u).  Returns d."""
+    V = int(gs.shape[-2])
+    d, _, _ = challenge(ctx, MSG_SUM_COMMITMENT, cp, cs, gs, tp, ts, u, V=V, aux=aux)
+    return d
+
+
+def sum_verify_short(ctx, cs, cp, gs, d, zs, zp, aux=None):
+    """Verifier of the short Sum proof: Context.sum_recover gives the only (ts', tp', u') that satisfy sum.rs:277-319,
+    with the norm rule on every z_i and zp; accept iff the transcript of the full commitment message gives d again."""
+    V = int(gs.shape[-2])
+    ts, tp, u, acc = ctx.sum_recover(zs, zp, cs, cp, gs, d)
+    d2, _, okf = challenge(ctx, MSG_SUM_COMMITMENT, cp, cs, gs, tp, ts, u, V=V, aux=aux)
+    return acc & okf & _same_challenge(ctx, d2, d)
+
+
+def sum_verify_short_packed(ctx, records, V: int, aux=None):
+    """sum_verify_short from packed MSG_SUM_SHORT records of V summands."""
+    cp, cs, gs, d, zp, zs, ok = packed.decode_batch(ctx, MSG_SUM_SHORT, records, V=V)
+    return sum_verify_short(ctx, cs, cp, gs, d, zs, zp, aux=aux) & ok
 
 
 # ---- provers that draw their own randomness (backend.KeyedSampler: ChaCha20 on the device, DESIGN.md §11) ---------------

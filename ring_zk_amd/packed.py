@@ -4,8 +4,9 @@ The compact stored form of the protocol messages: every record of a kind has the
 coefficient takes the bits its field class needs (`widths`), and both directions are one GPU launch
 (rzk_packed_{encode,decode}_batch[_dev]).  `wire.py` remains the reference's bincode form.
 
-Kinds: the MSG_* values of `wire.py` except MSG_OPENING, plus MSG_LINEAR_RESPONSE { z, zp } and MSG_OPEN_SHORT
-{ c, d, z } (the signature form of an Open proof, fiat_shamir.open_verify_short).  Inputs are numpy arrays (host entry
+Kinds: the MSG_* values of `wire.py` except MSG_OPENING, plus MSG_LINEAR_RESPONSE { z, zp } and the short (signature)
+forms of the three proofs, MSG_OPEN_SHORT { c, d, z }, MSG_LINEAR_SHORT { c, cp, g, d, z, zp } and MSG_SUM_SHORT
+{ cp, cs, gs, d, zp, zs } (fiat_shamir.*_verify_short).  Inputs are numpy arrays (host entry
 points) or torch CUDA tensors (device entry points on torch's current stream), as everywhere in the package.
 """
 from __future__ import annotations
@@ -17,11 +18,12 @@ import numpy as np
 
 from . import wire
 from ._lib import (MSG_CHALLENGE, MSG_COMMITMENT, MSG_LINEAR_COMMITMENT, MSG_LINEAR_RESPONSE,  # noqa: F401
-                   MSG_OPEN_COMMITMENT, MSG_OPEN_RESPONSE, MSG_OPEN_SHORT, MSG_OPENING, MSG_SUM_COMMITMENT,
-                   MSG_SUM_RESPONSE)
+                   MSG_LINEAR_SHORT, MSG_OPEN_COMMITMENT, MSG_OPEN_RESPONSE, MSG_OPEN_SHORT, MSG_OPENING,
+                   MSG_SUM_COMMITMENT, MSG_SUM_RESPONSE, MSG_SUM_SHORT)
 
 KINDS = (MSG_COMMITMENT, MSG_CHALLENGE, MSG_OPEN_COMMITMENT, MSG_OPEN_RESPONSE, MSG_LINEAR_COMMITMENT, MSG_SUM_COMMITMENT,
          MSG_SUM_RESPONSE, MSG_LINEAR_RESPONSE, MSG_OPEN_SHORT)
+SHORT_KINDS = (MSG_LINEAR_SHORT, MSG_SUM_SHORT)   # the short Linear and Sum proofs; also packed kinds
 
 
 def widths(ctx) -> Tuple[int, int]:
@@ -40,12 +42,18 @@ def record_bytes(ctx, kind: int, V: Optional[int] = None) -> int:
 
 
 def field_shapes(ctx, kind: int, V: Optional[int] = None) -> List[Tuple[str, tuple]]:
-    """wire.field_shapes extended by the two kinds of the packed format; MSG_OPENING is not a packed kind."""
+    """wire.field_shapes extended by the kinds of the packed format only; MSG_OPENING is not a packed kind."""
     N, n, k, l = ctx.N, ctx.n, ctx.k, ctx.l
     if kind == MSG_LINEAR_RESPONSE:
         return [("z", (k, N)), ("zp", (k, N))]
     if kind == MSG_OPEN_SHORT:
         return [("c", (n + l, N)), ("d", (N,)), ("z", (k, N))]
+    if kind == MSG_LINEAR_SHORT:
+        return [("c", (n + l, N)), ("cp", (n + l, N)), ("g", (N,)), ("d", (N,)), ("z", (k, N)), ("zp", (k, N))]
+    if kind == MSG_SUM_SHORT:
+        if V is None or V < 1:
+            raise ValueError("MSG_SUM_SHORT needs V >= 1")
+        return [("cp", (n + l, N)), ("cs", (V, n + l, N)), ("gs", (V, N)), ("d", (N,)), ("zp", (k, N)), ("zs", (V, k, N))]
     if kind not in KINDS:
         raise ValueError("not a kind of the packed format")
     return wire.field_shapes(ctx, kind, V)
