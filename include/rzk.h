@@ -622,6 +622,14 @@ int rzk_prof_read_kernels(rzk_ctx* ctx, char* buf, size_t cap, size_t* needed);
  *                          team evaluates a whole batch entry)
  *   RZK_UNIT_IO=0|1        key-product programs without vector operands: unit_io_kernel (operands read once, per-prime sums
  *                          parked on chip) instead of unit_kernel (default 1 at N = 512, 0 otherwise)
+ *   RZK_ROT_LAST=0         unit_kernel: every row's rotation terms (c1 (.) d of the verifier relation) run before the transforms and
+ *                          their sum waits in the wavefront's scratch line (default 1: in single-row units of one-wavefront
+ *                          teams, N <= 1024, they run after the last inverse transform and accumulate in registers)
+ *   RZK_DOT2=0             unit_kernel: each key product of a row is reduced on its own (default 1: a unit of exactly two key
+ *                          products into its first row parks the first transform and reduces x1 k1 + x2 k2 once; one-wavefront
+ *                          teams, N <= 1024)
+ *   RZK_CRT2_SHORT=0       unit kernels: the two-prime reconstruction with two reductions mod q and a 64-bit sign test
+ *                          (default 1: digit compares and one reduction, crt2_zq_short)
  *   RZK_GRID_CUS=<c>       testing: size every grid cap, and the scratch behind it, for c CUs instead of the device's count
  *                          (clamped to 1 .. multiProcessorCount; 0 or a non-number gives 1), so that small batches make
  *                          several grid-stride trips.  The batch at which RZK_UPT's default switches to all units per

@@ -302,6 +302,16 @@ RZK_HD uint32_t mac_sub(uint32_t acc, uint32_t x, uint32_t k, const PrimeConsts&
   return csub(acc + pc.twop - mont_lazy(x, k, pc.p, pc.npinv), pc.twop);
 }
 
+// x1*k1 + x2*k2 with ONE Montgomery reduction -> [0,2p), congruent to mac_add(mont_lazy(x1,k1), x2, k2).
+// x < 2^32 and k <= p < 2^30 (Montgomery form; a minus term passes p - k), so T = x1 k1 + x2 k2 < 2^63; m p < 2^62, so
+// T + m p < 2^64 does not wrap; its high word is < 2^31 + 2^30 = 3 * 2^30 < 4p, so csub(., 2p) yields a value in [0,2p).
+RZK_HD uint32_t dot2_lazy(uint32_t x1, uint32_t k1, uint32_t x2, uint32_t k2, const PrimeConsts& pc) {
+  const uint64_t t = (uint64_t)x1 * k1 + (uint64_t)x2 * k2;
+  const uint32_t m = (uint32_t)t * pc.npinv;
+  const uint64_t u = (uint64_t)m * pc.p + t;   // low 32 bits are zero
+  return csub((uint32_t)(u >> 32), pc.twop);
+}
+
 // ---- CRT reconstruction and reduction to the centred representative mod q ------------------------------------
 struct CrtConsts {
   uint32_t q, qinv;        // ring modulus (odd, < 2^32) and q^{-1} mod 2^32
@@ -321,6 +331,10 @@ struct CrtConsts {
   uint32_t hmodq[4];       // H_np mod q
   uint32_t r2q;            // 2^64 mod q   (montq_u(a, r2q) = a * 2^32 mod q)
   uint32_t r48q;           // 2^48 mod q   (montq_u(a, r48q) = a * 2^16 mod q)
+  // crt2_zq_short: (p0 p1 + 1)/2 = half2_d1 * p0 + half2_d0 (mixed-radix digits), and the weights of its one reduction
+  uint32_t half2_d1, half2_d0;
+  uint32_t r1q;            // 2^32 mod q
+  uint32_t knq;            // (q - p0 p1 mod q) * 2^32 mod q
 };
 
 // a*c*2^{-32} mod q as a signed value in (-q, q);  a, c < 2^32
@@ -426,6 +440,26 @@ RZK_HD uint32_t crt2_zq(uint32_t r1, uint32_t d0, const PrimeConsts* pc, const C
   const uint32_t va = addq(d0, montq_u(d1, C.c1, C), C.q);                   // (d0 + d1 p0) mod q
   const uint64_t x01 = (uint64_t)d1 * pc[0].p + d0;                          // X mod p0 p1, exact
   return subq(va, x01 >= C.half2 ? C.pmodq[2] : 0u, C.q);                    // negative X: minus P mod q
+}
+// The same value with one reduction mod q (19.2 vector instructions per coefficient against 26.6 in unit_kernel at
+// N = 1024, tools/inst_budget.py): the sign of
+// X' = d0 + d1 p0 against (P+1)/2 = half2_d0 + half2_d1 p0 is a comparison of mixed-radix digits (both low digits are
+// below p0, so the order is lexicographic: no 64-bit product or compare), and
+//     T = d0 * 2^32 + d1 * p0 2^32 + neg * (q - P) 2^32      (each weight reduced mod q)
+// is accumulated in 64 bits and divided by 2^32 mod q once.  T <= (p0 - 1)(q - 1) + (p1 - 1)(q - 1) + (q - 1)
+// < (p0 + p1) q < 2^31 q, so T < 2^63 never wraps and its high word is below q/2: t - m q is an exact multiple of 2^32
+// whose quotient hi(t) - hi(m q) lies in (-q, q), and one conditional add of q lands in [0, q).
+RZK_HD uint32_t crt2_zq_short(uint32_t r1, uint32_t d0, const PrimeConsts* pc, const CrtConsts& C) {   // np = 2: X mod q in [0,q)
+  const uint32_t t1 = r1 + pc[1].twop - d0;
+  const uint32_t d1 = csub(mont_lazy(t1, C.inv01_r, pc[1].p, pc[1].npinv), pc[1].p);   // canonical second digit
+  const bool neg = d1 >= C.half2_d1 + (d0 < C.half2_d0 ? 1u : 0u);            // X' >= (P+1)/2; half2_d1 < 2^30: no wrap
+  uint64_t t = (uint64_t)d1 * C.c1 + (uint64_t)(neg ? C.knq : 0u);   // two v_mad_u64_u32, the selected weight as the first addend
+  t += (uint64_t)d0 * C.r1q;
+  const uint32_t m = (uint32_t)t * C.qinv;
+  const uint32_t h = (uint32_t)(((uint64_t)m * C.q) >> 32);
+  uint32_t d;
+  const bool borrow = __builtin_sub_overflow((uint32_t)(t >> 32), h, &d);    // as in csub: subtract with borrow-out, then select
+  return borrow ? d + C.q : d;
 }
 // second digit d1 = (X' mod p1 - d0) * p0^{-1} mod p1 from the prime-1 residue r and d0
 RZK_HD uint32_t crt_digit1(uint32_t r, uint32_t d0, int np, const PrimeConsts* pc, const CrtConsts& C) {

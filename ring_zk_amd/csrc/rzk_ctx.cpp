@@ -106,6 +106,9 @@ const Knob kKnobs[] = {
     {"RZK_PAIR_POLY", &rzk_ctx::pair_poly, "0: one wavefront per polynomial at N = 2048"},
     {"RZK_UNIT_IO", &rzk_ctx::unit_io, "0 / 1: force unit_kernel / unit_io_kernel for key-product programs (default: N = 512 only)"},
     {"RZK_BLOCK_MIN_LOGN", &rzk_ctx::block_min_logn, "row blocks from this log2 N on (12: never)"},
+    {"RZK_ROT_LAST", &rzk_ctx::rot_last, "0: unit_kernel evaluates every row's rotation terms first, through its scratch line"},
+    {"RZK_DOT2", &rzk_ctx::dot2, "0: unit_kernel reduces each of a two-product row's products on its own"},
+    {"RZK_CRT2_SHORT", &rzk_ctx::crt2_short, "0: two-prime reconstruction with two reductions mod q (crt2_zq)"},
 };
 
 // needs num_cus, group_max and unit_io at their defaults
@@ -182,6 +185,7 @@ int rzk_ctx_create(rzk_ctx** out, int64_t q, uint32_t N, uint32_t n, uint32_t k,
   c->group_max = group_max_for((int)c->logn);
   c->unit_io = c->logn == 9;
   read_knobs(c);
+  c->hT.diet = (c->rot_last ? DIET_ROT_LAST : 0u) | (c->crt2_short ? DIET_CRT2 : 0u);   // (RZK_DOT2 goes into the plans: plan_env)
   if ((de = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking)) != hipSuccess) {
     delete c;
     return create_fail(RZK_E_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(de));

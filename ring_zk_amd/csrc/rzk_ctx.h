@@ -82,6 +82,9 @@ struct rzk_ctx {
   bool pair_poly = true;               // N = 2048: two wavefronts per polynomial (RZK_PAIR_POLY=0: one, the round-2 kernels)
   bool trusted = false;                // rzk_ctx_trust_device_outputs: skip the canonical test of loaded coefficients
   bool use_pairs = true;               // unit_kernel: pair rows that share their last operand (RZK_PAIRS=0 turns it off, tuning)
+  bool rot_last = true;                // unit_kernel: rotation terms of single-row units after the transforms, sums in registers (RZK_ROT_LAST=0: first, through the scratch line)
+  bool dot2 = true;                    // unit_kernel: two-product key rows park the transform and reduce once (RZK_DOT2=0: one reduction per product)
+  bool crt2_short = true;              // two-prime reconstruction with one reduction mod q (RZK_CRT2_SHORT=0: crt2_zq)
   int group_max = 1;                   // rows per group of row_group_kernel (group_max_for; RZK_GROUP_MAX overrides, tuning)
   bool use_shift = true;               // challenge products as signed rotations (shift_row_kernel) instead of transforms
   bool shift_bytes = true;             // ... of short operands as packed bytes (shift_row_kernel, N <= 1024; RZK_SHIFT_BYTES=0: words only)

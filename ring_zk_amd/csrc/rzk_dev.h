@@ -18,6 +18,14 @@ struct DevTables {
   PrimeConsts pc[kMaxPrimes];
   CrtConsts crt;
   double cap[kMaxPrimes + 1];           // cap[np] = largest |exact result| np primes can represent
+  uint32_t diet;                        // DIET_* bits: which shorter forms the unit kernels take (all compute the same values)
+  uint32_t pad;
+};
+// DevTables::diet (rzk_ctx_create: RZK_ROT_LAST / RZK_CRT2_SHORT, default on)
+// (the third knob of the family, RZK_DOT2, reaches the kernel through the plan: ITEM_DOT2 below)
+enum : uint32_t {
+  DIET_ROT_LAST = 1,   // unit_kernel, single-row units of one wavefront: rotation terms after the last inverse transform, sums in registers
+  DIET_CRT2 = 2,       // two-prime reconstruction with one reduction mod q (crt2_zq_short)
 };
 
 // ---- row programs ------------------------------------------------------------------------------------
@@ -118,9 +126,12 @@ struct Program {
 enum : uint8_t { ITEM_KEY = 0, ITEM_VEC = 1 };
 constexpr uint16_t kNoKey = 0xffff;
 constexpr uint16_t kNoRow = 0xffff;
+// Item::flags, on both items of a unit whose row A is exactly two key products (set by plan_units when PlanEnv::dot2):
+// unit_kernel parks the first TRANSFORM instead of the first product and forms x1 k1 + x2 k2 with one reduction (dot2_lazy)
+constexpr uint8_t ITEM_DOT2 = 0x01;
 struct alignas(8) Item {
   uint8_t kind;        // ITEM_KEY / ITEM_VEC
-  uint8_t flags;       // TERM_CHECK / TERM_CHECK2: the b operand carries a fused norm mark
+  uint8_t flags;       // TERM_CHECK / TERM_CHECK2: the b operand carries a fused norm mark; ITEM_DOT2 (below)
   uint8_t b_op, a_op;
   uint16_t b_off, a_off;
   uint16_t keyA, keyB;   // key entries (kNoKey = the item does not feed that row)

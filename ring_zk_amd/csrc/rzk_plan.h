@@ -72,6 +72,7 @@ struct PlanEnv {
   double slot_share_min;     // shared-operand path when (operand transforms) / (distinct operands) >= this
   const uint8_t* key_class;  // (n+l)*k KeyClass values, row-major; only read by programs with key products
   const int32_t* key_entry;  // index into the NTT-domain store, -1 if not GENERAL
+  bool dot2 = false;         // units whose row A is exactly two key products are marked ITEM_DOT2 (one reduction for both)
 };
 
 struct PlanFacts {
@@ -532,7 +533,8 @@ inline uint32_t plan_groups(Program& p, uint32_t gmax) {
 // Wave program of unit_kernel: one unit per row; two consecutive rows become a PAIR when the second has exactly
 // one key product and its operand is the last operand of the first (c0 / c1 of a commitment share r_{k-1};
 // t = a1.y and a2.y share y_{k-1}): that transform is then computed once for both.  Returns the work per entry.
-inline uint32_t plan_units(const Program& p, bool use_pairs, WaveProgram& wp) {
+// dot2: a unit of exactly two items, both key products into row A, is marked ITEM_DOT2 on both (with or without a row B).
+inline uint32_t plan_units(const Program& p, bool use_pairs, WaveProgram& wp, bool dot2 = false) {
   auto key_only = [&](const Row& rr) {
     for (uint32_t t = 0; t < rr.nterms; ++t)
       if (kind_of(p.terms[rr.term0 + t]) != TERM_KEY) return false;
@@ -575,6 +577,11 @@ inline uint32_t plan_units(const Program& p, bool use_pairs, WaveProgram& wp) {
           step = 2;
         }
       }
+    }
+    if (dot2 && un.nitems == 2) {
+      Item* two = &wp.items[un.item0];
+      if (two[0].kind == ITEM_KEY && two[1].kind == ITEM_KEY && two[0].keyA != kNoKey && two[1].keyA != kNoKey)
+        two[0].flags |= ITEM_DOT2, two[1].flags |= ITEM_DOT2;
     }
     work += (un.nitems ? un.nitems : 1u) + (un.rowB != kNoRow ? 2u : 1u);
     r += step;
@@ -678,7 +685,7 @@ inline int plan_program(const PlanEnv& env, int id, uint32_t var, Plan& plan) {
     p.ngroups = f.ngroups = plan_groups(p, (uint32_t)env.group_max);
   if (!env.small) {
     plan.use_wave = true;
-    f.work = plan_units(p, env.use_pairs, plan.wave);
+    f.work = plan_units(p, env.use_pairs, plan.wave, env.dot2);
     f.nunits = plan.wave.nunits;
   }
   if (!env.small && env.slot_share_min > 0 && p.nterms > 0 && f.ngroups == 0 && !f.shift && !f.has_shift &&

@@ -359,9 +359,12 @@ __device__ __forceinline__ void shift_fill_from(const int64_t* __restrict__ pv, 
 // TO_MEM: res is a per-team line in global memory indexed by coefficient (each thread touches only its own
 // coefficients) and `fresh` says that it holds nothing yet; otherwise res are the thread's E registers.
 // Sums are exact 64-bit integers (v_mad_i64_i32) as long as |a|_1 |v|_inf < 2^62; beyond that v goes in as
-// two 16-bit halves.  Eight of a thread's outputs are accumulated at a time (register budget).
+// two 16-bit halves.  The register form accumulates HREG of a thread's outputs per scan over the multiplier (eight by
+// default, the register budget of shift_row_kernel), the TO_MEM form kShiftHMem / kShiftHMemPair.
 // fault: set when v holds a non-canonical coefficient (the caller tests `a`).
-template <int LOGN, bool PAIR, bool TO_MEM, class TM = WaveTeam>
+// HREG: outputs per scan of the register form (unit_kernel's rotation-last path runs it with nothing else live and
+// takes all 16 of a lane's outputs in one scan, as the TO_MEM form does).
+template <int LOGN, bool PAIR, bool TO_MEM, class TM = WaveTeam, int HREG = kShiftH>
 __device__ __forceinline__ void shift_product(uint32_t* res, bool fresh, bool minus, const int32_t* a,
                                               const int64_t* __restrict__ pv, int lane_in, int32_t* ext,
                                               const DevTables& T, bool& fault, bool trusted) {
@@ -370,7 +373,7 @@ __device__ __forceinline__ void shift_product(uint32_t* res, bool fresh, bool mi
   if (LL != 6) asm volatile("" : "+v"(lane));   // per call: keeps the thread's 64-bit line / image addresses out of the kernel prologue
   using S = ShiftGeo<LOGN, PAIR, LL>;
   constexpr int E = S::E;
-  constexpr int HW = TO_MEM ? (LL == 6 ? kShiftHMem : kShiftHMemPair) : kShiftH;   // (the in-kernel rotation terms run with nothing else live)
+  constexpr int HW = TO_MEM ? (LL == 6 ? kShiftHMem : kShiftHMemPair) : HREG;   // (the in-kernel rotation terms run with nothing else live)
   constexpr int H = HW < E ? HW : E;   // outputs per scan; chunk c covers registers c*H .. c*H+H-1
   constexpr int NCH = E / H;
   constexpr bool LIST = LL != 6;

@@ -15,7 +15,7 @@ namespace {
 
 PlanEnv plan_env(const rzk_ctx* c) {
   return PlanEnv{c->n, c->k, c->l, c->logn, c->small, shift_ok(c), c->block_min_logn, c->use_groups, c->group_max,
-                 c->use_pairs, c->slot_share_min, c->key_class.data(), c->key_entry.data()};
+                 c->use_pairs, c->slot_share_min, c->key_class.data(), c->key_entry.data(), c->dot2};
 }
 
 template <class T>

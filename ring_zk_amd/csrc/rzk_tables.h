@@ -116,6 +116,10 @@ inline bool make_crt_consts(uint64_t q, CrtConsts& C) {
   }
   C.r2q = (uint32_t)((((u128)1) << 64) % q);
   C.r48q = (uint32_t)((((u128)1) << 48) % q);
+  C.half2_d1 = (uint32_t)(C.half2 / p0);
+  C.half2_d0 = (uint32_t)(C.half2 % p0);
+  C.r1q = (uint32_t)((((u128)1) << 32) % q);
+  C.knq = (uint32_t)(((u128)((q - C.pmodq[2]) % q) << 32) % q);
   return true;
 }
 

@@ -19,8 +19,11 @@ namespace rzk {
 //   * the accumulator of a pair's row B is born with that last item and parked in P while row A is transformed back;
 //   * the Garner state (one or two words per coefficient and row) lives in a per-wave global scratch line
 //     ([g][lane][4] order, 16-byte accesses; L2 / Infinity-Cache resident), not in registers or LDS;
-//   * rotation terms run after the transforms, accumulating straight into the row's value in registers, with the
-//     2N-word image in the (then idle) slab + P.
+//   * rotation terms of a single row (one wavefront, DIET_ROT_LAST) run after the transforms, accumulating straight into
+//     the row's value in registers, with the 2N-word image in the (then idle) slab + P; every other unit runs them first
+//     and leaves their sum in a scratch line for finish_row;
+//   * a unit of exactly two key products (ITEM_DOT2) parks the first transform, not the first product, and reduces the
+//     two-term sum once with the last item.
 // LDS per wavefront: transposition slab (N + N/32 words) + P (N words) = 8.1 KiB at N = 1024.
 // =============================================================================================
 // lines (of N words) of per-wave global scratch the unit / short kernels address
@@ -151,6 +154,16 @@ __device__ __forceinline__ bool inverse_fold_global(int pi, int np, uint32_t* ac
     return false;
   }
   if (pi == 1 && np == 2) {
+    if (T.diet & DIET_CRT2) {   // (the choice is made outside the element loops, as in mac_park)
+#pragma unroll
+      for (int g = 0; g < E / 4; ++g) {
+        const uint4 dv = sa[g];
+        const uint32_t d0[4] = {dv.x, dv.y, dv.z, dv.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[4 * g + i] = crt2_zq_short(acc[4 * g + i], d0[i], T.pc, T.crt);
+      }
+      return true;
+    }
 #pragma unroll
     for (int g = 0; g < E / 4; ++g) {
       const uint4 dv = sa[g];
@@ -299,7 +312,13 @@ unit_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__ wp
       const uint32_t un_items = un.nitems;
       const bool null_unit = un_items == 0;   // no products: additions / rotation terms only
       const bool has_shift = HAS_SHIFT && rowA.nshift > 0;
-      if (has_shift) {
+      // A single row evaluated by one wavefront takes its challenge products LAST (DIET_ROT_LAST): once its last inverse
+      // transform is done the slab and P are idle (no sum of a row B is parked there), so the rotations accumulate
+      // straight into the row's value in registers and the scratch line's N words are neither written nor read back.
+      // (N <= 1024: rotation terms at N = 2048 exist on teams of two only — launch_units starts no one-wavefront
+      // instantiation with HAS_SHIFT there — and those run their rotations first.)
+      const bool rot_last = has_shift && TM::LL == 6 && E <= 16 && !pair && (T.diet & DIET_ROT_LAST) != 0;
+      if (has_shift && !rot_last) {
         // challenge products first (rotations, image in slab + P); their sum mod q is built in the wave's scratch line
         // (every lane reads and writes only its own coefficients) and waits there for finish_row
         bool fault = false;
@@ -358,12 +377,17 @@ unit_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__ wp
             }
             if (chk && !below && (lane & 63) == 0) fail_check(flags + bo, ops.pad != 0, (im.flags & TERM_CHECK2) != 0);
             const bool vec = HAS_VEC && im.kind == ITEM_VEC;
+            // ITEM_DOT2: row A is x1 k1 + x2 k2.  The first item parks its TRANSFORM in P (the same N words as its product) and
+            // requests no key entry; the last one takes both entries and reduces the two-term sum once (dot2_lazy).
+            // One wavefront, N <= 1024 (two key entries in registers next to the transform).
+            const bool dot2 = !HAS_VEC && TM::LL == 6 && E <= 16 && (im.flags & ITEM_DOT2) != 0;
             // the resident key entry of row A's product is requested before the transform, which hides its latency
             // (N <= 1024; at N = 2048 the registers are not there and the entry is loaded after the transform)
             constexpr bool EARLY = E <= 16 && !HAS_VEC;   // (and not next to vector x vector items: their second transform needs the registers)
             uint32_t kreg[E];
             const uint4* __restrict__ kpA = reinterpret_cast<const uint4*>(key_ntt + ((size_t)im.keyA * kKeyImages + pi) * N);
-            if (EARLY && !vec && im.keyA != kNoKey) {
+            const bool want_key = !vec && im.keyA != kNoKey && !(dot2 && !last);
+            if (EARLY && want_key) {
 #pragma unroll
               for (int g = 0; g < E / 4; ++g) {
                 const uint4 kv = kpA[G::key4(ln, g)];
@@ -375,7 +399,7 @@ unit_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__ wp
               wave_fwd<LOGN, TM>(x, ln, lds, twf, pc);
               RZK_T1(t_fwd);
             }
-            if (!EARLY && !vec && im.keyA != kNoKey) {
+            if (!EARLY && want_key) {
 #pragma unroll
               for (int g = 0; g < E / 4; ++g) {
                 const uint4 kv = kpA[G::key4(ln, g)];
@@ -399,8 +423,14 @@ unit_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__ wp
             const bool feedsA = vec || im.keyA != kNoKey;
             if (!last) {
               RZK_T0();
-              if (vec) mac_park<LOGN, false, TM>(x, xb, im.signA < 0, P4, ln, it == 0, pc);
-              else if (feedsA) mac_park<LOGN, false, TM>(x, kreg, im.signA < 0, P4, ln, it == 0, pc);
+              if (vec) {
+                mac_park<LOGN, false, TM>(x, xb, im.signA < 0, P4, ln, it == 0, pc);
+              } else if (dot2) {
+#pragma unroll
+                for (int g = 0; g < E / 4; ++g) P4[G::own4(ln, g)] = make_uint4(x[4 * g], x[4 * g + 1], x[4 * g + 2], x[4 * g + 3]);
+              } else if (feedsA) {
+                mac_park<LOGN, false, TM>(x, kreg, im.signA < 0, P4, ln, it == 0, pc);
+              }
               RZK_T1(t_mac);
               continue;
             }
@@ -412,6 +442,32 @@ unit_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__ wp
             for (int c = 0; c < E; ++c) acc[c] = x[c];
             if (vec) {
               mac_park<LOGN, true, TM>(acc, xb, im.signA < 0, P4, ln, it == 0, pc);
+            } else if (dot2) {
+              // the first item's entry is requested only now (before its transform nothing could hold it); a minus term
+              // multiplies by p - k instead (<= p: the bound of dot2_lazy holds)
+              const Item im0 = table_load(&wp->items[un.item0]);
+              const uint4* __restrict__ kp1 = reinterpret_cast<const uint4*>(key_ntt + ((size_t)im0.keyA * kKeyImages + pi) * N);
+              uint32_t k1[E];
+#pragma unroll
+              for (int g = 0; g < E / 4; ++g) {
+                const uint4 kv = kp1[G::key4(ln, g)];
+                k1[4 * g] = kv.x, k1[4 * g + 1] = kv.y, k1[4 * g + 2] = kv.z, k1[4 * g + 3] = kv.w;
+              }
+              if (im.signA < 0) {
+#pragma unroll
+                for (int c = 0; c < E; ++c) kreg[c] = pc.p - kreg[c];
+              }
+              if (im0.signA < 0) {
+#pragma unroll
+                for (int c = 0; c < E; ++c) k1[c] = pc.p - k1[c];
+              }
+#pragma unroll
+              for (int g = 0; g < E / 4; ++g) {
+                const uint4 v = P4[G::own4(ln, g)];   // x1, consumed before a row B's product takes the slot (below)
+                const uint32_t x1[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int i = 0; i < 4; ++i) acc[4 * g + i] = dot2_lazy(x1[i], k1[4 * g + i], x[4 * g + i], kreg[4 * g + i], pc);
+              }
             } else if (feedsA) {
               mac_park<LOGN, true, TM>(acc, kreg, im.signA < 0, P4, ln, it == 0, pc);
             } else {   // (an item that only feeds row B)
@@ -451,10 +507,34 @@ unit_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__ wp
                                                     st + (size_t)(2 * r + 1) * N, T);
               RZK_T1(t_inv);
             }
+            if (done && rot_last) {   // (a single row: r == 0) acc[e] is the value of coefficient e*64 + lane, the register layout of the rotations
+              RZK_T0();
+              bool sfault = false;
+#pragma unroll 1
+              for (uint32_t t = 0; t < rowA.nshift; ++t) {
+                const Term tm = table_load(&prog->terms[rowA.term0 + rowA.nterms + t]);
+                const int64_t* __restrict__ pa = operand_ptr(ops, tm.a_op, tm.a_off, b, bo, N);
+                int32_t a[E];
+                if (trusted) {
+#pragma unroll
+                  for (int e = 0; e < E; ++e) a[e] = (int32_t)pa[G::j_p1(lane, e)];
+                } else {
+                  uint32_t abad = 0, amx = 0;
+#pragma unroll
+                  for (int e = 0; e < E; ++e) a[e] = canon_lo_mx(pa[G::j_p1(lane, e)], qhalf, abad, amx);
+                  sfault = sfault || canon_fail(abad, amx, qhalf);
+                }
+                shift_product<LOGN, false, false, TM, kShiftHMem>(acc, false, tm.sign < 0, a, operand_ptr(ops, tm.b_op, tm.b_off, b, bo, N), lane,
+                                                  reinterpret_cast<int32_t*>(lds), T, sfault, trusted);
+              }
+              if (sfault) input_fault(ops, flags, bo, lane);
+              TM::sync();   // the image is dead: slab and P may be overwritten
+              RZK_T1(t_rot);
+            }
             if (done) {
               RZK_T0();
               finish_row<LOGN, 16, TM>(acc, prog, table_load(&prog->rows[r ? un.rowB : un.rowA]), ops, b, bo, lane, T, flags,
-                               (has_shift && r == 0) ? st_sh : nullptr);
+                               (has_shift && !rot_last && r == 0) ? st_sh : nullptr);
               RZK_T1(t_fin);
             }
           }
@@ -776,8 +856,13 @@ unit_io_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__
             RZK_STEP_PRIORITY();
             RZK_OPAQUE(li);
             wave_inv<LOGN, TM>(a, li, lds, tw_all + (size_t)(2 * 1 + 1) * kTableLen, T.pc[1]);
+            if (T.diet & DIET_CRT2) {
 #pragma unroll
-            for (int e = 0; e < E; ++e) u[e] = crt2_zq(a[e], u[e], T.pc, T.crt);
+              for (int e = 0; e < E; ++e) u[e] = crt2_zq_short(a[e], u[e], T.pc, T.crt);
+            } else {
+#pragma unroll
+              for (int e = 0; e < E; ++e) u[e] = crt2_zq(a[e], u[e], T.pc, T.crt);
+            }
           } else {   // three primes: the offset form, words A and B in registers
             uint32_t wb[E];
 #pragma unroll
