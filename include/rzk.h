@@ -50,9 +50,9 @@ extern "C" {
 typedef struct rzk_ctx rzk_ctx;
 
 /* Version of this C ABI: bumped whenever an existing signature changes (rzk_wire_mat_decode gained `q` in 2,
- * version 3 added the entry points marked "v3", version 4 those marked "v4", version 5 those marked "v5", version 6 those marked "v6", version 7 those marked "v7", version 8 those marked "v8", version 9 those marked "v9", version 10 those marked "v10", version 11 those marked "v11", version 12 those marked "v12").  A binding checks rzk_abi_version() == RZK_ABI_VERSION after loading
+ * version 3 added the entry points marked "v3", version 4 those marked "v4", version 5 those marked "v5", version 6 those marked "v6", version 7 those marked "v7", version 8 those marked "v8", version 9 those marked "v9", version 10 those marked "v10", version 11 those marked "v11", version 12 those marked "v12", version 13 those marked "v13").  A binding checks rzk_abi_version() == RZK_ABI_VERSION after loading
  * the library, so that a stale or variant .so fails at load time instead of reading shifted arguments. */
-#define RZK_ABI_VERSION 12u
+#define RZK_ABI_VERSION 13u
 uint32_t rzk_abi_version(void);
 
 /* Which block of the commitment key a matrix-vector product uses (src/commit.rs:19-25). */
@@ -499,6 +499,33 @@ int rzk_reject_batch(rzk_ctx* ctx, uint32_t nparts, const int64_t* const* z, con
                      const int64_t* coin, uint64_t R, double lnM, uint8_t* accept, int64_t* E, size_t B);
 int rzk_reject_batch_dev(rzk_ctx* ctx, uint32_t nparts, const int64_t* const* z, const int64_t* const* y, const uint32_t* rows,
                          const int64_t* coin, uint64_t R, double lnM, uint8_t* accept, int64_t* E, size_t B);
+/* The response and its test in one call (v13): "give me z, and tell me whether I may release it".
+ * z (z', z_s) is byte for byte what rzk_*_response_batch writes; accept and E (may be NULL) are what rzk_reject_batch
+ * returns for the parts [(z, y)] (Open), [(z, y), (z', y')] (Linear), [(z_s, y_s), (z', y')] (Sum) with the same coin, R
+ * and lnM.  Argument rules and messages are those of rzk_reject_batch with rows = k, 2k, (V + 1) k; y and z slabs of the
+ * _dev variants are 16-byte aligned; B == 0 is a no-op.  At N = 512 and 1024 the response rows accumulate the statistic
+ * themselves from the product d r, the addend y and the sum z they hold in registers (response_stat_kernel): z and y are
+ * never read back.  At N = 2048 (two wavefronts per polynomial), N <= 256 and under RZK_SHIFT=0 the call runs the
+ * response launch and then the statistic kernel of rzk_reject_batch: same outputs.
+ * One deliberate tightening where the fused rows run: a non-canonical coefficient of r or d, which the two-call form only
+ * reports through the sticky word, also clears accept[b] of its proof.  As there it is an input fault of the call
+ * (RZK_E_ARG from the host variant, the sticky word from _dev), and E of such a proof is unspecified. */
+int rzk_open_response_reject_batch(rzk_ctx* ctx, const int64_t* y, const int64_t* r, const int64_t* d, const int64_t* coin,
+                                   uint64_t R, double lnM, int64_t* z, uint8_t* accept, int64_t* E, size_t B);
+int rzk_open_response_reject_batch_dev(rzk_ctx* ctx, const int64_t* y, const int64_t* r, const int64_t* d, const int64_t* coin,
+                                       uint64_t R, double lnM, int64_t* z, uint8_t* accept, int64_t* E, size_t B);
+int rzk_linear_response_reject_batch(rzk_ctx* ctx, const int64_t* y, const int64_t* yp, const int64_t* r, const int64_t* rp,
+                                     const int64_t* d, const int64_t* coin, uint64_t R, double lnM, int64_t* z, int64_t* zp,
+                                     uint8_t* accept, int64_t* E, size_t B);
+int rzk_linear_response_reject_batch_dev(rzk_ctx* ctx, const int64_t* y, const int64_t* yp, const int64_t* r, const int64_t* rp,
+                                         const int64_t* d, const int64_t* coin, uint64_t R, double lnM, int64_t* z, int64_t* zp,
+                                         uint8_t* accept, int64_t* E, size_t B);
+int rzk_sum_response_reject_batch(rzk_ctx* ctx, uint32_t V, const int64_t* ys, const int64_t* yp, const int64_t* rs,
+                                  const int64_t* rp, const int64_t* d, const int64_t* coin, uint64_t R, double lnM, int64_t* zs,
+                                  int64_t* zp, uint8_t* accept, int64_t* E, size_t B);
+int rzk_sum_response_reject_batch_dev(rzk_ctx* ctx, uint32_t V, const int64_t* ys, const int64_t* yp, const int64_t* rs,
+                                      const int64_t* rp, const int64_t* d, const int64_t* coin, uint64_t R, double lnM,
+                                      int64_t* zs, int64_t* zp, uint8_t* accept, int64_t* E, size_t B);
 
 /* ---- fixed-width packed records "RZKP1" (v8; batched, on the GPU) ----------------------------------------------------------
  * The bincode form above is the reference's: 8 bytes per coefficient and polynomials of variable length.  For proofs that

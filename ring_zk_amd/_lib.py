@@ -100,6 +100,11 @@ SIGNATURES = {
     "rzk_reject_lnm": (C.c_double, [C.c_double]),
     "rzk_reject_batch": (C.c_int, [_CTX, C.c_uint32, C.c_void_p, C.c_void_p, _U32P, _I64, C.c_uint64, C.c_double, _U8, _I64,
                                    _SZ]),
+    # v13: response and rejection test in one call (y.., r.., d, coin, R, lnM, z.., accept, E, B)
+    "rzk_open_response_reject_batch": (C.c_int, [_CTX] + [_I64] * 4 + [C.c_uint64, C.c_double, _I64, _U8, _I64, _SZ]),
+    "rzk_linear_response_reject_batch": (C.c_int, [_CTX] + [_I64] * 6 + [C.c_uint64, C.c_double, _I64, _I64, _U8, _I64, _SZ]),
+    "rzk_sum_response_reject_batch": (C.c_int, [_CTX, C.c_uint32] + [_I64] * 6 + [C.c_uint64, C.c_double, _I64, _I64, _U8, _I64,
+                                                                                 _SZ]),
     # v8: fixed-width packed records
     "rzk_packed_record_bytes": (C.c_size_t, [_CTX, C.c_int, C.c_uint32]),
     "rzk_packed_widths": (C.c_int, [_CTX, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
@@ -118,7 +123,7 @@ SIGNATURES = {
     "rzk_prof_read_all": (C.c_int, [_CTX, C.POINTER(C.c_double), _SZ, C.POINTER(C.c_size_t)]),
     "rzk_prof_read_kernels": (C.c_int, [_CTX, C.c_char_p, _SZ, C.POINTER(C.c_size_t)]),
 }
-ABI_VERSION = 12   # include/rzk.h: RZK_ABI_VERSION
+ABI_VERSION = 13   # include/rzk.h: RZK_ABI_VERSION
 # every batched entry point also exists as a device-pointer variant with the same signature
 for _name in list(SIGNATURES):
     if _name.endswith("_batch"):

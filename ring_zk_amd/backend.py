@@ -449,6 +449,50 @@ class Context:
                                                       p[2 * n + 1], p[2 * n + 2], B))
         return accept, E
 
+    # The response and its rejection test in one call (include/rzk.h v13): z as *_response writes it, accept and
+    # E as reject returns them for that z; at N = 512 / 1024 the response rows accumulate the statistic themselves.
+    def _response_reject(self, name, head, ins, outs, coin, R, lnM):
+        B = int(coin.shape[0])
+        if coin.ndim != 1:
+            raise ValueError(f"{name}: coin must be [B]")
+        accept = self._empty(coin, (B,), np.uint8)
+        E = self._empty(coin, (B,), np.int64)
+        dev, p = self._prep(ins + [coin] + outs + [accept, E], [np.int64] * (len(ins) + 1 + len(outs)) + [np.uint8, np.int64])
+        n = len(ins) + 1
+        self._check(self._fn(name, dev)(self._h, *head, *p[:n], R, float(lnM), *p[n:], B))
+        return accept, E
+
+    def open_response_reject(self, y, r, d, coin, R: int, lnM: float):
+        """open_response and reject([(z, y)], coin, R, lnM) in one call: (z, accept, E)."""
+        B = self._shape(y, self.k, self.N)
+        if self._shape(r, self.k, self.N) != B or self._shape(d, self.N) != B or int(coin.shape[0]) != B:
+            raise ValueError("open_response_reject: batch / shape mismatch")
+        z = self._empty(y, tuple(y.shape))
+        accept, E = self._response_reject("rzk_open_response_reject_batch", (), [y, r, d], [z], coin, R, lnM)
+        return z, accept, E
+
+    def linear_response_reject(self, y, yp, r, rp, d, coin, R: int, lnM: float):
+        """linear_response and reject([(z, y), (zp, yp)], coin, R, lnM) in one call: (z, zp, accept, E)."""
+        B = self._shape(y, self.k, self.N)
+        if any(self._shape(a, self.k, self.N) != B for a in (yp, r, rp)) or self._shape(d, self.N) != B or int(coin.shape[0]) != B:
+            raise ValueError("linear_response_reject: batch / shape mismatch")
+        z = self._empty(y, tuple(y.shape))
+        zp = self._empty(y, tuple(y.shape))
+        accept, E = self._response_reject("rzk_linear_response_reject_batch", (), [y, yp, r, rp, d], [z, zp], coin, R, lnM)
+        return z, zp, accept, E
+
+    def sum_response_reject(self, ys, yp, rs, rp, d, coin, R: int, lnM: float):
+        """sum_response and reject([(zs, ys), (zp, yp)], coin, R, lnM) in one call: (zs, zp, accept, E)."""
+        V = int(ys.shape[-3])
+        B = self._shape(ys, V, self.k, self.N)
+        if (self._shape(rs, V, self.k, self.N) != B or self._shape(yp, self.k, self.N) != B or self._shape(rp, self.k, self.N) != B
+                or self._shape(d, self.N) != B or int(coin.shape[0]) != B):
+            raise ValueError("sum_response_reject: batch / shape mismatch")
+        zs = self._empty(ys, tuple(ys.shape))
+        zp = self._empty(yp, tuple(yp.shape))
+        accept, E = self._response_reject("rzk_sum_response_reject_batch", (V,), [ys, yp, rs, rp, d], [zs, zp], coin, R, lnM)
+        return zs, zp, accept, E
+
     # ---- commitment scheme (src/commit.rs) --------------------------------------------------------------------
     def commit(self, x, r):
         """CommitmentKey::commit (commit.rs:88-128) with caller-supplied r: (c, ok)."""

@@ -259,6 +259,158 @@ int rzk_reject_batch(rzk_ctx* c, uint32_t nparts, const int64_t* const* z, const
   return h.run([&] { return rzk_reject_batch_dev(c, nparts, dz, dy, rows, dcoin, R, lnM, daccept, dE, B); });
 }
 
+// ---- v13: the response and its rejection test in one call (rzk_response_stat_dev.hip) ------------------
+namespace {
+
+// One call = the response launches of `response` and the decision over the parts (z_f, y_f).  Where the rotation kernel
+// runs with one wavefront per polynomial (response_stat_fused) the response rows leave the partials themselves
+// (response(&stat)); everywhere else the chain runs inside the call: response(NULL), then reject_stat_kernel on (z, y).
+// Either way one reject_decide_kernel over ws_reject ends the call.
+template <class F>
+int response_reject(rzk_ctx* c, uint32_t nparts, const int64_t* const* z, const int64_t* const* y, const uint32_t* rows,
+                    const int64_t* coin, uint64_t R, double lnM, uint8_t* accept, int64_t* E, size_t B, F response) {
+  uint64_t total = 0;
+  int rc = reject_args(c, nparts, z, y, rows, coin, R, lnM, accept, &total);
+  if (rc != RZK_OK) return rc;
+  RejectParts m{};
+  m.nparts = nparts;
+  m.N = c->N;
+  m.rows = (uint32_t)total;
+  for (uint32_t f = 0; f < nparts; ++f) {
+    if (((uintptr_t)z[f] | (uintptr_t)y[f]) & 15u) return fail(c, RZK_E_ARG, "reject: slabs must be 16-byte aligned");
+    m.first[f + 1] = m.first[f] + rows[f];
+    m.z[f] = z[f];
+    m.y[f] = y[f];
+  }
+  rc = arena_reserve(c, c->ws_reject, (size_t)B * total * sizeof(RejectPartial));
+  if (rc != RZK_OK) return rc;
+  RejectPartial* part = (RejectPartial*)c->ws_reject.p;
+  const uint64_t limit = (c->verify_bound + 1) * (c->verify_bound + 1);   // <= 2^48 (reject_args_ok)
+  const ResponseStat stat{part, m.rows, 0, (int64_t)(c->b * c->kappa), limit};
+  const bool fused = response_stat_fused(c);
+  rc = response(fused ? &stat : nullptr);
+  if (rc != RZK_OK) return rc;
+  if (!fused) {
+    rc = run_profiled(c, (uint64_t)B * total * c->N * 2 * sizeof(int64_t), "reject stat kernel", [&](const LaunchCfg& cfg) {
+      return launch_reject_stat(cfg, m, c->q, c->b * c->kappa, limit, c->trusted, part, B);
+    });
+    if (rc != RZK_OK) return rc;
+  }
+  const double sg = (double)c->sigma;
+  return run_profiled(c, (uint64_t)B * total * sizeof(RejectPartial), "reject decide kernel", [&](const LaunchCfg& cfg) {
+    return launch_reject_decide(cfg, part, m.rows, coin, R, lnM, 2.0 * sg * sg, accept, E, c->d_bad, B);
+  });
+}
+
+// `stat` with its partials moved to where a later launch of the call starts
+ResponseStat stat_at(const ResponseStat& s, uint32_t off) {
+  ResponseStat t = s;
+  t.part_off = off;
+  return t;
+}
+
+const char* const kResponseRejectNull = "response reject: non-NULL y, r, d, coin, z, accept expected";
+
+}  // namespace
+
+int rzk_open_response_reject_batch_dev(rzk_ctx* c, const int64_t* y, const int64_t* r, const int64_t* d, const int64_t* coin,
+                                       uint64_t R, double lnM, int64_t* z, uint8_t* accept, int64_t* E, size_t B) {
+  if (!c) return RZK_E_ARG;
+  if (B == 0) return RZK_OK;
+  if (!y || !r || !d || !coin || !z || !accept) return fail(c, RZK_E_ARG, kResponseRejectNull);
+  const uint32_t k = c->k;
+  const int64_t *zs[1] = {z}, *ys[1] = {y};
+  const uint32_t rows[1] = {k};
+  return response_reject(c, 1, zs, ys, rows, coin, R, lnM, accept, E, B, [&](const ResponseStat* st) {
+    return run_program(c, PG_RESPONSE, 1, {{d, 1, 0}, {y, k, 0}, {r, k, 0}, {z, k, 0}}, nullptr, 1, B, 0, true, 0, 0, st);
+  });
+}
+
+int rzk_linear_response_reject_batch_dev(rzk_ctx* c, const int64_t* y, const int64_t* yp, const int64_t* r, const int64_t* rp,
+                                         const int64_t* d, const int64_t* coin, uint64_t R, double lnM, int64_t* z, int64_t* zp,
+                                         uint8_t* accept, int64_t* E, size_t B) {
+  if (!c) return RZK_E_ARG;
+  if (B == 0) return RZK_OK;
+  if (!y || !yp || !r || !rp || !d || !coin || !z || !zp || !accept) return fail(c, RZK_E_ARG, kResponseRejectNull);
+  const uint32_t k = c->k;
+  const int64_t *zs[2] = {z, zp}, *ys[2] = {y, yp};
+  const uint32_t rows[2] = {k, k};
+  return response_reject(c, 2, zs, ys, rows, coin, R, lnM, accept, E, B, [&](const ResponseStat* st) {
+    // the 2k rows of the program are z then zp: the order of the parts
+    return run_program(c, PG_RESPONSE, 2, {{d, 1, 0}, {y, k, 0}, {r, k, 0}, {z, k, 0}, {yp, k, 0}, {rp, k, 0}, {zp, k, 0}}, nullptr, 1,
+                       B, 0, true, 0, 0, st);
+  });
+}
+
+int rzk_sum_response_reject_batch_dev(rzk_ctx* c, uint32_t V, const int64_t* ys, const int64_t* yp, const int64_t* rs,
+                                      const int64_t* rp, const int64_t* d, const int64_t* coin, uint64_t R, double lnM, int64_t* zs,
+                                      int64_t* zp, uint8_t* accept, int64_t* E, size_t B) {
+  if (!c) return RZK_E_ARG;
+  if (B == 0) return RZK_OK;
+  if (!ys || !yp || !rs || !rp || !d || !coin || !zs || !zp || !accept) return fail(c, RZK_E_ARG, kResponseRejectNull);
+  if (V == 0 || V > (1u << 20)) return fail(c, RZK_E_ARG, "response reject: V must lie in 1 .. 2^20");
+  const uint32_t k = c->k;
+  const int64_t *z2[2] = {zs, zp}, *y2[2] = {ys, yp};
+  const uint32_t rows[2] = {V * k, k};
+  return response_reject(c, 2, z2, y2, rows, coin, R, lnM, accept, E, B, [&](const ResponseStat* st) {
+    // as rzk_sum_response_batch_dev: the summands as batch entries that share d, then zp; partial (b, s k + i) and (b, V k + i)
+    ResponseStat s0, s1;
+    if (st) s0 = stat_at(*st, 0), s1 = stat_at(*st, V * k);
+    int rc = run_program(c, PG_RESPONSE, 1, {{d, 1, 1}, {ys, k, 0}, {rs, k, 0}, {zs, k, 0}}, nullptr, V, (uint64_t)B * V, 0, true, 0, 0,
+                         st ? &s0 : nullptr);
+    if (rc != RZK_OK) return rc;
+    return run_program(c, PG_RESPONSE, 1, {{d, 1, 0}, {yp, k, 0}, {rp, k, 0}, {zp, k, 0}}, nullptr, 1, B, 0, true, 0, 0, st ? &s1 : nullptr);
+  });
+}
+
+int rzk_open_response_reject_batch(rzk_ctx* c, const int64_t* y, const int64_t* r, const int64_t* d, const int64_t* coin, uint64_t R,
+                                   double lnM, int64_t* z, uint8_t* accept, int64_t* E, size_t B) {
+  if (!c) return RZK_E_ARG;
+  if (B == 0) return RZK_OK;
+  if (!y || !r || !d || !coin || !z || !accept) return fail(c, RZK_E_ARG, kResponseRejectNull);
+  const size_t kb = B * c->k;
+  HostCall h(c);
+  const auto dy = h.pin(y, kb), dr = h.pin(r, kb), dd = h.pin(d, B);
+  const auto dcoin = h.in(coin, B * sizeof(int64_t));
+  const auto dz = h.pout(z, kb);
+  const auto daccept = h.out(accept, B);
+  const auto dE = h.out(E, B * sizeof(int64_t));
+  return h.run([&] { return rzk_open_response_reject_batch_dev(c, dy, dr, dd, dcoin, R, lnM, dz, daccept, dE, B); });
+}
+
+int rzk_linear_response_reject_batch(rzk_ctx* c, const int64_t* y, const int64_t* yp, const int64_t* r, const int64_t* rp,
+                                     const int64_t* d, const int64_t* coin, uint64_t R, double lnM, int64_t* z, int64_t* zp,
+                                     uint8_t* accept, int64_t* E, size_t B) {
+  if (!c) return RZK_E_ARG;
+  if (B == 0) return RZK_OK;
+  if (!y || !yp || !r || !rp || !d || !coin || !z || !zp || !accept) return fail(c, RZK_E_ARG, kResponseRejectNull);
+  const size_t kb = B * c->k;
+  HostCall h(c);
+  const auto dy = h.pin(y, kb), dyp = h.pin(yp, kb), dr = h.pin(r, kb), drp = h.pin(rp, kb), dd = h.pin(d, B);
+  const auto dcoin = h.in(coin, B * sizeof(int64_t));
+  const auto dz = h.pout(z, kb), dzp = h.pout(zp, kb);
+  const auto daccept = h.out(accept, B);
+  const auto dE = h.out(E, B * sizeof(int64_t));
+  return h.run([&] { return rzk_linear_response_reject_batch_dev(c, dy, dyp, dr, drp, dd, dcoin, R, lnM, dz, dzp, daccept, dE, B); });
+}
+
+int rzk_sum_response_reject_batch(rzk_ctx* c, uint32_t V, const int64_t* ys, const int64_t* yp, const int64_t* rs, const int64_t* rp,
+                                  const int64_t* d, const int64_t* coin, uint64_t R, double lnM, int64_t* zs, int64_t* zp,
+                                  uint8_t* accept, int64_t* E, size_t B) {
+  if (!c) return RZK_E_ARG;
+  if (B == 0) return RZK_OK;
+  if (!ys || !yp || !rs || !rp || !d || !coin || !zs || !zp || !accept) return fail(c, RZK_E_ARG, kResponseRejectNull);
+  if (V == 0 || V > (1u << 20)) return fail(c, RZK_E_ARG, "response reject: V must lie in 1 .. 2^20");
+  const size_t kb = B * c->k;
+  HostCall h(c);
+  const auto dys = h.pin(ys, kb * V), dyp = h.pin(yp, kb), drs = h.pin(rs, kb * V), drp = h.pin(rp, kb), dd = h.pin(d, B);
+  const auto dcoin = h.in(coin, B * sizeof(int64_t));
+  const auto dzs = h.pout(zs, kb * V), dzp = h.pout(zp, kb);
+  const auto daccept = h.out(accept, B);
+  const auto dE = h.out(E, B * sizeof(int64_t));
+  return h.run([&] { return rzk_sum_response_reject_batch_dev(c, V, dys, dyp, drs, drp, dd, dcoin, R, lnM, dzs, dzp, daccept, dE, B); });
+}
+
 // ---- v8: fixed-width packed records "RZKP1" (rzk_packed_dev.hip, rzk_packed.h) -----------------------------------------
 static_assert(RZK_MSG_LINEAR_RESPONSE == PK_LINEAR_RESPONSE && RZK_MSG_OPEN_SHORT == PK_OPEN_SHORT &&
                   RZK_MSG_OPENING == PK_OPENING && RZK_MSG_SUM_RESPONSE == PK_SUM_RESPONSE &&

@@ -173,8 +173,10 @@ int run_profiled(rzk_ctx* c, uint64_t bytes, const char* what, L launch) {
   return rc != RZK_OK ? rc : prof_end(c);
 }
 bool shift_ok(const rzk_ctx* c);
+bool response_stat_fused(const rzk_ctx* c);
 int run_program(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSpec>& specs, uint8_t* flags, uint32_t group,
-                uint64_t batch, uint64_t norm_limit = 0, bool sticky = true, uint8_t preset_value = 0, uint64_t nflags = 0);
+                uint64_t batch, uint64_t norm_limit = 0, bool sticky = true, uint8_t preset_value = 0, uint64_t nflags = 0,
+                const ResponseStat* stat = nullptr);
 int run_norm(rzk_ctx* c, const int64_t* v, uint32_t rows, uint64_t bound, uint8_t* ok, uint64_t B, int mode, int shift,
              bool sticky = true);
 struct NormSpec {   // one launch of the norm kernel: flags (mode, shift) sum c^2 of v's `rows` polynomials per flag < (bound+1)^2

@@ -354,6 +354,19 @@ int launch_reject_stat(const LaunchCfg& cfg, const RejectParts& m, int64_t q, ui
 // accept[b], E[b] (may be NULL) from the partials and coin[b]; a non-canonical coefficient also sets *bad_word
 int launch_reject_decide(const LaunchCfg& cfg, const RejectPartial* part, uint32_t rows, const int64_t* coin, uint64_t R,
                          double lnM, double two_sigma_sq, uint8_t* accept, int64_t* E, uint32_t* bad_word, uint64_t B);
+// ---- response rows fused with the rejection statistic (rzk_response_stat_dev.hip) -----------------------
+struct ResponseStat {   // where a launch of response_stat_kernel leaves its partials, and what it tests
+  RejectPartial* part;    // [B][rows_total], the layout launch_reject_decide reads
+  uint32_t rows_total;    // response polynomials per proof over all launches of the call
+  uint32_t part_off;      // first partial of this launch inside a proof's rows_total
+  int64_t vmax;           // kappa b
+  uint64_t norm_limit;    // (verify_bound + 1)^2
+};
+// The rows of a PG_RESPONSE program (rzk_plan.h) as launch_shift_rows runs them, one wavefront per row, N = 512 / 1024 only
+// (-1 otherwise); the partial of row `rowi` of batch entry b goes to part[(b / group) * rows_total + part_off +
+// (b mod group) * nrows + rowi], group = Operands::group.
+int launch_response_stat(int logn, const LaunchCfg& cfg, const Program* d_prog, uint32_t nrows, const Operands& ops,
+                         const DevTables* d_T, uint64_t batch, const ResponseStat& so);
 // ---- fixed-width packed records (rzk_packed_dev.hip; format in rzk_packed.h) -------------------------------------------
 struct PackedSlabs {
   int64_t* ptr[kPackedMaxFields];   // dense slab of every field ([B][rows of the field][N]), 16-byte aligned

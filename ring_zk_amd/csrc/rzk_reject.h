@@ -62,6 +62,23 @@ RZK_HD void reject_step(RejectAcc& a, int64_t z, int64_t y, int64_t q, int64_t h
   a.zsq += (uint64_t)m * m;
 }
 
+// The same step for a producer that still holds v: the response rows fused with the statistic (rzk_response_stat_dev.hip,
+// DESIGN.md §17) have the centred product sum v = d r and the centred z = y + v in registers and take both from there
+// instead of deriving v from z - y.  For a canonical y, centred((z - y) mod q) IS the centred product sum, so the two
+// steps add the same s1, s2, zsq and flags; z is canonical by construction, y_noncanon is the producer's own test of y
+// (and of the other coefficients it loaded), vmax as above.
+template <bool CHECK>
+RZK_HD void reject_step_v(RejectAcc& a, int64_t z, int64_t v, bool y_noncanon, int64_t vmax) {
+  if (CHECK && y_noncanon) a.flags |= kRejNonCanon;
+  if (v > vmax || v < -vmax) a.flags |= kRejVmax;
+  const int32_t zl = (int32_t)(uint32_t)(uint64_t)z, vl = (int32_t)(uint32_t)(uint64_t)v;
+  a.s1 += (uint64_t)((int64_t)zl * vl);
+  a.s2 += (uint64_t)((int64_t)vl * vl);
+  uint32_t m = zl < 0 ? 0u - (uint32_t)zl : (uint32_t)zl;
+  m = m < (1u << 24) ? m : (1u << 24);
+  a.zsq += (uint64_t)m * m;
+}
+
 // what one polynomial hands to the decision: e = S2 - 2 S1 of its coefficients, flags with the norm verdict folded in
 struct alignas(16) RejectPartial {
   int64_t e;

@@ -9,6 +9,9 @@ namespace rzk::api {
 // per polynomial (16 outputs per thread): with one, a lane holds 32 outputs, the rotation kernels need > 200 VGPRs
 // (one or two waves per SIMD) and measured slower than the transform path (round 2).
 bool shift_ok(const rzk_ctx* c) { return c->use_shift && !c->small && (c->logn <= 10 || c->pair_poly); }
+// The response rows fused with the rejection statistic (response_stat_kernel): where the rotation kernel
+// runs with one wavefront per polynomial.  N = 2048 (two wavefronts), small rings and RZK_SHIFT=0 keep the chain.
+bool response_stat_fused(const rzk_ctx* c) { return shift_ok(c) && c->logn <= 10; }
 
 // ---- row programs: planned on the host (rzk_plan.h), uploaded once per (program, shape) --------------------------
 namespace {
@@ -103,12 +106,13 @@ int prof_end(rzk_ctx* c) {
 }
 
 // `group` > 1: the batch is B*group (proof, summand) pairs; operands with outer != 0 and the flags are per proof
+// stat != NULL (PG_RESPONSE on the rotation path only, response_stat_fused): the rows also leave their rejection partials.
 // sticky: a non-canonical input coefficient fails the CALL (prover-side / Mat-level entry points); verifier-side
 // programs pass false — there the offending proof's verdict flag is cleared and the call succeeds.
 // preset_value != 0: every verdict flag (nflags of them) starts at that value — written by the launch itself when one
 // team evaluates all rows of a batch entry (no 5-us fill launch in front of a 75-us kernel), by a fill launch otherwise.
 int run_program(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSpec>& specs, uint8_t* flags, uint32_t group,
-                uint64_t batch, uint64_t norm_limit, bool sticky, uint8_t preset_value, uint64_t nflags) {
+                uint64_t batch, uint64_t norm_limit, bool sticky, uint8_t preset_value, uint64_t nflags, const ResponseStat* stat) {
   DevProg dp;
   int rc = get_program(c, id, var, dp);
   if (rc != RZK_OK) return rc;
@@ -118,6 +122,7 @@ int run_program(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSpec>& spe
   uint32_t upt = batch >= (uint64_t)c->num_cus * 16 ? dp.nunits : 1;
   if (c->units_per_task) upt = c->units_per_task;   // RZK_UPT (tuning)
   const Path path = path_of(dp, c->small, c->vec_rows);
+  if (stat && (id != PG_RESPONSE || path != Path::Shift || !response_stat_fused(c))) return fail(c, RZK_E_STATE, "fused response rows need the one-wavefront rotation kernel");
   const bool preset_in_kernel = preset_value && flags && c->preset_in_kernel && path == Path::Units && upt >= dp.nunits && dp.nunits > 0 &&
                                 (group ? group : 1) == 1 && nflags == batch;
   if (preset_value && flags && !preset_in_kernel) {
@@ -157,7 +162,8 @@ int run_program(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSpec>& spe
       lrc = launch_row_program_small(c->N, cfg, dp.d, dp.nrows, ops, c->d_key_mont, c->dT, c->r2q, flags, batch);
       break;
     case Path::Shift:
-      lrc = launch_shift_rows((int)c->logn, cfg, dp.d, dp.nrows, ops, c->dT, flags, batch);
+      lrc = stat ? launch_response_stat((int)c->logn, cfg, dp.d, dp.nrows, ops, c->dT, batch, *stat)
+                 : launch_shift_rows((int)c->logn, cfg, dp.d, dp.nrows, ops, c->dT, flags, batch);
       break;
     case Path::Blocks:
       if (!c->d_block_scratch)

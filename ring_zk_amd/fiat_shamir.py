@@ -33,7 +33,7 @@ from typing import Optional
 import numpy as np
 
 from . import packed, wire
-from ._lib import (MSG_LINEAR_COMMITMENT, MSG_LINEAR_RESPONSE, MSG_LINEAR_SHORT, MSG_OPEN_COMMITMENT, MSG_OPEN_RESPONSE,
+from ._lib import (KEY_A1, MSG_LINEAR_COMMITMENT, MSG_LINEAR_RESPONSE, MSG_LINEAR_SHORT, MSG_OPEN_COMMITMENT, MSG_OPEN_RESPONSE,
                    MSG_OPEN_SHORT, MSG_SUM_COMMITMENT, MSG_SUM_RESPONSE, MSG_SUM_SHORT)
 
 KINDS = (MSG_OPEN_COMMITMENT, MSG_LINEAR_COMMITMENT, MSG_SUM_COMMITMENT)
@@ -327,19 +327,18 @@ def zk_lnm(m: int) -> float:
     return reject_lnm(11.0 / math.sqrt(m))
 
 
-def _zk_rounds(ctx, sampler, m: int, max_rounds: int, prove, fresh):
-    """prove(idx) -> (outputs, ok, parts) proves the whole batch (idx None) or the proofs idx with a fresh y; outputs[i]
-    for i in `fresh` depend on y.  Returns (outputs, ok, rounds)."""
+def _zk_rounds(ctx, sampler, m: int, max_rounds: int, attempt, fresh):
+    """attempt(idx, lnM) -> (outputs, ok, accept) proves the whole batch (idx None) or the proofs idx with a fresh y and
+    tests the response in the same call (Context.*_response_reject); it draws y and then the coins
+    (draw_coins) from the sampler, in that order.  outputs[i] for i in `fresh` depend on y.  Returns (outputs, ok, rounds)."""
     import torch
 
     if not 1 <= max_rounds <= 255:
         raise ValueError("max_rounds must lie in 1 .. 255")
     lnM = zk_lnm(m)
-    outs, ok, parts = prove(None)
+    outs, ok, acc = attempt(None, lnM)
     outs = list(outs)
     B = int(ok.shape[0])
-    coin, R = draw_coins(sampler, (B,))
-    acc, _ = ctx.reject(parts, coin, R, lnM)
     live = ok != 0                      # r passed the commit constraint: worth another y
     done = live & (acc != 0)
     rounds = torch.zeros(B, dtype=torch.uint8, device=ok.device)
@@ -347,9 +346,7 @@ def _zk_rounds(ctx, sampler, m: int, max_rounds: int, prove, fresh):
         idx = torch.nonzero(live & ~done).flatten()
         if idx.numel() == 0:
             break
-        o2, _, parts = prove(idx)
-        coin, R = draw_coins(sampler, (int(idx.numel()),))
-        acc, _ = ctx.reject(parts, coin, R, lnM)
+        o2, _, acc = attempt(idx, lnM)
         a = acc != 0
         sel = idx[a]
         for i in fresh:
@@ -374,13 +371,24 @@ def open_prove_zk(ctx, x, sampler, aux=None, max_rounds: int = 64):
     B = _batch3(x, 2, "open_prove_zk")
     r = sampler.uniform(ctx.b, (B, ctx.k))
 
-    def prove(idx):
-        xs, rs = (x, r) if idx is None else (x[idx], r[idx])
-        y = sampler.gauss(ctx.sigma, (int(xs.shape[0]), ctx.k))
-        c, t, z, ok = open_prove(ctx, xs, rs, y, aux=aux)
-        return (c, t, z), ok, [(z, y)]
+    first = {}
 
-    (c, t, z), ok, rounds = _zk_rounds(ctx, sampler, 1, max_rounds, prove, fresh=(1, 2))
+    def attempt(idx, lnM):
+        xs, rs = (x, r) if idx is None else (x[idx], r[idx])
+        nb = int(xs.shape[0])
+        y = sampler.gauss(ctx.sigma, (nb, ctx.k))
+        coin, R = draw_coins(sampler, (nb,))
+        if idx is None:
+            c, t, ok = ctx.open_commit(xs, rs, y)
+            first["c"] = c
+        else:               # c = commit(x; r) does not depend on y: a retry computes t = a1.y alone
+            c, ok = first["c"][idx], None
+            t = ctx.matvec(KEY_A1, y)
+        d, _, okf = challenge(ctx, MSG_OPEN_COMMITMENT, c, t, aux=aux)
+        z, acc, _ = ctx.open_response_reject(y, rs, d, coin, R, lnM)
+        return (c, t, z), (okf if ok is None else ok & okf), acc
+
+    (c, t, z), ok, rounds = _zk_rounds(ctx, sampler, 1, max_rounds, attempt, fresh=(1, 2))
     return c, t, z, ok, r, rounds
 
 
@@ -390,14 +398,18 @@ def linear_prove_zk(ctx, g, x, sampler, aux=None, max_rounds: int = 64):
     r = sampler.uniform(ctx.b, (B, ctx.k))
     rp = sampler.uniform(ctx.b, (B, ctx.k))
 
-    def prove(idx):
+    def attempt(idx, lnM):
         gs, xs, rs, rps = (g, x, r, rp) if idx is None else (g[idx], x[idx], r[idx], rp[idx])
-        y = sampler.gauss(ctx.sigma, (int(xs.shape[0]), ctx.k))
-        yp = sampler.gauss(ctx.sigma, (int(xs.shape[0]), ctx.k))
-        c, cp, t, tp, u, z, zp, ok = linear_prove(ctx, gs, xs, rs, rps, y, yp, aux=aux)
-        return (c, cp, t, tp, u, z, zp), ok, [(z, y), (zp, yp)]
+        nb = int(xs.shape[0])
+        y = sampler.gauss(ctx.sigma, (nb, ctx.k))
+        yp = sampler.gauss(ctx.sigma, (nb, ctx.k))
+        coin, R = draw_coins(sampler, (nb,))
+        c, cp, t, tp, u, ok = ctx.linear_commit(gs, xs, rs, rps, y, yp)
+        d, _, okf = challenge(ctx, MSG_LINEAR_COMMITMENT, c, cp, gs, t, tp, u, aux=aux)
+        z, zp, acc, _ = ctx.linear_response_reject(y, yp, rs, rps, d, coin, R, lnM)
+        return (c, cp, t, tp, u, z, zp), _flag(ok == 3) & okf, acc
 
-    outs, ok, rounds = _zk_rounds(ctx, sampler, 2, max_rounds, prove, fresh=(2, 3, 4, 5, 6))
+    outs, ok, rounds = _zk_rounds(ctx, sampler, 2, max_rounds, attempt, fresh=(2, 3, 4, 5, 6))
     return tuple(outs) + (ok, r, rp, rounds)
 
 
@@ -409,12 +421,16 @@ def sum_prove_zk(ctx, gs, xs, sampler, aux=None, max_rounds: int = 64):
     rs = sampler.uniform(ctx.b, (B, V, ctx.k))
     rp = sampler.uniform(ctx.b, (B, ctx.k))
 
-    def prove(idx):
+    def attempt(idx, lnM):
         g_, x_, rs_, rp_ = (gs, xs, rs, rp) if idx is None else (gs[idx], xs[idx], rs[idx], rp[idx])
-        ys = sampler.gauss(ctx.sigma, (int(x_.shape[0]), V, ctx.k))
-        yp = sampler.gauss(ctx.sigma, (int(x_.shape[0]), ctx.k))
-        cs, cp, ts, tp, u, zs, zp, ok = sum_prove(ctx, g_, x_, rs_, rp_, ys, yp, aux=aux)
-        return (cs, cp, ts, tp, u, zs, zp), ok, [(zs, ys), (zp, yp)]
+        nb = int(x_.shape[0])
+        ys = sampler.gauss(ctx.sigma, (nb, V, ctx.k))
+        yp = sampler.gauss(ctx.sigma, (nb, ctx.k))
+        coin, R = draw_coins(sampler, (nb,))
+        cs, cp, ts, tp, u, ok = ctx.sum_commit(g_, x_, rs_, rp_, ys, yp)
+        d, _, okf = challenge(ctx, MSG_SUM_COMMITMENT, cp, cs, g_, tp, ts, u, V=V, aux=aux)
+        zs, zp, acc, _ = ctx.sum_response_reject(ys, yp, rs_, rp_, d, coin, R, lnM)
+        return (cs, cp, ts, tp, u, zs, zp), ok & okf, acc
 
-    outs, ok, rounds = _zk_rounds(ctx, sampler, V + 1, max_rounds, prove, fresh=(2, 3, 4, 5, 6))
+    outs, ok, rounds = _zk_rounds(ctx, sampler, V + 1, max_rounds, attempt, fresh=(2, 3, 4, 5, 6))
     return tuple(outs) + (ok, rs, rp, rounds)

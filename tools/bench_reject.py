@@ -1,12 +1,17 @@
 #!/usr/bin/env python3
 """The rejection-sampling step at Open N = 1024, (1,3,1), B = 4096, in one process: one JSON line (also written to
-profiles/reject_open1024_bench.json with --record).
+profiles/reject_open1024_bench.json with --record, or to profiles/NAME with --record-as NAME).
 
-  kernels   reject_stat_kernel / reject_decide_kernel from the library's per-launch events (rzk_prof_*), median of
-            --iters calls; GB/s on the 2 x rows x N x 8 bytes per proof the stat kernel reads;
+  kernels   the response rows (shift_row_kernel), reject_stat_kernel / reject_decide_kernel and the fused response rows
+            (response_stat_kernel) on one honest batch, from the library's per-launch events (rzk_prof_*),
+            median of --iters calls; GB/s on the 2 x rows x N x 8 bytes per proof the stat kernel reads;
+  calls     the chain (open_response, then reject) against the fused entry point (open_response_reject), timed
+            alternately in --repeats windows after a warm-up of both; every window pair is reported;
   provers   fiat_shamir.open_prove_zk against fiat_shamir.open_prove_sampled, both over a SeededSampler, timed
             alternately in --repeats windows after a warm-up of both, device events around each window; rounds used
             and the round-0 acceptance rate of the batch.
+
+On a library without the fused entry points (the parent of the change that added them) the fields that need them are left out.
 """
 import argparse
 import json
@@ -41,6 +46,7 @@ def main():
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--window-s", type=float, default=0.5, help="least duration of a timed window")
     ap.add_argument("--record", action="store_true", help="write the line to profiles/reject_open1024_bench.json")
+    ap.add_argument("--record-as", default=None, metavar="NAME", help="write the line to profiles/NAME")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_reject.py needs a GPU"
     N, n, k, l, B = 1024, 1, 3, 1, args.batch
@@ -56,18 +62,57 @@ def main():
     lnM = reject_lnm(11.0)
     for _ in range(3):
         acc, _ = ctx.reject([(z, y)], coin, R, lnM)
+    has_fused = hasattr(ctx, "open_response_reject")
+
+    def chain():
+        zz = ctx.open_response(y, r, d)
+        return ctx.reject([(zz, y)], coin, R, lnM)
+
+    def fused():
+        return ctx.open_response_reject(y, r, d, coin, R, lnM)
+
+    if has_fused:
+        for _ in range(3):
+            zf, accf, Ef = fused()
+        acc_c, E_c = chain()
+        assert torch.equal(zf, z) and torch.equal(accf, acc_c) and torch.equal(Ef, E_c), "fused and chain disagree"
     ctx.prof_enable(True)
-    stat, decide = [], []
+    by_prefix = {"shift_row_kernel": [], "reject_stat_kernel": [], "reject_decide_kernel": [], "response_stat_kernel": []}
     for _ in range(args.iters):
-        ctx.prof_reset()
-        ctx.reject([(z, y)], coin, R, lnM)
-        us = ctx.prof_read_all()
-        names = [kn for kn, _ in ctx.prof_read_kernels()]
-        stat.append(sum(u for u, kn in zip(us, names) if kn.startswith("reject_stat_kernel")))
-        decide.append(sum(u for u, kn in zip(us, names) if kn == "reject_decide_kernel"))
+        for call in (chain, fused) if has_fused else (chain,):
+            ctx.prof_reset()
+            call()
+            us = ctx.prof_read_all()
+            names = [kn for kn, _ in ctx.prof_read_kernels()]
+            if call is chain:
+                for pre in ("shift_row_kernel", "reject_stat_kernel", "reject_decide_kernel"):
+                    by_prefix[pre].append(sum(u for u, kn in zip(us, names) if kn.startswith(pre)))
+            else:
+                by_prefix["response_stat_kernel"].append(sum(u for u, kn in zip(us, names) if kn.startswith("response_stat_kernel")))
     ctx.prof_enable(False)
-    stat_us, decide_us = float(np.median(stat)), float(np.median(decide))
+    med = lambda pre: float(np.median(by_prefix[pre]))
+    response_us, stat_us, decide_us = med("shift_row_kernel"), med("reject_stat_kernel"), med("reject_decide_kernel")
     read_bytes = 2 * k * N * 8 * B
+
+    # ---- the entry points, alternated -----------------------------------------------------------------------------------
+    calls = {}
+    if has_fused:
+        for _ in range(3):
+            chain()
+            fused()
+        torch.cuda.synchronize()
+        it_c = max(args.iters, int(args.window_s * 1e6 / window(chain, args.iters)) + 1)
+        tc, tf = [], []
+        for _ in range(args.repeats):
+            tc.append(window(chain, it_c))
+            tf.append(window(fused, it_c))
+        calls = {
+            "response_stat_kernel_us": round(med("response_stat_kernel"), 1),
+            "chain_call_us": round(float(np.median(tc)), 1), "fused_call_us": round(float(np.median(tf)), 1),
+            "window_pairs_chain_fused_us": [[round(a, 1), round(b, 1)] for a, b in zip(tc, tf)],
+            "fused_faster_in_every_pair": bool(all(b < a for a, b in zip(tc, tf))),
+            "call_iters": it_c,
+        }
 
     # ---- the provers, alternated --------------------------------------------------------------------------------------
     seeds = iter(range(1000, 1 << 30))
@@ -99,6 +144,7 @@ def main():
     rr = torch.stack(rounds_used).to(torch.float64)
     line = {
         "config": f"open N={N} ({n},{k},{l}) B={B}", "iters": [it_s, it_z], "repeats": args.repeats,
+        "response_kernel_us": round(response_us, 1),
         "reject_stat_kernel_us": round(stat_us, 1), "reject_decide_kernel_us": round(decide_us, 1),
         "stat_read_bytes": read_bytes, "stat_GBs": round(read_bytes / stat_us / 1e3, 1),
         "decide_GBs": round(B * k * 16 / decide_us / 1e3, 2),
@@ -109,12 +155,14 @@ def main():
         "rounds_max": int(rr.max().item()) + 1, "rounds_mean_per_proof": round(float(rr.mean().item()) + 1, 3),
         "round0_accept_rate": round(float((rr == 0).double().mean().item()), 4),
         "zk_proofs_per_s": round(B / float(np.median(tz)) * 1e6),
+        "open_prove_zk_windows_us": [round(v, 1) for v in tz],
     }
+    line.update(calls)
     ctx.close()
     text = json.dumps(line)
     print(text)
-    if args.record:
-        with open(os.path.join(ROOT, "profiles", "reject_open1024_bench.json"), "w") as f:
+    if args.record or args.record_as:
+        with open(os.path.join(ROOT, "profiles", args.record_as or "reject_open1024_bench.json"), "w") as f:
             f.write(text + "\n")
 
 
