@@ -50,9 +50,9 @@ extern "C" {
 typedef struct rzk_ctx rzk_ctx;
 
 /* Version of this C ABI: bumped whenever an existing signature changes (rzk_wire_mat_decode gained `q` in 2,
- * version 3 added the entry points marked "v3", version 4 those marked "v4", version 5 those marked "v5", version 6 those marked "v6", version 7 those marked "v7", version 8 those marked "v8", version 9 those marked "v9", version 10 those marked "v10", version 11 those marked "v11", version 12 those marked "v12", version 13 those marked "v13").  A binding checks rzk_abi_version() == RZK_ABI_VERSION after loading
+ * version 3 added the entry points marked "v3", version 4 those marked "v4", version 5 those marked "v5", version 6 those marked "v6", version 7 those marked "v7", version 8 those marked "v8", version 9 those marked "v9", version 10 those marked "v10", version 11 those marked "v11", version 12 those marked "v12", version 13 those marked "v13", version 14 those marked "v14").  A binding checks rzk_abi_version() == RZK_ABI_VERSION after loading
  * the library, so that a stale or variant .so fails at load time instead of reading shifted arguments. */
-#define RZK_ABI_VERSION 13u
+#define RZK_ABI_VERSION 14u
 uint32_t rzk_abi_version(void);
 
 /* Which block of the commitment key a matrix-vector product uses (src/commit.rs:19-25). */
@@ -499,6 +499,47 @@ int rzk_reject_batch(rzk_ctx* ctx, uint32_t nparts, const int64_t* const* z, con
                      const int64_t* coin, uint64_t R, double lnM, uint8_t* accept, int64_t* E, size_t B);
 int rzk_reject_batch_dev(rzk_ctx* ctx, uint32_t nparts, const int64_t* const* z, const int64_t* const* y, const uint32_t* rows,
                          const int64_t* coin, uint64_t R, double lnM, uint8_t* accept, int64_t* E, size_t B);
+
+/* ---- 32-bit slabs (v14) ---------------------------------------------------------------------------------------
+ * A "slab32" is the dense row-major [batch][row][N] layout of every coefficient slab above with int32_t centred residues: the
+ * same values, half the bytes.  It exists because (q - 1) / 2 < 2^31 for every modulus rzk_ctx_create accepts.  Opt-in: a caller
+ * that keeps data on the device (sampler outputs narrowed once, this library's own outputs fed to the next call) gets the same
+ * proofs and verdicts from slabs half the size; nothing about the 64-bit entry points changes.
+ *   canonical   still |c| <= (q - 1) / 2: the int32 range is wider than that, so every call tests as its sibling does
+ *   alignment   device slabs are 16-byte aligned (RZK_E_ARG otherwise)
+ *   width       all slabs of one call have the same width
+ * rzk_narrow_batch   out = in as int32 (count polynomials).  A non-canonical coefficient is an input fault of the call, reported
+ *                    as the Mat-level calls report theirs (host form: RZK_E_ARG; _dev form: the sticky condition, at the next
+ *                    synchronising call / rzk_ctx_check_inputs); its output value is then unspecified.  Trusted-producer mode
+ *                    (rzk_ctx_trust_device_outputs): no test.
+ * rzk_widen_batch    out = in sign-extended.  No test: the consuming call tests.
+ * rzk_open_*32_batch the Open cycle: arguments, verdict bytes, fused norm predicate and fault rules of rzk_open_commit_batch,
+ *                    rzk_open_response_batch, rzk_open_verify_batch and rzk_open_recover_batch, every slab int32_t.  Prover side
+ *                    (commit32, response32) a non-canonical coefficient fails the call; verifier side (verify32, recover32) it
+ *                    clears that proof's verdict and the call succeeds.  Bit-identical to narrow() of the siblings' outputs.
+ * Native 32-bit kernels run at N = 512 and N = 1024 with n = 1 and the default rotation knobs; every other context converts
+ * inside the call (widen into a grow-only arena, the sibling's launches, narrow): same results, no gain.  The _dev forms make
+ * no allocation and no host synchronisation in the steady state.  NULL pointers: RZK_E_ARG (ok of commit32 may be NULL);
+ * B == 0 / count == 0 is a no-op. */
+int rzk_narrow_batch(rzk_ctx* ctx, const int64_t* in, int32_t* out, size_t count);
+int rzk_narrow_batch_dev(rzk_ctx* ctx, const int64_t* in, int32_t* out, size_t count);
+int rzk_widen_batch(rzk_ctx* ctx, const int32_t* in, int64_t* out, size_t count);
+int rzk_widen_batch_dev(rzk_ctx* ctx, const int32_t* in, int64_t* out, size_t count);
+int rzk_open_commit32_batch(rzk_ctx* ctx, const int32_t* x, const int32_t* r, const int32_t* y, int32_t* c, int32_t* t,
+                            uint8_t* ok, size_t B);
+int rzk_open_commit32_batch_dev(rzk_ctx* ctx, const int32_t* x, const int32_t* r, const int32_t* y, int32_t* c, int32_t* t,
+                                uint8_t* ok, size_t B);
+int rzk_open_response32_batch(rzk_ctx* ctx, const int32_t* y, const int32_t* r, const int32_t* d, int32_t* z, size_t B);
+int rzk_open_response32_batch_dev(rzk_ctx* ctx, const int32_t* y, const int32_t* r, const int32_t* d, int32_t* z, size_t B);
+int rzk_open_verify32_batch(rzk_ctx* ctx, const int32_t* z, const int32_t* t, const int32_t* c, const int32_t* d,
+                            uint8_t* accept, size_t B);
+int rzk_open_verify32_batch_dev(rzk_ctx* ctx, const int32_t* z, const int32_t* t, const int32_t* c, const int32_t* d,
+                                uint8_t* accept, size_t B);
+int rzk_open_recover32_batch(rzk_ctx* ctx, const int32_t* z, const int32_t* c, const int32_t* d, int32_t* t_out,
+                             uint8_t* accept, size_t B);
+int rzk_open_recover32_batch_dev(rzk_ctx* ctx, const int32_t* z, const int32_t* c, const int32_t* d, int32_t* t_out,
+                                 uint8_t* accept, size_t B);
+
 /* The response and its test in one call (v13): "give me z, and tell me whether I may release it".
  * z (z', z_s) is byte for byte what rzk_*_response_batch writes; accept and E (may be NULL) are what rzk_reject_batch
  * returns for the parts [(z, y)] (Open), [(z, y), (z', y')] (Linear), [(z_s, y_s), (z', y')] (Sum) with the same coin, R

@@ -20,6 +20,7 @@ MSG_LINEAR_SHORT, MSG_SUM_SHORT = 11, 12   # v12; 10 is unassigned
 _lib = None
 
 _I64 = C.c_void_p  # int64_t* (host or device pointer, passed as an address)
+_I32 = C.c_void_p  # int32_t* (32-bit coefficient slabs, v14)
 _U8 = C.c_void_p
 _U32P = C.c_void_p
 _SZ = C.c_size_t
@@ -105,6 +106,13 @@ SIGNATURES = {
     "rzk_linear_response_reject_batch": (C.c_int, [_CTX] + [_I64] * 6 + [C.c_uint64, C.c_double, _I64, _I64, _U8, _I64, _SZ]),
     "rzk_sum_response_reject_batch": (C.c_int, [_CTX, C.c_uint32] + [_I64] * 6 + [C.c_uint64, C.c_double, _I64, _I64, _U8, _I64,
                                                                                  _SZ]),
+    # v14: 32-bit coefficient slabs (int32_t* where the siblings take int64_t*)
+    "rzk_narrow_batch": (C.c_int, [_CTX, _I64, _I32, _SZ]),
+    "rzk_widen_batch": (C.c_int, [_CTX, _I32, _I64, _SZ]),
+    "rzk_open_commit32_batch": (C.c_int, [_CTX] + [_I32] * 5 + [_U8, _SZ]),
+    "rzk_open_response32_batch": (C.c_int, [_CTX] + [_I32] * 4 + [_SZ]),
+    "rzk_open_verify32_batch": (C.c_int, [_CTX] + [_I32] * 4 + [_U8, _SZ]),
+    "rzk_open_recover32_batch": (C.c_int, [_CTX] + [_I32] * 4 + [_U8, _SZ]),
     # v8: fixed-width packed records
     "rzk_packed_record_bytes": (C.c_size_t, [_CTX, C.c_int, C.c_uint32]),
     "rzk_packed_widths": (C.c_int, [_CTX, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
@@ -123,7 +131,7 @@ SIGNATURES = {
     "rzk_prof_read_all": (C.c_int, [_CTX, C.POINTER(C.c_double), _SZ, C.POINTER(C.c_size_t)]),
     "rzk_prof_read_kernels": (C.c_int, [_CTX, C.c_char_p, _SZ, C.POINTER(C.c_size_t)]),
 }
-ABI_VERSION = 13   # include/rzk.h: RZK_ABI_VERSION
+ABI_VERSION = 14   # include/rzk.h: RZK_ABI_VERSION
 # every batched entry point also exists as a device-pointer variant with the same signature
 for _name in list(SIGNATURES):
     if _name.endswith("_batch"):

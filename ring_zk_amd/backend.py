@@ -97,7 +97,7 @@ class Context:
             if dev:
                 import torch
 
-                want = {np.int64: torch.int64, np.uint32: torch.int32, np.uint8: torch.uint8}[dt]
+                want = {np.int64: torch.int64, np.int32: torch.int32, np.uint32: torch.int32, np.uint8: torch.uint8}[dt]
                 if a.dtype != want or not a.is_cuda or not a.is_contiguous():
                     raise ValueError("device buffers must be contiguous CUDA tensors of the right dtype")
                 ptrs.append(C.c_void_p(a.data_ptr()))
@@ -113,7 +113,7 @@ class Context:
         if _is_torch(like):
             import torch
 
-            tdt = {np.int64: torch.int64, np.uint32: torch.int32, np.uint8: torch.uint8}[dtype]
+            tdt = {np.int64: torch.int64, np.int32: torch.int32, np.uint32: torch.int32, np.uint8: torch.uint8}[dtype]
             return torch.empty(shape, dtype=tdt, device=like.device)
         return np.empty(shape, dtype=dtype)
 
@@ -560,6 +560,66 @@ class Context:
         acc = self._empty(z, (B,), np.uint8)
         dev, p = self._prep([z, c, d, t, acc], [np.int64] * 4 + [np.uint8])
         self._check(self._fn("rzk_open_recover_batch", dev)(self._h, *p, B))
+        return t, acc
+
+    # ---- 32-bit coefficient slabs (include/rzk.h "32-bit slabs", v14) ------------------------------------------
+    # The same values as int32: numpy int32 arrays or torch int32 tensors.  The methods above keep rejecting int32.
+    def narrow(self, a):
+        """int64 slab -> int32 slab; a non-canonical coefficient is an input fault of the call (host arrays: raises;
+        device tensors: the sticky condition, reported by synchronize())."""
+        count = self._shape(a, self.N)
+        out = self._empty(a, tuple(a.shape), np.int32)
+        dev, p = self._prep([a, out], [np.int64, np.int32])
+        self._check(self._fn("rzk_narrow_batch", dev)(self._h, *p, count))
+        return out
+
+    def widen(self, a):
+        """int32 slab -> int64 slab (sign extension; the consuming call tests the range)."""
+        count = self._shape(a, self.N)
+        out = self._empty(a, tuple(a.shape), np.int64)
+        dev, p = self._prep([a, out], [np.int32, np.int64])
+        self._check(self._fn("rzk_widen_batch", dev)(self._h, *p, count))
+        return out
+
+    def open_commit32(self, x, r, y):
+        B = self._shape(x, self.l, self.N)
+        if self._shape(r, self.k, self.N) != B or self._shape(y, self.k, self.N) != B:
+            raise ValueError("open_commit32: batch / shape mismatch (commit.rs:95)")
+        lead = tuple(x.shape[:-2])
+        c = self._empty(x, lead + (self.n + self.l, self.N), np.int32)
+        t = self._empty(x, lead + (self.n, self.N), np.int32)
+        ok = self._empty(x, (B,), np.uint8)
+        dev, p = self._prep([x, r, y, c, t, ok], [np.int32] * 5 + [np.uint8])
+        self._check(self._fn("rzk_open_commit32_batch", dev)(self._h, *p, B))
+        return c, t, ok
+
+    def open_response32(self, y, r, d):
+        B = self._shape(y, self.k, self.N)
+        if self._shape(r, self.k, self.N) != B or self._shape(d, self.N) != B:
+            raise ValueError("open_response32: batch / shape mismatch")
+        z = self._empty(y, tuple(y.shape), np.int32)
+        dev, p = self._prep([y, r, d, z], [np.int32] * 4)
+        self._check(self._fn("rzk_open_response32_batch", dev)(self._h, *p, B))
+        return z
+
+    def open_verify32(self, z, t, c, d):
+        B = self._shape(z, self.k, self.N)
+        if (self._shape(t, self.n, self.N) != B or self._shape(c, self.n + self.l, self.N) != B
+                or self._shape(d, self.N) != B):
+            raise ValueError("open_verify32: batch / shape mismatch")
+        acc = self._empty(z, (B,), np.uint8)
+        dev, p = self._prep([z, t, c, d, acc], [np.int32] * 4 + [np.uint8])
+        self._check(self._fn("rzk_open_verify32_batch", dev)(self._h, *p, B))
+        return acc
+
+    def open_recover32(self, z, c, d):
+        B = self._shape(z, self.k, self.N)
+        if self._shape(c, self.n + self.l, self.N) != B or self._shape(d, self.N) != B:
+            raise ValueError("open_recover32: batch / shape mismatch")
+        t = self._empty(z, tuple(z.shape[:-2]) + (self.n, self.N), np.int32)
+        acc = self._empty(z, (B,), np.uint8)
+        dev, p = self._prep([z, c, d, t, acc], [np.int32] * 4 + [np.uint8])
+        self._check(self._fn("rzk_open_recover32_batch", dev)(self._h, *p, B))
         return t, acc
 
     # ---- LinearProof (src/prove/linear.rs) ------------------------------------------------------------------------

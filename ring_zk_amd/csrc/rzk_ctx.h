@@ -24,6 +24,7 @@
 #include "rzk_packed.h"
 #include "rzk_plan.h"
 #include "rzk_reject.h"
+#include "rzk_slab32.h"
 #include "rzk_tables.h"
 #include "rzk_xof.h"
 
@@ -113,6 +114,7 @@ struct rzk_ctx {
   double* d_key_l2 = nullptr;
   std::map<std::pair<int, uint32_t>, DevProg> progs;
   Arena ws, stage, ws_slots;
+  Arena ws32;                          // convert path of the 32-bit entry points: the call's slabs widened to int64 (rzk_slab32.cpp)
   Arena ws_wire;                       // message codec: position table (decode) / lengths, positions, sizes (encode)
   Arena ws_fs;                         // Fiat-Shamir transcript: leaf digests of the call (and the key while it is hashed)
   Arena ws_reject;                     // rejection sampling: one RejectPartial per response polynomial of the call
@@ -131,7 +133,7 @@ struct rzk_ctx {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
   struct ProfInfo {
     std::string kernel;     // the kernel template instance the launch ran
-    uint64_t bytes = 0;     // algorithmic bytes of the launch: 8 N x (distinct polynomials read + rows stored)
+    uint64_t bytes = 0;     // algorithmic bytes of the launch: (8 or 4) N x (distinct polynomials read + rows stored)
   };
   std::vector<ProfInfo> prof_info;   // parallel to the used part of prof_events
   size_t prof_used = 0;
@@ -176,7 +178,12 @@ bool shift_ok(const rzk_ctx* c);
 bool response_stat_fused(const rzk_ctx* c);
 int run_program(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSpec>& specs, uint8_t* flags, uint32_t group,
                 uint64_t batch, uint64_t norm_limit = 0, bool sticky = true, uint8_t preset_value = 0, uint64_t nflags = 0,
-                const ResponseStat* stat = nullptr);
+                const ResponseStat* stat = nullptr, uint32_t width = 8);
+// width 4: the operands are int32_t slabs (their addresses travel as int64_t*) and the program must have native 32-bit
+// kernels on this context (program_native32, asked by the entry point before its first launch)
+bool program_native32(rzk_ctx* c, int id, uint32_t var);
+// the fused (var | 1) form of a checked program can run on this context with this bound (run_checked then takes no fallback)
+bool checked_fuses(rzk_ctx* c, int id, uint32_t var, uint64_t bound);
 int run_norm(rzk_ctx* c, const int64_t* v, uint32_t rows, uint64_t bound, uint8_t* ok, uint64_t B, int mode, int shift,
              bool sticky = true);
 struct NormSpec {   // one launch of the norm kernel: flags (mode, shift) sum c^2 of v's `rows` polynomials per flag < (bound+1)^2
@@ -185,7 +192,8 @@ struct NormSpec {   // one launch of the norm kernel: flags (mode, shift) sum c^
   int mode, shift;   // launch_norm: 0 = overwrite, 1 = and, 2 = or (result << shift)
 };
 int run_checked(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSpec>& specs, uint8_t* flags, uint32_t group,
-                uint64_t batch, uint64_t nflags, uint64_t bound, bool preset, bool sticky, std::initializer_list<NormSpec> norms);
+                uint64_t batch, uint64_t nflags, uint64_t bound, bool preset, bool sticky, std::initializer_list<NormSpec> norms,
+                uint32_t width = 8);
 int prepare_dkey(rzk_ctx* c, const int64_t* g, uint64_t entries, uint32_t per_entry, uint32_t uses, uint8_t* flags, bool sticky);
 int prepare_oimg(rzk_ctx* c, uint64_t B, uint32_t V, uint32_t uses);
 bool sum_uses_d(const rzk_ctx* c, uint32_t V);

@@ -367,6 +367,19 @@ struct ResponseStat {   // where a launch of response_stat_kernel leaves its par
 // (b mod group) * nrows + rowi], group = Operands::group.
 int launch_response_stat(int logn, const LaunchCfg& cfg, const Program* d_prog, uint32_t nrows, const Operands& ops,
                          const DevTables* d_T, uint64_t batch, const ResponseStat& so);
+// ---- 32-bit coefficient slabs (rzk_slab32_dev.hip; format and routing in rzk_slab32.h) ------------------
+// launch_units / launch_shift_rows for a launch whose Operands::base address int32_t slabs: key-product programs, one-wavefront
+// teams, N = 512 / 1024, the packed-byte rotation kernel (-1 otherwise: the caller converts, slab32_native)
+int launch_units32(int logn, const LaunchCfg& cfg, const Program* d_prog, const WaveProgram* d_wp, uint32_t nunits,
+                   uint32_t units_per_task, uint32_t work_per_entry, bool has_shift, const Operands& ops,
+                   const uint32_t* d_key_ntt, const double* d_key_l2, const DevTables* d_T, const uint32_t* d_tw,
+                   uint32_t* d_scratch, uint8_t* d_flags, uint64_t batch);
+int launch_shift_rows32(int logn, const LaunchCfg& cfg, const Program* d_prog, uint32_t nrows, const Operands& ops,
+                        const DevTables* d_T, uint8_t* d_flags, uint64_t batch);
+// out = the low words of in (bad_word != NULL: a non-canonical coefficient sets it); out = in sign-extended.  ncoef even,
+// both slabs 16-byte aligned
+int launch_narrow(const LaunchCfg& cfg, const int64_t* in, int32_t* out, uint64_t ncoef, uint32_t qhalf, uint32_t* bad_word);
+int launch_widen(const LaunchCfg& cfg, const int32_t* in, int64_t* out, uint64_t ncoef);
 // ---- fixed-width packed records (rzk_packed_dev.hip; format in rzk_packed.h) -------------------------------------------
 struct PackedSlabs {
   int64_t* ptr[kPackedMaxFields];   // dense slab of every field ([B][rows of the field][N]), 16-byte aligned

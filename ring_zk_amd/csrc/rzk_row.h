@@ -125,12 +125,14 @@ struct ShiftCfg {   // teams per workgroup: one team's image is 8 * N bytes of L
 // rotate packed bytes instead of words (shift_product_bytes); every other term takes shift_product as before.  One
 // wavefront only, and the default there (so `shift_row_kernel<10, false>` IS the packed-byte kernel, in C++ as in the names
 // the launcher reports); RZK_SHIFT_BYTES=0 launches shift_row_kernel<., ., WaveTeam, false>.
+// The coefficient type of the slabs comes with the team (TeamCoef, rzk_wave.h), as in unit_kernel.
 template <int LOGN, bool TRUSTED, class TM = WaveTeam, bool BYTES = (TM::LL == 6)>   // TRUSTED (Operands::trusted) is a template flag here: as a run-time branch around the loads
                                                          // it changed the compiler's load scheduling (79 instead of 116 VGPRs, 86 us instead of 77)
 __global__ void __launch_bounds__((ShiftCfg<LOGN, TM>::TPB << TM::LL), (BYTES ? RZK_SHIFT_BYTES_WAVES : TM::LL == 6 ? 1 : 4))   // BYTES: the register budget of the waves per SIMD the LDS request allows
 shift_row_kernel(const Program* __restrict__ prog, const Operands ops, const DevTables* __restrict__ Tp,
                  uint8_t* __restrict__ flags, const uint32_t ntasks) {
   using S = ShiftGeo<LOGN, true, TM::LL>;
+  using C = typename TeamCoef<TM>::type;   // coefficient type of the slabs
   constexpr int E = S::E;
   constexpr int N = S::N;
   constexpr int LANES = S::LANES;
@@ -162,12 +164,12 @@ shift_row_kernel(const Program* __restrict__ prog, const Operands ops, const Dev
         const Term tm = prog->terms[row.term0 + t];
         int32_t a[E];
         uint32_t abad = 0, amx = 0;
-        load_pairs<LOGN, TM::LL>(a, operand_ptr(ops, tm.a_op, tm.a_off, b, bo, N), lane, qhalf, abad, amx, trusted);
+        load_pairs<LOGN, TM::LL, C>(a, operand_ptr<C>(ops, tm.a_op, tm.a_off, b, bo, N), lane, qhalf, abad, amx, trusted);
         if (!trusted) fault = fault || canon_fail(abad, amx, qhalf);
-        const int64_t* __restrict__ pv = operand_ptr(ops, tm.b_op, tm.b_off, b, bo, N);
+        const C* __restrict__ pv = operand_ptr<C>(ops, tm.b_op, tm.b_off, b, bo, N);
         bool done = false;
-        if constexpr (BYTES) done = shift_product_bytes<LOGN>(res, tm.sign < 0, a, pv, lane, slab, T, fault, trusted);
-        if (!done) shift_product<LOGN, true, false, TM>(res, false, tm.sign < 0, a, pv, lane, slab, T, fault, trusted);
+        if constexpr (BYTES) done = shift_product_bytes<LOGN, C>(res, tm.sign < 0, a, pv, lane, slab, T, fault, trusted);
+        if (!done) shift_product<LOGN, true, false, TM, kShiftH, C>(res, false, tm.sign < 0, a, pv, lane, slab, T, fault, trusted);
       }
       // The sums move to the (now idle) image, each thread's pairs in its own 8-byte slots, so that the additions and
       // the store can run as a rolled loop with few registers and four 16-byte loads in flight per addition.
@@ -191,14 +193,15 @@ shift_row_kernel(const Program* __restrict__ prog, const Operands ops, const Dev
 #pragma unroll 1
       for (uint32_t ai = 0; ai < row.nadds; ++ai) {
         const AddTerm ad = prog->adds[row.add0 + ai];
-        const longlong2* __restrict__ p =
-            reinterpret_cast<const longlong2*>(operand_ptr(ops, ad.op & ADD_OP_MASK, ad.off, b, bo, N)) + g0 * LANES + lane;
+        using P2 = typename CoefPair<C>::type;
+        const P2* __restrict__ p =
+            reinterpret_cast<const P2*>(operand_ptr<C>(ops, ad.op & ADD_OP_MASK, ad.off, b, bo, N)) + g0 * LANES + lane;
         int32_t av[2 * GC];
         if (trusted) {
 #pragma unroll
           for (int g = 0; g < GC; ++g) {
-            const longlong2 t = ld_stream(p + g * LANES);
-            av[2 * g] = (int32_t)t.x, av[2 * g + 1] = (int32_t)t.y;
+            const P2 t = ld_stream(p + g * LANES);
+            pair_words(t, av[2 * g], av[2 * g + 1]);
           }
         } else {
 #pragma unroll
@@ -213,12 +216,20 @@ shift_row_kernel(const Program* __restrict__ prog, const Operands ops, const Dev
         }
       }
       if (row.mode == MODE_STORE) {
-        int4* __restrict__ dst =
-            reinterpret_cast<int4*>(const_cast<int64_t*>(operand_ptr(ops, row.out_op, row.out_off, b, bo, N))) + g0 * LANES + lane;
+        if constexpr (sizeof(C) == 8) {
+          int4* __restrict__ dst =
+              reinterpret_cast<int4*>(const_cast<C*>(operand_ptr<C>(ops, row.out_op, row.out_off, b, bo, N))) + g0 * LANES + lane;
 #pragma unroll
-        for (int g = 0; g < GC; ++g) {
-          const int64_t c0 = center_from_zq(r[2 * g], T.crt), c1 = center_from_zq(r[2 * g + 1], T.crt);
-          st_stream(dst + g * LANES, make_int4((int32_t)c0, (int32_t)(c0 >> 32), (int32_t)c1, (int32_t)(c1 >> 32)));
+          for (int g = 0; g < GC; ++g) {
+            const int64_t c0 = center_from_zq(r[2 * g], T.crt), c1 = center_from_zq(r[2 * g + 1], T.crt);
+            st_stream(dst + g * LANES, make_int4((int32_t)c0, (int32_t)(c0 >> 32), (int32_t)c1, (int32_t)(c1 >> 32)));
+          }
+        } else {   // the pair layout with 8-byte accesses
+          int2* __restrict__ dst =
+              reinterpret_cast<int2*>(const_cast<C*>(operand_ptr<C>(ops, row.out_op, row.out_off, b, bo, N))) + g0 * LANES + lane;
+#pragma unroll
+          for (int g = 0; g < GC; ++g)
+            st_stream(dst + g * LANES, make_int2((int32_t)center_from_zq(r[2 * g], T.crt), (int32_t)center_from_zq(r[2 * g + 1], T.crt)));
         }
       } else {
 #pragma unroll

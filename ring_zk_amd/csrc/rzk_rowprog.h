@@ -1,6 +1,7 @@
 // rzk_rowprog.h - building blocks of the row-program kernels: canonical-input test, load_lift, the rotation (shift) terms, term_direct, epilogues, primes_for.
 // Part of the one translation unit rzk_kernels.hip (device code only; no include guards beyond #pragma once).
 #pragma once
+#include "rzk_slab32.h"
 #include "rzk_wave.h"
 
 namespace rzk {
@@ -29,6 +30,25 @@ __device__ __forceinline__ void canon_pair(const longlong2 t, uint32_t qhalf, ui
   lo0 = canon_lo_mx(t.x, qhalf, bad, mx);
   lo1 = canon_lo_mx(t.y, qhalf, bad, mx);
 }
+// The same tests on the coefficients of a 32-bit slab (rzk_slab32.h): no high word, so `bad` stays untouched and the one
+// unsigned compare of canon_fail on the max-ed word (c + h mod 2^32 <= 2h) is the whole test.
+__device__ __forceinline__ int32_t canon_lo(int32_t c, uint32_t, uint32_t&) { return c; }   // (callers also test max |c| > h)
+__device__ __forceinline__ int32_t canon_lo_mx(int32_t c, uint32_t qhalf, uint32_t&, uint32_t& mx) {
+  const uint32_t lo = slab32_test_word(c, qhalf);
+  mx = lo > mx ? lo : mx;
+  return c;
+}
+__device__ __forceinline__ void canon_pair(const int2 t, uint32_t qhalf, uint32_t& bad, uint32_t& mx, int32_t& lo0, int32_t& lo1) {
+  lo0 = canon_lo_mx(t.x, qhalf, bad, mx);
+  lo1 = canon_lo_mx(t.y, qhalf, bad, mx);
+}
+// Coefficient type of a launch's slabs (int64_t, the default, or int32_t): the 16- / 8-byte pair of the rotation kernels'
+// accesses, and the store of a centred result (the value is below 2^31 in magnitude for every modulus: the cast is exact).
+template <class C> struct CoefPair;
+template <> struct CoefPair<int64_t> { using type = longlong2; };
+template <> struct CoefPair<int32_t> { using type = int2; };
+__device__ __forceinline__ void pair_words(const longlong2 t, int32_t& lo0, int32_t& lo1) { lo0 = (int32_t)t.x, lo1 = (int32_t)t.y; }
+__device__ __forceinline__ void pair_words(const int2 t, int32_t& lo0, int32_t& lo1) { lo0 = t.x, lo1 = t.y; }
 // wave-uniform verdict of the per-lane accumulators (mx holds max (lo + h) mod 2^32, canonical <=> <= 2h)
 __device__ __forceinline__ bool canon_fail(uint32_t bad, uint32_t mx, uint32_t qhalf) {
   return __any((bad != 0) | (mx > 2u * qhalf)) != 0;
@@ -48,10 +68,12 @@ __device__ __forceinline__ void input_fault(const Operands& ops, uint8_t* flags,
   if (ops.bad) *ops.bad = 1u;
 }
 
-__device__ __forceinline__ const int64_t* operand_ptr(const Operands& ops, uint32_t op, uint32_t off,
-                                                       uint32_t b, uint32_t bo, int n_coef) {
+// C: the coefficient type of the launch's slabs (Operands::base holds the addresses; the element width is the launch's)
+template <class C = int64_t>
+__device__ __forceinline__ const C* operand_ptr(const Operands& ops, uint32_t op, uint32_t off,
+                                                uint32_t b, uint32_t bo, int n_coef) {
   const uint32_t idx = ops.outer[op] ? bo : b;
-  return ops.base[op] + ((uint64_t)idx * ops.stride[op] + off) * (uint64_t)n_coef;
+  return reinterpret_cast<const C*>(ops.base[op]) + ((uint64_t)idx * ops.stride[op] + off) * (uint64_t)n_coef;
 }
 
 constexpr int kEpiChunk = 16;   // coefficients per lane handled together in the epilogue (4 was slower: fewer loads in flight)
@@ -82,8 +104,8 @@ enum : int { LL_FUSED = 0, LL_HALVES = 1, LL_L1INF = 2 };
 // bytes of scratch: 213 k / 4.10 M).  Teams of two (N = 2048) stay spill-free only with LL_HALVES.
 template <class TM>
 constexpr int kRowLoadMode = TM::LL == 7 ? LL_HALVES : LL_L1INF;   // row_kernel, both operands of a term
-template <int LOGN, class TM = WaveTeam, int MODE = LL_FUSED>
-__device__ __forceinline__ void load_lift(uint32_t* x, const int64_t* __restrict__ src, int lane, const PrimeConsts& pc,
+template <int LOGN, class TM = WaveTeam, int MODE = LL_FUSED, class C = int64_t>
+__device__ __forceinline__ void load_lift(uint32_t* x, const C* __restrict__ src, int lane, const PrimeConsts& pc,
                                           bool measure, float& nrm2, bool check, uint64_t limit, bool& below,
                                           uint32_t qhalf, bool trusted, bool& fault) {
   using G = Geo<LOGN, TM::LL>;
@@ -134,7 +156,7 @@ __device__ __forceinline__ void load_lift(uint32_t* x, const int64_t* __restrict
         uint32_t y[H];
 #pragma unroll
         for (int e2 = 0; e2 < H; ++e2) {
-          const int64_t c = ld_stream(src + (size_t)(h * H + e2) * G::LANES + lane);
+          const C c = ld_stream(src + (size_t)(h * H + e2) * G::LANES + lane);
           const int32_t v = trusted ? (int32_t)c : canon_lo_mx(c, qhalf, bad, mx);
           const float f = (float)v;
           part = __builtin_fmaf(f, f, part);
@@ -217,16 +239,17 @@ __device__ __forceinline__ void load_lift(uint32_t* x, const int64_t* __restrict
 // ---- challenge products as signed rotations (ShiftGeo, rzk_core.h): shared by shift_row_kernel and the
 // shift terms of row_kernel ---------------------------------------------------------------------------------
 
-template <int LOGN, int LL = 6>
-__device__ __forceinline__ void load_pairs(int32_t* v, const int64_t* __restrict__ src, int lane, uint32_t qhalf,
+template <int LOGN, int LL = 6, class C = int64_t>
+__device__ __forceinline__ void load_pairs(int32_t* v, const C* __restrict__ src, int lane, uint32_t qhalf,
                                            uint32_t& bad, uint32_t& mx, bool trusted) {
   using S = ShiftGeo<LOGN, true, LL>;
-  const longlong2* __restrict__ p = reinterpret_cast<const longlong2*>(src);
+  using P2 = typename CoefPair<C>::type;
+  const P2* __restrict__ p = reinterpret_cast<const P2*>(src);
   if (trusted) {
 #pragma unroll
     for (int g = 0; g < S::G; ++g) {
-      const longlong2 t = ld_stream(p + g * S::LANES + lane);
-      v[2 * g] = (int32_t)t.x, v[2 * g + 1] = (int32_t)t.y;
+      const P2 t = ld_stream(p + g * S::LANES + lane);
+      pair_words(t, v[2 * g], v[2 * g + 1]);
     }
   } else {
 #pragma unroll
@@ -305,8 +328,8 @@ __device__ __forceinline__ void shift_scan_list(int64_t* acc, const int32_t* lis
 // Build the wave's 2N-word extended image of v (ShiftGeo, rzk_core.h) straight from global memory, in two rolled
 // halves so that only E/2 sixty-four-bit coefficients are in flight at a time.  measure: this is the first fill —
 // it also proves that v is canonical (canon_lo) and returns max |v| over the lane's coefficients.
-template <int LOGN, bool PAIR, int LL = 6>
-__device__ __forceinline__ void shift_fill_from(const int64_t* __restrict__ pv, int lane, int32_t* ext, int part,
+template <int LOGN, bool PAIR, int LL = 6, class C = int64_t>
+__device__ __forceinline__ void shift_fill_from(const C* __restrict__ pv, int lane, int32_t* ext, int part,
                                                 bool measure, bool canon, uint32_t qhalf, uint32_t& bad, uint32_t& mx,
                                                 uint32_t& maxabs) {
   using S = ShiftGeo<LOGN, PAIR, LL>;
@@ -316,22 +339,22 @@ __device__ __forceinline__ void shift_fill_from(const int64_t* __restrict__ pv, 
   for (int h = 0; h < 2; ++h) {
     int32_t vh[H];
     if (PAIR) {
-      const longlong2* __restrict__ p = reinterpret_cast<const longlong2*>(pv) + (size_t)h * (H / 2) * S::LANES;
+      using P2 = typename CoefPair<C>::type;
+      const P2* __restrict__ p = reinterpret_cast<const P2*>(pv) + (size_t)h * (H / 2) * S::LANES;
 #pragma unroll
       for (int g = 0; g < H / 2; ++g) {
-        const longlong2 t = ld_stream(p + g * S::LANES + lane);   // coefficients (h*H/2 + g)*2*LANES + 2*lane, +1
+        const P2 t = ld_stream(p + g * S::LANES + lane);   // coefficients (h*H/2 + g)*2*LANES + 2*lane, +1
         if (canon) {
           canon_pair(t, qhalf, bad, mx, vh[2 * g], vh[2 * g + 1]);
         } else {
-          vh[2 * g] = (int32_t)t.x;
-          vh[2 * g + 1] = (int32_t)t.y;
+          pair_words(t, vh[2 * g], vh[2 * g + 1]);
         }
       }
     } else {
-      const int64_t* __restrict__ p = pv + (size_t)h * H * S::LANES;
+      const C* __restrict__ p = pv + (size_t)h * H * S::LANES;
 #pragma unroll
       for (int i = 0; i < H; ++i) {
-        const int64_t c = p[i * S::LANES + lane];
+        const C c = p[i * S::LANES + lane];
         vh[i] = canon ? canon_lo_mx(c, qhalf, bad, mx) : (int32_t)c;
       }
     }
@@ -364,9 +387,9 @@ __device__ __forceinline__ void shift_fill_from(const int64_t* __restrict__ pv, 
 // fault: set when v holds a non-canonical coefficient (the caller tests `a`).
 // HREG: outputs per scan of the register form (unit_kernel's rotation-last path runs it with nothing else live and
 // takes all 16 of a lane's outputs in one scan, as the TO_MEM form does).
-template <int LOGN, bool PAIR, bool TO_MEM, class TM = WaveTeam, int HREG = kShiftH>
+template <int LOGN, bool PAIR, bool TO_MEM, class TM = WaveTeam, int HREG = kShiftH, class C = int64_t>
 __device__ __forceinline__ void shift_product(uint32_t* res, bool fresh, bool minus, const int32_t* a,
-                                              const int64_t* __restrict__ pv, int lane_in, int32_t* ext,
+                                              const C* __restrict__ pv, int lane_in, int32_t* ext,
                                               const DevTables& T, bool& fault, bool trusted) {
   constexpr int LL = TM::LL;
   int lane = lane_in;
@@ -381,7 +404,7 @@ __device__ __forceinline__ void shift_product(uint32_t* res, bool fresh, bool mi
   // optimistic first fill with the whole values; it also measures v
   uint32_t vbad = 0, vmx = 0, maxv = 0;
   TM::sync();   // earlier reads of the image are done before it is overwritten
-  shift_fill_from<LOGN, PAIR, LL>(pv, lane, ext, SHIFT_WHOLE, true, !trusted, qhalf, vbad, vmx, maxv);
+  shift_fill_from<LOGN, PAIR, LL, C>(pv, lane, ext, SHIFT_WHOLE, true, !trusted, qhalf, vbad, vmx, maxv);
   if (!trusted) fault = fault || canon_fail(vbad, vmx, qhalf);
   uint64_t suma = 0;
 #pragma unroll
@@ -410,7 +433,7 @@ __device__ __forceinline__ void shift_product(uint32_t* res, bool fresh, bool mi
     if (npass == 2) {   // (never for a sparse +-1 challenge) the image is rebuilt from 16-bit halves
       uint32_t u0 = 0, u1 = 0, u2 = 0;
       TM::sync();
-      shift_fill_from<LOGN, PAIR, LL>(pv, lane, ext, pass == 0 ? SHIFT_LOW16 : SHIFT_HIGH16, false, false, qhalf, u0, u1, u2);
+      shift_fill_from<LOGN, PAIR, LL, C>(pv, lane, ext, pass == 0 ? SHIFT_LOW16 : SHIFT_HIGH16, false, false, qhalf, u0, u1, u2);
     }
     if (!LIST || npass == 2) TM::sync();
 #pragma unroll 1
@@ -457,8 +480,8 @@ __device__ __forceinline__ void shift_product(uint32_t* res, bool fresh, bool mi
 // registers.  Returns false, with nothing but `fault` touched, when they are not: the caller then runs shift_product.
 // The multiplier's non-zeros are walked as in shift_scan.  The sums leave through the image to get from the scan's dword ownership back to the
 // PAIR layout of res[] and of the global accesses.
-template <int LOGN>
-__device__ __forceinline__ bool shift_product_bytes(uint32_t* res, bool minus, const int32_t* a, const int64_t* __restrict__ pv,
+template <int LOGN, class C = int64_t>
+__device__ __forceinline__ bool shift_product_bytes(uint32_t* res, bool minus, const int32_t* a, const C* __restrict__ pv,
                                                     int lane, int32_t* slab, const DevTables& T, bool& fault, bool trusted) {
   using S = ShiftGeo<LOGN, true>;
   using B = ByteGeo<LOGN>;
@@ -475,14 +498,15 @@ __device__ __forceinline__ bool shift_product_bytes(uint32_t* res, bool minus, c
   if (norm1 > 255u) return false;   // (before v is touched: the word path loads it itself)
   wave_sync();   // earlier reads of the image are done before it is overwritten
   constexpr int GH = S::G / 2;   // pairs per half: two rolled halves, as shift_fill_from, to keep few 16-byte loads' registers live
-  const longlong2* __restrict__ p = reinterpret_cast<const longlong2*>(pv) + lane;
+  using P2 = typename CoefPair<C>::type;
+  const P2* __restrict__ p = reinterpret_cast<const P2*>(pv) + lane;
 #pragma unroll 1
   for (int h = 0; h < 2; ++h) {
     int32_t vh[2 * GH];
 #pragma unroll
     for (int g = 0; g < GH; ++g) {
-      const longlong2 t = ld_stream(p + (h * GH + g) * 64);   // coefficients (h*GH + g)*128 + 2*lane, +1
-      if (trusted) vh[2 * g] = (int32_t)t.x, vh[2 * g + 1] = (int32_t)t.y;
+      const P2 t = ld_stream(p + (h * GH + g) * 64);   // coefficients (h*GH + g)*128 + 2*lane, +1
+      if (trusted) pair_words(t, vh[2 * g], vh[2 * g + 1]);
       else canon_pair(t, qhalf, vbad, vmx, vh[2 * g], vh[2 * g + 1]);
     }
 #pragma unroll
@@ -680,7 +704,7 @@ __device__ __forceinline__ void inverse_and_fold(int pi, int np, uint32_t* acc, 
 // fused norm predicate sum c^2 < limit of the polynomial an addition loads.  The epilogues accumulate the float sum
 // of squares per marked addition while they load it; the verdict is taken here, exactly (see "norms" above: float
 // total outside the rounding band of the limit, otherwise the polynomial is re-read and summed in integers).
-template <int LOGN, class TM = WaveTeam>
+template <int LOGN, class TM = WaveTeam, class C = int64_t>
 __device__ __forceinline__ void checked_add_verdicts(const Program* __restrict__ prog, const Row row, const Operands& ops,
                                                      uint32_t b, uint32_t bo, int lane, const float* add_ss,
                                                      uint8_t* __restrict__ flags) {
@@ -699,7 +723,7 @@ __device__ __forceinline__ void checked_add_verdicts(const Program* __restrict__
     } else if (sfl * (1.0 - 2.0 * (double)kNormSlack) >= lim) {
       below = false;
     } else {
-      const int64_t* __restrict__ src = operand_ptr(ops, ad.op & ADD_OP_MASK, ad.off, b, bo, G::N);
+      const C* __restrict__ src = operand_ptr<C>(ops, ad.op & ADD_OP_MASK, ad.off, b, bo, G::N);
       int32_t v[G::E];
 #pragma unroll
       for (int e = 0; e < G::E; ++e) v[e] = (int32_t)src[G::j_p1(lane, e)];
@@ -711,8 +735,8 @@ __device__ __forceinline__ void checked_add_verdicts(const Program* __restrict__
 
 // One chunk of one plain addition: u[i] +/-= operand coefficient (j_p1(lane, e0 + i)) in 32-bit arithmetic mod q;
 // canonical test unless trusted; float sum of squares into add_ss[slot] for checked additions.
-template <int LOGN, int CH, class TM = WaveTeam>
-__device__ __forceinline__ void add_chunk(uint32_t* u, const AddTerm ad, uint32_t a, const int64_t* __restrict__ src, int lane,
+template <int LOGN, int CH, class TM = WaveTeam, class C = int64_t>
+__device__ __forceinline__ void add_chunk(uint32_t* u, const AddTerm ad, uint32_t a, const C* __restrict__ src, int lane,
                                           int e0, uint32_t q, uint32_t qhalf, bool trusted, uint32_t& in_bad, uint32_t& in_mx,
                                           float* add_ss) {
   using G = Geo<LOGN, TM::LL>;
@@ -746,7 +770,7 @@ __device__ __forceinline__ void add_chunk(uint32_t* u, const AddTerm ad, uint32_
 
 // plain additions in 32-bit arithmetic mod q, then centre and store / zero test; kEpiChunk coefficients
 // per lane at a time.  Checked additions also evaluate the fused norm predicate.
-template <int LOGN, class TM = WaveTeam>
+template <int LOGN, class TM = WaveTeam, class C = int64_t>
 __device__ __forceinline__ void row_epilogue(const Program* __restrict__ prog, const Row row, const Operands& ops,
                                              uint32_t b, uint32_t bo, int lane, bool has_terms, int np,
                                              const uint32_t* st_lds, const DevTables& T, uint8_t* __restrict__ flags,
@@ -777,13 +801,13 @@ __device__ __forceinline__ void row_epilogue(const Program* __restrict__ prog, c
 #pragma unroll 1
     for (uint32_t a = 0; a < row.nadds; ++a) {
       const AddTerm ad = table_load(&prog->adds[row.add0 + a]);
-      add_chunk<LOGN, CH, TM>(u, ad, a, operand_ptr(ops, ad.op & ADD_OP_MASK, ad.off, b, bo, N), lane, e0, q, T.crt.qhalf, trusted,
+      add_chunk<LOGN, CH, TM, C>(u, ad, a, operand_ptr<C>(ops, ad.op & ADD_OP_MASK, ad.off, b, bo, N), lane, e0, q, T.crt.qhalf, trusted,
                           in_bad, in_mx, add_ss);
     }
     if (row.mode == MODE_STORE) {
-      int64_t* __restrict__ dst = const_cast<int64_t*>(operand_ptr(ops, row.out_op, row.out_off, b, bo, N));
+      C* __restrict__ dst = const_cast<C*>(operand_ptr<C>(ops, row.out_op, row.out_off, b, bo, N));
 #pragma unroll
-      for (int i = 0; i < CH; ++i) st_stream(dst + G::j_p1(lane, e0 + i), center_from_zq(u[i], T.crt));
+      for (int i = 0; i < CH; ++i) st_stream(dst + G::j_p1(lane, e0 + i), (C)center_from_zq(u[i], T.crt));
     } else {
 #pragma unroll
       for (int i = 0; i < CH; ++i) nz |= (u[i] != 0);
@@ -793,7 +817,7 @@ __device__ __forceinline__ void row_epilogue(const Program* __restrict__ prog, c
     if (__any(nz) && (lane & 63) == 0) flags[bo] = 0;
   }
   if (row.nadds && !trusted && canon_fail(in_bad, in_mx, T.crt.qhalf)) input_fault(ops, flags, bo, lane);
-  if (ops.norm_limit) checked_add_verdicts<LOGN, TM>(prog, row, ops, b, bo, lane, add_ss, flags);
+  if (ops.norm_limit) checked_add_verdicts<LOGN, TM, C>(prog, row, ops, b, bo, lane, add_ss, flags);
 }
 
 __device__ __forceinline__ int primes_for(float fbound, const DevTables& T) {

@@ -65,7 +65,23 @@ int get_program(rzk_ctx* c, int id, uint32_t var, DevProg& out) {
   return RZK_OK;
 }
 
+// routing of a 32-bit launch (slab32_native, rzk_slab32.h) from the plan's facts and the context's knobs
+bool native32(const rzk_ctx* c, const DevProg& dp) {
+  const Path path = path_of(dp, c->small, c->vec_rows);
+  const Slab32Facts f = slab32_facts(dp, path == Path::Units, path == Path::Shift, c->n, shift_ok(c), c->shift_bytes);
+  return slab32_native(f, c->logn, c->small, (c->logn >= 11 && c->pair_poly) ? 7 : 6);
+}
+
 }  // namespace
+
+bool program_native32(rzk_ctx* c, int id, uint32_t var) {
+  DevProg dp;
+  if (get_program(c, id, var, dp) != RZK_OK) {
+    c->err.clear();   // (the 64-bit call the caller falls back to reports it)
+    return false;
+  }
+  return native32(c, dp);
+}
 
 void drop_programs(rzk_ctx* c) {
   for (auto& kv : c->progs) free_program(kv.second);
@@ -112,10 +128,12 @@ int prof_end(rzk_ctx* c) {
 // preset_value != 0: every verdict flag (nflags of them) starts at that value — written by the launch itself when one
 // team evaluates all rows of a batch entry (no 5-us fill launch in front of a 75-us kernel), by a fill launch otherwise.
 int run_program(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSpec>& specs, uint8_t* flags, uint32_t group,
-                uint64_t batch, uint64_t norm_limit, bool sticky, uint8_t preset_value, uint64_t nflags, const ResponseStat* stat) {
+                uint64_t batch, uint64_t norm_limit, bool sticky, uint8_t preset_value, uint64_t nflags, const ResponseStat* stat,
+                uint32_t width) {
   DevProg dp;
   int rc = get_program(c, id, var, dp);
   if (rc != RZK_OK) return rc;
+  if (width != 8 && (width != 4 || stat || !native32(c, dp))) return fail(c, RZK_E_STATE, "no 32-bit kernels for this program");
   if (specs.size() > (size_t)kMaxOperands) return fail(c, RZK_E_ARG, "too many operands");
   // units of one batch entry per task: all of them (one team per entry: equal-cost tasks, no tail) once the batch alone
   // fills the chip's wave slots; one unit per task below that
@@ -152,7 +170,7 @@ int run_program(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSpec>& spe
   uint64_t bytes = 0;   // what the launch has to move at least: its operands in, its results out
   for (size_t i = 0; i < specs.size(); ++i)
     bytes += (uint64_t)dp.polys_in[i] * (specs[i].outer ? batch / (group ? group : 1) : batch);
-  bytes = (bytes + (uint64_t)dp.polys_out * batch) * 8ull * c->N;
+  bytes = (bytes + (uint64_t)dp.polys_out * batch) * (uint64_t)width * c->N;
   LaunchCfg cfg;
   rc = prof_begin(c, bytes, cfg);
   if (rc != RZK_OK) return rc;
@@ -162,8 +180,9 @@ int run_program(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSpec>& spe
       lrc = launch_row_program_small(c->N, cfg, dp.d, dp.nrows, ops, c->d_key_mont, c->dT, c->r2q, flags, batch);
       break;
     case Path::Shift:
-      lrc = stat ? launch_response_stat((int)c->logn, cfg, dp.d, dp.nrows, ops, c->dT, batch, *stat)
-                 : launch_shift_rows((int)c->logn, cfg, dp.d, dp.nrows, ops, c->dT, flags, batch);
+      lrc = stat         ? launch_response_stat((int)c->logn, cfg, dp.d, dp.nrows, ops, c->dT, batch, *stat)
+            : width == 4 ? launch_shift_rows32((int)c->logn, cfg, dp.d, dp.nrows, ops, c->dT, flags, batch)
+                         : launch_shift_rows((int)c->logn, cfg, dp.d, dp.nrows, ops, c->dT, flags, batch);
       break;
     case Path::Blocks:
       if (!c->d_block_scratch)
@@ -209,8 +228,10 @@ int run_program(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSpec>& spe
                         c->d_row_scratch, flags, batch, dp.has_dd);
       break;
     case Path::Units:
-      lrc = launch_units((int)c->logn, cfg, dp.d, dp.d_wp, dp.nunits, upt, 2 * dp.work, dp.has_vec, dp.has_shift, ops,
-                         c->d_key_ntt, c->d_key_l2, c->dT, c->d_tw, c->d_row_scratch, flags, batch);
+      lrc = width == 4 ? launch_units32((int)c->logn, cfg, dp.d, dp.d_wp, dp.nunits, upt, 2 * dp.work, dp.has_shift, ops, c->d_key_ntt,
+                                        c->d_key_l2, c->dT, c->d_tw, c->d_row_scratch, flags, batch)
+                       : launch_units((int)c->logn, cfg, dp.d, dp.d_wp, dp.nunits, upt, 2 * dp.work, dp.has_vec, dp.has_shift, ops,
+                                      c->d_key_ntt, c->d_key_l2, c->dT, c->d_tw, c->d_row_scratch, flags, batch);
       break;
   }
   if (lrc == -2) return fail(c, RZK_E_UNSUPPORTED, "batch * rows must stay below 2^32");
@@ -236,7 +257,7 @@ uint64_t fused_limit(const rzk_ctx* c, uint64_t bound) {
 // Runs the checked variant (var | 1) of a program with the norm predicate fused into it: flags are
 // preset to 1 and cleared by failing rows.  Returns RZK_E_UNSUPPORTED when fusion is not possible.
 int run_program_checked(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSpec>& specs, uint8_t* flags,
-                        uint32_t group, uint64_t batch, uint64_t nflags, uint64_t bound, bool preset, bool sticky) {
+                        uint32_t group, uint64_t batch, uint64_t nflags, uint64_t bound, bool preset, bool sticky, uint32_t width) {
   const uint64_t lim = fused_limit(c, bound);
   if (!lim || !flags) return RZK_E_UNSUPPORTED;
   DevProg dp;
@@ -245,10 +266,20 @@ int run_program_checked(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSp
   // two-bit verdicts are cleared with word atomics: the flag array must be made of whole aligned words
   if (dp.two_bit && ((reinterpret_cast<uintptr_t>(flags) & 3u) || (nflags & 3u))) return RZK_E_UNSUPPORTED;
   const uint8_t all_ok = dp.two_bit ? 3 : 1;
-  return run_program(c, id, var | 1, specs, flags, group, batch, lim, sticky, preset ? all_ok : (uint8_t)0, nflags);
+  return run_program(c, id, var | 1, specs, flags, group, batch, lim, sticky, preset ? all_ok : (uint8_t)0, nflags, nullptr, width);
 }
 
 }  // namespace
+
+bool checked_fuses(rzk_ctx* c, int id, uint32_t var, uint64_t bound) {
+  if (!fused_limit(c, bound)) return false;
+  DevProg dp;
+  if (get_program(c, id, var | 1, dp) != RZK_OK) {
+    c->err.clear();
+    return false;
+  }
+  return !dp.two_bit;   // (two-bit verdicts depend on the flag array's alignment: not asked for here)
+}
 
 // A program whose rows decide a norm predicate of `bound` into `flags` (nflags of them, one per proof): the checked
 // variant with the predicate fused into the rows that load the vector anyway; where that cannot run (small rings, a
@@ -257,15 +288,17 @@ int run_program_checked(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSp
 // (a prover that does not ask) the norms are skipped.  preset: the fused launch initialises the flags; the first of
 // `norms` does so in the fallback (mode 0), or the caller has (mode 1 throughout).
 int run_checked(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSpec>& specs, uint8_t* flags, uint32_t group,
-                uint64_t batch, uint64_t nflags, uint64_t bound, bool preset, bool sticky, std::initializer_list<NormSpec> norms) {
-  int rc = run_program_checked(c, id, var, specs, flags, group, batch, nflags, bound, preset, sticky);
+                uint64_t batch, uint64_t nflags, uint64_t bound, bool preset, bool sticky, std::initializer_list<NormSpec> norms,
+                uint32_t width) {
+  int rc = run_program_checked(c, id, var, specs, flags, group, batch, nflags, bound, preset, sticky, width);
   if (rc != RZK_E_UNSUPPORTED) return rc;
+  if (width != 8 && flags) return fail(c, RZK_E_STATE, "the norm kernels read 64-bit slabs");   // (the 32-bit entry points ask checked_fuses first)
   for (const NormSpec& n : norms) {
     if (!flags) break;
     rc = run_norm(c, n.v, n.rows, bound, flags, nflags, n.mode, n.shift, sticky);
     if (rc != RZK_OK) return rc;
   }
-  return run_program(c, id, var, specs, flags, group, batch, 0, sticky);
+  return run_program(c, id, var, specs, flags, group, batch, 0, sticky, 0, 0, nullptr, width);
 }
 
 // The scalar multipliers of a Linear / Sum call (g: one per proof; g_i: V per proof) transformed once into the form of the

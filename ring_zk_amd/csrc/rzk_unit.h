@@ -207,7 +207,7 @@ __device__ __forceinline__ bool inverse_fold_global(int pi, int np, uint32_t* ac
 // u[e] = the row's product sum mod q (coefficient e*64 + lane; zero when the row has no products): adds the sum of
 // the row's rotation terms (st_sh, left in the wave's scratch line by the same lanes), the plain additions, then
 // store / zero test, norm marks of checked additions, canonical-input test of everything loaded.
-template <int LOGN, int CHMAX = 16, class TM = WaveTeam>
+template <int LOGN, int CHMAX = 16, class TM = WaveTeam, class C = int64_t>
 __device__ __forceinline__ void finish_row(uint32_t* u, const Program* __restrict__ prog, const Row row,
                                            const Operands& ops, uint32_t b, uint32_t bo, int lane, const DevTables& T,
                                            uint8_t* __restrict__ flags, const uint32_t* __restrict__ st_sh) {
@@ -231,13 +231,13 @@ __device__ __forceinline__ void finish_row(uint32_t* u, const Program* __restric
 #pragma unroll 1
     for (uint32_t a = 0; a < row.nadds; ++a) {
       const AddTerm ad = table_load(&prog->adds[row.add0 + a]);
-      add_chunk<LOGN, CH, TM>(u + e0, ad, a, operand_ptr(ops, ad.op & ADD_OP_MASK, ad.off, b, bo, N), lane, e0, q, qhalf, trusted,
+      add_chunk<LOGN, CH, TM, C>(u + e0, ad, a, operand_ptr<C>(ops, ad.op & ADD_OP_MASK, ad.off, b, bo, N), lane, e0, q, qhalf, trusted,
                           in_bad, in_mx, add_ss);
     }
     if (row.mode == MODE_STORE) {
-      int64_t* __restrict__ dst = const_cast<int64_t*>(operand_ptr(ops, row.out_op, row.out_off, b, bo, N));
+      C* __restrict__ dst = const_cast<C*>(operand_ptr<C>(ops, row.out_op, row.out_off, b, bo, N));
 #pragma unroll
-      for (int i = 0; i < CH; ++i) st_stream(dst + G::j_p1(lane, e0 + i), center_from_zq(u[e0 + i], T.crt));
+      for (int i = 0; i < CH; ++i) st_stream(dst + G::j_p1(lane, e0 + i), (C)center_from_zq(u[e0 + i], T.crt));
     } else {
 #pragma unroll
       for (int i = 0; i < CH; ++i) nz |= (u[e0 + i] != 0);
@@ -247,13 +247,15 @@ __device__ __forceinline__ void finish_row(uint32_t* u, const Program* __restric
     if (__any(nz) && (lane & 63) == 0) flags[bo] = 0;
   }
   if (row.nadds && !trusted && canon_fail(in_bad, in_mx, qhalf)) input_fault(ops, flags, bo, lane);
-  if (ops.norm_limit) checked_add_verdicts<LOGN, TM>(prog, row, ops, b, bo, lane, add_ss, flags);
+  if (ops.norm_limit) checked_add_verdicts<LOGN, TM, C>(prog, row, ops, b, bo, lane, add_ss, flags);
 }
 
 // Workgroups: four independent one-wavefront teams (16-wave workgroups whose SIMD mates ranked each other through an LDS
 // table for exact fairness measured slower in round 2 — verify rows 90 vs 81 us — and were removed), or ONE
 // two-wavefront team (PairTeam, N = 2048).  Teams of two are compiled for 4 waves per SIMD (<= 128 VGPRs: 16
 // coefficients per thread, the budget of the N = 1024 kernels).
+// The coefficient type of the launch's slabs comes with the team (TeamCoef, rzk_wave.h): int64_t for every team of
+// rzk_kernels.hip, int32_t for WaveTeam32, which rzk_slab32_dev.hip instantiates.
 template <int LOGN, bool HAS_VEC, bool HAS_SHIFT, class TM = WaveTeam>
 __global__ void __launch_bounds__(TM::kTeamsPerBlock << TM::LL, ((LOGN <= 10 && HAS_VEC) || TM::LL == 7 ? 4 : 1))   // vector x vector variants: hold the 4 waves per SIMD the LDS allows
 unit_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__ wp, const Operands ops,
@@ -262,6 +264,7 @@ unit_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__ wp
             const uint32_t ntasks, const uint32_t units_per_task, const uint32_t tasks_per_entry,
             const uint32_t work_per_task) {
   using G = Geo<LOGN, TM::LL>;
+  using C = typename TeamCoef<TM>::type;   // coefficient type of the slabs
   constexpr int E = G::E;
   constexpr int N = G::N;
   constexpr bool OPQ = true;   // opaque lane ids: stops hoisting of lane-dependent addresses (91 vs 137 VGPRs at N = 1024)
@@ -326,7 +329,7 @@ unit_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__ wp
 #pragma unroll 1
         for (uint32_t t = 0; t < rowA.nshift; ++t) {
           const Term tm = table_load(&prog->terms[rowA.term0 + rowA.nterms + t]);
-          const int64_t* __restrict__ pa = operand_ptr(ops, tm.a_op, tm.a_off, b, bo, N);
+          const C* __restrict__ pa = operand_ptr<C>(ops, tm.a_op, tm.a_off, b, bo, N);
           int32_t a[E];
           if (trusted) {
 #pragma unroll
@@ -337,7 +340,7 @@ unit_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__ wp
             for (int e = 0; e < E; ++e) a[e] = canon_lo_mx(pa[G::j_p1(lane, e)], qhalf, abad, amx);
             fault = fault || canon_fail(abad, amx, qhalf);
           }
-          shift_product<LOGN, false, true, TM>(st_sh, t == 0, tm.sign < 0, a, operand_ptr(ops, tm.b_op, tm.b_off, b, bo, N), lane,
+          shift_product<LOGN, false, true, TM, kShiftH, C>(st_sh, t == 0, tm.sign < 0, a, operand_ptr<C>(ops, tm.b_op, tm.b_off, b, bo, N), lane,
                                            reinterpret_cast<int32_t*>(lds), T, fault, trusted);
         }
         if (fault) input_fault(ops, flags, bo, lane);
@@ -371,7 +374,7 @@ unit_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__ wp
             const bool chk = first && (im.flags & (TERM_CHECK | TERM_CHECK2));
             {
               RZK_T0();
-              load_lift<LOGN, TM>(x, operand_ptr(ops, im.b_op, im.b_off, b, bo, N), ln, pc, first, nb, chk, ops.norm_limit, below, qhalf,
+              load_lift<LOGN, TM, LL_FUSED, C>(x, operand_ptr<C>(ops, im.b_op, im.b_off, b, bo, N), ln, pc, first, nb, chk, ops.norm_limit, below, qhalf,
                               trusted, fault);
               RZK_T1(t_load);
             }
@@ -412,7 +415,7 @@ unit_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__ wp
               for (int c = 0; c < E; ++c) xb[c] = csub(mont_lazy(x[c], pc.ninv_r2, pc.p, pc.npinv), pc.p);
               float na = 0.f;
               bool unused_below = true;
-              load_lift<LOGN, TM>(x, operand_ptr(ops, im.a_op, im.a_off, b, bo, N), ln, pc, first, na, false, 0, unused_below, qhalf,
+              load_lift<LOGN, TM, LL_FUSED, C>(x, operand_ptr<C>(ops, im.a_op, im.a_off, b, bo, N), ln, pc, first, na, false, 0, unused_below, qhalf,
                               trusted, fault);
               wave_fwd<LOGN, TM>(x, ln, lds, twf, pc);
               if (first) boundA = bound_fma(na, nb, boundA);
@@ -513,7 +516,7 @@ unit_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__ wp
 #pragma unroll 1
               for (uint32_t t = 0; t < rowA.nshift; ++t) {
                 const Term tm = table_load(&prog->terms[rowA.term0 + rowA.nterms + t]);
-                const int64_t* __restrict__ pa = operand_ptr(ops, tm.a_op, tm.a_off, b, bo, N);
+                const C* __restrict__ pa = operand_ptr<C>(ops, tm.a_op, tm.a_off, b, bo, N);
                 int32_t a[E];
                 if (trusted) {
 #pragma unroll
@@ -524,7 +527,7 @@ unit_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__ wp
                   for (int e = 0; e < E; ++e) a[e] = canon_lo_mx(pa[G::j_p1(lane, e)], qhalf, abad, amx);
                   sfault = sfault || canon_fail(abad, amx, qhalf);
                 }
-                shift_product<LOGN, false, false, TM, kShiftHMem>(acc, false, tm.sign < 0, a, operand_ptr(ops, tm.b_op, tm.b_off, b, bo, N), lane,
+                shift_product<LOGN, false, false, TM, kShiftHMem, C>(acc, false, tm.sign < 0, a, operand_ptr<C>(ops, tm.b_op, tm.b_off, b, bo, N), lane,
                                                   reinterpret_cast<int32_t*>(lds), T, sfault, trusted);
               }
               if (sfault) input_fault(ops, flags, bo, lane);
@@ -533,7 +536,7 @@ unit_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__ wp
             }
             if (done) {
               RZK_T0();
-              finish_row<LOGN, 16, TM>(acc, prog, table_load(&prog->rows[r ? un.rowB : un.rowA]), ops, b, bo, lane, T, flags,
+              finish_row<LOGN, 16, TM, C>(acc, prog, table_load(&prog->rows[r ? un.rowB : un.rowA]), ops, b, bo, lane, T, flags,
                                (has_shift && !rot_last && r == 0) ? st_sh : nullptr);
               RZK_T1(t_fin);
             }
@@ -580,8 +583,8 @@ unit_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__ wp
 // faults, progress priorities, teams of one or two wavefronts — is unit_kernel's.
 // Parking lines of a team (N words each): 0 = A/p1, 1 = B/p0, 2 = B/p1, 3 = A/p2, 4 = rotation sums, 5 = B/p2.
 // =============================================================================================
-template <int LOGN, class TM = WaveTeam>
-__device__ __forceinline__ void load_measure(int32_t* v, const int64_t* __restrict__ src, int lane, bool measure, float& nrm2,
+template <int LOGN, class TM = WaveTeam, class C = int64_t>
+__device__ __forceinline__ void load_measure(int32_t* v, const C* __restrict__ src, int lane, bool measure, float& nrm2,
                                              bool check, uint64_t limit, bool& below, uint32_t qhalf, bool trusted, bool& fault) {
   using G = Geo<LOGN, TM::LL>;
   if (!measure || trusted) {
@@ -635,6 +638,7 @@ unit_io_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__
                const uint32_t ntasks, const uint32_t units_per_task, const uint32_t tasks_per_entry,
                const uint32_t work_per_task) {
   using G = Geo<LOGN, TM::LL>;
+  using C = typename TeamCoef<TM>::type;   // coefficient type of the slabs
   constexpr int E = G::E;
   constexpr int N = G::N;
   constexpr bool OPQ = true;
@@ -692,7 +696,7 @@ unit_io_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__
 #pragma unroll 1
         for (uint32_t t = 0; t < rowA.nshift; ++t) {
           const Term tm = table_load(&prog->terms[rowA.term0 + rowA.nterms + t]);
-          const int64_t* __restrict__ pa = operand_ptr(ops, tm.a_op, tm.a_off, b, bo, N);
+          const C* __restrict__ pa = operand_ptr<C>(ops, tm.a_op, tm.a_off, b, bo, N);
           int32_t a[E];
           if (trusted) {
 #pragma unroll
@@ -703,7 +707,7 @@ unit_io_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__
             for (int e = 0; e < E; ++e) a[e] = canon_lo_mx(pa[G::j_p1(lane, e)], qhalf, abad, amx);
             fault = fault || canon_fail(abad, amx, qhalf);
           }
-          shift_product<LOGN, false, true, TM>(st_sh, t == 0, tm.sign < 0, a, operand_ptr(ops, tm.b_op, tm.b_off, b, bo, N), lane,
+          shift_product<LOGN, false, true, TM, kShiftH, C>(st_sh, t == 0, tm.sign < 0, a, operand_ptr<C>(ops, tm.b_op, tm.b_off, b, bo, N), lane,
                                            reinterpret_cast<int32_t*>(lds), T, fault, trusted);
         }
         if (fault) input_fault(ops, flags, bo, lane);
@@ -714,7 +718,7 @@ unit_io_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__
 #pragma unroll
         for (int e = 0; e < E; ++e) u[e] = 0;
         RZK_STEP_PRIORITY();
-        finish_row<LOGN, 16, TM>(u, prog, rowA, ops, b, bo, lane, T, flags, has_shift ? st_sh : nullptr);
+        finish_row<LOGN, 16, TM, C>(u, prog, rowA, ops, b, bo, lane, T, flags, has_shift ? st_sh : nullptr);
         continue;
       }
       // ---- the items: pass 0 = primes 0 and 1 (operands measured), pass 1 = prime 2, only when the bound asks for it
@@ -730,7 +734,7 @@ unit_io_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__
           int ln = lane;
           RZK_OPAQUE(ln);
           const Item im = table_load(&wp->items[un.item0 + it]);
-          const int64_t* __restrict__ src = operand_ptr(ops, im.b_op, im.b_off, b, bo, N);
+          const C* __restrict__ src = operand_ptr<C>(ops, im.b_op, im.b_off, b, bo, N);
           const bool chk = pass == 0 && (im.flags & (TERM_CHECK | TERM_CHECK2));
           const bool feedsA = im.keyA != kNoKey;
           const bool feedsB = pair && last && im.keyB != kNoKey;
@@ -744,7 +748,7 @@ unit_io_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__
           if (RETAIN) {
             float nb = 0.f;
             bool below = true;
-            load_measure<LOGN, TM>(vkeep, src, ln, pass == 0, nb, chk, ops.norm_limit, below, qhalf, trusted, fault);
+            load_measure<LOGN, TM, C>(vkeep, src, ln, pass == 0, nb, chk, ops.norm_limit, below, qhalf, trusted, fault);
             if (chk && !below && (lane & 63) == 0) fail_check(flags + bo, ops.pad != 0, (im.flags & TERM_CHECK2) != 0);
             if (pass == 0) {
               if (feedsA) boundA = bound_fma((float)key_l2[im.keyA], nb, boundA);
@@ -765,7 +769,7 @@ unit_io_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__
               int32_t v[E];
               float nb = 0.f;
               bool below = true;
-              load_measure<LOGN, TM>(v, src, ln, pass == 0, nb, chk, ops.norm_limit, below, qhalf, trusted, fault);
+              load_measure<LOGN, TM, C>(v, src, ln, pass == 0, nb, chk, ops.norm_limit, below, qhalf, trusted, fault);
               if (chk && !below && (lane & 63) == 0) fail_check(flags + bo, ops.pad != 0, (im.flags & TERM_CHECK2) != 0);
               if (pass == 0) {
                 if (feedsA) boundA = bound_fma((float)key_l2[im.keyA], nb, boundA);
@@ -776,7 +780,7 @@ unit_io_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__
             } else {
               const int32_t* __restrict__ lo32 = reinterpret_cast<const int32_t*>(src);
 #pragma unroll
-              for (int e = 0; e < E; ++e) x[e] = lift(lo32[2 * G::j_p1(ln, e)], pc);
+              for (int e = 0; e < E; ++e) x[e] = lift(lo32[(int)(sizeof(C) / 4) * G::j_p1(ln, e)], pc);
             }
             // (requesting row A's key entry before the transform, as unit_kernel does, does not pay here:)
             constexpr bool EARLY = false;   // (measured at N = 512: 42.3 us against 40.4 for the verify rows; at N = 1024 the entry
@@ -888,7 +892,7 @@ unit_io_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__
             }
           }
         }
-        finish_row<LOGN, 16, TM>(u, prog, table_load(&prog->rows[r ? un.rowB : un.rowA]), ops, b, bo, lane, T, flags,
+        finish_row<LOGN, 16, TM, C>(u, prog, table_load(&prog->rows[r ? un.rowB : un.rowA]), ops, b, bo, lane, T, flags,
                                  (has_shift && r == 0) ? st_sh : nullptr);
       }
     }

@@ -35,6 +35,12 @@ __device__ __forceinline__ void st_stream(int4* p, int4 v) {
   t.x = v.x, t.y = v.y, t.z = v.z, t.w = v.w;
   __builtin_nontemporal_store(t, reinterpret_cast<v4i*>(p));
 }
+__device__ __forceinline__ void st_stream(int2* p, int2 v) {
+  typedef int v2i __attribute__((ext_vector_type(2)));
+  v2i t;
+  t.x = v.x, t.y = v.y;
+  __builtin_nontemporal_store(t, reinterpret_cast<v2i*>(p));
+}
 
 // ---- wave reductions ------------------------------------------------------------------------------------
 // Butterfly inside the 16-lane rows with DPP operand modifiers (xor 1, xor 2, half-row mirror, row mirror), then the
@@ -154,6 +160,16 @@ struct WaveTeam {
   __device__ __forceinline__ static uint64_t sum_u56(uint64_t v) { return wave_sum_u56(v); }
   __device__ __forceinline__ static uint32_t max_u32(uint32_t v) { return wave_max_u32(v); }
 };
+// One wavefront per polynomial over int32_t coefficient slabs (rzk_slab32.h): WaveTeam in everything but the element
+// type of the launch's operands.  The type travels with the team, not as a template parameter of its own, so that the
+// kernels of the 64-bit slabs keep their template arguments (and with them their symbols and profiler names), and
+// without a wrapper around a shared body (measured: inlining the body into a __global__ wrapper loses the kernel
+// arguments' restrict information and cost unit_kernel<10, false, true> 14 VGPRs and a wave per SIMD).
+struct WaveTeam32 : WaveTeam {
+  static constexpr const char* kName = "i32";
+};
+template <class TM> struct TeamCoef { using type = int64_t; };
+template <> struct TeamCoef<WaveTeam32> { using type = int32_t; };
 struct PairTeam {
   static constexpr const char* kName = "PairTeam";   // as a profiler prints it (launchers, rzk_kernels.hip)
   static constexpr int LL = 7;
