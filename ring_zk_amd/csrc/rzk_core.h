@@ -197,8 +197,57 @@ RZK_HD void lds_get_p3(uint32_t* x, int lane, const uint32_t* lds) {
   for (int c = 0; c < Geo<LOGN, LL>::E; ++c) x[c] = p[LdsMap<LOGN, LL>::off_p3(c)];
 }
 
+// ---- phase-2 twiddles as an LDS image (N = 1024, one-wavefront teams) ----------------------------------------------
+// Phase 2 of either direction reads only entries [2^LE, 2^(2 LE)) of a prime's table: stage sp takes the 2^sp entries
+// 2^(LE+sp) + (hi << sp) + k.  At LE = 4 these are the 240 entries 16 .. 255, and a lane needs 1 + 2 + 4 + 8 = 15 of them.
+// A workgroup keeps them in LDS, re-ordered so that ONE per-lane base (16 bytes x hi) plus compile-time offsets addresses
+// all of them with four 16-byte reads:
+//     block 0 (words   0 ..  63): [hi][4] = { stage 0, pad, stage 1 k = 0, stage 1 k = 1 }
+//     block 1 (words  64 .. 127): [hi][4] =   stage 2 k = 0 .. 3
+//     block 2 (words 128 .. 191): [hi][4] =   stage 3 k = 0 .. 3
+//     block 3 (words 192 .. 255): [hi][4] =   stage 3 k = 4 .. 7
+// 256 words per table (16 pads), 2 kMaxPrimes tables.  Bank picture (ds_read_b128: banks (addr / 4) mod 64, four groups of
+// 16 lanes): hi = lane & 15, so every group holds each hi exactly once and its 16 lanes read the 16 consecutive 16-byte slots
+// of one 64-word block: every bank once, conflict-free; lanes of different groups with equal hi read the same words.
+// (Entries in table order, stage 3 at 8 hi + k, would put hi and hi + 8 on the same banks: 2-way.)  The compiler narrows
+// the read of block 0, whose pad nothing uses, to ds_read_b32 + ds_read_b64: the b64 (banks mod 64, 32-lane halves, each hi
+// twice at one address) is conflict-free, the b32 (banks mod 32: hi and hi + 8 on one bank) 2-way, one extra LDS cycle per half.
+template <int LOGN, int LL = 6>
+struct Tw2Img {
+  using G = Geo<LOGN, LL>;
+  static constexpr bool kFits = LL == 6 && G::LE == 4;   // the layout above
+  static constexpr int FIRST = 1 << G::LE, END = 1 << (2 * G::LE);   // table entries phase 2 may touch: [FIRST, END)
+  static constexpr int WORDS = 256;                       // per table
+  static constexpr int TABLES = 2 * kMaxPrimes;           // [prime][forward, inverse], the order of the global tables
+  RZK_HD static int base(int hi) { return hi << 2; }
+  // register slot (= word inside the lane's four quads, in block order) of twiddle k of stage sp
+  static constexpr int slot(int sp, int k) { return sp == 0 ? 0 : (sp == 1 ? 2 + k : (sp == 2 ? 4 + k : 8 + k)); }
+  // table entry that image word w holds: what the kernels' fill loop copies.  A pad holds entry 0, which lies outside
+  // [FIRST, END) and is never read (a copy like every other word: no branch in the fill loop).
+  RZK_HD static int src(int w) {
+    const int blk = w >> 6, hi = (w >> 2) & 15, c = w & 3;
+    if (blk == 0) return c == 0 ? (1 << G::LE) + hi : (c == 1 ? 0 : (1 << (G::LE + 1)) + (hi << 1) + (c - 2));
+    if (blk == 1) return (1 << (G::LE + 2)) + (hi << 2) + c;
+    return (1 << (G::LE + 3)) + (hi << 3) + ((blk - 2) << 2) + c;
+  }
+  // the lane's 16 words (15 twiddles): four 16-byte reads at compile-time offsets from one base
+  RZK_HD static void load(uint32_t* w, const uint32_t* img, int hi) {
+    const uint32_t* row = img + base(hi);
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+      const uint4 v = *reinterpret_cast<const uint4*>(row + 64 * b);
+      w[4 * b] = v.x, w[4 * b + 1] = v.y, w[4 * b + 2] = v.z, w[4 * b + 3] = v.w;
+#else
+      for (int c = 0; c < 4; ++c) w[4 * b + c] = row[64 * b + c];
+#endif
+    }
+  }
+};
+
 // ---- forward transform, register phases ----------------------------------------------------------------
 // tw: Montgomery-form table, tw[m + i] = psi^{bitrev(m+i)} * R mod p (first N entries used).
+// Phase 2 takes its table through a pointer of its own: the global table (IMG = false), or the prime's Tw2Img image.
 template <int LOGN, int LL = 6>
 RZK_HD void fwd_phase1(uint32_t* x, const uint32_t* tw, const PrimeConsts& pc) {
   using G = Geo<LOGN, LL>;
@@ -213,10 +262,14 @@ RZK_HD void fwd_phase1(uint32_t* x, const uint32_t* tw, const PrimeConsts& pc) {
     }
   }
 }
-template <int LOGN, int LL = 6>
+template <int LOGN, int LL = 6, bool IMG = false>
 RZK_HD void fwd_phase2(uint32_t* x, int lane, const uint32_t* tw, const PrimeConsts& pc) {
   using G = Geo<LOGN, LL>;
+  using I = Tw2Img<LOGN, LL>;
+  static_assert(!IMG || I::kFits, "the LDS image is laid out for N = 1024 on one wavefront");
   const int hi = G::p2_hi(lane);
+  uint32_t wi[16];
+  if (IMG) I::load(wi, tw, hi);
 #pragma unroll
   for (int sp = 0; sp < G::LE; ++sp) {
     const int half = G::E >> (sp + 1);
@@ -224,7 +277,7 @@ RZK_HD void fwd_phase2(uint32_t* x, int lane, const uint32_t* tw, const PrimeCon
 #pragma unroll
     for (int r = 0; r < G::E; ++r) {
       if (r & half) continue;
-      bfly_fwd(x[r], x[r + half], twl[r >> (G::LE - sp)], pc);
+      bfly_fwd(x[r], x[r + half], IMG ? wi[I::slot(sp, r >> (G::LE - sp)) & 15] : twl[r >> (G::LE - sp)], pc);
     }
   }
 }
@@ -260,10 +313,14 @@ RZK_HD void inv_phase3(uint32_t* x, int lane, const uint32_t* tw, const PrimeCon
     }
   }
 }
-template <int LOGN, int LL = 6>
+template <int LOGN, int LL = 6, bool IMG = false>
 RZK_HD void inv_phase2(uint32_t* x, int lane, const uint32_t* tw, const PrimeConsts& pc) {
   using G = Geo<LOGN, LL>;
+  using I = Tw2Img<LOGN, LL>;
+  static_assert(!IMG || I::kFits, "the LDS image is laid out for N = 1024 on one wavefront");
   const int hi = G::p2_hi(lane);
+  uint32_t wi[16];
+  if (IMG) I::load(wi, tw, hi);
 #pragma unroll
   for (int sp = G::LE - 1; sp >= 0; --sp) {
     const int half = G::E >> (sp + 1);
@@ -271,7 +328,7 @@ RZK_HD void inv_phase2(uint32_t* x, int lane, const uint32_t* tw, const PrimeCon
 #pragma unroll
     for (int r = 0; r < G::E; ++r) {
       if (r & half) continue;
-      bfly_inv(x[r], x[r + half], twl[r >> (G::LE - sp)], pc);
+      bfly_inv(x[r], x[r + half], IMG ? wi[I::slot(sp, r >> (G::LE - sp)) & 15] : twl[r >> (G::LE - sp)], pc);
     }
   }
 }

@@ -59,14 +59,15 @@ static int with_logn(int logn, F&& f) {
 // (team_arg) by every kernel but row_kernel, which always names its team.
 static const char* tf(bool v) { return v ? "true" : "false"; }
 template <class TM>
-static std::string team_arg() {
-  return std::is_same<TM, WaveTeam>::value ? std::string() : std::string(", ") + TM::kName;
+static std::string team_arg() {   // (the teams with the twiddle image report as the teams they derive from)
+  return std::is_same<TM, WaveTeam>::value || std::is_same<TM, WaveTeamTw>::value ? std::string() : std::string(", ") + TM::kName;
 }
 
 size_t row_scratch_words(int logn, int num_cus) { return (size_t)num_cus * 8 * 4 * (((size_t)kScratchLines << logn) + 16); }
 
 // LDS words of one team in unit_kernel / row_kernel: transposition slab + one N-word buffer; a rotation term's image
-// (2N words) fits inside that, the non-zero list of a two-wavefront team comes on top
+// (2N words) fits inside that, the non-zero list of a two-wavefront team comes on top.  Teams with the phase-2 twiddles in
+// LDS (TeamTwLds) share one set of images per workgroup behind the teams' buffers: block_tw_words.
 template <int LOGN, class TM, bool HAS_SHIFT>
 constexpr size_t team_lds_words() {
   using G = Geo<LOGN, TM::LL>;
@@ -76,14 +77,25 @@ constexpr size_t team_lds_words() {
   return (((base > rot ? base : rot) + 3) / 4) * 4;
 }
 
+template <int LOGN, class TM>
+constexpr size_t block_tw_words() {
+  return TeamTwLds<TM>::value ? (size_t)Tw2Img<LOGN, TM::LL>::TABLES * Tw2Img<LOGN, TM::LL>::WORDS : 0;
+}
+// N = 1024, four one-wavefront teams: 4 x 8 320 + 6 144 = 39 424 bytes, four workgroups (4 waves per SIMD) in 157 696 of the
+// CU's 163 840
+static_assert(4 * (WaveTeamTw::kTeamsPerBlock * team_lds_words<10, WaveTeamTw, true>() + block_tw_words<10, WaveTeamTw>()) * sizeof(uint32_t) <= 160 * 1024,
+              "the twiddle images must leave room for four workgroups per CU");
+
 template <int LOGN, bool HAS_VEC, bool HAS_SHIFT, class TM = WaveTeam>
 static int launch_units_t(const LaunchCfg& cfg, const Program* d_prog, const WaveProgram* d_wp, const Operands& ops,
                           const uint32_t* d_key_ntt, const double* d_key_l2, const DevTables* T, const uint32_t* d_tw,
                           uint32_t* d_scratch, uint8_t* d_flags, uint32_t ntasks, uint32_t upt, uint32_t tpe, uint32_t wpt) {
   using G = Geo<LOGN, TM::LL>;
   constexpr int TPB = TM::kTeamsPerBlock;
-  // per team: transposition slab + P
-  const size_t lds = TPB * team_lds_words<LOGN, TM, HAS_SHIFT>() * sizeof(uint32_t);
+  // per team: transposition slab + P; per workgroup: the twiddle images
+  const size_t lds = (TPB * team_lds_words<LOGN, TM, HAS_SHIFT>() + block_tw_words<LOGN, TM>()) * sizeof(uint32_t);
+  static_assert(!TeamTwLds<TM>::value || team_lds_words<LOGN, TM, HAS_SHIFT>() == (size_t)(G::LDS_WORDS + G::N),
+                "unit_kernel puts the images right behind the teams' slab + P");
   if (lds > 48 * 1024) {   // large dynamic LDS needs an opt-in; per device, so set before every launch (cheap, idempotent)
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&unit_kernel<LOGN, HAS_VEC, HAS_SHIFT, TM>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -184,6 +196,11 @@ int launch_units(int logn, const LaunchCfg& cfg, const Program* d_prog, const Wa
         return cfg.pair_poly ? launch_units_io_t<11, false, PairTeam>(RZK_UNIT_ARGS) : launch_units_io_t<11, false>(RZK_UNIT_ARGS);
     }
     return -1;
+  }
+  if (logn == 10 && cfg.tw_lds) {   // phase-2 twiddles from LDS (RZK_TW_LDS): N = 1024, one-wavefront teams
+    if (has_shift)
+      return has_vec ? launch_units_t<10, true, true, WaveTeamTw>(RZK_UNIT_ARGS) : launch_units_t<10, false, true, WaveTeamTw>(RZK_UNIT_ARGS);
+    return has_vec ? launch_units_t<10, true, false, WaveTeamTw>(RZK_UNIT_ARGS) : launch_units_t<10, false, false, WaveTeamTw>(RZK_UNIT_ARGS);
   }
 #define RZK_UNIT_CASE(L)                                                                                            \
   case L:                                                                                                           \

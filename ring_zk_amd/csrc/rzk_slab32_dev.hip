@@ -73,14 +73,16 @@ struct UnitArgs {
   uint32_t ntasks, upt, tpe, wpt;
 };
 
-template <int LOGN, bool HAS_SHIFT>
+template <int LOGN, bool HAS_SHIFT, class TM = WaveTeam32>
 int launch_units32_t(const LaunchCfg& cfg, const Operands& ops, const UnitArgs& a) {
   using G = Geo<LOGN, 6>;
   constexpr int TPB = WaveTeam::kTeamsPerBlock;
-  const size_t lds = TPB * (size_t)(((G::LDS_WORDS + G::N + 3) / 4) * 4) * sizeof(uint32_t);   // per team: transposition slab + P
-  static_assert(TPB * (((G::LDS_WORDS + G::N + 3) / 4) * 4) * 4 <= 48 * 1024, "no opt-in for large dynamic LDS needed");
+  // per team: transposition slab + P; per workgroup of a team with the phase-2 twiddles in LDS (TeamTwLds): the images
+  constexpr size_t kTwWords = TeamTwLds<TM>::value ? (size_t)Tw2Img<LOGN, 6>::TABLES * Tw2Img<LOGN, 6>::WORDS : 0;
+  const size_t lds = (TPB * (size_t)(((G::LDS_WORDS + G::N + 3) / 4) * 4) + kTwWords) * sizeof(uint32_t);
+  static_assert((TPB * (((G::LDS_WORDS + G::N + 3) / 4) * 4) + kTwWords) * 4 <= 48 * 1024, "no opt-in for large dynamic LDS needed");
   const unsigned grid = grid_for(a.ntasks, cfg.num_cus, TPB, 32 / TPB);
-  hipLaunchKernelGGL((unit_kernel<LOGN, false, HAS_SHIFT, WaveTeam32>), dim3(grid), dim3(TPB << 6), lds, (hipStream_t)cfg.stream, a.d_prog, a.d_wp, ops,
+  hipLaunchKernelGGL((unit_kernel<LOGN, false, HAS_SHIFT, TM>), dim3(grid), dim3(TPB << 6), lds, (hipStream_t)cfg.stream, a.d_prog, a.d_wp, ops,
                      a.d_key_ntt, a.d_key_l2, a.T, a.d_tw, a.d_scratch, a.d_flags, a.ntasks, a.upt, a.tpe, a.wpt);
   RZK_LAUNCH_CHECK();
   if (cfg.launched) *cfg.launched = "unit_kernel<" + std::to_string(LOGN) + ", false, " + tf(HAS_SHIFT) + ", i32>";
@@ -147,7 +149,9 @@ int launch_units32(int logn, const LaunchCfg& cfg, const Program* d_prog, const 
   }
   switch (logn) {
     case 9: return has_shift ? launch_units32_t<9, true>(cfg, ops, a) : launch_units32_t<9, false>(cfg, ops, a);
-    case 10: return has_shift ? launch_units32_t<10, true>(cfg, ops, a) : launch_units32_t<10, false>(cfg, ops, a);
+    case 10:
+      if (cfg.tw_lds) return has_shift ? launch_units32_t<10, true, WaveTeam32Tw>(cfg, ops, a) : launch_units32_t<10, false, WaveTeam32Tw>(cfg, ops, a);
+      return has_shift ? launch_units32_t<10, true>(cfg, ops, a) : launch_units32_t<10, false>(cfg, ops, a);
   }
   return -1;   // (slab32_native, rzk_slab32.h: every other shape takes the convert path)
 }

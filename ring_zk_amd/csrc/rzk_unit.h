@@ -108,7 +108,7 @@ template <int LOGN, bool OPQ, class TM = WaveTeam>
 __device__ __forceinline__ bool inverse_fold_global(int pi, int np, uint32_t* acc, int lane, uint32_t* lds,
                                                     const uint32_t* __restrict__ twi, const PrimeConsts& pc,
                                                     uint32_t* __restrict__ stA, uint32_t* __restrict__ stB,
-                                                    const DevTables& T) {
+                                                    const DevTables& T, const uint32_t* __restrict__ tw2i = nullptr) {
   using G = Geo<LOGN, TM::LL>;
   constexpr int E = G::E;
   int li = lane;
@@ -127,7 +127,7 @@ __device__ __forceinline__ bool inverse_fold_global(int pi, int np, uint32_t* ac
 #pragma unroll
     for (int g = 0; g < E / 4; ++g) sb[g] = B4[G::own4(li, g)];
   }
-  wave_inv<LOGN, TM>(acc, li, lds, twi, pc);
+  wave_inv<LOGN, TM, TeamTwLds<TM>::value>(acc, li, lds, twi, pc, tw2i);
   if (!EARLY && pi >= 1) {
 #pragma unroll
     for (int g = 0; g < E / 4; ++g) sa[g] = A4[G::own4(li, g)];
@@ -274,6 +274,21 @@ unit_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__ wp
   constexpr int WPB = TM::kTeamsPerBlock;
   uint32_t* lds = smem + wave * (G::LDS_WORDS + N);             // transposition slab, then P
   uint4* P4 = reinterpret_cast<uint4*>(lds + G::LDS_WORDS);     // G::LDS_WORDS * 4 is a multiple of 16 bytes
+  // Teams with the phase-2 twiddles in LDS (TeamTwLds): the images of every prime and direction lie behind the teams'
+  // slabs, are copied from the global tables once per workgroup, and are read-only from the barrier on, over every
+  // grid-stride trip.  Nothing else in the kernel meets at a workgroup barrier: the teams stay independent.
+  constexpr bool TWL = TeamTwLds<TM>::value;
+  using TWI = Tw2Img<LOGN, TM::LL>;
+  const uint32_t* tw2_img = smem + WPB * (G::LDS_WORDS + N);
+  if (TWL) {
+    static_assert(!TWL || (TWI::kFits && WPB * (G::LDS_WORDS + N) % 4 == 0 && (WPB << TM::LL) == TWI::WORDS),
+                  "one image word per thread and table, 16-byte aligned behind the slabs");
+    const int src = TWI::src((int)threadIdx.x);
+#pragma unroll
+    for (int t = 0; t < TWI::TABLES; ++t)
+      smem[WPB * (G::LDS_WORDS + N) + t * TWI::WORDS + threadIdx.x] = tw_all[(size_t)t * kTableLen + src];
+    __syncthreads();
+  }
   // per-wave global scratch: Garner words [row A | B][word A | B][N], then the sum of row A's rotation terms
   uint32_t* st = scratch + ((size_t)blockIdx.x * WPB + wave) * (size_t)(kScratchLines * N + 16);
   uint32_t* st_sh = st + 4 * N;
@@ -354,6 +369,7 @@ unit_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__ wp
       for (int pi = 0; pi < np; ++pi) {
         const PrimeConsts pc = T.pc[pi];
         const uint32_t* __restrict__ twf = tw_all + (size_t)(2 * pi) * kTableLen;
+        const uint32_t* __restrict__ tw2f = tw2_img + (2 * pi) * TWI::WORDS;   // (TWL) forward image, then the inverse one
         const bool first = pi == 0;
         bool fault = false;
 #pragma unroll 1
@@ -399,7 +415,7 @@ unit_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__ wp
             }
             {
               RZK_T0();
-              wave_fwd<LOGN, TM>(x, ln, lds, twf, pc);
+              wave_fwd<LOGN, TM, TWL>(x, ln, lds, twf, pc, tw2f);
               RZK_T1(t_fwd);
             }
             if (!EARLY && want_key) {
@@ -417,7 +433,7 @@ unit_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__ wp
               bool unused_below = true;
               load_lift<LOGN, TM, LL_FUSED, C>(x, operand_ptr<C>(ops, im.a_op, im.a_off, b, bo, N), ln, pc, first, na, false, 0, unused_below, qhalf,
                               trusted, fault);
-              wave_fwd<LOGN, TM>(x, ln, lds, twf, pc);
+              wave_fwd<LOGN, TM, TWL>(x, ln, lds, twf, pc, tw2f);
               if (first) boundA = bound_fma(na, nb, boundA);
             } else if (first) {
               if (im.keyA != kNoKey) boundA = bound_fma((float)key_l2[im.keyA], nb, boundA);
@@ -507,7 +523,7 @@ unit_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__ wp
             if (!null_unit) {
               RZK_T0();
               done = inverse_fold_global<LOGN, OPQ, TM>(pi, np, acc, lane, lds, twf + kTableLen, pc, st + (size_t)(2 * r) * N,
-                                                    st + (size_t)(2 * r + 1) * N, T);
+                                                    st + (size_t)(2 * r + 1) * N, T, tw2f + TWI::WORDS);
               RZK_T1(t_inv);
             }
             if (done && rot_last) {   // (a single row: r == 0) acc[e] is the value of coefficient e*64 + lane, the register layout of the rotations

@@ -170,6 +170,15 @@ struct WaveTeam32 : WaveTeam {
 };
 template <class TM> struct TeamCoef { using type = int64_t; };
 template <> struct TeamCoef<WaveTeam32> { using type = int32_t; };
+// The same two teams with the phase-2 twiddles of their transforms in an LDS image behind the workgroup's slabs (Tw2Img,
+// rzk_core.h; N = 1024, RZK_TW_LDS).  Like the coefficient type, the switch travels with the team: the kernels of the
+// global-table path keep their template arguments and symbols, and the launchers report both under the same name.
+struct WaveTeamTw : WaveTeam {};
+struct WaveTeam32Tw : WaveTeam32 {};
+template <> struct TeamCoef<WaveTeam32Tw> { using type = int32_t; };
+template <class TM> struct TeamTwLds { static constexpr bool value = false; };
+template <> struct TeamTwLds<WaveTeamTw> { static constexpr bool value = true; };
+template <> struct TeamTwLds<WaveTeam32Tw> { static constexpr bool value = true; };
 struct PairTeam {
   static constexpr const char* kName = "PairTeam";   // as a profiler prints it (launchers, rzk_kernels.hip)
   static constexpr int LL = 7;
@@ -265,16 +274,17 @@ struct BlockPairTeam {
   }
 };
 
-template <int LOGN, class TM = WaveTeam>
+// tw2: the table phase 2 reads.  Left out, it is the global table tw; with IMG it is the prime's LDS image (Tw2Img).
+template <int LOGN, class TM = WaveTeam, bool IMG = false>
 __device__ __forceinline__ void wave_fwd(uint32_t* x, int lane, uint32_t* lds, const uint32_t* __restrict__ tw,
-                                         const PrimeConsts& pc) {
+                                         const PrimeConsts& pc, const uint32_t* __restrict__ tw2 = nullptr) {
   constexpr int LL = TM::LL;
   fwd_phase1<LOGN, LL>(x, tw, pc);
   lds_put_p1<LOGN, LL>(x, lane, lds);
   TM::sync();
   lds_get_p2<LOGN, LL>(x, lane, lds);
   TM::sync();
-  fwd_phase2<LOGN, LL>(x, lane, tw, pc);
+  fwd_phase2<LOGN, LL, IMG>(x, lane, IMG ? tw2 : tw, pc);
   lds_put_p2<LOGN, LL>(x, lane, lds);
   TM::sync();
   lds_get_p3<LOGN, LL>(x, lane, lds);
@@ -282,16 +292,16 @@ __device__ __forceinline__ void wave_fwd(uint32_t* x, int lane, uint32_t* lds, c
   fwd_phase3<LOGN, LL>(x, lane, tw, pc);
 }
 
-template <int LOGN, class TM = WaveTeam>
+template <int LOGN, class TM = WaveTeam, bool IMG = false>
 __device__ __forceinline__ void wave_inv(uint32_t* x, int lane, uint32_t* lds, const uint32_t* __restrict__ tw,
-                                         const PrimeConsts& pc) {
+                                         const PrimeConsts& pc, const uint32_t* __restrict__ tw2 = nullptr) {
   constexpr int LL = TM::LL;
   inv_phase3<LOGN, LL>(x, lane, tw, pc);
   lds_put_p3<LOGN, LL>(x, lane, lds);
   TM::sync();
   lds_get_p2<LOGN, LL>(x, lane, lds);
   TM::sync();
-  inv_phase2<LOGN, LL>(x, lane, tw, pc);
+  inv_phase2<LOGN, LL, IMG>(x, lane, IMG ? tw2 : tw, pc);
   lds_put_p2<LOGN, LL>(x, lane, lds);
   TM::sync();
   lds_get_p1<LOGN, LL>(x, lane, lds);

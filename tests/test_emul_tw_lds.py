@@ -1,0 +1,49 @@
+"""CPU statement of the phase-2 twiddle image of the N = 1024 unit kernels (Tw2Img, ring_zk_amd/csrc/rzk_core.h; RZK_TW_LDS).
+
+tests/emul/tw_lds_driver.cpp is a stand-alone program over the header the kernels compile:
+  * it builds the image of every prime and direction as the kernels' fill loop does, each in an allocation of its own;
+  * every index phase 2 forms lies in [16, 256), the image word it reads holds exactly that table entry, and the image
+    holds every entry of [16, 256) once;
+  * all 64 lanes of the forward and inverse transforms at LOGN = 10, phase 2 reading the image, equal the run on the
+    global table word for word: three primes, seeded random polynomials over the lazy ranges and the all-maximum one.
+It is built twice, optimised and under -fsanitize=address,undefined as that stand-alone program.  Host logic testing: no
+GPU, and the product never loads this program.
+"""
+import os
+import subprocess
+
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+SRC = os.path.join(HERE, "emul", "tw_lds_driver.cpp")
+BUILDS = {
+    "O2": ["-O2"],
+    "sanitized": ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"],
+}
+
+
+@pytest.fixture(scope="module", params=sorted(BUILDS))
+def report(request, tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("tw_lds_" + request.param) / "tw_lds_driver")
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wno-unknown-pragmas"] + BUILDS[request.param] + ["-o", exe, SRC])
+    p = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    return p.returncode, p.stdout.splitlines(), p.stderr
+
+
+def test_every_case_matches(report):
+    code, lines, err = report
+    assert code == 0 and lines and lines[-1] == "all cases passed", "\n".join(lines) + err
+    assert not [l for l in lines if l.startswith("FAIL")]
+    assert "runtime error" not in err and "AddressSanitizer" not in err
+
+
+def test_the_cases_the_image_is_checked_on(report):
+    _, lines, _ = report
+    assert any(l.startswith("ok   image holds entries 16..255 once each") for l in lines)
+    idx = [l for l in lines if l.startswith("ok   phase-2 indices inside [16, 256)")]
+    assert len(idx) == 1 and int(idx[0].rsplit(":", 1)[1].split()[0]) == 64 * 6 * 15   # lanes x tables x twiddles per lane
+    for pi in range(3):
+        for what in ("forward, image against global table", "inverse, image against global table",
+                     "inverse(forward(x)) == x through the image"):
+            hit = [l for l in lines if l.startswith("ok   prime %d %s" % (pi, what))]
+            assert len(hit) == 1 and int(hit[0].rsplit(":", 1)[1].split()[0]) == 5 * 1024
