@@ -217,7 +217,7 @@ struct Operands {
   int8_t oimg_col[32];   // column of the vector -> image index, or -1
 };
 
-// ---- launchers (defined in rzk_kernels.hip) --------------------------------------------------------------------
+// ---- launchers (defined in rzk_kernels.hip; their shared launch rules: rzk_launch.h) ----------------------------
 struct LaunchCfg {
   void* stream;   // hipStream_t
   int num_cus;
@@ -228,37 +228,48 @@ struct LaunchCfg {
   std::string* launched = nullptr;   // out: the row-program launchers write the name of the instantiation they started here
 };
 
+// The device pointers of a row-program launch: run_program (rzk_run.cpp) fills one per call, only `scratch` differs per path.
+struct RowArgs {
+  const Program* prog;
+  const WaveProgram* wp;      // the unit kernels' view of the program (NULL for a program planned without one)
+  const uint32_t* key_ntt;    // resident key images and their 2-norms
+  const double* key_l2;
+  const DevTables* T;
+  const uint32_t* tw;         // twiddle tables
+  uint32_t* scratch;          // the path's global scratch lines (row_scratch_words / group_scratch_words / block_scratch_words)
+  uint8_t* flags;             // verdict flags, or NULL
+};
+// What the unit kernels' launchers need to know of the planned program.
 // units_per_task: how many consecutive units of one batch entry a wavefront evaluates back to back (all of them =
 // one wavefront per proof: equal-cost tasks, no tail)
-// row_kernel: one wavefront per (batch entry, row); programs with vector x vector products
-int launch_rows(int logn, const LaunchCfg& cfg, const Program* d_prog, uint32_t nrows, bool has_shift, const Operands& ops,
-                const uint32_t* d_key_ntt, const double* d_key_l2, const DevTables* d_T, const uint32_t* d_tw,
-                uint32_t* d_scratch, uint8_t* d_flags, uint64_t batch, bool has_dd = false);
 // work_per_entry: transforms one batch entry costs at two primes (the progress priorities only need an estimate)
-int launch_units(int logn, const LaunchCfg& cfg, const Program* d_prog, const WaveProgram* d_wp, uint32_t nunits,
-                 uint32_t units_per_task, uint32_t work_per_entry, bool has_vec, bool has_shift, const Operands& ops,
-                 const uint32_t* d_key_ntt, const double* d_key_l2, const DevTables* d_T, const uint32_t* d_tw,
-                 uint32_t* d_scratch, uint8_t* d_flags, uint64_t batch);
-int launch_row_program_slots(int logn, const LaunchCfg& cfg, const Program* d_prog, const SlotTable* d_slots,
-                             uint32_t nslots, const Operands& ops, const uint32_t* d_key_ntt,
-                             const double* d_key_l2, const DevTables* d_T, const uint32_t* d_tw, uint32_t* d_ws,
-                             double* d_norms, uint32_t* d_scratch, uint8_t* d_flags, uint64_t batch,
-                             uint32_t np_store);
-int launch_row_groups(int logn, const LaunchCfg& cfg, const Program* d_prog, uint32_t ngroups, const Operands& ops,
-                      const uint32_t* d_key_ntt, const double* d_key_l2, const DevTables* d_T, const uint32_t* d_tw,
-                      uint32_t* d_scratch, uint8_t* d_flags, uint64_t batch);
+struct UnitShape {
+  uint32_t nunits, units_per_task, work_per_entry;
+  bool has_vec, has_shift;
+};
+// The shared-operand path's workspace of stored transforms (np_store primes each) and their norms
+struct SlotStore {
+  uint32_t* ws;
+  double* norms;
+  uint32_t np_store;
+};
+// row_kernel: one wavefront per (batch entry, row); programs with vector x vector products
+int launch_rows(int logn, const LaunchCfg& cfg, const RowArgs& a, const Operands& ops, uint32_t nrows, bool has_shift, uint64_t batch,
+                bool has_dd = false);
+int launch_units(int logn, const LaunchCfg& cfg, const RowArgs& a, const Operands& ops, const UnitShape& u, uint64_t batch);
+int launch_row_program_slots(int logn, const LaunchCfg& cfg, const RowArgs& a, const Operands& ops, const SlotTable* d_slots,
+                             uint32_t nslots, const SlotStore& st, uint64_t batch);
+int launch_row_groups(int logn, const LaunchCfg& cfg, const RowArgs& a, const Operands& ops, uint32_t ngroups, uint64_t batch);
 size_t group_scratch_words(int logn, int num_cus);
-int launch_row_blocks(int logn, const LaunchCfg& cfg, const Program* d_prog, const BlockPlan* d_plan, uint32_t nblocks,
-                      const Operands& ops, const uint32_t* d_key_ntt, const double* d_key_l2, const DevTables* d_T,
-                      const uint32_t* d_tw, uint32_t* d_scratch, uint8_t* d_flags, uint64_t batch);
+int launch_row_blocks(int logn, const LaunchCfg& cfg, const RowArgs& a, const Operands& ops, const BlockPlan* d_plan, uint32_t nblocks,
+                      uint64_t batch);
 size_t block_scratch_words(int logn, int num_cus);
-// rows whose products all have a sparse multiplier (the challenge) as `a` operand: shift-add kernel, no transforms
 // images of `count` scalar multipliers (dkey_n per batch entry) for TERM_DKEY terms; flags / bad as in Operands
 int launch_dkey_transform(int logn, const LaunchCfg& cfg, const int64_t* g, uint64_t count, uint32_t dkey_n, uint32_t* img,
                           double* l2, const DevTables* T, const uint32_t* d_tw, uint8_t* d_flags, uint32_t* d_bad, bool two_bit,
                           bool trusted);
-int launch_shift_rows(int logn, const LaunchCfg& cfg, const Program* d_prog, uint32_t nrows, const Operands& ops,
-                      const DevTables* d_T, uint8_t* d_flags, uint64_t batch);
+// rows whose products all have a sparse multiplier (the challenge) as `a` operand: shift-add kernel, no transforms
+int launch_shift_rows(int logn, const LaunchCfg& cfg, const RowArgs& a, const Operands& ops, uint32_t nrows, uint64_t batch);
 // Rows per group of row_group_kernel.  Two numbers, on purpose:
 //   group_accumulators  how many accumulators (= rows per group, at most kGroupMax) the instantiation launched for this
 //                       size is COMPILED with: 4 at N <= 1024, 2 at N = 2048;
@@ -366,17 +377,13 @@ struct ResponseStat {   // where a launch of response_stat_kernel leaves its par
 // The rows of a PG_RESPONSE program (rzk_plan.h) as launch_shift_rows runs them, one wavefront per row, N = 512 / 1024 only
 // (-1 otherwise); the partial of row `rowi` of batch entry b goes to part[(b / group) * rows_total + part_off +
 // (b mod group) * nrows + rowi], group = Operands::group.
-int launch_response_stat(int logn, const LaunchCfg& cfg, const Program* d_prog, uint32_t nrows, const Operands& ops,
-                         const DevTables* d_T, uint64_t batch, const ResponseStat& so);
+int launch_response_stat(int logn, const LaunchCfg& cfg, const RowArgs& a, const Operands& ops, uint32_t nrows, uint64_t batch,
+                         const ResponseStat& so);
 // ---- 32-bit coefficient slabs (rzk_slab32_dev.hip; format and routing in rzk_slab32.h) ------------------
 // launch_units / launch_shift_rows for a launch whose Operands::base address int32_t slabs: key-product programs, one-wavefront
 // teams, N = 512 / 1024, the packed-byte rotation kernel (-1 otherwise: the caller converts, slab32_native)
-int launch_units32(int logn, const LaunchCfg& cfg, const Program* d_prog, const WaveProgram* d_wp, uint32_t nunits,
-                   uint32_t units_per_task, uint32_t work_per_entry, bool has_shift, const Operands& ops,
-                   const uint32_t* d_key_ntt, const double* d_key_l2, const DevTables* d_T, const uint32_t* d_tw,
-                   uint32_t* d_scratch, uint8_t* d_flags, uint64_t batch);
-int launch_shift_rows32(int logn, const LaunchCfg& cfg, const Program* d_prog, uint32_t nrows, const Operands& ops,
-                        const DevTables* d_T, uint8_t* d_flags, uint64_t batch);
+int launch_units32(int logn, const LaunchCfg& cfg, const RowArgs& a, const Operands& ops, const UnitShape& u, uint64_t batch);
+int launch_shift_rows32(int logn, const LaunchCfg& cfg, const RowArgs& a, const Operands& ops, uint32_t nrows, uint64_t batch);
 // out = the low words of in (bad_word != NULL: a non-canonical coefficient sets it); out = in sign-extended.  ncoef even,
 // both slabs 16-byte aligned
 int launch_narrow(const LaunchCfg& cfg, const int64_t* in, int32_t* out, uint64_t ncoef, uint32_t qhalf, uint32_t* bad_word);

@@ -17,20 +17,12 @@
 #include "rzk_dev.h"
 #include "rzk_reject.h"
 #include "rzk_rowprog.h"
+#include "rzk_launch.h"   // (templates only: this file instantiates none of the kernels it names)
 
 namespace rzk {
 
-#define RZK_LAUNCH_CHECK()                      \
-  do {                                          \
-    hipError_t e_ = hipGetLastError();          \
-    if (e_ != hipSuccess) return (int)e_;       \
-  } while (0)
-
 namespace {
 
-#ifndef RZK_SHIFT_BYTES_WAVES
-#define RZK_SHIFT_BYTES_WAVES 4   // as rzk_row.h: waves per SIMD the packed-byte instantiations are compiled and launched for
-#endif
 constexpr int kTeams = 4;   // wavefronts per workgroup, one 8 N-byte image each (ShiftCfg<LOGN, WaveTeam>)
 
 template <int LOGN, bool TRUSTED, bool BYTES>
@@ -140,36 +132,31 @@ response_stat_kernel(const Program* __restrict__ prog, const Operands ops, const
 }
 
 template <int LOGN, bool BYTES>
-int launch_t(const LaunchCfg& cfg, const Program* d_prog, const Operands& ops, const DevTables* T, uint32_t ntasks,
-             const ResponseStat& so) {
-  // the LDS request and the grid of launch_shift_t (rzk_kernels.hip): one 8 N-byte image per wavefront, at least 40 KiB
-  // per workgroup at N = 1024 so that a CU holds four workgroups = 4 waves per SIMD; 16 workgroups per CU under the cap
-  size_t lds = (size_t)kTeams * ShiftGeo<LOGN, true, 6>::WORDS * sizeof(uint32_t);
-  if ((!BYTES || RZK_SHIFT_BYTES_WAVES < 5) && LOGN >= 10 && lds < 40 * 1024) lds = 40 * 1024;
-  uint64_t blocks = ((uint64_t)ntasks + kTeams - 1) / kTeams;
-  const uint64_t cap = (uint64_t)cfg.num_cus * 16;
-  if (blocks > cap) blocks = cap;
-  const dim3 grid((unsigned)blocks), block(64 * kTeams);
+int launch_t(const LaunchCfg& cfg, const RowArgs& a, const Operands& ops, uint32_t ntasks, const ResponseStat& so) {
+  // the workgroup of shift_row_kernel<LOGN, ., WaveTeam, BYTES>, so its LDS request and grid cap (shift_launch, rzk_launch.h)
+  static_assert(ShiftCfg<LOGN, WaveTeam>::TPB == kTeams && ShiftCfg<LOGN, WaveTeam>::WORDS == ShiftGeo<LOGN, true, 6>::WORDS,
+                "response_stat_kernel lays its images out as shift_row_kernel does");
+  constexpr ShiftLaunch g = shift_launch<LOGN, WaveTeam, BYTES>();
+  const dim3 grid(grid_for(ntasks, cfg.num_cus, kTeams, g.blocks_per_cu)), block(64 * kTeams);
   if (ops.trusted)
-    hipLaunchKernelGGL((response_stat_kernel<LOGN, true, BYTES>), grid, block, lds, (hipStream_t)cfg.stream, d_prog, ops, T, ntasks, so);
+    hipLaunchKernelGGL((response_stat_kernel<LOGN, true, BYTES>), grid, block, g.lds, (hipStream_t)cfg.stream, a.prog, ops, a.T, ntasks, so);
   else
-    hipLaunchKernelGGL((response_stat_kernel<LOGN, false, BYTES>), grid, block, lds, (hipStream_t)cfg.stream, d_prog, ops, T, ntasks, so);
+    hipLaunchKernelGGL((response_stat_kernel<LOGN, false, BYTES>), grid, block, g.lds, (hipStream_t)cfg.stream, a.prog, ops, a.T, ntasks, so);
   RZK_LAUNCH_CHECK();
   if (cfg.launched)
-    *cfg.launched = "response_stat_kernel<" + std::to_string(LOGN) + ", " + (ops.trusted ? "true" : "false") + (BYTES ? "" : ", false") + ">";
+    *cfg.launched = "response_stat_kernel<" + std::to_string(LOGN) + ", " + tf(ops.trusted) + (BYTES ? "" : ", false") + ">";
   return 0;
 }
 
 }  // namespace
 
-int launch_response_stat(int logn, const LaunchCfg& cfg, const Program* d_prog, uint32_t nrows, const Operands& ops,
-                         const DevTables* d_T, uint64_t batch, const ResponseStat& so) {
-  if (batch == 0 || nrows == 0) return 0;
-  if (batch * nrows >= (1ull << 32)) return -2;
-  const uint32_t ntasks = (uint32_t)(batch * nrows);
+int launch_response_stat(int logn, const LaunchCfg& cfg, const RowArgs& a, const Operands& ops, uint32_t nrows, uint64_t batch,
+                         const ResponseStat& so) {
+  uint32_t ntasks;
+  if (const int rc = task_count(batch, nrows, ntasks); rc <= 0) return rc;
   switch (logn) {
-    case 9: return cfg.shift_bytes ? launch_t<9, true>(cfg, d_prog, ops, d_T, ntasks, so) : launch_t<9, false>(cfg, d_prog, ops, d_T, ntasks, so);
-    case 10: return cfg.shift_bytes ? launch_t<10, true>(cfg, d_prog, ops, d_T, ntasks, so) : launch_t<10, false>(cfg, d_prog, ops, d_T, ntasks, so);
+    case 9: return cfg.shift_bytes ? launch_t<9, true>(cfg, a, ops, ntasks, so) : launch_t<9, false>(cfg, a, ops, ntasks, so);
+    case 10: return cfg.shift_bytes ? launch_t<10, true>(cfg, a, ops, ntasks, so) : launch_t<10, false>(cfg, a, ops, ntasks, so);
   }
   return -1;   // two-wavefront teams and small rings: the caller runs the chain (response_stat_fused, rzk_run.cpp)
 }

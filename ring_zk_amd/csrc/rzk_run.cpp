@@ -174,27 +174,29 @@ int run_program(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSpec>& spe
   LaunchCfg cfg;
   rc = prof_begin(c, bytes, cfg);
   if (rc != RZK_OK) return rc;
+  const int logn = (int)c->logn;
+  RowArgs a{dp.d, dp.d_wp, c->d_key_ntt, c->d_key_l2, c->dT, c->d_tw, c->d_row_scratch, flags};   // (scratch: Blocks and Groups have their own)
   int lrc = 0;
   switch (path) {
     case Path::Small:
       lrc = launch_row_program_small(c->N, cfg, dp.d, dp.nrows, ops, c->d_key_mont, c->dT, c->r2q, flags, batch);
       break;
     case Path::Shift:
-      lrc = stat         ? launch_response_stat((int)c->logn, cfg, dp.d, dp.nrows, ops, c->dT, batch, *stat)
-            : width == 4 ? launch_shift_rows32((int)c->logn, cfg, dp.d, dp.nrows, ops, c->dT, flags, batch)
-                         : launch_shift_rows((int)c->logn, cfg, dp.d, dp.nrows, ops, c->dT, flags, batch);
+      lrc = stat         ? launch_response_stat(logn, cfg, a, ops, dp.nrows, batch, *stat)
+            : width == 4 ? launch_shift_rows32(logn, cfg, a, ops, dp.nrows, batch)
+                         : launch_shift_rows(logn, cfg, a, ops, dp.nrows, batch);
       break;
     case Path::Blocks:
       if (!c->d_block_scratch)
-        HIPCHK(c, hipMalloc((void**)&c->d_block_scratch, block_scratch_words((int)c->logn, c->num_cus) * sizeof(uint32_t)));
-      lrc = launch_row_blocks((int)c->logn, cfg, dp.d, dp.d_blocks, dp.nblocks, ops, c->d_key_ntt, c->d_key_l2, c->dT,
-                              c->d_tw, c->d_block_scratch, flags, batch);
+        HIPCHK(c, hipMalloc((void**)&c->d_block_scratch, block_scratch_words(logn, c->num_cus) * sizeof(uint32_t)));
+      a.scratch = c->d_block_scratch;
+      lrc = launch_row_blocks(logn, cfg, a, ops, dp.d_blocks, dp.nblocks, batch);
       break;
     case Path::Groups:
       if (!c->d_group_scratch)
-        HIPCHK(c, hipMalloc((void**)&c->d_group_scratch, group_scratch_words((int)c->logn, c->num_cus) * sizeof(uint32_t)));
-      lrc = launch_row_groups((int)c->logn, cfg, dp.d, dp.ngroups, ops, c->d_key_ntt, c->d_key_l2, c->dT, c->d_tw,
-                              c->d_group_scratch, flags, batch);
+        HIPCHK(c, hipMalloc((void**)&c->d_group_scratch, group_scratch_words(logn, c->num_cus) * sizeof(uint32_t)));
+      a.scratch = c->d_group_scratch;
+      lrc = launch_row_groups(logn, cfg, a, ops, dp.ngroups, batch);
       break;
     case Path::Slots: {
       // shared-operand path; the workspace of stored transforms is bounded, so large batches go in chunks
@@ -217,22 +219,19 @@ int run_program(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSpec>& spe
           const uint64_t first = o2.outer[i] ? b0 / grp : b0;
           o2.base[i] += first * o2.stride[i] * c->N;
         }
-        lrc = launch_row_program_slots((int)c->logn, cfg, dp.d, dp.d_slots, dp.nslots, o2, c->d_key_ntt,
-                                       c->d_key_l2, c->dT, c->d_tw, d_ws, d_norms, c->d_row_scratch,
-                                       flags ? flags + b0 / grp : nullptr, nb, dp.np_store);
+        a.flags = flags ? flags + b0 / grp : nullptr;
+        lrc = launch_row_program_slots(logn, cfg, a, o2, dp.d_slots, dp.nslots, SlotStore{d_ws, d_norms, dp.np_store}, nb);
       }
       break;
     }
     case Path::Rows:
-      lrc = launch_rows((int)c->logn, cfg, dp.d, dp.nrows, dp.has_shift, ops, c->d_key_ntt, c->d_key_l2, c->dT, c->d_tw,
-                        c->d_row_scratch, flags, batch, dp.has_dd);
+      lrc = launch_rows(logn, cfg, a, ops, dp.nrows, dp.has_shift, batch, dp.has_dd);
       break;
-    case Path::Units:
-      lrc = width == 4 ? launch_units32((int)c->logn, cfg, dp.d, dp.d_wp, dp.nunits, upt, 2 * dp.work, dp.has_shift, ops, c->d_key_ntt,
-                                        c->d_key_l2, c->dT, c->d_tw, c->d_row_scratch, flags, batch)
-                       : launch_units((int)c->logn, cfg, dp.d, dp.d_wp, dp.nunits, upt, 2 * dp.work, dp.has_vec, dp.has_shift, ops,
-                                      c->d_key_ntt, c->d_key_l2, c->dT, c->d_tw, c->d_row_scratch, flags, batch);
+    case Path::Units: {
+      const UnitShape u{dp.nunits, upt, 2 * dp.work, dp.has_vec, dp.has_shift};
+      lrc = width == 4 ? launch_units32(logn, cfg, a, ops, u, batch) : launch_units(logn, cfg, a, ops, u, batch);
       break;
+    }
   }
   if (lrc == -2) return fail(c, RZK_E_UNSUPPORTED, "batch * rows must stay below 2^32");
   rc = check_launch(c, lrc, "row kernel launch");
