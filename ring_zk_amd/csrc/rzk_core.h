@@ -608,12 +608,17 @@ RZK_HD void shift_accum(T* acc, int lane, int s, int32_t coef, const int32_t* ex
 #pragma unroll
   for (int i = 0; i < IN; ++i) acc[i] += (T)coef * (T)base[S::off(I0 + i)];
 }
-// exact integer -> [0,q), |a| < 2^62
+// exact integer -> [0,q), |a| < 2^62 and |a| < q 2^32.  The second bound is the narrower one for q < 2^30 only; it holds for
+// every supported modulus through the pass split of shift_product (bound < 4.0e18, rzk_rowprog.h): 4.0e18 < p0 2^32 < q 2^32.
 RZK_HD uint32_t zq_from_i64(int64_t a, const CrtConsts& C) {
-  const int32_t hi = (int32_t)(a >> 32);          // |hi| < 2^30 < q
-  uint32_t lo = (uint32_t)a;                      // < 2^32 < 4q
-  lo = lo >= C.q ? lo - C.q : lo;
-  lo = lo >= C.q ? lo - C.q : lo;
+  const int32_t hi = (int32_t)(a >> 32);          // |hi| < q (above): zq_from_centered lands in [0,q)
+  // The low word is < 2^32 < 5q, and NOT < 4q: a modulus below 2^30 has 4q < 2^32 (by up to 196596 at q = p0 + 2), so three
+  // subtractions of q do not reach [0,q) there.  Three steps still do when the first two take 2q (wave-uniform, scalar unit;
+  // q >= 2^31, where 2q leaves 32 bits and lo < 2q anyway, keeps q):  q < 2^31: < 5q -> < 3q -> < 2q -> < q;  else < 2q -> < q.
+  const uint32_t q2 = C.q < 0x80000000u ? 2u * C.q : C.q;
+  uint32_t lo = (uint32_t)a;
+  lo = lo >= q2 ? lo - q2 : lo;
+  lo = lo >= q2 ? lo - q2 : lo;
   lo = lo >= C.q ? lo - C.q : lo;
   return addq(montq_u(zq_from_centered(hi, C.q), C.r2q, C), lo, C.q);
 }

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from test_emul_modq import MODULI
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 EMUL_DIR = os.path.join(HERE, "emul")
@@ -143,11 +144,36 @@ def test_emulated_polymul_fewer_primes(emul, logn):
     assert np.array_equal(_polymul(emul, logn, 1, a, b), O.poly_mul(a, b))
 
 
+def negacyclic_exact(a, b):
+    """a * b in Z[X]/(X^N + 1) over the integers, for operands small enough for int64."""
+    N = len(a)
+    full = np.convolve(np.asarray(a, dtype=np.int64), np.asarray(b, dtype=np.int64))
+    out = full[:N].copy()
+    out[:N - 1] -= full[N:]
+    return out
+
+
 @pytest.mark.parametrize("pair", [1, 0])
 @pytest.mark.parametrize("logn", [9, 10, 11, 1011])
 def test_emulated_shift_product(emul, logn, pair):
     """Challenge products as signed negacyclic rotations (ShiftGeo in rzk_core.h), one and two passes
-    (1011: N = 2048 in the layout of a two-wavefront team)."""
+    (1011: N = 2048 in the layout of a two-wavefront team), at the protocols' modulus."""
+    shift_product_cases(emul, logn, pair, Q)
+
+
+@pytest.mark.parametrize("pair", [1, 0])
+@pytest.mark.parametrize("logn", [9, 10, 11, 1011])
+@pytest.mark.parametrize("qname", sorted(set(MODULI) - {"Q_DEF"}))
+def test_emulated_shift_product_at_the_edge_moduli(emul, logn, pair, qname):
+    """The same cases at the other moduli of the edge set (test_emul_modq.MODULI; Q_DEF is the test above).  Below 2^30
+    the low word of a small negative rotation sum, 2^32 - |a|, lies past 4q, where three subtractions of q do not bring
+    it into [0, q) (zq_from_i64); the ternary x challenge input is asserted to hold such sums."""
+    assert MODULI["Q_DEF"] == Q
+    shift_product_cases(emul, logn, pair, MODULI[qname])
+
+
+def shift_product_cases(emul, logn, pair, q):
+    half = (q - 1) // 2
     N = 1 << (logn % 1000)
     rng = np.random.default_rng(500 + logn)
 
@@ -155,7 +181,7 @@ def test_emulated_shift_product(emul, logn, pair):
         out = np.empty(N, dtype=np.int64)
         d = np.ascontiguousarray(d, dtype=np.int64)
         v = np.ascontiguousarray(v, dtype=np.int64)
-        assert emul.emul_shift_product(logn, pair, passes, C.c_uint64(Q), _i64p(d), _i64p(v), _i64p(out)) == 0
+        assert emul.emul_shift_product(logn, pair, passes, C.c_uint64(q), _i64p(d), _i64p(v), _i64p(out)) == 0
         return out
 
     d = np.zeros(N, dtype=np.int64)
@@ -163,16 +189,26 @@ def test_emulated_shift_product(emul, logn, pair):
     d[pos] = rng.choice([-1, 1], 36)
     d[0], d[1], d[N - 1], d[N - 2] = 1, -1, -1, 1            # both parities at both ends
     r = rng.integers(-1, 2, N, dtype=np.int64)
-    assert np.array_equal(run(1, d, r), O.poly_mul(d, r))
-    c1 = rng.integers(-HALF, HALF + 1, N, dtype=np.int64)     # full-range commitment row
-    c1[:2] = [HALF, -HALF]
+    assert np.array_equal(run(1, d, r), O.poly_mul(d, r, q))
+    c1 = rng.integers(-half, half + 1, N, dtype=np.int64)     # full-range commitment row
+    c1[:2] = [half, -half]
     for passes in (1, 2):
-        assert np.array_equal(run(passes, d, c1), O.poly_mul(d, c1))
-    dd = rng.integers(-HALF, HALF + 1, N, dtype=np.int64)     # dense full-range multiplier: sums up to 2^72
-    dd[:2] = [-HALF, HALF]
-    assert np.array_equal(run(2, dd, c1), O.poly_mul(dd, c1))
+        assert np.array_equal(run(passes, d, c1), O.poly_mul(d, c1, q))
+    dd = rng.integers(-half, half + 1, N, dtype=np.int64)     # dense full-range multiplier: sums up to 2^72
+    dd[:2] = [-half, half]
+    assert np.array_equal(run(2, dd, c1), O.poly_mul(dd, c1, q))
     small = rng.integers(-1000, 1001, N, dtype=np.int64)
-    assert np.array_equal(run(1, small, c1), O.poly_mul(small, c1))
+    assert np.array_equal(run(1, small, c1), O.poly_mul(small, c1, q))
+    # ternary multiplier x +-1 challenge: exact sums in [-36, 36], about half of them negative
+    exact = negacyclic_exact(r, d)
+    if 4 * q < 2 ** 32:
+        band = (exact >= -(2 ** 32 - 4 * q)) & (exact <= -1)
+        assert band.any(), "no rotation sum whose low word lies in [4q, 2^32)"
+    want = np.where(exact < 0, exact + q, exact)
+    want = np.where(want > half, want - q, want)              # |exact| <= 36 < q: the centred representative
+    for passes in (1, 2):
+        assert np.array_equal(run(passes, r, d), want)
+    assert np.array_equal(want, O.poly_mul(r, d, q))
 
 
 def test_philox_known_answers(emul):

@@ -54,7 +54,73 @@ def make_ctx(N, n, k, l, env=None, **kw):
 
 
 def P_of(ctx):
-    return O.Params(N=ctx.N, n=ctx.n, k=ctx.k, l=ctx.l, kappa=ctx.kappa, b=ctx.b)
+    return O.Params(N=ctx.N, n=ctx.n, k=ctx.k, l=ctx.l, kappa=ctx.kappa, b=ctx.b, q=ctx.q)
+
+
+# ---- edge operands (edges=True of the helpers below; tests/test_gpu_moduli.py) ------------------------------------------
+# Every operand a kernel lifts and transforms gets +-h, h = (q-1)/2, where the lanes and registers of a team meet
+# (coefficients 0, 63, 64, N-1), one polynomial that is +h throughout and one that alternates -h, +h, ...: with these the
+# one-add lift x + 2p reaches both ends of [0, 4p), and the three-prime sums are the largest the range allows
+# (N h^2 k < 2^77, far below P3 / 2).  Planted after the draw, so the random part of every input stays what it was.
+def edge_positions(N):
+    return sorted({0, min(63, N - 1), min(64, N - 1), N - 1})
+
+
+def plant_edges(a, half):
+    """a [B >= 2][...][N], in place.  Entry 0: +h, -h, +h, -h at edge_positions in its first polynomial, and (when an
+    entry has several polynomials) its last polynomial all +h; entry 1: first polynomial -h, +h, -h, ... (the opposite
+    signs at the same positions); a third entry of single-polynomial operands takes the all +h polynomial."""
+    B, N = a.shape[0], a.shape[-1]
+    assert B >= 2
+    flat = a.reshape(B, -1, N)
+    assert flat.base is not None and np.shares_memory(flat, a)
+    pos = edge_positions(N)
+    flat[0, 0, pos] = np.array([half, -half] * 2, dtype=np.int64)[:len(pos)]
+    flat[1, 0] = half * np.where(np.arange(N) % 2 == 0, -1, 1)
+    if flat.shape[1] > 1:
+        flat[0, -1] = half
+    elif B >= 3:
+        flat[2, 0] = half
+    # the conditions themselves
+    assert [int(v) for v in flat[0, 0, pos]] == [half, -half, half, -half][:len(pos)]
+    assert [int(v) for v in flat[1, 0, pos]] == [(-half if i % 2 == 0 else half) for i in pos]
+    assert int(a.max()) == half and int(a.min()) == -half
+    return a
+
+
+def plant_key_edges(A, n, l, half):
+    """A [n + l][k][N] in place: the first entry of a1' takes +h, -h, +h, -h at edge_positions; where a2' has entries,
+    its first one alternates -h, +h, ... throughout and its last one takes -h, +h, -h, +h at edge_positions."""
+    N = A.shape[-1]
+    pos = edge_positions(N)
+    A[0, n, pos] = np.array([half, -half] * 2, dtype=np.int64)[:len(pos)]
+    if A.shape[1] - n - l > 0:
+        A[n, n + l] = half * np.where(np.arange(N) % 2 == 0, -1, 1)
+        A[n + l - 1, A.shape[1] - 1, pos] = np.array([-half, half] * 2, dtype=np.int64)[:len(pos)]
+    return A
+
+
+def negacyclic_exact(a, b):
+    """a * b in Z[X]/(X^N + 1) over the integers (numpy; operands small enough for int64)."""
+    N = a.shape[-1]
+    full = np.convolve(np.asarray(a, dtype=np.int64), np.asarray(b, dtype=np.int64))
+    out = full[:N].copy()
+    out[:N - 1] -= full[N:]
+    return out
+
+
+def assert_rotation_band(r, d, q):
+    """Below 2^30 the rotation sums r (.) d must include values in [-(2^32 - 4q), -1]: their low words lie past 4q, where
+    three subtractions of q do not reduce a 64-bit sum to [0, q) (zq_from_i64).  r [B][rows][N], d [B][N]."""
+    if 4 * q >= 2 ** 32:
+        return
+    width = 2 ** 32 - 4 * q
+    for b in range(r.shape[0]):
+        for row in r[b].reshape(-1, r.shape[-1]):
+            s = negacyclic_exact(row, d[b])
+            if ((s >= -width) & (s <= -1)).any():
+                return
+    raise AssertionError("no rotation sum in [-(2^32 - 4q), -1]")
 
 
 def dev(torch, a):
@@ -63,20 +129,25 @@ def dev(torch, a):
 
 def sum_inputs(rng, P, B, V):
     N, k, l = P.N, P.k, P.l
-    gs = synth.uniform(rng, (B, V, N))
-    xs = synth.uniform(rng, (B, V, l, N))
+    gs = synth.uniform(rng, (B, V, N), P.q)
+    xs = synth.uniform(rng, (B, V, l, N), P.q)
     rs, rp = synth.small(rng, (B, V, k, N), P.b), synth.small(rng, (B, k, N), P.b)
     ys, yp = synth.gauss(rng, (B, V, k, N), P.sigma), synth.gauss(rng, (B, k, N), P.sigma)
     d = synth.challenge(rng, (B,), N, P.kappa)
     return gs, xs, rs, rp, ys, yp, d
 
 
-def check_sum_cycle(torch, ctx, A, B, V, seed, device_too=True, entries=None):
+def check_sum_cycle(torch, ctx, A, B, V, seed, device_too=True, entries=None, edges=False):
     """Every phase of the Sum cycle vs the oracle, one tampered proof; returns nothing, asserts.  `entries`: the batch
-    entries compared with the oracle (default all of them)."""
+    entries compared with the oracle (default all of them).  The modulus is the context's; `edges`: plant_edges in the
+    transformed operands g_i and x_i, and (below 2^30) the rotation sums are asserted to reach the band past 4q."""
     P = P_of(ctx)
+    q = ctx.q
     rng = np.random.default_rng(seed)
     gs, xs, rs, rp, ys, yp, d = sum_inputs(rng, P, B, V)
+    if edges:
+        plant_edges(gs, (q - 1) // 2), plant_edges(xs, (q - 1) // 2)
+        assert_rotation_band(rs, d, q)
     cs, cp, ts, tp, u, ok = ctx.sum_commit(gs, xs, rs, rp, ys, yp)
     zs, zp = ctx.sum_response(ys, yp, rs, rp, d)
     acc = ctx.sum_verify(zs, zp, cs, cp, gs, ts, tp, u, d)
@@ -92,11 +163,11 @@ def check_sum_cycle(torch, ctx, A, B, V, seed, device_too=True, entries=None):
     # tampered proofs: a response coefficient, a t coefficient of the last summand, the masked sum u
     last = B - 1
     zst = zs.copy()
-    zst[last, V - 1, ctx.k - 1, 7] = O.center(int(zst[last, V - 1, ctx.k - 1, 7]) + 1)
+    zst[last, V - 1, ctx.k - 1, 7] = O.center(int(zst[last, V - 1, ctx.k - 1, 7]) + 1, q)
     assert ctx.sum_verify(zst, zp, cs, cp, gs, ts, tp, u, d).tolist() == [1] * last + [0]
     assert O.sum_verify(P, A, zst[last], zp[last], cs[last], cp[last], gs[last], ts[last], tp[last], u[last], d[last]) != 1
     ut = u.copy()
-    ut[0, ctx.l - 1, ctx.N - 1] = O.center(int(ut[0, ctx.l - 1, ctx.N - 1]) - 1)
+    ut[0, ctx.l - 1, ctx.N - 1] = O.center(int(ut[0, ctx.l - 1, ctx.N - 1]) - 1, q)
     assert ctx.sum_verify(zs, zp, cs, cp, gs, ts, tp, ut, d).tolist() == [0] + [1] * last
     if device_too:   # device-pointer entry points give the same bytes
         D = lambda a: dev(torch, a)
@@ -109,29 +180,40 @@ def check_sum_cycle(torch, ctx, A, B, V, seed, device_too=True, entries=None):
         assert accd.cpu().numpy().tolist() == [1] * last + [0]
 
 
-def check_key_products_and_open(ctx, A, B, seed, entries=None):
+def check_key_products_and_open(ctx, A, B, seed, entries=None, edges=False):
     """matvec(A1 / A2 / A), commit, Commitment::verify and the Open cycle vs the oracle (commit.rs:109-125,
     open.rs:80-174), with full-range and ternary vectors.  `entries`: the batch entries compared with the oracle
-    (default all of them)."""
+    (default all of them).  The modulus and the bound b of r are the context's.  `edges`: plant_edges in v and x; the verifier is also given
+    c and t with planted edges (its verdict against the oracle's), open_recover is compared value by value with
+    a1.z - c1 (.) d for the honest c, for a c with planted edges and with a ternary c1 in the last entry (small negative
+    rotation sums inside the unit kernels), and (below 2^30) r (.) d is asserted to reach the band past 4q."""
     entries = range(B) if entries is None else entries
     P = P_of(ctx)
+    q = ctx.q
+    half = (q - 1) // 2
     N, n, k, l = ctx.N, ctx.n, ctx.k, ctx.l
     rng = np.random.default_rng(seed)
-    v = synth.uniform(rng, (B, k, N))
+    v = synth.uniform(rng, (B, k, N), q)
     v[B - 1] = synth.small(rng, (k, N))
+    if edges:
+        assert B >= 3          # (entries 0 and 1 carry the edges, the last one stays ternary)
+        plant_edges(v, half)
     for which, sl in ((0, slice(0, n)), (1, slice(n, n + l)), (2, slice(0, n + l))):
         out = ctx.matvec(which, v)
         for b in entries:
-            assert np.array_equal(out[b], O.mat_dot(A[sl], v[b][:, None, :])[:, 0, :]), (which, b)
-    x = synth.uniform(rng, (B, l, N))
-    r = synth.small(rng, (B, k, N))
+            assert np.array_equal(out[b], O.mat_dot(A[sl], v[b][:, None, :], q)[:, 0, :]), (which, b)
+    x = synth.uniform(rng, (B, l, N), q)
+    r = synth.small(rng, (B, k, N), ctx.b)
     y = synth.gauss(rng, (B, k, N), P.sigma)
     d = synth.challenge(rng, (B,), N, P.kappa)
+    if edges:
+        plant_edges(x, half)
+        assert_rotation_band(r, d, q)
     cm, okc = ctx.commit(x, r)
     c, t, ok = ctx.open_commit(x, r, y)
     z = ctx.open_response(y, r, d)
     zt = z.copy()
-    zt[0, 0, 0] = O.center(int(zt[0, 0, 0]) + 1)
+    zt[0, 0, 0] = O.center(int(zt[0, 0, 0]) + 1, q)
     acc, acct = ctx.open_verify(z, t, c, d), ctx.open_verify(zt, t, c, d)
     for b in entries:
         c_ref, t_ref, ok_ref = O.open_commit(P, A, x[b], r[b], y[b])
@@ -141,6 +223,21 @@ def check_key_products_and_open(ctx, A, B, seed, entries=None):
         assert O.open_verify(P, A, z[b], t[b], c[b], d[b]) == 1
     assert acc.tolist() == [1] * B and acct.tolist() == [0] + [1] * (B - 1)
     assert ctx.commitment_verify(c, x, r).tolist() == [1] * B
+    if edges:
+        ce, te = plant_edges(c.copy(), half), plant_edges(t.copy(), half)
+        acce = ctx.open_verify(z, te, ce, d)
+        assert acce.tolist() == [int(O.open_verify(P, A, z[b], te[b], ce[b], d[b]) == 1) for b in range(B)]
+        ct = ce.copy()
+        ct[B - 1, :n] = synth.small(np.random.default_rng(seed + 1), (n, N))
+        assert_rotation_band(ct[B - 1:, :n], d[B - 1:], q)
+        for cc in (c, ct):
+            tr, accr = ctx.open_recover(z, cc, d)
+            for b in sorted(set(entries) | {B - 1}):
+                az = O.mat_dot(A[:n], z[b][:, None, :], q)[:, 0, :]
+                want = np.stack([O.poly_sub(az[i], O.poly_mul(cc[b, i], d[b], q), q) for i in range(n)])
+                assert np.array_equal(tr[b], want), ("open_recover", b)
+            assert accr.tolist() == [1] * B
+        assert np.array_equal(ctx.open_recover(z, c, d)[0], t)
 
 
 # ---- BASELINE config 3: SumProof, N = 1024, (4,9,4), V = 8 ----------------------------------------------------------

@@ -653,7 +653,8 @@ def test_device_buffers_at_8_byte_alignment(torch_mod):
 @pytest.mark.parametrize("q", [1073741827, 4294606851])
 @pytest.mark.parametrize("N", [512, 1024])
 def test_other_moduli_and_parameters(torch_mod, N, q):
-    """Smallest and largest supported ring moduli (just above 2^30; just below 4 p2, include/rzk.h) with kappa = 60
+    """The first ring modulus above 2^30 and the largest supported one (4 p2 - 1, include/rzk.h; the smallest, p0 + 2,
+    and the moduli below 2^30 are swept in tests/test_gpu_moduli.py) with kappa = 60
     (the reference's own challenge-set test, challenge_space.rs:60) and b = 3: every mod-q path of the kernels
     (32-bit add/sub with wrap-around, 64-bit reductions of the rotation sums, CRT constants) against the oracle."""
     from ring_zk_amd import Context

@@ -14,7 +14,8 @@ import pytest
 from oracle import oracle as O
 from ring_zk_amd import synth
 
-from test_gpu_baseline_shapes import P_of, check_key_products_and_open, check_sum_cycle, make_ctx, torch_mod  # noqa: F401
+from test_gpu_baseline_shapes import (P_of, assert_rotation_band, check_key_products_and_open, check_sum_cycle, make_ctx,  # noqa: F401
+                                      plant_edges, torch_mod)
 
 pytestmark = pytest.mark.gpu
 
@@ -60,20 +61,25 @@ def draw_case(seed):
     return dict(N=N, n=nl, k=k, l=nl, B=B, V=V, env=env, seed=seed)
 
 
-def check_linear_cycle(ctx, A, B, seed, entries=None):
-    """Linear cycle vs the oracle at `entries` (default every batch entry), the last proof tampered."""
+def check_linear_cycle(ctx, A, B, seed, entries=None, edges=False):
+    """Linear cycle vs the oracle at `entries` (default every batch entry), the last proof tampered.  The modulus and the
+    bound b of r are the context's; `edges`: plant_edges (test_gpu_baseline_shapes) in the transformed operands g and x."""
     P = P_of(ctx)
+    q = ctx.q
     N, k, l = ctx.N, ctx.k, ctx.l
     rng = np.random.default_rng(seed)
-    g = synth.uniform(rng, (B, N))
-    x = synth.uniform(rng, (B, l, N))
-    r, rp = synth.small(rng, (B, k, N)), synth.small(rng, (B, k, N))
+    g = synth.uniform(rng, (B, N), q)
+    x = synth.uniform(rng, (B, l, N), q)
+    r, rp = synth.small(rng, (B, k, N), ctx.b), synth.small(rng, (B, k, N), ctx.b)
     y, yp = synth.gauss(rng, (B, k, N), P.sigma), synth.gauss(rng, (B, k, N), P.sigma)
     d = synth.challenge(rng, (B,), N, P.kappa)
+    if edges:
+        plant_edges(g, (q - 1) // 2), plant_edges(x, (q - 1) // 2)
+        assert_rotation_band(r, d, q)
     c, cp, t, tp, u, ok = ctx.linear_commit(g, x, r, rp, y, yp)
     z, zp = ctx.linear_response(y, yp, r, rp, d)
     zt = z.copy()
-    zt[B - 1, k - 1, N - 1] = O.center(int(zt[B - 1, k - 1, N - 1]) + 1)
+    zt[B - 1, k - 1, N - 1] = O.center(int(zt[B - 1, k - 1, N - 1]) + 1, q)
     acc, acct = ctx.linear_verify(z, zp, c, cp, g, t, tp, u, d), ctx.linear_verify(zt, zp, c, cp, g, t, tp, u, d)
     for b in range(B) if entries is None else entries:
         ref = O.linear_commit(P, A, g[b], x[b], r[b], rp[b], y[b], yp[b])          # linear.rs:82-140
