@@ -542,6 +542,40 @@ int rzk_open_recover32_batch(rzk_ctx* ctx, const int32_t* z, const int32_t* c, c
 int rzk_open_recover32_batch_dev(rzk_ctx* ctx, const int32_t* z, const int32_t* c, const int32_t* d, int32_t* t_out,
                                  uint8_t* accept, size_t B);
 
+/* ---- 32-bit slabs: messages (v14, slab32 messages) ------------------------------------------------------------
+ * The transcript hash, the packed codec and the compare of the short verifier on int32_t slabs, so that a stored proof goes
+ * record -> verdict and operands -> record without a 64-bit slab or a convert launch.  Additions only: RZK_ABI_VERSION stays
+ * 14, every earlier signature is unchanged, and a binding that resolves these names fails at load on a library without them.
+ * Argument rules, NULL rules, B == 0, fault reporting and trusted-producer mode are those of the 64-bit sibling named below;
+ * device slabs (fields, d, a, b) are 16-byte aligned as everywhere in the section above (RZK_E_ARG otherwise).  All kinds
+ * the sibling takes are supported (the kernels do not depend on the kind).
+ * rzk_fs_challenge32_batch    sibling rzk_fs_challenge_batch.  digest and ok are byte for byte what the sibling returns on
+ *                             widen(fields); d is narrow() of its d.  FS1 hashes a coefficient as the little-endian int32 of
+ *                             its centred value, so a slab32 is the hash's input as it stands; the range test is made on
+ *                             the int32 (|c| <= (q-1)/2), with the sibling's consequences.
+ * rzk_packed_encode32_batch   sibling rzk_packed_encode_batch.  records and ok are byte for byte the sibling's on widen(fields).
+ * rzk_packed_decode32_batch   sibling rzk_packed_decode_batch.  ok is identical; every field of a record with ok = 1 is
+ *                             narrow() of the sibling's (every valid value lies in [-bias, limit - bias], inside [-(q-1)/2,
+ *                             (q-1)/2]); slabs of a rejected record are unspecified, as there.
+ *                             Records have no width: one written by either encoder decodes with either decoder.
+ * rzk_eq32_batch              eq[b] = 1 iff the two [rows][N] blocks of entry b are equal word for word.  Unlike rzk_eq_batch
+ *                             there is no range test and no input fault: the verdict of the call that consumes or produced
+ *                             the slabs (rzk_open_recover32_batch for the short verifier) has tested them.  rows >= 1. */
+int rzk_fs_challenge32_batch(rzk_ctx* ctx, int kind, uint32_t V, const int32_t* const* fields, const uint8_t* aux32,
+                             int32_t* d, uint8_t* digest, uint8_t* ok, size_t B);
+int rzk_fs_challenge32_batch_dev(rzk_ctx* ctx, int kind, uint32_t V, const int32_t* const* fields, const uint8_t* aux32,
+                                 int32_t* d, uint8_t* digest, uint8_t* ok, size_t B);
+int rzk_packed_encode32_batch(rzk_ctx* ctx, int kind, uint32_t V, const int32_t* const* fields, uint8_t* records, uint8_t* ok,
+                              size_t B);
+int rzk_packed_encode32_batch_dev(rzk_ctx* ctx, int kind, uint32_t V, const int32_t* const* fields, uint8_t* records,
+                                  uint8_t* ok, size_t B);
+int rzk_packed_decode32_batch(rzk_ctx* ctx, int kind, uint32_t V, const uint8_t* records, int32_t* const* fields, uint8_t* ok,
+                              size_t B);
+int rzk_packed_decode32_batch_dev(rzk_ctx* ctx, int kind, uint32_t V, const uint8_t* records, int32_t* const* fields,
+                                  uint8_t* ok, size_t B);
+int rzk_eq32_batch(rzk_ctx* ctx, const int32_t* a, const int32_t* b, uint32_t rows, uint8_t* eq, size_t B);
+int rzk_eq32_batch_dev(rzk_ctx* ctx, const int32_t* a, const int32_t* b, uint32_t rows, uint8_t* eq, size_t B);
+
 /* The response and its test in one call (v13): "give me z, and tell me whether I may release it".
  * z (z', z_s) is byte for byte what rzk_*_response_batch writes; accept and E (may be NULL) are what rzk_reject_batch
  * returns for the parts [(z, y)] (Open), [(z, y), (z', y')] (Linear), [(z_s, y_s), (z', y')] (Sum) with the same coin, R

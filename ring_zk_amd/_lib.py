@@ -113,6 +113,11 @@ SIGNATURES = {
     "rzk_open_response32_batch": (C.c_int, [_CTX] + [_I32] * 4 + [_SZ]),
     "rzk_open_verify32_batch": (C.c_int, [_CTX] + [_I32] * 4 + [_U8, _SZ]),
     "rzk_open_recover32_batch": (C.c_int, [_CTX] + [_I32] * 4 + [_U8, _SZ]),
+    # v14, slab32 messages: the transcript hash, the packed codec and the short verifier's compare on int32_t slabs
+    "rzk_fs_challenge32_batch": (C.c_int, [_CTX, C.c_int, C.c_uint32, C.c_void_p, _U8, _I32, _U8, _U8, _SZ]),
+    "rzk_packed_encode32_batch": (C.c_int, [_CTX, C.c_int, C.c_uint32, C.c_void_p, _U8, _U8, _SZ]),
+    "rzk_packed_decode32_batch": (C.c_int, [_CTX, C.c_int, C.c_uint32, _U8, C.c_void_p, _U8, _SZ]),
+    "rzk_eq32_batch": (C.c_int, [_CTX, _I32, _I32, C.c_uint32, _U8, _SZ]),
     # v8: fixed-width packed records
     "rzk_packed_record_bytes": (C.c_size_t, [_CTX, C.c_int, C.c_uint32]),
     "rzk_packed_widths": (C.c_int, [_CTX, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

@@ -622,6 +622,18 @@ class Context:
         self._check(self._fn("rzk_open_recover32_batch", dev)(self._h, *p, B))
         return t, acc
 
+    def eq32(self, a, b):
+        """eq[b] = 1 iff the int32 blocks a[b], b[b] ([rows][N]) are equal word for word (rzk_eq32_batch); no range test,
+        unlike eq: the verdict of the call that read or wrote the slabs has tested them."""
+        if tuple(a.shape) != tuple(b.shape):
+            raise ValueError("eq32: shape mismatch")
+        rows = int(a.shape[-2])
+        B = self._shape(a, rows, self.N)
+        out = self._empty(a, (B,), np.uint8)
+        dev, p = self._prep([a, b, out], [np.int32, np.int32, np.uint8])
+        self._check(self._fn("rzk_eq32_batch", dev)(self._h, p[0], p[1], rows, p[2], B))
+        return out
+
     # ---- LinearProof (src/prove/linear.rs) ------------------------------------------------------------------------
     def linear_commit(self, g, x, r, rp, y, yp):
         B = self._shape(x, self.l, self.N)

@@ -127,10 +127,16 @@ namespace {
 bool fs_kind_ok(int kind) {
   return kind == RZK_MSG_OPEN_COMMITMENT || kind == RZK_MSG_LINEAR_COMMITMENT || kind == RZK_MSG_SUM_COMMITMENT;
 }
-}  // namespace
 
-int rzk_fs_challenge_batch_dev(rzk_ctx* c, int kind, uint32_t V, const int64_t* const* fields, const uint8_t* aux32,
-                               int64_t* d, uint8_t* digest, uint8_t* ok, size_t B) {
+// 32-bit slabs (v14, slab32 messages): the entry points below and of the packed codec exist at both
+// coefficient widths over one body.  width = bytes per coefficient of every slab of the call (8, or 4 for int32_t slabs,
+// whose addresses travel as int64_t* as in rzk_slab32.cpp); at width 4 device slabs are 16-byte aligned.
+const int64_t* const* as64(const int32_t* const* fields) { return reinterpret_cast<const int64_t* const*>(fields); }
+int64_t* as64(int32_t* p) { return reinterpret_cast<int64_t*>(p); }
+size_t width_bytes(const rzk_ctx* c, size_t count, uint32_t width) { return polys(c, count) / 8 * width; }
+
+int fs_challenge_dev(rzk_ctx* c, int kind, uint32_t V, const int64_t* const* fields, const uint8_t* aux32, int64_t* d,
+                     uint8_t* digest, uint8_t* ok, size_t B, uint32_t width) {
   WireSchema s;
   if (!c) return RZK_E_ARG;
   HIPCHK(c, hipSetDevice(c->device));   // the memsets below come before the first cfg_of
@@ -140,6 +146,11 @@ int rzk_fs_challenge_batch_dev(rzk_ctx* c, int kind, uint32_t V, const int64_t* 
   if (B == 0) return RZK_OK;
   WireSlabs sl;
   if (!d || !wire_slabs(s, kind, fields, false, &sl)) return fail(c, RZK_E_ARG, "fs challenge: NULL pointer");
+  if (width == 4) {
+    uintptr_t bits = (uintptr_t)d;
+    for (uint32_t f = 0; f < s.nfields; ++f) bits |= (uintptr_t)sl.ptr[f];
+    if (bits & 15u) return fail(c, RZK_E_ARG, "slab32: device slabs must be 16-byte aligned");
+  }
   FsMsg m{};
   m.nfields = s.nfields;
   m.N = c->N;
@@ -159,18 +170,18 @@ int rzk_fs_challenge_batch_dev(rzk_ctx* c, int kind, uint32_t V, const int64_t* 
   if (rc != RZK_OK) return rc;
   uint64_t* dig = (uint64_t*)c->ws_fs.p;
   if (ok) HIPCHK(c, hipMemsetAsync(ok, 1, B, c->stream));
-  HIPCHK(c, hipMemsetAsync(d, 0, polys(c, B), c->stream));   // the sampler writes the kappa non-zero coefficients only
-  const uint64_t hashed = (uint64_t)B * s.polys * c->N * sizeof(int64_t);
+  HIPCHK(c, hipMemsetAsync(d, 0, width_bytes(c, B, width), c->stream));   // the sampler writes the kappa non-zero coefficients only
+  const uint64_t hashed = (uint64_t)B * s.polys * c->N * width;
   rc = run_profiled(c, hashed, "fs leaf kernel", [&](const LaunchCfg& cfg) {
-    return launch_fs_leaves(cfg, m, (c->q - 1) / 2, c->trusted ? 0 : 1, dig, ok, c->d_bad, B);
+    return launch_fs_leaves(cfg, m, (c->q - 1) / 2, c->trusted ? 0 : 1, dig, ok, c->d_bad, B, width);
   });
   if (rc != RZK_OK) return rc;
   return run_profiled(c, (uint64_t)B * r.leaves * 32, "fs root kernel",
-                      [&](const LaunchCfg& cfg) { return launch_fs_roots(cfg, r, dig, d, digest, B); });
+                      [&](const LaunchCfg& cfg) { return launch_fs_roots(cfg, r, dig, d, digest, B, width); });
 }
 
-int rzk_fs_challenge_batch(rzk_ctx* c, int kind, uint32_t V, const int64_t* const* fields, const uint8_t* aux32,
-                           int64_t* d, uint8_t* digest, uint8_t* ok, size_t B) {
+int fs_challenge_host(rzk_ctx* c, int kind, uint32_t V, const int64_t* const* fields, const uint8_t* aux32, int64_t* d,
+                      uint8_t* digest, uint8_t* ok, size_t B, uint32_t width) {
   WireSchema s;
   if (!c) return RZK_E_ARG;
   if (!fs_kind_ok(kind) || !wire_schema_of(c, kind, V, 8, &s)) return fail(c, RZK_E_ARG, "fs challenge: bad kind or V");
@@ -178,11 +189,30 @@ int rzk_fs_challenge_batch(rzk_ctx* c, int kind, uint32_t V, const int64_t* cons
   WireSlabs sl;
   if (!d || !wire_slabs(s, kind, fields, false, &sl)) return fail(c, RZK_E_ARG, "fs challenge: NULL pointer");
   HostCall h(c);
-  const auto dd = h.pout(d, B);
+  const auto dd = h.out(d, width_bytes(c, B, width));
   const auto ddigest = h.out(digest, B * 32), dok = h.out(ok, B);
   const int64_t* dev_fields[kWireMaxFields] = {};
-  for (uint32_t f = 0; f < s.nfields; ++f) h.in_to(&dev_fields[f], fields[f], wire_field_bytes(c, s, f, B));
-  return h.run([&] { return rzk_fs_challenge_batch_dev(c, kind, V, dev_fields, aux32, dd, ddigest, dok, B); });
+  for (uint32_t f = 0; f < s.nfields; ++f) h.in_to(&dev_fields[f], fields[f], wire_field_bytes(c, s, f, B) / 8 * width);
+  return h.run([&] { return fs_challenge_dev(c, kind, V, dev_fields, aux32, dd, ddigest, dok, B, width); });
+}
+
+}  // namespace
+
+int rzk_fs_challenge_batch_dev(rzk_ctx* c, int kind, uint32_t V, const int64_t* const* fields, const uint8_t* aux32,
+                               int64_t* d, uint8_t* digest, uint8_t* ok, size_t B) {
+  return fs_challenge_dev(c, kind, V, fields, aux32, d, digest, ok, B, 8);
+}
+int rzk_fs_challenge_batch(rzk_ctx* c, int kind, uint32_t V, const int64_t* const* fields, const uint8_t* aux32,
+                           int64_t* d, uint8_t* digest, uint8_t* ok, size_t B) {
+  return fs_challenge_host(c, kind, V, fields, aux32, d, digest, ok, B, 8);
+}
+int rzk_fs_challenge32_batch_dev(rzk_ctx* c, int kind, uint32_t V, const int32_t* const* fields, const uint8_t* aux32,
+                                 int32_t* d, uint8_t* digest, uint8_t* ok, size_t B) {
+  return fs_challenge_dev(c, kind, V, as64(fields), aux32, as64(d), digest, ok, B, 4);
+}
+int rzk_fs_challenge32_batch(rzk_ctx* c, int kind, uint32_t V, const int32_t* const* fields, const uint8_t* aux32,
+                             int32_t* d, uint8_t* digest, uint8_t* ok, size_t B) {
+  return fs_challenge_host(c, kind, V, as64(fields), aux32, as64(d), digest, ok, B, 4);
 }
 
 // ---- v7: the prover's rejection-sampling step (rzk_reject_dev.hip, rzk_reject.h) --------------------------------------
@@ -438,21 +468,77 @@ int packed_args(rzk_ctx* c, int kind, uint32_t V, const int64_t* const* fields, 
   return RZK_OK;
 }
 
-size_t packed_field_bytes(const rzk_ctx* c, const PackedSchema& s, uint32_t f, size_t B) { return polys(c, B * (size_t)s.f[f].rows); }
+size_t packed_field_bytes(const rzk_ctx* c, const PackedSchema& s, uint32_t f, size_t B, uint32_t width = 8) {
+  return polys(c, B * (size_t)s.f[f].rows) / 8 * width;
+}
 
 // one launch between preset and profile bookkeeping; decode != 0: records -> slabs
-int packed_run(rzk_ctx* c, const PackedSchema& s, const PackedSlabs& sl, uint8_t* records, uint8_t* ok, size_t B, int decode) {
+int packed_run(rzk_ctx* c, const PackedSchema& s, const PackedSlabs& sl, uint8_t* records, uint8_t* ok, size_t B, int decode,
+               uint32_t width) {
   for (uint32_t f = 0; f < s.nfields; ++f)
     if ((uintptr_t)sl.ptr[f] % 16) return fail(c, RZK_E_ARG, "packed codec: device slabs must be 16-byte aligned");
   HIPCHK(c, hipSetDevice(c->device));   // the memset below comes before the first cfg_of
   HIPCHK(c, hipMemsetAsync(ok, 1, B, c->stream));
   uint64_t slab_bytes = 0;
-  for (uint32_t f = 0; f < s.nfields; ++f) slab_bytes += packed_field_bytes(c, s, f, B);
+  for (uint32_t f = 0; f < s.nfields; ++f) slab_bytes += packed_field_bytes(c, s, f, B, width);
   return run_profiled(c, slab_bytes + (uint64_t)B * packed_record_bytes(s), decode ? "packed decode kernel" : "packed encode kernel",
                       [&](const LaunchCfg& cfg) {
-                        return decode ? launch_packed_decode(cfg, s, sl, (const uint64_t*)records, ok, B)
-                                      : launch_packed_encode(cfg, s, sl, (uint64_t*)records, ok, B);
+                        return decode ? launch_packed_decode(cfg, s, sl, (const uint64_t*)records, ok, B, width)
+                                      : launch_packed_encode(cfg, s, sl, (uint64_t*)records, ok, B, width);
                       });
+}
+
+int packed_encode_dev(rzk_ctx* c, int kind, uint32_t V, const int64_t* const* fields, uint8_t* records, uint8_t* ok, size_t B,
+                      uint32_t width) {
+  PackedSchema s;
+  PackedSlabs sl;
+  if (!c) return RZK_E_ARG;
+  const int rc = packed_args(c, kind, V, fields, records, ok, B, &s, &sl);
+  if (rc != RZK_OK || B == 0) return rc;
+  return packed_run(c, s, sl, records, ok, B, 0, width);
+}
+
+int packed_decode_dev(rzk_ctx* c, int kind, uint32_t V, const uint8_t* records, const int64_t* const* fields, uint8_t* ok, size_t B,
+                      uint32_t width) {
+  PackedSchema s;
+  PackedSlabs sl;
+  if (!c) return RZK_E_ARG;
+  const int rc = packed_args(c, kind, V, fields, records, ok, B, &s, &sl);
+  if (rc != RZK_OK || B == 0) return rc;
+  return packed_run(c, s, sl, const_cast<uint8_t*>(records), ok, B, 1, width);
+}
+
+int packed_encode_host(rzk_ctx* c, int kind, uint32_t V, const int64_t* const* fields, uint8_t* records, uint8_t* ok, size_t B,
+                       uint32_t width) {
+  PackedSchema s;
+  PackedSlabs sl;
+  if (!c) return RZK_E_ARG;
+  const int rc = packed_args(c, kind, V, fields, records, ok, B, &s, &sl);
+  if (rc != RZK_OK || B == 0) return rc;
+  HostCall h(c);
+  const auto drecords = h.out(records, B * (size_t)packed_record_bytes(s));
+  const auto dok = h.out(ok, B);
+  // sl.ptr: the staged slabs, on 256-byte boundaries (PackedSlabs serves both directions, so its pointers are not const)
+  for (uint32_t f = 0; f < s.nfields; ++f)
+    h.in_to(const_cast<const int64_t**>(&sl.ptr[f]), fields[f], packed_field_bytes(c, s, f, B, width));
+  return h.run([&] { return packed_run(c, s, sl, drecords, dok, B, 0, width); });
+}
+
+int packed_decode_host(rzk_ctx* c, int kind, uint32_t V, const uint8_t* records, const int64_t* const* fields, uint8_t* ok, size_t B,
+                       uint32_t width) {
+  PackedSchema s;
+  PackedSlabs sl;
+  if (!c) return RZK_E_ARG;
+  const int rc = packed_args(c, kind, V, fields, records, ok, B, &s, &sl);
+  if (rc != RZK_OK || B == 0) return rc;
+  HostCall h(c);
+  const auto drecords = h.in(records, B * (size_t)packed_record_bytes(s));
+  const auto dok = h.out(ok, B);
+  for (uint32_t f = 0; f < s.nfields; ++f) h.out_to(&sl.ptr[f], const_cast<int64_t*>(fields[f]), packed_field_bytes(c, s, f, B, width));
+  return h.run([&] {
+    const uint8_t* rec = drecords;
+    return packed_run(c, s, sl, const_cast<uint8_t*>(rec), dok, B, 1, width);
+  });
 }
 
 }  // namespace
@@ -474,55 +560,36 @@ int rzk_packed_widths(const rzk_ctx* c, uint32_t* wq, uint32_t* wz) {
 
 int rzk_packed_encode_batch_dev(rzk_ctx* c, int kind, uint32_t V, const int64_t* const* fields, uint8_t* records, uint8_t* ok,
                                 size_t B) {
-  PackedSchema s;
-  PackedSlabs sl;
-  if (!c) return RZK_E_ARG;
-  const int rc = packed_args(c, kind, V, fields, records, ok, B, &s, &sl);
-  if (rc != RZK_OK || B == 0) return rc;
-  return packed_run(c, s, sl, records, ok, B, 0);
+  return packed_encode_dev(c, kind, V, fields, records, ok, B, 8);
 }
-
 int rzk_packed_decode_batch_dev(rzk_ctx* c, int kind, uint32_t V, const uint8_t* records, int64_t* const* fields, uint8_t* ok,
                                 size_t B) {
-  PackedSchema s;
-  PackedSlabs sl;
-  if (!c) return RZK_E_ARG;
-  const int rc = packed_args(c, kind, V, (const int64_t* const*)fields, records, ok, B, &s, &sl);
-  if (rc != RZK_OK || B == 0) return rc;
-  return packed_run(c, s, sl, const_cast<uint8_t*>(records), ok, B, 1);
+  return packed_decode_dev(c, kind, V, records, (const int64_t* const*)fields, ok, B, 8);
 }
-
 int rzk_packed_encode_batch(rzk_ctx* c, int kind, uint32_t V, const int64_t* const* fields, uint8_t* records, uint8_t* ok,
                             size_t B) {
-  PackedSchema s;
-  PackedSlabs sl;
-  if (!c) return RZK_E_ARG;
-  const int rc = packed_args(c, kind, V, fields, records, ok, B, &s, &sl);
-  if (rc != RZK_OK || B == 0) return rc;
-  HostCall h(c);
-  const auto drecords = h.out(records, B * (size_t)packed_record_bytes(s));
-  const auto dok = h.out(ok, B);
-  // sl.ptr: the staged slabs, on 256-byte boundaries (PackedSlabs serves both directions, so its pointers are not const)
-  for (uint32_t f = 0; f < s.nfields; ++f)
-    h.in_to(const_cast<const int64_t**>(&sl.ptr[f]), fields[f], packed_field_bytes(c, s, f, B));
-  return h.run([&] { return packed_run(c, s, sl, drecords, dok, B, 0); });
+  return packed_encode_host(c, kind, V, fields, records, ok, B, 8);
 }
-
 int rzk_packed_decode_batch(rzk_ctx* c, int kind, uint32_t V, const uint8_t* records, int64_t* const* fields, uint8_t* ok,
                             size_t B) {
-  PackedSchema s;
-  PackedSlabs sl;
-  if (!c) return RZK_E_ARG;
-  const int rc = packed_args(c, kind, V, (const int64_t* const*)fields, records, ok, B, &s, &sl);
-  if (rc != RZK_OK || B == 0) return rc;
-  HostCall h(c);
-  const auto drecords = h.in(records, B * (size_t)packed_record_bytes(s));
-  const auto dok = h.out(ok, B);
-  for (uint32_t f = 0; f < s.nfields; ++f) h.out_to(&sl.ptr[f], fields[f], packed_field_bytes(c, s, f, B));
-  return h.run([&] {
-    const uint8_t* rec = drecords;
-    return packed_run(c, s, sl, const_cast<uint8_t*>(rec), dok, B, 1);
-  });
+  return packed_decode_host(c, kind, V, records, (const int64_t* const*)fields, ok, B, 8);
+}
+// the same four over int32_t slabs (v14, slab32 messages): records carry no width
+int rzk_packed_encode32_batch_dev(rzk_ctx* c, int kind, uint32_t V, const int32_t* const* fields, uint8_t* records, uint8_t* ok,
+                                  size_t B) {
+  return packed_encode_dev(c, kind, V, as64(fields), records, ok, B, 4);
+}
+int rzk_packed_decode32_batch_dev(rzk_ctx* c, int kind, uint32_t V, const uint8_t* records, int32_t* const* fields, uint8_t* ok,
+                                  size_t B) {
+  return packed_decode_dev(c, kind, V, records, as64((const int32_t* const*)fields), ok, B, 4);
+}
+int rzk_packed_encode32_batch(rzk_ctx* c, int kind, uint32_t V, const int32_t* const* fields, uint8_t* records, uint8_t* ok,
+                              size_t B) {
+  return packed_encode_host(c, kind, V, as64(fields), records, ok, B, 4);
+}
+int rzk_packed_decode32_batch(rzk_ctx* c, int kind, uint32_t V, const uint8_t* records, int32_t* const* fields, uint8_t* ok,
+                              size_t B) {
+  return packed_decode_host(c, kind, V, records, as64((const int32_t* const*)fields), ok, B, 4);
 }
 
 // ---- v10: public polynomials expanded from 32-byte seeds, "XP1" (rzk_xof_dev.hip, rzk_xof.h; keys: rzk_key.cpp) ------------

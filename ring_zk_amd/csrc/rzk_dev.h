@@ -334,11 +334,13 @@ struct FsRoot {
 // leaf digests of B proofs: word w of leaf j = p * C + c of proof b at dig[(j * 4 + w) * B + b].  check != 0: every
 // coefficient is range-tested while it is loaded; a violation clears ok[b], or with ok == NULL sets *bad_word (the
 // context's sticky bad-input word), so that a non-canonical coefficient is never hashed silently as its low 32 bits.
+// width 4: the slabs of m hold int32_t coefficients (32-bit slabs; the addresses travel as int64_t*), fs_leaf_kernel<i32>
 int launch_fs_leaves(const LaunchCfg& cfg, const FsMsg& m, int64_t half, int check, uint64_t* dig, uint8_t* ok,
-                     uint32_t* bad_word, uint64_t B);
+                     uint32_t* bad_word, uint64_t B, uint32_t width = 8);
 // root of every proof: digest [B][32] (may be NULL) and, with d != NULL, the challenge into d [B][N] (zeroed before)
+// width 4: d addresses an int32_t slab, fs_root_kernel<i32>
 int launch_fs_roots(const LaunchCfg& cfg, const FsRoot& r, const uint64_t* dig, int64_t* d, uint8_t* digest,
-                    uint64_t B);
+                    uint64_t B, uint32_t width = 8);
 // ---- keyed samplers (rzk_csprng_dev.hip; stream and maps in rzk_chacha.h): the distributions of launch_sample_*,
 // drawn from ChaCha20 blocks under the call's subkey = HChaCha20(key, nonce)
 int launch_sample_uniform_chacha(const LaunchCfg& cfg, int64_t* out, uint64_t npoly, uint32_t n_ring, const uint32_t subkey[8],
@@ -388,15 +390,20 @@ int launch_shift_rows32(int logn, const LaunchCfg& cfg, const RowArgs& a, const 
 // both slabs 16-byte aligned
 int launch_narrow(const LaunchCfg& cfg, const int64_t* in, int32_t* out, uint64_t ncoef, uint32_t qhalf, uint32_t* bad_word);
 int launch_widen(const LaunchCfg& cfg, const int32_t* in, int64_t* out, uint64_t ncoef);
+// eq[b] = (the two blocks of `words` int32 words of entry b are equal word for word), no range test; words % 4 == 0, both
+// slabs 16-byte aligned
+int launch_eq32(const LaunchCfg& cfg, const int32_t* a, const int32_t* b, uint64_t words, uint8_t* eq, uint64_t B);
 // ---- fixed-width packed records (rzk_packed_dev.hip; format in rzk_packed.h) -------------------------------------------
 struct PackedSlabs {
   int64_t* ptr[kPackedMaxFields];   // dense slab of every field ([B][rows of the field][N]), 16-byte aligned
 };
 // rec: [B][s.rec_words] 64-bit words.  ok[b] must hold 1 before the launch; it is cleared for a message with a coefficient
 // outside its class's range (encode: the marker is written in its place) / a record that does not decode
-int launch_packed_encode(const LaunchCfg& cfg, const PackedSchema& s, const PackedSlabs& sl, uint64_t* rec, uint8_t* ok, uint64_t B);
+// width 4: the slabs hold int32_t coefficients (their addresses travel as int64_t*), packed_*_kernel<i32>
+int launch_packed_encode(const LaunchCfg& cfg, const PackedSchema& s, const PackedSlabs& sl, uint64_t* rec, uint8_t* ok, uint64_t B,
+                         uint32_t width = 8);
 int launch_packed_decode(const LaunchCfg& cfg, const PackedSchema& s, const PackedSlabs& sl, const uint64_t* rec, uint8_t* ok,
-                         uint64_t B);
+                         uint64_t B, uint32_t width = 8);
 // ---- seed expansion "XP1" (rzk_xof_dev.hip; format in rzk_xof.h) ---------------------------------------------------------
 struct XofJob {
   uint64_t q;

@@ -138,7 +138,9 @@ RZK_FS_HD uint32_t shake256_next16(uint64_t (&s)[25], ShakeWords16& r) {
 // The FS1 challenge from stream[32:]: exactly kappa coefficients +-1, uniform over positions and signs (an inside-out
 // Fisher-Yates over the last kappa indices; a draw j = w & mask is accepted when j <= i, with probability > 1/2; bit 15
 // of the accepted word is the sign, free because N <= 2048).  c[0 .. N) must be zero on entry; kappa <= N.
-RZK_FS_HD void fs_sample_challenge(uint64_t (&s)[25], int64_t* c, uint32_t N, uint32_t kappa) {
+// Coef: int64_t, or int32_t for a 32-bit slab (the values are 0 and +-1 either way).
+template <class Coef>
+RZK_FS_HD void fs_sample_challenge(uint64_t (&s)[25], Coef* c, uint32_t N, uint32_t kappa) {
   ShakeWords16 r{kFsDigestWords, 0, 0};
   for (uint32_t i = N - kappa; i < N; ++i) {
     uint32_t mask = i;   // (1 << bit_length(i)) - 1
@@ -152,7 +154,7 @@ RZK_FS_HD void fs_sample_challenge(uint64_t (&s)[25], int64_t* c, uint32_t N, ui
       j = w & mask;
     } while (j > i);
     c[i] = c[j];
-    c[j] = 1 - 2 * (int64_t)(w >> 15);
+    c[j] = 1 - 2 * (Coef)(w >> 15);
   }
 }
 
@@ -187,8 +189,11 @@ RZK_FS_HD uint32_t fs_leaf_words(uint32_t N) { return 2 + fs_leaf_len(N) / 2; }
 // word i >= 2 of a leaf: coefficients 2(i-2) and 2(i-2)+1 as little-endian two's-complement int32
 RZK_FS_HD uint64_t fs_pack_coefs(int64_t lo, int64_t hi) { return (uint64_t)(uint32_t)lo | ((uint64_t)(uint32_t)hi << 32); }
 
-struct FsLeafWords {   // leaf (p, c) over coefficients that sit in memory as int64 (the CPU form; the kernel stages them)
-  const int64_t* coef;   // P_p + c * LEAF
+// leaf (p, c) over coefficients that sit in memory as int64, or as the int32 of a 32-bit slab: the word the hash takes is
+// the int32 itself (the CPU form; the kernel stages them)
+template <class Coef>
+struct FsLeafWordsT {
+  const Coef* coef;   // P_p + c * LEAF
   uint32_t p, c;
   RZK_FS_HD uint64_t operator()(uint32_t i) const {
     if (i == 0) return kFsTagLeaf;
@@ -196,9 +201,11 @@ struct FsLeafWords {   // leaf (p, c) over coefficients that sit in memory as in
     return fs_pack_coefs(coef[2 * (i - 2)], coef[2 * (i - 2) + 1]);
   }
 };
-RZK_FS_HD void fs_leaf(const int64_t* poly, uint32_t N, uint32_t p, uint32_t c, uint64_t out[kFsDigestWords]) {
+using FsLeafWords = FsLeafWordsT<int64_t>;
+template <class Coef>
+RZK_FS_HD void fs_leaf(const Coef* poly, uint32_t N, uint32_t p, uint32_t c, uint64_t out[kFsDigestWords]) {
   uint64_t s[25];
-  FsLeafWords word{poly + (uint64_t)c * fs_leaf_len(N), p, c};
+  FsLeafWordsT<Coef> word{poly + (uint64_t)c * fs_leaf_len(N), p, c};
   shake256_absorb(s, word, fs_leaf_words(N), 0, 0);
   for (uint32_t i = 0; i < kFsDigestWords; ++i) out[i] = s[i];
 }

@@ -196,6 +196,18 @@ RZK_PK_HD bool packed_raw(int64_t c, const PackedWidth& w, uint32_t* raw) {
   return ok;
 }
 
+// The same rule for a coefficient of a 32-bit slab, in 32-bit arithmetic: raw = (uint32_t)c + bias, bad = raw > limit.
+// Exact for every class because limit = 2 bias and bias < 2^31 (Q: bias = h = (q-1)/2 < 2^31; Z: bias = verify_bound <= h;
+// D: bias = 1).  c > limit - bias = bias: c + bias <= 2^31 - 1 + bias < 2^32 does not wrap and exceeds the limit.
+// c < -bias: c + bias lies in [-2^31 + bias, -1], which wraps to at least 2^31 + bias > 2 bias = limit.  So for Q every
+// out-of-range c lands above 2h, and for Z and D, whose bias is small, a negative overshoot lands far above the limit.
+RZK_PK_HD bool packed_raw32(int32_t c, const PackedWidth& w, uint32_t* raw) {
+  const uint32_t u = (uint32_t)c + w.bias;
+  const bool ok = u <= w.limit;
+  *raw = ok ? u : (uint32_t)((1ull << w.W) - 1);
+  return ok;
+}
+
 // "put coefficient i": ORs raw (below 2^W) into the polynomial's words, which start out zero
 RZK_PK_HD void packed_put(uint64_t* words, uint32_t i, uint32_t W, uint32_t raw) {
   const uint64_t bit = (uint64_t)i * W;

@@ -1,5 +1,6 @@
 // rzk_slab32.cpp — the entry points over 32-bit coefficient slabs (include/rzk.h "32-bit slabs", v14; format and routing in
-// rzk_slab32.h): narrow / widen and the Open cycle.  A call whose programs have native 32-bit kernels on
+// rzk_slab32.h): narrow / widen, the Open cycle and the word-for-word compare rzk_eq32_batch (§19; the hash
+// and the packed codec on 32-bit slabs sit beside their 64-bit siblings in rzk_codec.cpp).  A call whose programs have native 32-bit kernels on
 // this context (slab32_native) launches them on the caller's slabs; every other call converts: it widens its inputs into
 // the context's grow-only arena ws32, calls its 64-bit sibling there and narrows the outputs — a completeness path, not a
 // performance path.  Verdicts, fault rules and the fused norm predicate are the siblings' in both.
@@ -156,6 +157,18 @@ int rzk_open_recover32_batch_dev(rzk_ctx* c, const int32_t* z, const int32_t* cm
   return a1_relation32(c, z, t_out, cm, d, accept, B, true);
 }
 
+// v14, slab32 messages: the compare of the short verifier.  No range test: the verdict of the consuming
+// call (rzk_open_recover32_batch) has tested what it read.
+int rzk_eq32_batch_dev(rzk_ctx* c, const int32_t* a, const int32_t* b, uint32_t rows, uint8_t* eq, size_t B) {
+  if (c && B == 0) return RZK_OK;
+  if (!c || !a || !b || !eq) return RZK_E_ARG;
+  if (rows == 0) return fail(c, RZK_E_ARG, "eq32: rows must be at least 1");
+  if (misaligned({a, b})) return align_fail(c);
+  const uint64_t words = (uint64_t)rows * c->N;   // a multiple of 4 (N >= 4 is a power of two)
+  return run_profiled(c, (uint64_t)B * words * 8ull, "eq32 kernel",
+                      [&](const LaunchCfg& cfg) { return launch_eq32(cfg, a, b, words, eq, B); });
+}
+
 // ---- host-pointer forms: staged through HostCall like every other entry point ------------------------------------------
 int rzk_narrow_batch(rzk_ctx* c, const int64_t* in, int32_t* out, size_t count) {
   if (c && count == 0) return RZK_OK;
@@ -173,6 +186,15 @@ int rzk_widen_batch(rzk_ctx* c, const int32_t* in, int64_t* out, size_t count) {
   const auto din = h.in(in, polys(c, count) / 2);
   const auto dout = h.pout(out, count);
   return h.run([&] { return rzk_widen_batch_dev(c, din, dout, count); });
+}
+
+int rzk_eq32_batch(rzk_ctx* c, const int32_t* a, const int32_t* b, uint32_t rows, uint8_t* eq, size_t B) {
+  if (c && B == 0) return RZK_OK;
+  if (!c || !a || !b || !eq) return RZK_E_ARG;
+  HostCall h(c);
+  const auto da = h.in(a, polys(c, B * rows) / 2), db = h.in(b, polys(c, B * rows) / 2);
+  const auto deq = h.out(eq, B);
+  return h.run([&] { return rzk_eq32_batch_dev(c, da, db, rows, deq, B); });
 }
 
 int rzk_open_commit32_batch(rzk_ctx* c, const int32_t* x, const int32_t* r, const int32_t* y, int32_t* cm, int32_t* t, uint8_t* ok,

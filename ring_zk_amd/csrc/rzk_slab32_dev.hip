@@ -12,6 +12,9 @@
 //   widen_kernel     int32 slab -> int64 slab (sign extension)
 //                    plain streaming kernels, two coefficients per thread and trip: 16-byte accesses on the wide side,
 //                    8-byte on the narrow one, grid-stride under the context's grid cap.
+//   eq32_kernel      eq[b] = (two blocks of int32 words are equal word for word): the compare of the short verifier on
+//                    32-bit slabs.  One wavefront per batch entry, 16-byte loads, lane-consecutive, four
+//                    wavefronts per workgroup, grid-stride; every entry's byte is written, so there is no preset.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -45,6 +48,25 @@ __global__ void __launch_bounds__(256) widen_kernel(const int2* __restrict__ in,
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < npairs; i += (uint64_t)gridDim.x * 256) {
     const int2 t = ld_stream(in + i);
     st_stream(o4 + i, make_int4(t.x, t.x >> 31, t.y, t.y >> 31));
+  }
+}
+
+constexpr uint32_t kEqWaves = 4;
+
+__global__ void __launch_bounds__(64 * kEqWaves) eq32_kernel(const int4* __restrict__ a, const int4* __restrict__ b, uint64_t quads,
+                                                             uint8_t* __restrict__ eq, uint64_t B) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  for (uint64_t e = (uint64_t)blockIdx.x * kEqWaves + wave; e < B; e += (uint64_t)gridDim.x * kEqWaves) {
+    const int4* pa = a + e * quads;
+    const int4* pb = b + e * quads;
+    uint32_t diff = 0;
+    for (uint64_t i = lane; i < quads; i += 64) {
+      const int4 x = ld_stream(pa + i), y = ld_stream(pb + i);
+      diff |= (uint32_t)((x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w));
+    }
+    const bool any = __builtin_amdgcn_ballot_w64(diff != 0) != 0;
+    if (lane == 0) eq[e] = any ? 0 : 1;
   }
 }
 
@@ -103,6 +125,18 @@ int launch_narrow(const LaunchCfg& cfg, const int64_t* in, int32_t* out, uint64_
                      reinterpret_cast<const longlong2*>(in), reinterpret_cast<int2*>(out), npairs, qhalf, bad_word);
   RZK_LAUNCH_CHECK();
   if (cfg.launched) *cfg.launched = "narrow_kernel";
+  return 0;
+}
+
+int launch_eq32(const LaunchCfg& cfg, const int32_t* a, const int32_t* b, uint64_t words, uint8_t* eq, uint64_t B) {
+  if (B == 0) return 0;
+  uint64_t blocks = (B + kEqWaves - 1) / kEqWaves;
+  const uint64_t cap = (uint64_t)cfg.num_cus * 8;
+  if (blocks > cap) blocks = cap;
+  hipLaunchKernelGGL(eq32_kernel, dim3((unsigned)blocks), dim3(64 * kEqWaves), 0, (hipStream_t)cfg.stream,
+                     reinterpret_cast<const int4*>(a), reinterpret_cast<const int4*>(b), words / 4, eq, B);
+  RZK_LAUNCH_CHECK();
+  if (cfg.launched) *cfg.launched = "eq32_kernel";
   return 0;
 }
 

@@ -10,6 +10,8 @@ rzk_fs_challenge_batch[_dev]): a proof is (commitment message, response), and an
   * `verify_open_wire`: the same verdict from serialized OpenProofCommitment / OpenProofResponse messages;
   * `open_verify_packed`, `linear_verify_packed`, `sum_verify_packed`: the same verdicts from fixed-width packed records
     (`packed.py`, DESIGN.md §13);
+  * `challenge32`, `open_prove32`, `open_verify32`, `open_short32`, `open_verify_short32`, `open_verify_packed32`,
+    `open_verify_short_packed32`: the Open proof on int32 slabs (DESIGN.md §19);
   * `open_short` / `open_verify_short` / `open_verify_short_packed`: the signature form of an Open proof, (c, d, z): the
     verifier recomputes t from the verification equation and accepts iff the transcript of (c, t) gives d again;
   * `linear_short` / `linear_verify_short[_packed]`, `sum_short` / `sum_verify_short[_packed]`: the same for Linear and
@@ -60,6 +62,18 @@ def challenge(ctx, kind: int, *slabs, V: Optional[int] = None, aux=None):
 
     d [B][N] int64: the challenges; digest [B][32] uint8: the transcript digests; ok [B] uint8: 0 where a coefficient
     of the proof is not a centred residue mod q (its d and digest are then unspecified)."""
+    return _challenge(ctx, kind, slabs, V, aux, np.int64)
+
+
+def challenge32(ctx, kind: int, *slabs, V: Optional[int] = None, aux=None):
+    """challenge for int32 slabs (numpy int32 arrays or torch int32 CUDA tensors, rzk_fs_challenge32_batch[_dev]): the
+    same digest and ok as challenge on the widened slabs, and the same d as int32.  The transcript hashes a coefficient
+    as its int32, so nothing is converted."""
+    return _challenge(ctx, kind, slabs, V, aux, np.int32)
+
+
+def _challenge(ctx, kind, slabs, V, aux, dt):
+    w32 = dt is np.int32
     if kind not in KINDS:
         raise ValueError("challenge: kind must be MSG_OPEN_COMMITMENT, MSG_LINEAR_COMMITMENT or MSG_SUM_COMMITMENT")
     shapes = wire.field_shapes(ctx, kind, V)
@@ -74,19 +88,21 @@ def challenge(ctx, kind: int, *slabs, V: Optional[int] = None, aux=None):
         import torch
 
         slabs = [s.contiguous() for s in slabs]
-        if any(s.dtype != torch.int64 or not s.is_cuda for s in slabs):
-            raise ValueError("device slabs must be int64 CUDA tensors")
-        d = torch.empty((B, ctx.N), dtype=torch.int64, device=slabs[0].device)
+        if any(s.dtype != (torch.int32 if w32 else torch.int64) or not s.is_cuda for s in slabs):
+            raise ValueError("device slabs must be %s CUDA tensors" % ("int32" if w32 else "int64"))
+        d = torch.empty((B, ctx.N), dtype=torch.int32 if w32 else torch.int64, device=slabs[0].device)
         digest = torch.empty((B, 32), dtype=torch.uint8, device=slabs[0].device)
         ok = torch.empty(B, dtype=torch.uint8, device=slabs[0].device)
         ctx._bind_torch_stream()
-        fn = ctx._L.rzk_fs_challenge_batch_dev
+        fn = ctx._L.rzk_fs_challenge32_batch_dev if w32 else ctx._L.rzk_fs_challenge_batch_dev
     else:
-        slabs = [np.ascontiguousarray(s, dtype=np.int64) for s in slabs]
-        d = np.empty((B, ctx.N), dtype=np.int64)
+        if w32 and any(s.dtype != np.int32 for s in slabs):
+            raise ValueError("host slabs must be int32 numpy arrays")
+        slabs = [np.ascontiguousarray(s, dtype=dt) for s in slabs]
+        d = np.empty((B, ctx.N), dtype=dt)
         digest = np.empty((B, 32), dtype=np.uint8)
         ok = np.empty(B, dtype=np.uint8)
-        fn = ctx._L.rzk_fs_challenge_batch
+        fn = ctx._L.rzk_fs_challenge32_batch if w32 else ctx._L.rzk_fs_challenge_batch
     fields = (C.c_void_p * len(slabs))(*[wire._ptr(s).value for s in slabs])
     ctx._check(fn(ctx._h, kind, V or 0, fields, _aux(aux), wire._ptr(d), wire._ptr(digest), wire._ptr(ok), B))
     return d, digest, ok
@@ -171,6 +187,50 @@ def open_verify_short_packed(ctx, records, aux=None):
     """open_verify_short from packed MSG_OPEN_SHORT records; a record that does not decode rejects its own proof."""
     c, d, z, ok = packed.decode_batch(ctx, MSG_OPEN_SHORT, records)
     return open_verify_short(ctx, c, d, z, aux=aux) & ok
+
+
+# ---- OpenProof on 32-bit slabs (DESIGN.md §19): the functions above restated on open_*32, challenge32, decode_batch32 and
+# eq32.  Every slab is int32 (numpy or torch CUDA); no 64-bit slab and no convert launch appears between record and verdict.
+def open_prove32(ctx, x, r, y, aux=None):
+    """open_prove on int32 slabs: (c, t, z, ok), each the int32 of open_prove's."""
+    c, t, ok = ctx.open_commit32(x, r, y)
+    d, _, okf = challenge32(ctx, MSG_OPEN_COMMITMENT, c, t, aux=aux)
+    z = ctx.open_response32(y, r, d)
+    return c, t, z, ok & okf
+
+
+def open_verify32(ctx, c, t, z, aux=None):
+    """open_verify on int32 slabs."""
+    d, _, okf = challenge32(ctx, MSG_OPEN_COMMITMENT, c, t, aux=aux)
+    return ctx.open_verify32(z, t, c, d) & okf
+
+
+def open_verify_packed32(ctx, commitment_records, response_records, aux=None):
+    """open_verify_packed through int32 slabs: the records are those of packed.encode_batch or encode_batch32."""
+    c, t, ok1 = packed.decode_batch32(ctx, MSG_OPEN_COMMITMENT, commitment_records)
+    (z, ok2) = packed.decode_batch32(ctx, MSG_OPEN_RESPONSE, response_records)
+    return open_verify32(ctx, c, t, z, aux=aux) & ok1 & ok2
+
+
+def open_short32(ctx, c, t, z, aux=None):
+    """open_short on int32 slabs: d = challenge32(c, t) as int32."""
+    d, _, _ = challenge32(ctx, MSG_OPEN_COMMITMENT, c, t, aux=aux)
+    return d
+
+
+def open_verify_short32(ctx, c, d, z, aux=None):
+    """open_verify_short on int32 slabs.  The recomputed challenge is compared with the caller's d word for word
+    (Context.eq32): a canonical d is its own canonical copy, and a non-canonical one has already cleared the verdict of
+    open_recover32, so the canonicalize launch of the 64-bit form has nothing to do here."""
+    t, acc = ctx.open_recover32(z, c, d)
+    d2, _, okf = challenge32(ctx, MSG_OPEN_COMMITMENT, c, t, aux=aux)
+    return acc & okf & ctx.eq32(d2.reshape(-1, 1, ctx.N), d.reshape(-1, 1, ctx.N))
+
+
+def open_verify_short_packed32(ctx, records, aux=None):
+    """open_verify_short_packed through int32 slabs: packed MSG_OPEN_SHORT records -> verdicts."""
+    c, d, z, ok = packed.decode_batch32(ctx, MSG_OPEN_SHORT, records)
+    return open_verify_short32(ctx, c, d, z, aux=aux) & ok
 
 
 # ---- LinearProof (src/prove/linear.rs) ---------------------------------------------------------------------------------

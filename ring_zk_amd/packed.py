@@ -1,4 +1,5 @@
-"""Fixed-width packed records "RZKP1" <-> dense int64 slabs (include/rzk.h "fixed-width packed records").
+"""Fixed-width packed records "RZKP1" <-> dense int64 slabs (include/rzk.h "fixed-width packed records"),
+or dense int32 slabs (`encode_batch32` / `decode_batch32`).
 
 The compact stored form of the protocol messages: every record of a kind has the same size (`record_bytes`), each
 coefficient takes the bits its field class needs (`widths`), and both directions are one GPU launch
@@ -69,6 +70,23 @@ def encode_batch(ctx, kind: int, *slabs, V: Optional[int] = None):
     records: uint8 [B][record_bytes]; ok: uint8 [B], 0 where a coefficient does not fit its field class (outside the
     centred range mod q, or a response coefficient beyond verify_bound): that record holds the all-ones marker in the
     coefficient's place and never decodes as valid."""
+    return _encode(ctx, kind, slabs, V, np.int64)
+
+
+def encode_batch32(ctx, kind: int, *slabs, V: Optional[int] = None):
+    """encode_batch for int32 slabs (numpy int32 arrays or torch int32 CUDA tensors, rzk_packed_encode32_batch[_dev]):
+    the same records and ok as encode_batch on the widened slabs.  Records carry no width."""
+    return _encode(ctx, kind, slabs, V, np.int32)
+
+
+def decode_batch32(ctx, kind: int, records, V: Optional[int] = None):
+    """decode_batch into int32 slabs (rzk_packed_decode32_batch[_dev]): the same ok, and for an accepted record the same
+    values as int32."""
+    return _decode(ctx, kind, records, V, np.int32)
+
+
+def _encode(ctx, kind, slabs, V, dt):
+    w32 = dt is np.int32
     shapes = field_shapes(ctx, kind, V)
     if len(slabs) != len(shapes):
         raise ValueError(f"{len(shapes)} field slabs expected, got {len(slabs)}")
@@ -82,17 +100,19 @@ def encode_batch(ctx, kind: int, *slabs, V: Optional[int] = None):
         import torch
 
         slabs = [s.contiguous() for s in slabs]
-        if any(s.dtype != torch.int64 or not s.is_cuda for s in slabs):
-            raise ValueError("device slabs must be int64 CUDA tensors")
+        if any(s.dtype != (torch.int32 if w32 else torch.int64) or not s.is_cuda for s in slabs):
+            raise ValueError("device slabs must be %s CUDA tensors" % ("int32" if w32 else "int64"))
         records = torch.empty((B, size), dtype=torch.uint8, device=slabs[0].device)
         ok = torch.empty(B, dtype=torch.uint8, device=slabs[0].device)
         ctx._bind_torch_stream()
-        fn = ctx._L.rzk_packed_encode_batch_dev
+        fn = ctx._L.rzk_packed_encode32_batch_dev if w32 else ctx._L.rzk_packed_encode_batch_dev
     else:
-        slabs = [np.ascontiguousarray(s, dtype=np.int64) for s in slabs]
+        if w32 and any(s.dtype != np.int32 for s in slabs):
+            raise ValueError("host slabs must be int32 numpy arrays")
+        slabs = [np.ascontiguousarray(s, dtype=dt) for s in slabs]
         records = np.empty((B, size // 8), dtype=np.uint64).view(np.uint8)   # 8-byte aligned
         ok = np.empty(B, dtype=np.uint8)
-        fn = ctx._L.rzk_packed_encode_batch
+        fn = ctx._L.rzk_packed_encode32_batch if w32 else ctx._L.rzk_packed_encode_batch
     if B:
         ctx._check(fn(ctx._h, kind, V or 0, _fields(slabs), wire._ptr(records), wire._ptr(ok), B))
     return records, ok
@@ -103,6 +123,11 @@ def decode_batch(ctx, kind: int, records, V: Optional[int] = None):
 
     ok[b] = 0 marks a record that does not decode (wrong header, a value above its class's limit, a set padding bit);
     its slabs are unspecified."""
+    return _decode(ctx, kind, records, V, np.int64)
+
+
+def _decode(ctx, kind, records, V, dt):
+    w32 = dt is np.int32
     shapes = field_shapes(ctx, kind, V)
     size = record_bytes(ctx, kind, V)
     total = int(np.prod(tuple(records.shape), dtype=np.int64))
@@ -117,19 +142,19 @@ def decode_batch(ctx, kind: int, records, V: Optional[int] = None):
         records = records.contiguous()
         if records.data_ptr() % 8:
             records = records.clone()
-        slabs = [torch.empty((B,) + sh, dtype=torch.int64, device=records.device) for _, sh in shapes]
+        slabs = [torch.empty((B,) + sh, dtype=torch.int32 if w32 else torch.int64, device=records.device) for _, sh in shapes]
         ok = torch.empty(B, dtype=torch.uint8, device=records.device)
         ctx._bind_torch_stream()
-        fn = ctx._L.rzk_packed_decode_batch_dev
+        fn = ctx._L.rzk_packed_decode32_batch_dev if w32 else ctx._L.rzk_packed_decode_batch_dev
     else:
         records = np.ascontiguousarray(records, dtype=np.uint8)
         if records.ctypes.data % 8:
             aligned = np.empty(total // 8, dtype=np.uint64).view(np.uint8)
             aligned[:] = records.reshape(-1)
             records = aligned
-        slabs = [np.empty((B,) + sh, dtype=np.int64) for _, sh in shapes]
+        slabs = [np.empty((B,) + sh, dtype=dt) for _, sh in shapes]
         ok = np.empty(B, dtype=np.uint8)
-        fn = ctx._L.rzk_packed_decode_batch
+        fn = ctx._L.rzk_packed_decode32_batch if w32 else ctx._L.rzk_packed_decode_batch
     if B:
         ctx._check(fn(ctx._h, kind, V or 0, wire._ptr(records), _fields(slabs), wire._ptr(ok), B))
     return (*slabs, ok)
