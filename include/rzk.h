@@ -604,6 +604,41 @@ int rzk_sum_response_reject_batch_dev(rzk_ctx* ctx, uint32_t V, const int64_t* y
                                       const int64_t* rp, const int64_t* d, const int64_t* coin, uint64_t R, double lnM,
                                       int64_t* zs, int64_t* zp, uint8_t* accept, int64_t* E, size_t B);
 
+/* ---- 32-bit slabs: the zero-knowledge Open prover (v14, slab32 prover) ---------------------------------------
+ * What a prover that draws its own r and y and loops over the rejection step needs on int32_t slabs, so that x -> (c, t, z)
+ * runs without a 64-bit slab or a convert launch.  Additions only: RZK_ABI_VERSION stays 14 and every earlier signature is
+ * unchanged.  Each call has the argument list of the 64-bit sibling named below with int32_t* slabs; argument rules, NULL
+ * rules, count == 0 / B == 0, fault reporting and trusted-producer mode are the sibling's; device slabs are 16-byte aligned
+ * (RZK_E_ARG otherwise), as everywhere in the 32-bit sections above.
+ * rzk_sample_{uniform,gauss,dgauss,challenge}_keyed32_dev
+ *                                   siblings rzk_sample_*_keyed_dev (device only).  The same stream: for the same key, nonce,
+ *                                   stream and arguments, out is narrow() of the sibling's out, coefficient by coefficient.
+ *                                   Every value an accepted argument can produce lies inside int32_t (uniform: |v| <=
+ *                                   (q-1)/2 < 2^31; gauss: |v| < 5.8e8 at sigma = 2^26; dgauss: tail cut at 9.4 sigma),
+ *                                   so there is no further range rule.
+ * rzk_matvec32_batch                sibling rzk_matvec_batch (addend may be NULL): out = narrow() of its out; prover side, a
+ *                                   non-canonical coefficient is an input fault of the call.
+ * rzk_open_response_reject32_batch  sibling rzk_open_response_reject_batch with y, r, d, z as int32_t slabs; coin and E stay
+ *                                   int64_t, accept uint8_t.  z is narrow() of the sibling's z; accept and E are byte for
+ *                                   byte the sibling's on widen(y, r, d).
+ * Native 32-bit kernels run where those of the Open cycle do (N = 512 and 1024, n = 1, default rotation knobs); every other
+ * context converts inside the call. */
+int rzk_sample_uniform_keyed32_dev(rzk_ctx* ctx, const uint8_t nonce[16], uint32_t stream, uint64_t bound, int32_t* out,
+                                   size_t count);
+int rzk_sample_gauss_keyed32_dev(rzk_ctx* ctx, const uint8_t nonce[16], uint32_t stream, double sigma, int32_t* out,
+                                 size_t count);
+int rzk_sample_challenge_keyed32_dev(rzk_ctx* ctx, const uint8_t nonce[16], uint32_t stream, int32_t* out, size_t count);
+int rzk_sample_dgauss_keyed32_dev(rzk_ctx* ctx, const uint8_t nonce[16], uint32_t stream, uint32_t sigma, int32_t* out,
+                                  size_t count);
+int rzk_matvec32_batch(rzk_ctx* ctx, int which, const int32_t* v, const int32_t* addend, int32_t* out,
+                       size_t B);
+int rzk_matvec32_batch_dev(rzk_ctx* ctx, int which, const int32_t* v, const int32_t* addend,
+                           int32_t* out, size_t B);
+int rzk_open_response_reject32_batch(rzk_ctx* ctx, const int32_t* y, const int32_t* r, const int32_t* d, const int64_t* coin,
+                                     uint64_t R, double lnM, int32_t* z, uint8_t* accept, int64_t* E, size_t B);
+int rzk_open_response_reject32_batch_dev(rzk_ctx* ctx, const int32_t* y, const int32_t* r, const int32_t* d, const int64_t* coin,
+                                         uint64_t R, double lnM, int32_t* z, uint8_t* accept, int64_t* E, size_t B);
+
 /* ---- fixed-width packed records "RZKP1" (v8; batched, on the GPU) ----------------------------------------------------------
  * The bincode form above is the reference's: 8 bytes per coefficient and polynomials of variable length.  For proofs that
  * are stored and verified later this is the compact form: every record of a kind has the same size, known on the host, and

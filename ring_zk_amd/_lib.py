@@ -118,6 +118,13 @@ SIGNATURES = {
     "rzk_packed_encode32_batch": (C.c_int, [_CTX, C.c_int, C.c_uint32, C.c_void_p, _U8, _U8, _SZ]),
     "rzk_packed_decode32_batch": (C.c_int, [_CTX, C.c_int, C.c_uint32, _U8, C.c_void_p, _U8, _SZ]),
     "rzk_eq32_batch": (C.c_int, [_CTX, _I32, _I32, C.c_uint32, _U8, _SZ]),
+    # v14, slab32 prover: keyed samplers writing int32 slabs, a1.y and the response with its rejection test on int32 slabs
+    "rzk_sample_uniform_keyed32_dev": (C.c_int, [_CTX, _U8, C.c_uint32, C.c_uint64, _I32, _SZ]),
+    "rzk_sample_gauss_keyed32_dev": (C.c_int, [_CTX, _U8, C.c_uint32, C.c_double, _I32, _SZ]),
+    "rzk_sample_challenge_keyed32_dev": (C.c_int, [_CTX, _U8, C.c_uint32, _I32, _SZ]),
+    "rzk_sample_dgauss_keyed32_dev": (C.c_int, [_CTX, _U8, C.c_uint32, C.c_uint32, _I32, _SZ]),
+    "rzk_matvec32_batch": (C.c_int, [_CTX, C.c_int, _I32, _I32, _I32, _SZ]),
+    "rzk_open_response_reject32_batch": (C.c_int, [_CTX] + [_I32] * 3 + [_I64, C.c_uint64, C.c_double, _I32, _U8, _I64, _SZ]),
     # v8: fixed-width packed records
     "rzk_packed_record_bytes": (C.c_size_t, [_CTX, C.c_int, C.c_uint32]),
     "rzk_packed_widths": (C.c_int, [_CTX, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

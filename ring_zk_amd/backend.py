@@ -634,6 +634,69 @@ class Context:
         self._check(self._fn("rzk_eq32_batch", dev)(self._h, p[0], p[1], rows, p[2], B))
         return out
 
+    # ---- the zero-knowledge Open prover on int32 slabs (include/rzk.h "slab32 prover") -----------------
+    def _sample_out32(self, lead):
+        import torch
+
+        self._bind_torch_stream()
+        shape = tuple(lead) + (self.N,)
+        out = torch.empty(shape, dtype=torch.int32, device=torch.device("cuda", self.device))
+        return out, int(np.prod(shape[:-1], dtype=np.int64))
+
+    def sample_uniform_keyed32(self, nonce: bytes, stream: int, bound: int, lead):
+        """sample_uniform_keyed as an int32 tensor: the same stream, the same values."""
+        out, cnt = self._sample_out32(lead)
+        self._check(self._L.rzk_sample_uniform_keyed32_dev(self._h, self._nonce(nonce), stream, bound,
+                                                           C.c_void_p(out.data_ptr()), cnt))
+        return out
+
+    def sample_gauss_keyed32(self, nonce: bytes, stream: int, sigma: float, lead):
+        """sample_gauss_keyed as an int32 tensor."""
+        out, cnt = self._sample_out32(lead)
+        self._check(self._L.rzk_sample_gauss_keyed32_dev(self._h, self._nonce(nonce), stream, float(sigma),
+                                                         C.c_void_p(out.data_ptr()), cnt))
+        return out
+
+    def sample_dgauss_keyed32(self, nonce: bytes, stream: int, sigma: int, lead):
+        """sample_dgauss_keyed as an int32 tensor."""
+        if int(sigma) != sigma:
+            raise ValueError("sample_dgauss_keyed32: sigma must be an integer")
+        out, cnt = self._sample_out32(lead)
+        self._check(self._L.rzk_sample_dgauss_keyed32_dev(self._h, self._nonce(nonce), stream, int(sigma),
+                                                          C.c_void_p(out.data_ptr()), cnt * self.N))
+        return out
+
+    def sample_challenge_keyed32(self, nonce: bytes, stream: int, lead):
+        """sample_challenge_keyed as an int32 tensor."""
+        out, cnt = self._sample_out32(lead)
+        self._check(self._L.rzk_sample_challenge_keyed32_dev(self._h, self._nonce(nonce), stream,
+                                                             C.c_void_p(out.data_ptr()), cnt))
+        return out
+
+    def matvec32(self, which: int, v, addend=None):
+        """matvec on int32 slabs (rzk_matvec32_batch): narrow() of matvec's output."""
+        B = self._shape(v, self.k, self.N)
+        rows = self._rows(which)
+        if addend is not None and self._shape(addend, rows, self.N) != B:
+            raise ValueError("matvec32: addend batch differs")
+        out = self._empty(v, tuple(v.shape[:-2]) + (rows, self.N), np.int32)
+        dev, p = self._prep([v, addend, out], [np.int32] * 3)
+        self._check(self._fn("rzk_matvec32_batch", dev)(self._h, which, p[0], p[1], p[2], B))
+        return out
+
+    def open_response_reject32(self, y, r, d, coin, R: int, lnM: float):
+        """open_response_reject on int32 slabs y, r, d (coin stays int64): (z int32, accept, E), z = narrow() of the
+        sibling's and accept, E byte for byte the sibling's."""
+        B = self._shape(y, self.k, self.N)
+        if self._shape(r, self.k, self.N) != B or self._shape(d, self.N) != B or int(coin.shape[0]) != B or coin.ndim != 1:
+            raise ValueError("open_response_reject32: batch / shape mismatch")
+        z = self._empty(y, tuple(y.shape), np.int32)
+        accept = self._empty(coin, (B,), np.uint8)
+        E = self._empty(coin, (B,), np.int64)
+        dev, p = self._prep([y, r, d, coin, z, accept, E], [np.int32] * 3 + [np.int64, np.int32, np.uint8, np.int64])
+        self._check(self._fn("rzk_open_response_reject32_batch", dev)(self._h, *p[:4], R, float(lnM), *p[4:], B))
+        return z, accept, E
+
     # ---- LinearProof (src/prove/linear.rs) ------------------------------------------------------------------------
     def linear_commit(self, g, x, r, rp, y, yp):
         B = self._shape(x, self.l, self.N)
@@ -818,3 +881,27 @@ class ExactKeyedSampler(KeyedSampler):
         if int(sigma) != sigma:
             raise ValueError("ExactKeyedSampler.gauss: sigma must be an integer")
         return self.ctx.sample_dgauss_keyed(self._next_nonce(), self.STREAM, int(sigma), lead)
+
+
+class KeyedSampler32(KeyedSampler):
+    """KeyedSampler whose draws are int32 tensors (Context.sample_*_keyed32).  Same key, nonce counter and
+    streams: a KeyedSampler32 and a KeyedSampler made with the same key and nonce0 consume nonces identically and
+    return the same values in two widths."""
+
+    def uniform(self, bound: int, lead):
+        return self.ctx.sample_uniform_keyed32(self._next_nonce(), self.STREAM, bound, lead)
+
+    def gauss(self, sigma: float, lead):
+        return self.ctx.sample_gauss_keyed32(self._next_nonce(), self.STREAM, sigma, lead)
+
+    def challenge(self, lead):
+        return self.ctx.sample_challenge_keyed32(self._next_nonce(), self.STREAM, lead)
+
+
+class ExactKeyedSampler32(KeyedSampler32):
+    """ExactKeyedSampler on int32 tensors: `gauss` draws from the exact discrete Gaussian (Context.sample_dgauss_keyed32)."""
+
+    def gauss(self, sigma, lead):
+        if int(sigma) != sigma:
+            raise ValueError("ExactKeyedSampler32.gauss: sigma must be an integer")
+        return self.ctx.sample_dgauss_keyed32(self._next_nonce(), self.STREAM, int(sigma), lead)

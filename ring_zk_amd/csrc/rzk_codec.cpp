@@ -356,6 +356,23 @@ int rzk_open_response_reject_batch_dev(rzk_ctx* c, const int64_t* y, const int64
   });
 }
 
+// v14, slab32 prover (rzk_slab32.cpp routes here): the same call with width 4.  The partials, the decision
+// kernel, coin, accept and E do not see the width; reject_args and RejectParts only carry the addresses of z and y.
+int rzk::api::open_response_reject_native32(rzk_ctx* c, const int32_t* y, const int32_t* r, const int32_t* d, const int64_t* coin,
+                                            uint64_t R, double lnM, int32_t* z, uint8_t* accept, int64_t* E, size_t B) {
+  const uint32_t k = c->k;
+  const int64_t* y64 = reinterpret_cast<const int64_t*>(y);
+  const int64_t* r64 = reinterpret_cast<const int64_t*>(r);
+  const int64_t* d64 = reinterpret_cast<const int64_t*>(d);
+  const int64_t* z64 = reinterpret_cast<const int64_t*>(z);
+  const int64_t *zs[1] = {z64}, *ys[1] = {y64};
+  const uint32_t rows[1] = {k};
+  return response_reject(c, 1, zs, ys, rows, coin, R, lnM, accept, E, B, [&](const ResponseStat* st) {
+    if (!st) return fail(c, RZK_E_STATE, "response reject on 32-bit slabs needs the fused rows");
+    return run_program(c, PG_RESPONSE, 1, {{d64, 1, 0}, {y64, k, 0}, {r64, k, 0}, {z64, k, 0}}, nullptr, 1, B, 0, true, 0, 0, st, 4);
+  });
+}
+
 int rzk_linear_response_reject_batch_dev(rzk_ctx* c, const int64_t* y, const int64_t* yp, const int64_t* r, const int64_t* rp,
                                          const int64_t* d, const int64_t* coin, uint64_t R, double lnM, int64_t* z, int64_t* zp,
                                          uint8_t* accept, int64_t* E, size_t B) {

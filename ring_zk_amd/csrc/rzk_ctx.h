@@ -221,6 +221,10 @@ struct OimgProducer {
 };
 
 // ---- rzk_codec.cpp ---------------------------------------------------------------------------------------------------
+// rzk_open_response_reject_batch_dev on int32_t slabs y, r, d, z where the fused rows run natively (the caller has asked
+// program_native32(c, PG_RESPONSE, 1) && response_stat_fused(c)): the sibling's argument rules, launches and outputs
+int open_response_reject_native32(rzk_ctx* c, const int32_t* y, const int32_t* r, const int32_t* d, const int64_t* coin, uint64_t R,
+                                  double lnM, int32_t* z, uint8_t* accept, int64_t* E, size_t B);
 // out[b][r] = polynomial p0 + r of XP1 under seeds[b] and `domain`; seeds and out on the device
 int run_xof(rzk_ctx* c, uint32_t domain, uint32_t p0, uint32_t rows, const uint64_t* seeds, int64_t* out, size_t B);
 

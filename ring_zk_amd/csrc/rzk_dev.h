@@ -343,16 +343,17 @@ int launch_fs_roots(const LaunchCfg& cfg, const FsRoot& r, const uint64_t* dig, 
                     uint64_t B, uint32_t width = 8);
 // ---- keyed samplers (rzk_csprng_dev.hip; stream and maps in rzk_chacha.h): the distributions of launch_sample_*,
 // drawn from ChaCha20 blocks under the call's subkey = HChaCha20(key, nonce)
+// width 4: out addresses an int32_t slab (16-byte aligned), sample_*_chacha_kernel_i32: the same streams, narrowed at the store
 int launch_sample_uniform_chacha(const LaunchCfg& cfg, int64_t* out, uint64_t npoly, uint32_t n_ring, const uint32_t subkey[8],
-                                 uint32_t stream, uint32_t bound);
+                                 uint32_t stream, uint32_t bound, uint32_t width = 8);
 int launch_sample_gauss_chacha(const LaunchCfg& cfg, int64_t* out, uint64_t npoly, uint32_t n_ring, const uint32_t subkey[8],
-                               uint32_t stream, double sigma);
+                               uint32_t stream, double sigma, uint32_t width = 8);
 int launch_sample_challenge_chacha(const LaunchCfg& cfg, int64_t* out, uint64_t npoly, uint32_t n_ring, const uint32_t subkey[8],
-                                   uint32_t stream, uint32_t kappa);
+                                   uint32_t stream, uint32_t kappa, uint32_t width = 8);
 // the exact discrete Gaussian D_sigma, integer sigma in [1, 2^26] (definition and stream: rzk_dgauss.h), and its trial
 // on chosen words: words [trials][8] -> out [trials][2] = (accepted, value)
 int launch_sample_dgauss_chacha(const LaunchCfg& cfg, int64_t* out, uint64_t npoly, uint32_t n_ring, const uint32_t subkey[8],
-                                uint32_t stream, uint32_t sigma);
+                                uint32_t stream, uint32_t sigma, uint32_t width = 8);
 int launch_debug_dgauss_trial(const LaunchCfg& cfg, uint32_t sigma, const uint32_t* words, int64_t* out, uint64_t trials);
 // ---- rejection sampling of the provers (rzk_reject_dev.hip; definition in rzk_reject.h) --------------------------------
 struct RejectPartial;
@@ -381,6 +382,10 @@ struct ResponseStat {   // where a launch of response_stat_kernel leaves its par
 // (b mod group) * nrows + rowi], group = Operands::group.
 int launch_response_stat(int logn, const LaunchCfg& cfg, const RowArgs& a, const Operands& ops, uint32_t nrows, uint64_t batch,
                          const ResponseStat& so);
+// ... on int32_t slabs (Operands::base address them): the packed-byte form at N = 512 / 1024, response_stat_kernel<., ., i32>
+// (-1 otherwise: the caller converts)
+int launch_response_stat32(int logn, const LaunchCfg& cfg, const RowArgs& a, const Operands& ops, uint32_t nrows, uint64_t batch,
+                           const ResponseStat& so);
 // ---- 32-bit coefficient slabs (rzk_slab32_dev.hip; format and routing in rzk_slab32.h) ------------------
 // launch_units / launch_shift_rows for a launch whose Operands::base address int32_t slabs: key-product programs, one-wavefront
 // teams, N = 512 / 1024, the packed-byte rotation kernel (-1 otherwise: the caller converts, slab32_native)

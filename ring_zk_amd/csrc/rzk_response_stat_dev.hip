@@ -10,9 +10,12 @@
 //                                 reject_decide_kernel expects it.  No atomics, no LDS beyond the image, no scratch.
 // One-wavefront teams only (N = 512, 1024); every other shape runs the response launch and reject_stat_kernel
 // (rzk_protocols.cpp, response_reject).
+// The kernel exists for int64_t slabs and, in its packed-byte form, for the 32-bit slabs of DESIGN.md §18 (reported as
+// response_stat_kernel<LOGN, TRUSTED, i32>), from one text (rzk_response_stat_kernel.inc).
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <type_traits>
 
 #include "rzk_dev.h"
 #include "rzk_reject.h"
@@ -25,111 +28,30 @@ namespace {
 
 constexpr int kTeams = 4;   // wavefronts per workgroup, one 8 N-byte image each (ShiftCfg<LOGN, WaveTeam>)
 
-template <int LOGN, bool TRUSTED, bool BYTES>
-__global__ void __launch_bounds__(64 * kTeams, (BYTES ? RZK_SHIFT_BYTES_WAVES : 1))
-response_stat_kernel(const Program* __restrict__ prog, const Operands ops, const DevTables* __restrict__ Tp, const uint32_t ntasks,
-                     const ResponseStat so) {
-  using S = ShiftGeo<LOGN, true, 6>;
-  constexpr int E = S::E;
-  constexpr int N = S::N;
-  constexpr int LANES = S::LANES;
-  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  const int lane = threadIdx.x & (LANES - 1);
-  const uint32_t team = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  int32_t* slab = reinterpret_cast<int32_t*>(smem) + team * S::WORDS;
-  const DevTables& T = *Tp;
-  const uint32_t q = T.crt.q;
-  const uint32_t nrows = prog->nrows;
-
-  for (uint32_t task = blockIdx.x * kTeams + team; task < ntasks; task += gridDim.x * kTeams) {
-    const uint32_t b = task / nrows;
-    const uint32_t rowi = task - b * nrows;
-    const uint32_t bo = ops.group > 1 ? b / ops.group : b;
-    const Row row = prog->rows[rowi];
-    const uint32_t qhalf = T.crt.qhalf;
-    constexpr bool trusted = TRUSTED;
-    bool fault = false;
-    {
-      uint32_t res[E];
-#pragma unroll
-      for (int i = 0; i < E; ++i) res[i] = 0;
-#pragma unroll 1
-      for (uint32_t t = 0; t < row.nterms; ++t) {
-        const Term tm = prog->terms[row.term0 + t];
-        int32_t a[E];
-        uint32_t abad = 0, amx = 0;
-        load_pairs<LOGN, 6>(a, operand_ptr(ops, tm.a_op, tm.a_off, b, bo, N), lane, qhalf, abad, amx, trusted);
-        if (!trusted) fault = fault || canon_fail(abad, amx, qhalf);
-        const int64_t* __restrict__ pv = operand_ptr(ops, tm.b_op, tm.b_off, b, bo, N);
-        bool done = false;
-        if constexpr (BYTES) done = shift_product_bytes<LOGN>(res, tm.sign < 0, a, pv, lane, slab, T, fault, trusted);
-        if (!done) shift_product<LOGN, true, false, WaveTeam>(res, false, tm.sign < 0, a, pv, lane, slab, T, fault, trusted);
-      }
-      // the sums move to the idle image, each thread's pairs in its own 8-byte slots (as shift_row_kernel)
-      wave_sync();
-      uint2* own = reinterpret_cast<uint2*>(slab) + lane;
-#pragma unroll
-      for (int g = 0; g < S::G; ++g) own[g * LANES] = make_uint2(res[2 * g], res[2 * g + 1]);
-    }
-    constexpr int GC = S::G < 4 ? S::G : 4;   // pairs per trip
-    uint32_t in_bad = 0, in_mx = 0;
-    RejectAcc acc{0, 0, 0, 0};
-#pragma unroll 1
-    for (int g0 = 0; g0 < S::G; g0 += GC) {
-      uint32_t r[2 * GC], vq[2 * GC];   // vq: the product sum mod q, r: with the additions
-      const uint2* own = reinterpret_cast<const uint2*>(slab) + lane + g0 * LANES;
-#pragma unroll
-      for (int g = 0; g < GC; ++g) {
-        const uint2 v = own[g * LANES];
-        r[2 * g] = vq[2 * g] = v.x, r[2 * g + 1] = vq[2 * g + 1] = v.y;
-      }
-#pragma unroll 1
-      for (uint32_t ai = 0; ai < row.nadds; ++ai) {
-        const AddTerm ad = prog->adds[row.add0 + ai];
-        const longlong2* __restrict__ p =
-            reinterpret_cast<const longlong2*>(operand_ptr(ops, ad.op & ADD_OP_MASK, ad.off, b, bo, N)) + g0 * LANES + lane;
-        int32_t av[2 * GC];
-        if (trusted) {
-#pragma unroll
-          for (int g = 0; g < GC; ++g) {
-            const longlong2 t = ld_stream(p + g * LANES);
-            av[2 * g] = (int32_t)t.x, av[2 * g + 1] = (int32_t)t.y;
-          }
-        } else {
-#pragma unroll
-          for (int g = 0; g < GC; ++g) canon_pair(ld_stream(p + g * LANES), qhalf, in_bad, in_mx, av[2 * g], av[2 * g + 1]);
-        }
-        if (ad.sign >= 0) {
-#pragma unroll
-          for (int i = 0; i < 2 * GC; ++i) r[i] = addq(r[i], zq_from_centered(av[i], q), q);
-        } else {
-#pragma unroll
-          for (int i = 0; i < 2 * GC; ++i) r[i] = subq(r[i], zq_from_centered(av[i], q), q);
-        }
-      }
-      int4* __restrict__ dst =
-          reinterpret_cast<int4*>(const_cast<int64_t*>(operand_ptr(ops, row.out_op, row.out_off, b, bo, N))) + g0 * LANES + lane;
-#pragma unroll
-      for (int g = 0; g < GC; ++g) {
-        const int64_t c0 = center_from_zq(r[2 * g], T.crt), c1 = center_from_zq(r[2 * g + 1], T.crt);
-        st_stream(dst + g * LANES, make_int4((int32_t)c0, (int32_t)(c0 >> 32), (int32_t)c1, (int32_t)(c1 >> 32)));
-        // the statistic of the pair (the canonical verdict of y, r and d is wave-uniform and joins the flags below)
-        reject_step_v<false>(acc, c0, center_from_zq(vq[2 * g], T.crt), false, so.vmax);
-        reject_step_v<false>(acc, c1, center_from_zq(vq[2 * g + 1], T.crt), false, so.vmax);
-      }
-    }
-    const bool noncanon = fault || canon_fail(in_bad, in_mx, qhalf);   // (both false in trusted mode)
-    if (noncanon) input_fault(ops, nullptr, bo, lane);
-    // a lane's clamped sum z^2 is at most 32 x 2^48 = 2^53: wave_sum_u56 is exact; S2 - 2 S1 is any 64-bit value
-    const uint64_t e = wave_sum_u64(reject_e(acc));
-    const uint64_t zsq = wave_sum_u56(acc.zsq);
-    const uint32_t flags = (noncanon ? (uint32_t)kRejNonCanon : 0u) | (__any(acc.flags & kRejVmax) ? (uint32_t)kRejVmax : 0u);
-    if (lane == 0)
-      so.part[(size_t)bo * so.rows_total + so.part_off + (b - bo * ops.group) * nrows + rowi] =
-          reject_partial(e, zsq, flags, so.norm_limit);
-    wave_sync();   // the next task's image overwrites the slots read above
-  }
+template <class C>
+using P2Out = std::conditional_t<sizeof(C) == 8, int4, int2>;   // the store of one result pair: 16 / 8 bytes
+__device__ __forceinline__ void store_result_pair(int4* p, int64_t c0, int64_t c1) {
+  st_stream(p, make_int4((int32_t)c0, (int32_t)(c0 >> 32), (int32_t)c1, (int32_t)(c1 >> 32)));
 }
+__device__ __forceinline__ void store_result_pair(int2* p, int64_t c0, int64_t c1) {   // (centred: below 2^31 in magnitude, the cast is exact)
+  st_stream(p, make_int2((int32_t)c0, (int32_t)c1));
+}
+
+// The kernel's text, once per coefficient width (see the head of rzk_response_stat_kernel.inc).
+#define RZK_RS_KERNEL(name) name
+#define RZK_RS_COEF int64_t
+#define RZK_RS_TEAM WaveTeam
+#include "rzk_response_stat_kernel.inc"
+#undef RZK_RS_KERNEL
+#undef RZK_RS_COEF
+#undef RZK_RS_TEAM
+#define RZK_RS_KERNEL(name) name##_i32
+#define RZK_RS_COEF int32_t
+#define RZK_RS_TEAM WaveTeam32
+#include "rzk_response_stat_kernel.inc"
+#undef RZK_RS_KERNEL
+#undef RZK_RS_COEF
+#undef RZK_RS_TEAM
 
 template <int LOGN, bool BYTES>
 int launch_t(const LaunchCfg& cfg, const RowArgs& a, const Operands& ops, uint32_t ntasks, const ResponseStat& so) {
@@ -148,6 +70,23 @@ int launch_t(const LaunchCfg& cfg, const RowArgs& a, const Operands& ops, uint32
   return 0;
 }
 
+// the packed-byte form on 32-bit slabs: the sibling's workgroup, LDS request and grid
+template <int LOGN>
+int launch32_t(const LaunchCfg& cfg, const RowArgs& a, const Operands& ops, uint32_t ntasks, const ResponseStat& so) {
+  static_assert(ShiftCfg<LOGN, WaveTeam32>::TPB == kTeams && ShiftCfg<LOGN, WaveTeam32>::WORDS == ShiftGeo<LOGN, true, 6>::WORDS,
+                "response_stat_kernel_i32 lays its images out as shift_row_kernel does");
+  constexpr ShiftLaunch g = shift_launch<LOGN, WaveTeam32, true>();
+  static_assert(g.lds <= 48 * 1024, "below the opt-in for large dynamic LDS");
+  const dim3 grid(grid_for(ntasks, cfg.num_cus, kTeams, g.blocks_per_cu)), block(64 * kTeams);
+  if (ops.trusted)
+    hipLaunchKernelGGL((response_stat_kernel_i32<LOGN, true, true>), grid, block, g.lds, (hipStream_t)cfg.stream, a.prog, ops, a.T, ntasks, so);
+  else
+    hipLaunchKernelGGL((response_stat_kernel_i32<LOGN, false, true>), grid, block, g.lds, (hipStream_t)cfg.stream, a.prog, ops, a.T, ntasks, so);
+  RZK_LAUNCH_CHECK();
+  if (cfg.launched) *cfg.launched = "response_stat_kernel<" + std::to_string(LOGN) + ", " + tf(ops.trusted) + ", " + WaveTeam32::kName + ">";
+  return 0;
+}
+
 }  // namespace
 
 int launch_response_stat(int logn, const LaunchCfg& cfg, const RowArgs& a, const Operands& ops, uint32_t nrows, uint64_t batch,
@@ -159,6 +98,18 @@ int launch_response_stat(int logn, const LaunchCfg& cfg, const RowArgs& a, const
     case 10: return cfg.shift_bytes ? launch_t<10, true>(cfg, a, ops, ntasks, so) : launch_t<10, false>(cfg, a, ops, ntasks, so);
   }
   return -1;   // two-wavefront teams and small rings: the caller runs the chain (response_stat_fused, rzk_run.cpp)
+}
+
+int launch_response_stat32(int logn, const LaunchCfg& cfg, const RowArgs& a, const Operands& ops, uint32_t nrows, uint64_t batch,
+                           const ResponseStat& so) {
+  uint32_t ntasks;
+  if (const int rc = task_count(batch, nrows, ntasks); rc <= 0) return rc;
+  if (!cfg.shift_bytes) return -1;   // the packed-byte kernel only
+  switch (logn) {
+    case 9: return launch32_t<9>(cfg, a, ops, ntasks, so);
+    case 10: return launch32_t<10>(cfg, a, ops, ntasks, so);
+  }
+  return -1;   // every other shape: the caller converts (slab32_native, rzk_slab32.h)
 }
 
 }  // namespace rzk

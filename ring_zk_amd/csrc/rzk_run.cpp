@@ -122,7 +122,8 @@ int prof_end(rzk_ctx* c) {
 }
 
 // `group` > 1: the batch is B*group (proof, summand) pairs; operands with outer != 0 and the flags are per proof
-// stat != NULL (PG_RESPONSE on the rotation path only, response_stat_fused): the rows also leave their rejection partials.
+// stat != NULL (PG_RESPONSE on the rotation path only, response_stat_fused): the rows also leave their rejection partials
+// (in either width: response_stat_kernel<., ., i32> for width 4).
 // sticky: a non-canonical input coefficient fails the CALL (prover-side / Mat-level entry points); verifier-side
 // programs pass false — there the offending proof's verdict flag is cleared and the call succeeds.
 // preset_value != 0: every verdict flag (nflags of them) starts at that value — written by the launch itself when one
@@ -133,7 +134,7 @@ int run_program(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSpec>& spe
   DevProg dp;
   int rc = get_program(c, id, var, dp);
   if (rc != RZK_OK) return rc;
-  if (width != 8 && (width != 4 || stat || !native32(c, dp))) return fail(c, RZK_E_STATE, "no 32-bit kernels for this program");
+  if (width != 8 && (width != 4 || !native32(c, dp))) return fail(c, RZK_E_STATE, "no 32-bit kernels for this program");
   if (specs.size() > (size_t)kMaxOperands) return fail(c, RZK_E_ARG, "too many operands");
   // units of one batch entry per task: all of them (one team per entry: equal-cost tasks, no tail) once the batch alone
   // fills the chip's wave slots; one unit per task below that
@@ -182,7 +183,8 @@ int run_program(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSpec>& spe
       lrc = launch_row_program_small(c->N, cfg, dp.d, dp.nrows, ops, c->d_key_mont, c->dT, c->r2q, flags, batch);
       break;
     case Path::Shift:
-      lrc = stat         ? launch_response_stat(logn, cfg, a, ops, dp.nrows, batch, *stat)
+      lrc = stat ? (width == 4 ? launch_response_stat32(logn, cfg, a, ops, dp.nrows, batch, *stat)
+                               : launch_response_stat(logn, cfg, a, ops, dp.nrows, batch, *stat))
             : width == 4 ? launch_shift_rows32(logn, cfg, a, ops, dp.nrows, batch)
                          : launch_shift_rows(logn, cfg, a, ops, dp.nrows, batch);
       break;

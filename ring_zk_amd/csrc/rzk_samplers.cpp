@@ -7,17 +7,25 @@ namespace {
 // One keyed draw of `npoly` polynomials: subkey = HChaCha20(key, nonce), the launch in a profiling slot (so that
 // rzk_prof_read_kernels names the form that ran); the launch has copied the subkey into its kernel arguments, so the
 // host copy is wiped whichever way the call ends.  launch(cfg, subkey) returns the launcher's status.
+// width: bytes per coefficient of `out` (8, or 4 for the slab32 forms)
 template <class L>
-int keyed_sample(rzk_ctx* c, const uint8_t* nonce, size_t npoly, L launch) {
+int keyed_sample(rzk_ctx* c, const uint8_t* nonce, size_t npoly, L launch, uint32_t width = 8) {
   if (!c->sampler_key_set) return fail(c, RZK_E_ARG, "keyed sampler: no key set (rzk_sampler_set_key)");
   if (!nonce) return fail(c, RZK_E_ARG, "keyed sampler: NULL nonce");
   uint32_t sk[8];
   chacha_sampler_subkey(c->sampler_key, nonce, sk);
-  const int rc = run_profiled(c, (uint64_t)npoly * c->N * sizeof(int64_t), "keyed sampler",
+  const int rc = run_profiled(c, (uint64_t)npoly * c->N * width, "keyed sampler",
                               [&](const LaunchCfg& cfg) { return launch(cfg, sk); });
   wipe(sk, sizeof(sk));
   return rc;
 }
+
+// the slab32 rule for a device slab (rzk_slab32.h)
+int out32_misaligned(rzk_ctx* c, const int32_t* out) {
+  if ((reinterpret_cast<uintptr_t>(out) & 15u) == 0) return RZK_OK;
+  return fail(c, RZK_E_ARG, "slab32: device slabs must be 16-byte aligned");
+}
+int64_t* as64(int32_t* p) { return reinterpret_cast<int64_t*>(p); }   // the launchers carry addresses; `width` says what they point at
 
 }  // namespace
 
@@ -84,6 +92,46 @@ int rzk_sample_challenge_keyed_dev(rzk_ctx* c, const uint8_t nonce[16], uint32_t
   return keyed_sample(c, nonce, count, [&](const LaunchCfg& cfg, const uint32_t* sk) {
     return launch_sample_challenge_chacha(cfg, out, count, c->N, sk, stream, c->kappa);
   });
+}
+
+// ---- v14, slab32 prover: the keyed samplers writing int32_t slabs ---------------------------------------
+// The siblings' argument rules, streams and launches; every value an accepted argument can produce fits int32_t
+// (tests/test_prove32_host.py), so there is no further range rule.  out is 16-byte aligned, the slab32 rule.
+int rzk_sample_uniform_keyed32_dev(rzk_ctx* c, const uint8_t nonce[16], uint32_t stream, uint64_t bound, int32_t* out,
+                                   size_t count) {
+  if (c && count == 0) return RZK_OK;
+  if (!c || !out || bound == 0 || bound > (uint64_t)(c->q - 1) / 2) return RZK_E_ARG;
+  if (const int rc = out32_misaligned(c, out)) return rc;
+  return keyed_sample(c, nonce, count, [&](const LaunchCfg& cfg, const uint32_t* sk) {
+    return launch_sample_uniform_chacha(cfg, as64(out), count, c->N, sk, stream, (uint32_t)bound, 4);
+  }, 4);
+}
+int rzk_sample_gauss_keyed32_dev(rzk_ctx* c, const uint8_t nonce[16], uint32_t stream, double sigma, int32_t* out,
+                                 size_t count) {
+  if (c && count == 0) return RZK_OK;
+  if (!c || !out || !(sigma > 0.0) || sigma > 67108864.0) return RZK_E_ARG;   // as rzk_sample_gauss_keyed_dev
+  if (const int rc = out32_misaligned(c, out)) return rc;
+  return keyed_sample(c, nonce, count, [&](const LaunchCfg& cfg, const uint32_t* sk) {
+    return launch_sample_gauss_chacha(cfg, as64(out), count, c->N, sk, stream, sigma, 4);
+  }, 4);
+}
+int rzk_sample_dgauss_keyed32_dev(rzk_ctx* c, const uint8_t nonce[16], uint32_t stream, uint32_t sigma, int32_t* out,
+                                  size_t count) {
+  if (c && count == 0) return RZK_OK;
+  if (!c || !out || sigma == 0 || sigma > kDgaussSigmaMax || count % c->N != 0) return RZK_E_ARG;
+  if (const int rc = out32_misaligned(c, out)) return rc;
+  const size_t npoly = count / c->N;
+  return keyed_sample(c, nonce, npoly, [&](const LaunchCfg& cfg, const uint32_t* sk) {
+    return launch_sample_dgauss_chacha(cfg, as64(out), npoly, c->N, sk, stream, sigma, 4);
+  }, 4);
+}
+int rzk_sample_challenge_keyed32_dev(rzk_ctx* c, const uint8_t nonce[16], uint32_t stream, int32_t* out, size_t count) {
+  if (c && count == 0) return RZK_OK;
+  if (!c || !out) return RZK_E_ARG;
+  if (const int rc = out32_misaligned(c, out)) return rc;
+  return keyed_sample(c, nonce, count, [&](const LaunchCfg& cfg, const uint32_t* sk) {
+    return launch_sample_challenge_chacha(cfg, as64(out), count, c->N, sk, stream, c->kappa, 4);
+  }, 4);
 }
 
 }  // extern "C"

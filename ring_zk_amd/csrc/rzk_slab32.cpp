@@ -157,6 +157,41 @@ int rzk_open_recover32_batch_dev(rzk_ctx* c, const int32_t* z, const int32_t* cm
   return a1_relation32(c, z, t_out, cm, d, accept, B, true);
 }
 
+// v14, slab32 prover: a1.y of a retry and the response with its rejection test.
+int rzk_matvec32_batch_dev(rzk_ctx* c, int which, const int32_t* v, const int32_t* addend, int32_t* out, size_t B) {
+  if (c && B == 0) return RZK_OK;
+  if (!c || !v || !out || which < 0 || which > 2) return RZK_E_ARG;
+  if (misaligned({v, addend, out})) return align_fail(c);
+  const uint32_t rows = which == RZK_KEY_A1 ? c->n : (which == RZK_KEY_A2 ? c->l : c->n + c->l);
+  const uint32_t var = (uint32_t)which * 2 + (addend ? 1 : 0);
+  if (program_native32(c, PG_MATVEC, var))
+    return run_program(c, PG_MATVEC, var, {{as64(v), c->k, 0}, {as64(addend), rows, 0}, {as64(out), rows, 0}}, nullptr, 1, B, 0, true, 0, 0,
+                       nullptr, 4);
+  Convert cv(c);
+  const size_t iv = cv.in(v, B * c->k), io = cv.out(out, B * rows);
+  const size_t ia = addend ? cv.in(addend, B * rows) : 0;
+  int rc = cv.widen_inputs();
+  if (rc != RZK_OK) return rc;
+  rc = rzk_matvec_batch_dev(c, which, cv.at(iv), addend ? cv.at(ia) : nullptr, cv.at(io), B);
+  return rc != RZK_OK ? rc : cv.narrow_outputs();
+}
+
+int rzk_open_response_reject32_batch_dev(rzk_ctx* c, const int32_t* y, const int32_t* r, const int32_t* d, const int64_t* coin,
+                                         uint64_t R, double lnM, int32_t* z, uint8_t* accept, int64_t* E, size_t B) {
+  if (!c) return RZK_E_ARG;
+  if (B == 0) return RZK_OK;
+  if (!y || !r || !d || !coin || !z || !accept) return fail(c, RZK_E_ARG, "response reject: non-NULL y, r, d, coin, z, accept expected");
+  if (misaligned({y, r, d, z})) return align_fail(c);
+  if (program_native32(c, PG_RESPONSE, 1) && response_stat_fused(c))
+    return open_response_reject_native32(c, y, r, d, coin, R, lnM, z, accept, E, B);
+  Convert cv(c);
+  const size_t iy = cv.in(y, B * c->k), ir = cv.in(r, B * c->k), id = cv.in(d, B), iz = cv.out(z, B * c->k);
+  int rc = cv.widen_inputs();
+  if (rc != RZK_OK) return rc;
+  rc = rzk_open_response_reject_batch_dev(c, cv.at(iy), cv.at(ir), cv.at(id), coin, R, lnM, cv.at(iz), accept, E, B);
+  return rc != RZK_OK ? rc : cv.narrow_outputs();
+}
+
 // v14, slab32 messages: the compare of the short verifier.  No range test: the verdict of the consuming
 // call (rzk_open_recover32_batch) has tested what it read.
 int rzk_eq32_batch_dev(rzk_ctx* c, const int32_t* a, const int32_t* b, uint32_t rows, uint8_t* eq, size_t B) {
@@ -195,6 +230,31 @@ int rzk_eq32_batch(rzk_ctx* c, const int32_t* a, const int32_t* b, uint32_t rows
   const auto da = h.in(a, polys(c, B * rows) / 2), db = h.in(b, polys(c, B * rows) / 2);
   const auto deq = h.out(eq, B);
   return h.run([&] { return rzk_eq32_batch_dev(c, da, db, rows, deq, B); });
+}
+
+int rzk_matvec32_batch(rzk_ctx* c, int which, const int32_t* v, const int32_t* addend, int32_t* out, size_t B) {
+  if (c && B == 0) return RZK_OK;
+  if (!c || !v || !out || which < 0 || which > 2) return RZK_E_ARG;
+  const uint32_t rows = which == RZK_KEY_A1 ? c->n : (which == RZK_KEY_A2 ? c->l : c->n + c->l);
+  HostCall h(c);
+  const auto dv = h.in(v, polys(c, B * c->k) / 2), da = h.in(addend, polys(c, B * rows) / 2);
+  const auto dout = h.out(out, polys(c, B * rows) / 2);
+  return h.run([&] { return rzk_matvec32_batch_dev(c, which, dv, da, dout, B); });
+}
+
+int rzk_open_response_reject32_batch(rzk_ctx* c, const int32_t* y, const int32_t* r, const int32_t* d, const int64_t* coin, uint64_t R,
+                                     double lnM, int32_t* z, uint8_t* accept, int64_t* E, size_t B) {
+  if (!c) return RZK_E_ARG;
+  if (B == 0) return RZK_OK;
+  if (!y || !r || !d || !coin || !z || !accept) return fail(c, RZK_E_ARG, "response reject: non-NULL y, r, d, coin, z, accept expected");
+  const size_t kb = B * c->k;
+  HostCall h(c);
+  const auto dy = h.in(y, polys(c, kb) / 2), dr = h.in(r, polys(c, kb) / 2), dd = h.in(d, polys(c, B) / 2);
+  const auto dcoin = h.in(coin, B * sizeof(int64_t));
+  const auto dz = h.out(z, polys(c, kb) / 2);
+  const auto daccept = h.out(accept, B);
+  const auto dE = h.out(E, B * sizeof(int64_t));
+  return h.run([&] { return rzk_open_response_reject32_batch_dev(c, dy, dr, dd, dcoin, R, lnM, dz, daccept, dE, B); });
 }
 
 int rzk_open_commit32_batch(rzk_ctx* c, const int32_t* x, const int32_t* r, const int32_t* y, int32_t* cm, int32_t* t, uint8_t* ok,

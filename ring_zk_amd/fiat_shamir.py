@@ -20,7 +20,9 @@ rzk_fs_challenge_batch[_dev]): a proof is (commitment message, response), and an
   * `open_prove_sampled`, `linear_prove_sampled`, `sum_prove_sampled`: the provers with r and y drawn on the device by a
     `backend.KeyedSampler` (ChaCha20, DESIGN.md §11) instead of supplied by the caller;
   * `open_prove_zk`, `linear_prove_zk`, `sum_prove_zk`: the sampled provers with the scheme's rejection step
-    (Context.reject): a response is released only once it passed, with a fresh y per attempt.
+    (Context.reject, DESIGN.md §12): a response is released only once it passed, with a fresh y per attempt;
+  * `open_prove_sampled32`, `open_prove_zk32`: the sampled and the zero-knowledge Open prover on int32 slabs with a
+    `backend.KeyedSampler32`.
 
 `aux` (32 bytes, default zeros) binds the proofs of a call to a session or statement; prover and verifier must agree.
 Like the rest of the package every function takes numpy arrays (host entry points) or torch CUDA tensors (device entry
@@ -446,6 +448,62 @@ def open_prove_zk(ctx, x, sampler, aux=None, max_rounds: int = 64):
             t = ctx.matvec(KEY_A1, y)
         d, _, okf = challenge(ctx, MSG_OPEN_COMMITMENT, c, t, aux=aux)
         z, acc, _ = ctx.open_response_reject(y, rs, d, coin, R, lnM)
+        return (c, t, z), (okf if ok is None else ok & okf), acc
+
+    (c, t, z), ok, rounds = _zk_rounds(ctx, sampler, 1, max_rounds, attempt, fresh=(1, 2))
+    return c, t, z, ok, r, rounds
+
+
+# ---- the zero-knowledge Open prover on 32-bit slabs: the two provers above restated on open_commit32,
+# matvec32, challenge32 and open_response_reject32 with a backend.KeyedSampler32 / ExactKeyedSampler32.  The draw order is the
+# same (r; then per round y and the two coin draws), so with the same key and nonce0 the outputs are the int32 of
+# open_prove_zk's; no 64-bit slab and no convert launch appears at N = 512 and 1024, n = 1.
+def open_prove_sampled32(ctx, x, sampler, aux=None):
+    """open_prove_sampled on int32 slabs, r and y from a KeyedSampler32: (c, t, z, ok, r)."""
+    lead = _lead(x, 2)
+    r = sampler.uniform(ctx.b, lead + (ctx.k,))
+    y = sampler.gauss(ctx.sigma, lead + (ctx.k,))
+    return open_prove32(ctx, x, r, y, aux=aux) + (r,)
+
+
+def draw_coins32(sampler, lead):
+    """draw_coins from a sampler that returns int32 tensors: the same two draws and coefficients; the two [*lead] vectors
+    are converted to int64 before (a + half) R0 + (b + half) is formed (the product overflows int32).  That is a gather of
+    one value per proof, not a pass over a slab.  The coin is int64, as Context.open_response_reject32 takes it."""
+    import torch
+
+    half = (COIN_R0 - 1) // 2
+    a = sampler.uniform(half, tuple(lead))[..., 0].to(torch.int64)
+    b = sampler.uniform(half, tuple(lead))[..., 1].to(torch.int64)
+    return ((a + half) * COIN_R0 + (b + half)).contiguous(), COIN_R0 * COIN_R0
+
+
+def open_prove_zk32(ctx, x, sampler, aux=None, max_rounds: int = 64):
+    """open_prove_zk on int32 slabs: x int32 [B, l, N] (torch CUDA), sampler a KeyedSampler32 / ExactKeyedSampler32 ->
+    (c, t, z, ok, r, rounds) with c, t, z, r int32.  Bit-identical to narrow() of open_prove_zk's outputs under the same
+    key and nonces; ok and rounds are the same."""
+    import torch
+
+    B = _batch3(x, 2, "open_prove_zk32")
+    if x.dtype != torch.int32:
+        raise ValueError("open_prove_zk32: x must be an int32 tensor")
+    r = sampler.uniform(ctx.b, (B, ctx.k))
+
+    first = {}
+
+    def attempt(idx, lnM):
+        xs, rs = (x, r) if idx is None else (x[idx], r[idx])
+        nb = int(xs.shape[0])
+        y = sampler.gauss(ctx.sigma, (nb, ctx.k))
+        coin, R = draw_coins32(sampler, (nb,))
+        if idx is None:
+            c, t, ok = ctx.open_commit32(xs, rs, y)
+            first["c"] = c
+        else:               # c = commit(x; r) does not depend on y: a retry computes t = a1.y alone
+            c, ok = first["c"][idx], None
+            t = ctx.matvec32(KEY_A1, y)
+        d, _, okf = challenge32(ctx, MSG_OPEN_COMMITMENT, c, t, aux=aux)
+        z, acc, _ = ctx.open_response_reject32(y, rs, d, coin, R, lnM)
         return (c, t, z), (okf if ok is None else ok & okf), acc
 
     (c, t, z), ok, rounds = _zk_rounds(ctx, sampler, 1, max_rounds, attempt, fresh=(1, 2))
