@@ -639,6 +639,56 @@ int rzk_open_response_reject32_batch(rzk_ctx* ctx, const int32_t* y, const int32
 int rzk_open_response_reject32_batch_dev(rzk_ctx* ctx, const int32_t* y, const int32_t* r, const int32_t* d, const int64_t* coin,
                                          uint64_t R, double lnM, int32_t* z, uint8_t* accept, int64_t* E, size_t B);
 
+/* ---- prover loop: the zero-knowledge Open prover in one call (v14, prover loop) ------------------------------
+ * x -> (c, t, z, ok, r, rounds) with the rejection loop inside the library: what a caller otherwise writes around
+ * rzk_open_commit*, rzk_matvec*, rzk_fs_challenge*, rzk_open_response_reject* and the keyed samplers, including which proofs
+ * are pending, under which nonces they are drawn and what must not leave the device.  Additions only: RZK_ABI_VERSION stays 14.
+ * One entry point per slab width; the int32_t form is narrow() of the int64_t form, slab for slab.
+ *   round 0   r = uniform(b) [B][k][N]; y = Gaussian [B][k][N]; two coin draws; c, t = open_commit(x, r, y);
+ *             d = challenge(c, t) under RZK_MSG_OPEN_COMMITMENT and aux32; z, accept = open_response_reject(y, r, d, coin,
+ *             R, lnM) with lnM = rzk_reject_lnm(11), R = (2^31 - 1)^2
+ *   retry     the proofs with ok_commit & ok_hash and no accepted response yet, in ascending order, as a dense sub-batch
+ *             (position = polynomial index of the samplers): fresh y and coins, t = a1.y, d = challenge(c, t), z, accept; the
+ *             accepted (t, z) replace the proof's, rounds[b] = the round
+ *   coin      (a + 2^30 - 1) (2^31 - 1) + (b + 2^30 - 1) from two uniform(2^30 - 1) draws of one polynomial per proof,
+ *             a = coefficient 0 of the first, b = coefficient 1 of the second
+ * gauss_kind  0: rzk_sample_gauss_keyed*_dev at rzk_sigma(ctx); 1: rzk_sample_dgauss_keyed*_dev at rzk_sigma(ctx); anything
+ *             else RZK_E_ARG.  The key is the one installed by rzk_sampler_set_key: RZK_E_STATE without one.
+ * stream      the samplers' stream argument, the same for every draw of the call.
+ * max_rounds  1 .. 255 (RZK_E_ARG otherwise); aux32: 32 HOST bytes or NULL, as for rzk_fs_challenge_batch.
+ * nonces      nonce i = nonce0 + i as a 128-bit little-endian integer.  The call consumes 1 + 3 * rounds_run of them, in this
+ *             order: r; then per round y, coin draw a, coin draw b.  A round with nothing pending does not run and consumes
+ *             nothing.  RZK_E_ARG, before anything is launched, when nonce0 + 1 + 3 * max_rounds leaves 128 bits.  The nonces
+ *             nonce0 .. nonce0 + 3 * max_rounds belong to the call; the caller continues at nonce0 + 1 + 3 * rounds_run or later.
+ * rounds_run  HOST memory (may be NULL): the number of rounds that ran, round 0 included.
+ * outputs     c:[B][n+l][N] and r:[B][k][N] are written for every proof.  ok[b] = 1 iff r passed the commit constraint, the
+ *             round-0 transcript hash was ok and the proof was accepted in round rounds[b] < max_rounds; t:[B][n][N] and
+ *             z:[B][k][N] of every other proof are zero (a rejected response is never released).  x:[B][l][N].
+ * Argument, fault and trusted-mode rules are those of the calls above; a non-canonical coefficient of x clears ok[b] and raises
+ * the sticky input-error word as in rzk_open_commit_batch_dev (the host form returns RZK_E_ARG).  Device slabs of both widths
+ * are 16-byte aligned (RZK_E_ARG).  B == 0 is a no-op; B >= 2^32 is RZK_E_ARG.  The _dev form synchronises the stream once per
+ * retry round (it reads the 4-byte pending count) and allocates only when a batch is larger than any before.  Its workspace
+ * copies of y, t, z and the coins are zeroed on the stream before it returns; when it fails after round 0 was started, t, z
+ * and ok are zeroed too (a failed call releases no response).  Bit-identical to fiat_shamir.open_prove_zk /
+ * open_prove_zk32 of the Python layer under the same key, stream and first nonce.
+ * Not claimed: constant time (the number of rounds, and the pending sets, depend on the secrets). */
+int rzk_open_prove_zk_batch(rzk_ctx* ctx, const int64_t* x, const uint8_t nonce0[16], uint32_t stream, int gauss_kind,
+                            const uint8_t* aux32, uint32_t max_rounds, int64_t* c, int64_t* t, int64_t* z, int64_t* r,
+                            uint8_t* ok, uint8_t* rounds, uint32_t* rounds_run, size_t B);
+int rzk_open_prove_zk_batch_dev(rzk_ctx* ctx, const int64_t* x, const uint8_t nonce0[16], uint32_t stream, int gauss_kind,
+                                const uint8_t* aux32, uint32_t max_rounds, int64_t* c, int64_t* t, int64_t* z, int64_t* r,
+                                uint8_t* ok, uint8_t* rounds, uint32_t* rounds_run, size_t B);
+int rzk_open_prove_zk32_batch(rzk_ctx* ctx, const int32_t* x, const uint8_t nonce0[16], uint32_t stream, int gauss_kind,
+                              const uint8_t* aux32, uint32_t max_rounds, int32_t* c, int32_t* t, int32_t* z, int32_t* r,
+                              uint8_t* ok, uint8_t* rounds, uint32_t* rounds_run, size_t B);
+int rzk_open_prove_zk32_batch_dev(rzk_ctx* ctx, const int32_t* x, const uint8_t nonce0[16], uint32_t stream, int gauss_kind,
+                                  const uint8_t* aux32, uint32_t max_rounds, int32_t* c, int32_t* t, int32_t* z, int32_t* r,
+                                  uint8_t* ok, uint8_t* rounds, uint32_t* rounds_run, size_t B);
+/* diagnostic: the loop's compaction kernel on flags the caller chose.  idx[0 .. *count) = the ascending b < B with
+ * live[b] != 0 && done[b] == 0; entries of idx from *count on are not written.  live, done:[B] uint8, idx:[B] uint32 and
+ * count (one uint32) are device pointers; asynchronous on the context's stream.  RZK_E_ARG for NULL pointers or B >= 2^32. */
+int rzk_debug_compact_dev(rzk_ctx* ctx, const uint8_t* live, const uint8_t* done, size_t B, uint32_t* idx, uint32_t* count);
+
 /* ---- fixed-width packed records "RZKP1" (v8; batched, on the GPU) ----------------------------------------------------------
  * The bincode form above is the reference's: 8 bytes per coefficient and polynomials of variable length.  For proofs that
  * are stored and verified later this is the compact form: every record of a kind has the same size, known on the host, and

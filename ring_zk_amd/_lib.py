@@ -125,6 +125,13 @@ SIGNATURES = {
     "rzk_sample_dgauss_keyed32_dev": (C.c_int, [_CTX, _U8, C.c_uint32, C.c_uint32, _I32, _SZ]),
     "rzk_matvec32_batch": (C.c_int, [_CTX, C.c_int, _I32, _I32, _I32, _SZ]),
     "rzk_open_response_reject32_batch": (C.c_int, [_CTX] + [_I32] * 3 + [_I64, C.c_uint64, C.c_double, _I32, _U8, _I64, _SZ]),
+    # v14, prover loop: the zero-knowledge Open prover with its rejection loop inside the library
+    # (x, nonce0, stream, gauss_kind, aux32, max_rounds, c, t, z, r, ok, rounds, rounds_run, B)
+    "rzk_open_prove_zk_batch": (C.c_int, [_CTX, _I64, _U8, C.c_uint32, C.c_int, _U8, C.c_uint32] + [_I64] * 4 +
+                                [_U8, _U8, C.POINTER(C.c_uint32), _SZ]),
+    "rzk_open_prove_zk32_batch": (C.c_int, [_CTX, _I32, _U8, C.c_uint32, C.c_int, _U8, C.c_uint32] + [_I32] * 4 +
+                                  [_U8, _U8, C.POINTER(C.c_uint32), _SZ]),
+    "rzk_debug_compact_dev": (C.c_int, [_CTX, _U8, _U8, _SZ, _U32P, _U32P]),
     # v8: fixed-width packed records
     "rzk_packed_record_bytes": (C.c_size_t, [_CTX, C.c_int, C.c_uint32]),
     "rzk_packed_widths": (C.c_int, [_CTX, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

@@ -697,6 +697,53 @@ class Context:
         self._check(self._fn("rzk_open_response_reject32_batch", dev)(self._h, *p[:4], R, float(lnM), *p[4:], B))
         return z, accept, E
 
+    # ---- the prover loop inside the library (include/rzk.h "prover loop") -------------------------------
+    def _open_prove_zk(self, name, dt, x, nonce0, stream, gauss_kind, aux, max_rounds):
+        B = self._shape(x, self.l, self.N)
+        if x.ndim != 3:
+            raise ValueError(f"{name}: x must be [B, l, N]")
+        if aux is not None:
+            aux = bytes(aux)
+            if len(aux) != 32:
+                raise ValueError("aux must be 32 bytes")
+            aux = (C.c_uint8 * 32).from_buffer_copy(aux)
+        c = self._empty(x, (B, self.n + self.l, self.N), dt)
+        t = self._empty(x, (B, self.n, self.N), dt)
+        z = self._empty(x, (B, self.k, self.N), dt)
+        r = self._empty(x, (B, self.k, self.N), dt)
+        ok = self._empty(x, (B,), np.uint8)
+        rounds = self._empty(x, (B,), np.uint8)
+        ran = C.c_uint32(0)
+        dev, p = self._prep([x, c, t, z, r, ok, rounds], [dt] * 5 + [np.uint8] * 2)
+        self._check(self._fn(name, dev)(self._h, p[0], self._nonce(nonce0), int(stream), int(gauss_kind), aux, int(max_rounds),
+                                        *p[1:], C.byref(ran), B))
+        return c, t, z, ok, r, rounds, int(ran.value)
+
+    def open_prove_zk(self, x, nonce0: bytes, stream: int = 0, gauss_kind: int = 0, aux=None, max_rounds: int = 64):
+        """The zero-knowledge Open prover with its rejection loop inside the library (rzk_open_prove_zk_batch[_dev]):
+        x [B, l, N] int64 -> (c, t, z, ok, r, rounds, rounds_run).  r, y and the coins are drawn by the keyed samplers under
+        the context's sampler key and the nonces nonce0, nonce0 + 1, ... (1 + 3 rounds_run of them); gauss_kind 0 is the
+        Box-Muller sampler, 1 the exact discrete Gaussian.  numpy in, numpy out (host form); torch CUDA in, torch out."""
+        return self._open_prove_zk("rzk_open_prove_zk_batch", np.int64, x, nonce0, stream, gauss_kind, aux, max_rounds)
+
+    def open_prove_zk32(self, x, nonce0: bytes, stream: int = 0, gauss_kind: int = 0, aux=None, max_rounds: int = 64):
+        """open_prove_zk on int32 slabs (rzk_open_prove_zk32_batch[_dev]): c, t, z, r are int32."""
+        return self._open_prove_zk("rzk_open_prove_zk32_batch", np.int32, x, nonce0, stream, gauss_kind, aux, max_rounds)
+
+    def debug_compact(self, live, done):
+        """Diagnostic (rzk_debug_compact_dev): live, done uint8 [B] (torch CUDA) -> (idx uint32-as-int32 [B], count [1]):
+        idx[:count] are the ascending b with live[b] and not done[b]; idx[count:] is not written (it keeps the -1 fill)."""
+        import torch
+
+        B = int(live.shape[0])
+        dev, p = self._prep([live, done], [np.uint8] * 2)
+        if not dev:
+            raise ValueError("debug_compact takes torch CUDA tensors")
+        idx = torch.full((max(B, 1),), -1, dtype=torch.int32, device=live.device)
+        count = torch.full((1,), -1, dtype=torch.int32, device=live.device)
+        self._check(self._L.rzk_debug_compact_dev(self._h, p[0], p[1], B, C.c_void_p(idx.data_ptr()), C.c_void_p(count.data_ptr())))
+        return idx[:B], count
+
     # ---- LinearProof (src/prove/linear.rs) ------------------------------------------------------------------------
     def linear_commit(self, g, x, r, rp, y, yp):
         B = self._shape(x, self.l, self.N)
@@ -844,6 +891,7 @@ class KeyedSampler:
     per context at a time."""
 
     STREAM = 0
+    GAUSS_KIND = 0   # what `gauss` draws, as rzk_open_prove_zk_batch names it: the Box-Muller sampler
 
     def __init__(self, ctx: Context, key: Optional[bytes] = None, nonce0: int = 0):
         import os
@@ -861,6 +909,17 @@ class KeyedSampler:
         self.counter += 1
         return nonce
 
+    def take_nonces(self, n: int) -> bytes:
+        """The current counter as 16 bytes, for a call that draws under n consecutive nonces itself (Context.open_prove_zk);
+        the counter advances by n.  Every nonce handed out stays below 2^128, as in _next_nonce."""
+        if n < 0:
+            raise ValueError("take_nonces: n must not be negative")
+        if self.counter + max(n, 1) > 1 << 128:
+            raise OverflowError("the nonce counter is exhausted: install a new key")
+        nonce = self.counter.to_bytes(16, "little")
+        self.counter += n
+        return nonce
+
     def uniform(self, bound: int, lead):
         return self.ctx.sample_uniform_keyed(self._next_nonce(), self.STREAM, bound, lead)
 
@@ -876,6 +935,8 @@ class ExactKeyedSampler(KeyedSampler):
     §15) instead of the truncated Box-Muller normal: the y that the provers' rejection step assumes.  sigma must be
     integral (the library's sigma = 11 kappa beta sqrt(kN) is rounded by rzk_sigma).  Nonces, uniform and challenge
     draws are KeyedSampler's."""
+
+    GAUSS_KIND = 1
 
     def gauss(self, sigma, lead):
         if int(sigma) != sigma:
@@ -900,6 +961,8 @@ class KeyedSampler32(KeyedSampler):
 
 class ExactKeyedSampler32(KeyedSampler32):
     """ExactKeyedSampler on int32 tensors: `gauss` draws from the exact discrete Gaussian (Context.sample_dgauss_keyed32)."""
+
+    GAUSS_KIND = 1
 
     def gauss(self, sigma, lead):
         if int(sigma) != sigma:

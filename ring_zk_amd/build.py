@@ -14,8 +14,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "librzk_hip.so")
-SOURCES = ["rzk_kernels.hip", "rzk_wire_dev.hip", "rzk_fs_dev.hip", "rzk_csprng_dev.hip", "rzk_reject_dev.hip", "rzk_response_stat_dev.hip", "rzk_packed_dev.hip", "rzk_xof_dev.hip", "rzk_slab32_dev.hip",
-           "rzk_ctx.cpp", "rzk_key.cpp", "rzk_run.cpp", "rzk_protocols.cpp", "rzk_host.cpp", "rzk_samplers.cpp", "rzk_codec.cpp", "rzk_slab32.cpp",
+SOURCES = ["rzk_kernels.hip", "rzk_wire_dev.hip", "rzk_fs_dev.hip", "rzk_csprng_dev.hip", "rzk_reject_dev.hip", "rzk_response_stat_dev.hip", "rzk_packed_dev.hip", "rzk_xof_dev.hip", "rzk_slab32_dev.hip", "rzk_prove_loop_dev.hip",
+           "rzk_ctx.cpp", "rzk_key.cpp", "rzk_run.cpp", "rzk_protocols.cpp", "rzk_host.cpp", "rzk_samplers.cpp", "rzk_codec.cpp", "rzk_slab32.cpp", "rzk_prove_loop.cpp",
            "rzk_wire.cpp"]
 ARCH = "gfx950"
 

@@ -233,11 +233,12 @@ void rzk_ctx_destroy(rzk_ctx* c) {
     (void)hipEventDestroy(ev.second);
   }
   void* const dev[] = {c->d_key_ntt,  c->d_key_l2, c->ws.p,   c->ws_slots.p,     c->ws_wire.p,       c->ws_fs.p,
-                       c->ws_reject.p, c->ws_dkey.p, c->ws_oimg.p, c->stage.p, c->ws32.p,     c->dT,              c->d_tw,
+                       c->ws_reject.p, c->ws_prove.p, c->ws_dkey.p, c->ws_oimg.p, c->stage.p, c->ws32.p,     c->dT,              c->d_tw,
                        c->d_row_scratch, c->d_block_scratch, c->d_group_scratch, c->d_key_mont, c->d_bad};
   for (void* p : dev)
     if (p) (void)hipFree(p);
   if (c->h_bad) (void)hipHostFree(c->h_bad);
+  if (c->h_pending) (void)hipHostFree(c->h_pending);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   wipe(c->sampler_key, sizeof(c->sampler_key));
   delete c;

@@ -398,6 +398,25 @@ int launch_widen(const LaunchCfg& cfg, const int32_t* in, int64_t* out, uint64_t
 // eq[b] = (the two blocks of `words` int32 words of entry b are equal word for word), no range test; words % 4 == 0, both
 // slabs 16-byte aligned
 int launch_eq32(const LaunchCfg& cfg, const int32_t* a, const int32_t* b, uint64_t words, uint8_t* eq, uint64_t B);
+// ---- the in-library Open prover loop (rzk_prove_loop_dev.hip; arithmetic in rzk_prove_loop.h) ------------
+// width: bytes per coefficient of the slabs (8 or 4); every slab 16-byte aligned.  count == 0 launches nothing.
+// idx[0 .. *count) = the ascending b < B with live[b] && !done[b]; entries from *count on are not written.  -2: B >= 2^32
+int launch_pending_compact(const LaunchCfg& cfg, const uint8_t* live, const uint8_t* done, uint64_t B, uint32_t* idx, uint32_t* count);
+// coin[i] = prove_coin(a[i][0], b[i][1]); a, b: [count][N]
+int launch_prove_coins(const LaunchCfg& cfg, const void* a, const void* b, uint32_t N, int64_t* coin, uint64_t count, uint32_t width);
+// dst0[i] = src0[idx[i]] ([rows0][N] each) and, with src1 != NULL, dst1[i] = src1[idx[i]] ([rows1][N]), i < count
+int launch_gather_rows(const LaunchCfg& cfg, const void* src0, void* dst0, uint32_t rows0, const void* src1, void* dst1, uint32_t rows1,
+                       uint32_t N, const uint32_t* idx, uint32_t count, uint32_t width);
+// accept[i] != 0: t[i] -> t_out[idx[i]], z[i] -> z_out[idx[i]], rounds[idx[i]] = rnd, done[idx[i]] = 1, i < count
+int launch_accept_scatter(const LaunchCfg& cfg, const void* t, const void* z, void* t_out, void* z_out, uint32_t t_rows, uint32_t z_rows,
+                          uint32_t N, const uint8_t* accept, const uint32_t* idx, uint32_t count, uint8_t rnd, uint8_t* rounds,
+                          uint8_t* done, uint32_t width);
+// after round 0: live = (ok_commit & ok_hash) != 0, done = live && accept, rounds = 0
+int launch_prove_first(const LaunchCfg& cfg, const uint8_t* ok_commit, const uint8_t* ok_hash, const uint8_t* accept, uint8_t* live,
+                       uint8_t* done, uint8_t* rounds, uint64_t B);
+// after the last round: rows of t_out, z_out of every proof with done == 0 zeroed; ok = done
+int launch_prove_last(const LaunchCfg& cfg, const uint8_t* done, void* t_out, void* z_out, uint32_t t_rows, uint32_t z_rows, uint32_t N,
+                      uint8_t* ok, uint64_t B, uint32_t width);
 // ---- fixed-width packed records (rzk_packed_dev.hip; format in rzk_packed.h) -------------------------------------------
 struct PackedSlabs {
   int64_t* ptr[kPackedMaxFields];   // dense slab of every field ([B][rows of the field][N]), 16-byte aligned

@@ -22,7 +22,9 @@ rzk_fs_challenge_batch[_dev]): a proof is (commitment message, response), and an
   * `open_prove_zk`, `linear_prove_zk`, `sum_prove_zk`: the sampled provers with the scheme's rejection step
     (Context.reject, DESIGN.md §12): a response is released only once it passed, with a fresh y per attempt;
   * `open_prove_sampled32`, `open_prove_zk32`: the sampled and the zero-knowledge Open prover on int32 slabs with a
-    `backend.KeyedSampler32`.
+    `backend.KeyedSampler32` (DESIGN.md §20);
+  * `open_prove_zk_native`: open_prove_zk / open_prove_zk32 with the rejection loop inside the library, one call
+    (rzk_open_prove_zk[32]_batch_dev).
 
 `aux` (32 bytes, default zeros) binds the proofs of a call to a session or statement; prover and verifier must agree.
 Like the rest of the package every function takes numpy arrays (host entry points) or torch CUDA tensors (device entry
@@ -507,6 +509,35 @@ def open_prove_zk32(ctx, x, sampler, aux=None, max_rounds: int = 64):
         return (c, t, z), (okf if ok is None else ok & okf), acc
 
     (c, t, z), ok, rounds = _zk_rounds(ctx, sampler, 1, max_rounds, attempt, fresh=(1, 2))
+    return c, t, z, ok, r, rounds
+
+
+# ---- the same prover with the loop inside the library (include/rzk.h "prover loop") ----------------------
+def open_prove_zk_native(ctx, x, sampler, aux=None, max_rounds: int = 64):
+    """open_prove_zk (x int64) / open_prove_zk32 (x int32) through Context.open_prove_zk[32]: one library call runs every
+    round, and nothing of the loop passes through torch.  Returns the tuple of open_prove_zk, bit for bit, and leaves the
+    sampler's counter where open_prove_zk would: the largest number of nonces the call may use (1 + 3 max_rounds) is taken
+    up front and the unused ones are given back.  `sampler` is a KeyedSampler of any kind (its GAUSS_KIND and STREAM pick
+    the draws); a SeededSampler is a ValueError: Philox has no keyed entry point."""
+    import torch
+
+    B = _batch3(x, 2, "open_prove_zk_native")
+    if not hasattr(sampler, "take_nonces") or not hasattr(sampler, "GAUSS_KIND"):
+        raise ValueError("open_prove_zk_native needs a KeyedSampler: the library draws from the keyed samplers only")
+    if not 1 <= max_rounds <= 255:
+        raise ValueError("max_rounds must lie in 1 .. 255")
+    if x.dtype not in (torch.int64, torch.int32):
+        raise ValueError("open_prove_zk_native: x must be an int64 or int32 tensor")
+    span = 1 + 3 * max_rounds
+    nonce0 = sampler.take_nonces(span)
+    ran = 0
+    try:
+        prove = ctx.open_prove_zk32 if x.dtype == torch.int32 else ctx.open_prove_zk
+        c, t, z, ok, r, rounds, ran = prove(x.contiguous(), nonce0, sampler.STREAM, sampler.GAUSS_KIND, aux, max_rounds)
+    finally:
+        # open_prove_zk draws r and round 0 even for an empty batch; a failed call keeps the nonces it may have drawn under
+        used = span if (ran == 0 and B) else 1 + 3 * max(ran, 1)
+        sampler.counter -= span - used
     return c, t, z, ok, r, rounds
 
 
