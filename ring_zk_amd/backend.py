@@ -161,16 +161,21 @@ class Context:
     def _rows(self, which: int) -> int:
         return {_lib.KEY_A1: self.n, _lib.KEY_A2: self.l, _lib.KEY_A: self.n + self.l}[which]
 
-    def matvec(self, which: int, v, addend=None):
-        """Mat::dot with the key on the left (src/mat.rs:95-115), optional `.add(&z)` (commit.rs:125)."""
+    # Entry points that exist for int64 and int32 slabs (include/rzk.h "32-bit slabs") share one private body, parametrised
+    # by the method's name (for its messages), the dtype of its slabs and the symbol: _prep rejects the other dtype.
+    def _matvec(self, name, dt, sym, which, v, addend):
         B = self._shape(v, self.k, self.N)
         rows = self._rows(which)
         if addend is not None and self._shape(addend, rows, self.N) != B:
-            raise ValueError("matvec: addend batch differs")
-        out = self._empty(v, tuple(v.shape[:-2]) + (rows, self.N))
-        dev, p = self._prep([v, addend, out], [np.int64] * 3)
-        self._check(self._fn("rzk_matvec_batch", dev)(self._h, which, p[0], p[1], p[2], B))
+            raise ValueError(f"{name}: addend batch differs")
+        out = self._empty(v, tuple(v.shape[:-2]) + (rows, self.N), dt)
+        dev, p = self._prep([v, addend, out], [dt] * 3)
+        self._check(self._fn(sym, dev)(self._h, which, p[0], p[1], p[2], B))
         return out
+
+    def matvec(self, which: int, v, addend=None):
+        """Mat::dot with the key on the left (src/mat.rs:95-115), optional `.add(&z)` (commit.rs:125)."""
+        return self._matvec("matvec", np.int64, "rzk_matvec_batch", which, v, addend)
 
     def cmul(self, m, p_):
         """Mat::componentwise_mul (src/mat.rs:168-178): m [B, rows, N], p [B, N]."""
@@ -301,12 +306,13 @@ class Context:
         self._check(self._L.rzk_ctx_trust_device_outputs(self._h, 1 if on else 0))
 
     # ---- device-side samplers (statistical parity with src/polynomial.rs:14-44, src/challenge_space.rs:12-33) ----
-    def _sample_out(self, lead):
+    def _sample_out(self, lead, dt=np.int64):
         import torch
 
         self._bind_torch_stream()
         shape = tuple(lead) + (self.N,)
-        out = torch.empty(shape, dtype=torch.int64, device=torch.device("cuda", self.device))
+        tdt = torch.int32 if dt is np.int32 else torch.int64
+        out = torch.empty(shape, dtype=tdt, device=torch.device("cuda", self.device))
         return out, int(np.prod(shape[:-1], dtype=np.int64))
 
     def sample_uniform(self, seed: int, stream: int, bound: int, lead):
@@ -378,36 +384,34 @@ class Context:
             raise ValueError("the nonce must be 16 bytes")
         return (C.c_uint8 * 16).from_buffer_copy(nonce)
 
+    def _sample_keyed(self, dt, sym, nonce, stream, args, lead, per_poly=1):
+        """One keyed draw into a fresh [*lead][N] tensor of dtype dt; the symbol counts polynomials, or coefficients
+        (per_poly = N)."""
+        out, cnt = self._sample_out(lead, dt)
+        self._check(getattr(self._L, sym)(self._h, self._nonce(nonce), stream, *args, C.c_void_p(out.data_ptr()), cnt * per_poly))
+        return out
+
+    def _sample_dgauss_keyed(self, name, dt, sym, nonce, stream, sigma, lead):
+        if int(sigma) != sigma:
+            raise ValueError(f"{name}: sigma must be an integer")
+        return self._sample_keyed(dt, sym, nonce, stream, (int(sigma),), lead, self.N)
+
     def sample_uniform_keyed(self, nonce: bytes, stream: int, bound: int, lead):
         """sample_uniform from the keyed generator.  A (key, nonce, stream) triple must never serve two draws."""
-        out, cnt = self._sample_out(lead)
-        self._check(self._L.rzk_sample_uniform_keyed_dev(self._h, self._nonce(nonce), stream, bound,
-                                                         C.c_void_p(out.data_ptr()), cnt))
-        return out
+        return self._sample_keyed(np.int64, "rzk_sample_uniform_keyed_dev", nonce, stream, (bound,), lead)
 
     def sample_gauss_keyed(self, nonce: bytes, stream: int, sigma: float, lead):
         """sample_gauss from the keyed generator."""
-        out, cnt = self._sample_out(lead)
-        self._check(self._L.rzk_sample_gauss_keyed_dev(self._h, self._nonce(nonce), stream, float(sigma),
-                                                       C.c_void_p(out.data_ptr()), cnt))
-        return out
+        return self._sample_keyed(np.int64, "rzk_sample_gauss_keyed_dev", nonce, stream, (float(sigma),), lead)
 
     def sample_dgauss_keyed(self, nonce: bytes, stream: int, sigma: int, lead):
         """[*lead][N] coefficients from the exact discrete Gaussian D_sigma over the integers (integer sigma in
         [1, 2^26]; rzk_sample_dgauss_keyed_dev), from the keyed generator."""
-        if int(sigma) != sigma:
-            raise ValueError("sample_dgauss_keyed: sigma must be an integer")
-        out, cnt = self._sample_out(lead)
-        self._check(self._L.rzk_sample_dgauss_keyed_dev(self._h, self._nonce(nonce), stream, int(sigma),
-                                                        C.c_void_p(out.data_ptr()), cnt * self.N))
-        return out
+        return self._sample_dgauss_keyed("sample_dgauss_keyed", np.int64, "rzk_sample_dgauss_keyed_dev", nonce, stream, sigma, lead)
 
     def sample_challenge_keyed(self, nonce: bytes, stream: int, lead):
         """sample_challenge from the keyed generator."""
-        out, cnt = self._sample_out(lead)
-        self._check(self._L.rzk_sample_challenge_keyed_dev(self._h, self._nonce(nonce), stream,
-                                                           C.c_void_p(out.data_ptr()), cnt))
-        return out
+        return self._sample_keyed(np.int64, "rzk_sample_challenge_keyed_dev", nonce, stream, (), lead)
 
     # ---- seed expansion: uniform ring elements from public seeds with SHAKE256 (include/rzk.h "XP1", DESIGN §14) ----------
     def xof_uniform(self, seeds, rows: int, domain: int):
@@ -451,25 +455,30 @@ class Context:
 
     # The response and its rejection test in one call (include/rzk.h v13): z as *_response writes it, accept and
     # E as reject returns them for that z; at N = 512 / 1024 the response rows accumulate the statistic themselves.
-    def _response_reject(self, name, head, ins, outs, coin, R, lnM):
+    def _response_reject(self, name, head, ins, outs, coin, R, lnM, dt=np.int64):
         B = int(coin.shape[0])
         if coin.ndim != 1:
             raise ValueError(f"{name}: coin must be [B]")
         accept = self._empty(coin, (B,), np.uint8)
         E = self._empty(coin, (B,), np.int64)
-        dev, p = self._prep(ins + [coin] + outs + [accept, E], [np.int64] * (len(ins) + 1 + len(outs)) + [np.uint8, np.int64])
+        dev, p = self._prep(ins + [coin] + outs + [accept, E], [dt] * len(ins) + [np.int64] + [dt] * len(outs) + [np.uint8, np.int64])
         n = len(ins) + 1
         self._check(self._fn(name, dev)(self._h, *head, *p[:n], R, float(lnM), *p[n:], B))
         return accept, E
 
+    def _open_response_reject(self, name, dt, sym, y, r, d, coin, R, lnM):
+        B = self._shape(y, self.k, self.N)
+        # (a coin that is not [B]: the int32 form says so here, the int64 form in _response_reject, as they always have)
+        if (self._shape(r, self.k, self.N) != B or self._shape(d, self.N) != B or int(coin.shape[0]) != B
+                or (dt is np.int32 and coin.ndim != 1)):
+            raise ValueError(f"{name}: batch / shape mismatch")
+        z = self._empty(y, tuple(y.shape), dt)
+        accept, E = self._response_reject(sym, (), [y, r, d], [z], coin, R, lnM, dt)
+        return z, accept, E
+
     def open_response_reject(self, y, r, d, coin, R: int, lnM: float):
         """open_response and reject([(z, y)], coin, R, lnM) in one call: (z, accept, E)."""
-        B = self._shape(y, self.k, self.N)
-        if self._shape(r, self.k, self.N) != B or self._shape(d, self.N) != B or int(coin.shape[0]) != B:
-            raise ValueError("open_response_reject: batch / shape mismatch")
-        z = self._empty(y, tuple(y.shape))
-        accept, E = self._response_reject("rzk_open_response_reject_batch", (), [y, r, d], [z], coin, R, lnM)
-        return z, accept, E
+        return self._open_response_reject("open_response_reject", np.int64, "rzk_open_response_reject_batch", y, r, d, coin, R, lnM)
 
     def linear_response_reject(self, y, yp, r, rp, d, coin, R: int, lnM: float):
         """linear_response and reject([(z, y), (zp, yp)], coin, R, lnM) in one call: (z, zp, accept, E)."""
@@ -519,48 +528,60 @@ class Context:
         return ok
 
     # ---- OpenProof (src/prove/open.rs) -----------------------------------------------------------------------
-    def open_commit(self, x, r, y):
+    def _open_commit(self, name, dt, sym, x, r, y):
         B = self._shape(x, self.l, self.N)
         if self._shape(r, self.k, self.N) != B or self._shape(y, self.k, self.N) != B:
-            raise ValueError("open_commit: batch / shape mismatch (commit.rs:95)")
+            raise ValueError(f"{name}: batch / shape mismatch (commit.rs:95)")
         lead = tuple(x.shape[:-2])
-        c = self._empty(x, lead + (self.n + self.l, self.N))
-        t = self._empty(x, lead + (self.n, self.N))
+        c = self._empty(x, lead + (self.n + self.l, self.N), dt)
+        t = self._empty(x, lead + (self.n, self.N), dt)
         ok = self._empty(x, (B,), np.uint8)
-        dev, p = self._prep([x, r, y, c, t, ok], [np.int64] * 5 + [np.uint8])
-        self._check(self._fn("rzk_open_commit_batch", dev)(self._h, *p, B))
+        dev, p = self._prep([x, r, y, c, t, ok], [dt] * 5 + [np.uint8])
+        self._check(self._fn(sym, dev)(self._h, *p, B))
         return c, t, ok
 
-    def open_response(self, y, r, d):
+    def _open_response(self, name, dt, sym, y, r, d):
         B = self._shape(y, self.k, self.N)
         if self._shape(r, self.k, self.N) != B or self._shape(d, self.N) != B:
-            raise ValueError("open_response: batch / shape mismatch")
-        z = self._empty(y, tuple(y.shape))
-        dev, p = self._prep([y, r, d, z], [np.int64] * 4)
-        self._check(self._fn("rzk_open_response_batch", dev)(self._h, *p, B))
+            raise ValueError(f"{name}: batch / shape mismatch")
+        z = self._empty(y, tuple(y.shape), dt)
+        dev, p = self._prep([y, r, d, z], [dt] * 4)
+        self._check(self._fn(sym, dev)(self._h, *p, B))
         return z
 
-    def open_verify(self, z, t, c, d):
+    def _open_verify(self, name, dt, sym, z, t, c, d):
         B = self._shape(z, self.k, self.N)
         if (self._shape(t, self.n, self.N) != B or self._shape(c, self.n + self.l, self.N) != B
                 or self._shape(d, self.N) != B):
-            raise ValueError("open_verify: batch / shape mismatch")
+            raise ValueError(f"{name}: batch / shape mismatch")
         acc = self._empty(z, (B,), np.uint8)
-        dev, p = self._prep([z, t, c, d, acc], [np.int64] * 4 + [np.uint8])
-        self._check(self._fn("rzk_open_verify_batch", dev)(self._h, *p, B))
+        dev, p = self._prep([z, t, c, d, acc], [dt] * 4 + [np.uint8])
+        self._check(self._fn(sym, dev)(self._h, *p, B))
         return acc
+
+    def _open_recover(self, name, dt, sym, z, c, d):
+        B = self._shape(z, self.k, self.N)
+        if self._shape(c, self.n + self.l, self.N) != B or self._shape(d, self.N) != B:
+            raise ValueError(f"{name}: batch / shape mismatch")
+        t = self._empty(z, tuple(z.shape[:-2]) + (self.n, self.N), dt)
+        acc = self._empty(z, (B,), np.uint8)
+        dev, p = self._prep([z, c, d, t, acc], [dt] * 4 + [np.uint8])
+        self._check(self._fn(sym, dev)(self._h, *p, B))
+        return t, acc
+
+    def open_commit(self, x, r, y):
+        return self._open_commit("open_commit", np.int64, "rzk_open_commit_batch", x, r, y)
+
+    def open_response(self, y, r, d):
+        return self._open_response("open_response", np.int64, "rzk_open_response_batch", y, r, d)
+
+    def open_verify(self, z, t, c, d):
+        return self._open_verify("open_verify", np.int64, "rzk_open_verify_batch", z, t, c, d)
 
     def open_recover(self, z, c, d):
         """The recompute step of a short Open proof (rzk_open_recover_batch): (t, accept) with t = a1.z - c1 (.) d, the
         only t for which open_verify's equation holds; accept[b] = norm rule on z and every coefficient read canonical."""
-        B = self._shape(z, self.k, self.N)
-        if self._shape(c, self.n + self.l, self.N) != B or self._shape(d, self.N) != B:
-            raise ValueError("open_recover: batch / shape mismatch")
-        t = self._empty(z, tuple(z.shape[:-2]) + (self.n, self.N))
-        acc = self._empty(z, (B,), np.uint8)
-        dev, p = self._prep([z, c, d, t, acc], [np.int64] * 4 + [np.uint8])
-        self._check(self._fn("rzk_open_recover_batch", dev)(self._h, *p, B))
-        return t, acc
+        return self._open_recover("open_recover", np.int64, "rzk_open_recover_batch", z, c, d)
 
     # ---- 32-bit coefficient slabs (include/rzk.h "32-bit slabs", v14) ------------------------------------------
     # The same values as int32: numpy int32 arrays or torch int32 tensors.  The methods above keep rejecting int32.
@@ -582,45 +603,16 @@ class Context:
         return out
 
     def open_commit32(self, x, r, y):
-        B = self._shape(x, self.l, self.N)
-        if self._shape(r, self.k, self.N) != B or self._shape(y, self.k, self.N) != B:
-            raise ValueError("open_commit32: batch / shape mismatch (commit.rs:95)")
-        lead = tuple(x.shape[:-2])
-        c = self._empty(x, lead + (self.n + self.l, self.N), np.int32)
-        t = self._empty(x, lead + (self.n, self.N), np.int32)
-        ok = self._empty(x, (B,), np.uint8)
-        dev, p = self._prep([x, r, y, c, t, ok], [np.int32] * 5 + [np.uint8])
-        self._check(self._fn("rzk_open_commit32_batch", dev)(self._h, *p, B))
-        return c, t, ok
+        return self._open_commit("open_commit32", np.int32, "rzk_open_commit32_batch", x, r, y)
 
     def open_response32(self, y, r, d):
-        B = self._shape(y, self.k, self.N)
-        if self._shape(r, self.k, self.N) != B or self._shape(d, self.N) != B:
-            raise ValueError("open_response32: batch / shape mismatch")
-        z = self._empty(y, tuple(y.shape), np.int32)
-        dev, p = self._prep([y, r, d, z], [np.int32] * 4)
-        self._check(self._fn("rzk_open_response32_batch", dev)(self._h, *p, B))
-        return z
+        return self._open_response("open_response32", np.int32, "rzk_open_response32_batch", y, r, d)
 
     def open_verify32(self, z, t, c, d):
-        B = self._shape(z, self.k, self.N)
-        if (self._shape(t, self.n, self.N) != B or self._shape(c, self.n + self.l, self.N) != B
-                or self._shape(d, self.N) != B):
-            raise ValueError("open_verify32: batch / shape mismatch")
-        acc = self._empty(z, (B,), np.uint8)
-        dev, p = self._prep([z, t, c, d, acc], [np.int32] * 4 + [np.uint8])
-        self._check(self._fn("rzk_open_verify32_batch", dev)(self._h, *p, B))
-        return acc
+        return self._open_verify("open_verify32", np.int32, "rzk_open_verify32_batch", z, t, c, d)
 
     def open_recover32(self, z, c, d):
-        B = self._shape(z, self.k, self.N)
-        if self._shape(c, self.n + self.l, self.N) != B or self._shape(d, self.N) != B:
-            raise ValueError("open_recover32: batch / shape mismatch")
-        t = self._empty(z, tuple(z.shape[:-2]) + (self.n, self.N), np.int32)
-        acc = self._empty(z, (B,), np.uint8)
-        dev, p = self._prep([z, c, d, t, acc], [np.int32] * 4 + [np.uint8])
-        self._check(self._fn("rzk_open_recover32_batch", dev)(self._h, *p, B))
-        return t, acc
+        return self._open_recover("open_recover32", np.int32, "rzk_open_recover32_batch", z, c, d)
 
     def eq32(self, a, b):
         """eq[b] = 1 iff the int32 blocks a[b], b[b] ([rows][N]) are equal word for word (rzk_eq32_batch); no range test,
@@ -635,67 +627,30 @@ class Context:
         return out
 
     # ---- the zero-knowledge Open prover on int32 slabs (include/rzk.h "slab32 prover") -----------------
-    def _sample_out32(self, lead):
-        import torch
-
-        self._bind_torch_stream()
-        shape = tuple(lead) + (self.N,)
-        out = torch.empty(shape, dtype=torch.int32, device=torch.device("cuda", self.device))
-        return out, int(np.prod(shape[:-1], dtype=np.int64))
-
     def sample_uniform_keyed32(self, nonce: bytes, stream: int, bound: int, lead):
         """sample_uniform_keyed as an int32 tensor: the same stream, the same values."""
-        out, cnt = self._sample_out32(lead)
-        self._check(self._L.rzk_sample_uniform_keyed32_dev(self._h, self._nonce(nonce), stream, bound,
-                                                           C.c_void_p(out.data_ptr()), cnt))
-        return out
+        return self._sample_keyed(np.int32, "rzk_sample_uniform_keyed32_dev", nonce, stream, (bound,), lead)
 
     def sample_gauss_keyed32(self, nonce: bytes, stream: int, sigma: float, lead):
         """sample_gauss_keyed as an int32 tensor."""
-        out, cnt = self._sample_out32(lead)
-        self._check(self._L.rzk_sample_gauss_keyed32_dev(self._h, self._nonce(nonce), stream, float(sigma),
-                                                         C.c_void_p(out.data_ptr()), cnt))
-        return out
+        return self._sample_keyed(np.int32, "rzk_sample_gauss_keyed32_dev", nonce, stream, (float(sigma),), lead)
 
     def sample_dgauss_keyed32(self, nonce: bytes, stream: int, sigma: int, lead):
         """sample_dgauss_keyed as an int32 tensor."""
-        if int(sigma) != sigma:
-            raise ValueError("sample_dgauss_keyed32: sigma must be an integer")
-        out, cnt = self._sample_out32(lead)
-        self._check(self._L.rzk_sample_dgauss_keyed32_dev(self._h, self._nonce(nonce), stream, int(sigma),
-                                                          C.c_void_p(out.data_ptr()), cnt * self.N))
-        return out
+        return self._sample_dgauss_keyed("sample_dgauss_keyed32", np.int32, "rzk_sample_dgauss_keyed32_dev", nonce, stream, sigma, lead)
 
     def sample_challenge_keyed32(self, nonce: bytes, stream: int, lead):
         """sample_challenge_keyed as an int32 tensor."""
-        out, cnt = self._sample_out32(lead)
-        self._check(self._L.rzk_sample_challenge_keyed32_dev(self._h, self._nonce(nonce), stream,
-                                                             C.c_void_p(out.data_ptr()), cnt))
-        return out
+        return self._sample_keyed(np.int32, "rzk_sample_challenge_keyed32_dev", nonce, stream, (), lead)
 
     def matvec32(self, which: int, v, addend=None):
         """matvec on int32 slabs (rzk_matvec32_batch): narrow() of matvec's output."""
-        B = self._shape(v, self.k, self.N)
-        rows = self._rows(which)
-        if addend is not None and self._shape(addend, rows, self.N) != B:
-            raise ValueError("matvec32: addend batch differs")
-        out = self._empty(v, tuple(v.shape[:-2]) + (rows, self.N), np.int32)
-        dev, p = self._prep([v, addend, out], [np.int32] * 3)
-        self._check(self._fn("rzk_matvec32_batch", dev)(self._h, which, p[0], p[1], p[2], B))
-        return out
+        return self._matvec("matvec32", np.int32, "rzk_matvec32_batch", which, v, addend)
 
     def open_response_reject32(self, y, r, d, coin, R: int, lnM: float):
         """open_response_reject on int32 slabs y, r, d (coin stays int64): (z int32, accept, E), z = narrow() of the
         sibling's and accept, E byte for byte the sibling's."""
-        B = self._shape(y, self.k, self.N)
-        if self._shape(r, self.k, self.N) != B or self._shape(d, self.N) != B or int(coin.shape[0]) != B or coin.ndim != 1:
-            raise ValueError("open_response_reject32: batch / shape mismatch")
-        z = self._empty(y, tuple(y.shape), np.int32)
-        accept = self._empty(coin, (B,), np.uint8)
-        E = self._empty(coin, (B,), np.int64)
-        dev, p = self._prep([y, r, d, coin, z, accept, E], [np.int32] * 3 + [np.int64, np.int32, np.uint8, np.int64])
-        self._check(self._fn("rzk_open_response_reject32_batch", dev)(self._h, *p[:4], R, float(lnM), *p[4:], B))
-        return z, accept, E
+        return self._open_response_reject("open_response_reject32", np.int32, "rzk_open_response_reject32_batch", y, r, d, coin, R, lnM)
 
     # ---- the prover loop inside the library (include/rzk.h "prover loop", DESIGN §21) -------------------------------
     def _open_prove_zk(self, name, dt, x, nonce0, stream, gauss_kind, aux, max_rounds):

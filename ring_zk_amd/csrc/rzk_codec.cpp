@@ -11,18 +11,20 @@ bool wire_schema_of(const rzk_ctx* c, int kind, uint32_t V, uint32_t coef_bytes,
 }
 
 // slabs of the fields; only the Option of an Opening may be NULL, and only on encode
-bool wire_slabs(const WireSchema& s, int kind, const int64_t* const* fields, bool allow_none, WireSlabs* sl) {
+template <class C>
+bool wire_slabs(const WireSchema& s, int kind, const C* const* fields, bool allow_none, WireSlabs* sl) {
   if (!fields) return false;
   for (int f = 0; f < kWireMaxFields; ++f) sl->ptr[f] = nullptr;
   for (uint32_t f = 0; f < s.nfields; ++f) {
-    sl->ptr[f] = const_cast<int64_t*>(fields[f]);
+    sl->ptr[f] = launch_addr(const_cast<C*>(fields[f]));
     if (!fields[f] && !(allow_none && kind == WIRE_OPENING && s.f[f].kind == WF_OPT)) return false;
   }
   return true;
 }
 
+template <class C = int64_t>
 size_t wire_field_bytes(const rzk_ctx* c, const WireSchema& s, uint32_t f, size_t B) {
-  return polys(c, B * (size_t)(s.first[f + 1] - s.first[f]));
+  return polys<C>(c, B * (size_t)(s.first[f + 1] - s.first[f]));
 }
 
 }  // namespace
@@ -128,15 +130,15 @@ bool fs_kind_ok(int kind) {
   return kind == RZK_MSG_OPEN_COMMITMENT || kind == RZK_MSG_LINEAR_COMMITMENT || kind == RZK_MSG_SUM_COMMITMENT;
 }
 
-// 32-bit slabs (v14, slab32 messages): the entry points below and of the packed codec exist at both
-// coefficient widths over one body.  width = bytes per coefficient of every slab of the call (8, or 4 for int32_t slabs,
-// whose addresses travel as int64_t* as in rzk_slab32.cpp); at width 4 device slabs are 16-byte aligned.
-const int64_t* const* as64(const int32_t* const* fields) { return reinterpret_cast<const int64_t* const*>(fields); }
-int64_t* as64(int32_t* p) { return reinterpret_cast<int64_t*>(p); }
-size_t width_bytes(const rzk_ctx* c, size_t count, uint32_t width) { return polys(c, count) / 8 * width; }
+}  // namespace
 
-int fs_challenge_dev(rzk_ctx* c, int kind, uint32_t V, const int64_t* const* fields, const uint8_t* aux32, int64_t* d,
-                     uint8_t* digest, uint8_t* ok, size_t B, uint32_t width) {
+// The entry points below and of the packed codec exist for int64_t and int32_t slabs (v14, slab32 messages; DESIGN.md
+// §19) over one body; 32-bit device slabs are 16-byte aligned.
+namespace rzk::api {
+
+template <class C>
+int fs_challenge_dev(rzk_ctx* c, int kind, uint32_t V, const C* const* fields, const uint8_t* aux32, C* d, uint8_t* digest, uint8_t* ok,
+                     size_t B) {
   WireSchema s;
   if (!c) return RZK_E_ARG;
   HIPCHK(c, hipSetDevice(c->device));   // the memsets below come before the first cfg_of
@@ -146,10 +148,10 @@ int fs_challenge_dev(rzk_ctx* c, int kind, uint32_t V, const int64_t* const* fie
   if (B == 0) return RZK_OK;
   WireSlabs sl;
   if (!d || !wire_slabs(s, kind, fields, false, &sl)) return fail(c, RZK_E_ARG, "fs challenge: NULL pointer");
-  if (width == 4) {
+  if constexpr (sizeof(C) == 4) {
     uintptr_t bits = (uintptr_t)d;
     for (uint32_t f = 0; f < s.nfields; ++f) bits |= (uintptr_t)sl.ptr[f];
-    if (bits & 15u) return fail(c, RZK_E_ARG, "slab32: device slabs must be 16-byte aligned");
+    if (bits & 15u) return align_fail(c);
   }
   FsMsg m{};
   m.nfields = s.nfields;
@@ -170,18 +172,23 @@ int fs_challenge_dev(rzk_ctx* c, int kind, uint32_t V, const int64_t* const* fie
   if (rc != RZK_OK) return rc;
   uint64_t* dig = (uint64_t*)c->ws_fs.p;
   if (ok) HIPCHK(c, hipMemsetAsync(ok, 1, B, c->stream));
-  HIPCHK(c, hipMemsetAsync(d, 0, width_bytes(c, B, width), c->stream));   // the sampler writes the kappa non-zero coefficients only
-  const uint64_t hashed = (uint64_t)B * s.polys * c->N * width;
-  rc = run_profiled(c, hashed, "fs leaf kernel", [&](const LaunchCfg& cfg) {
-    return launch_fs_leaves(cfg, m, (c->q - 1) / 2, c->trusted ? 0 : 1, dig, ok, c->d_bad, B, width);
+  HIPCHK(c, hipMemsetAsync(d, 0, polys<C>(c, B), c->stream));   // the sampler writes the kappa non-zero coefficients only
+  rc = run_profiled(c, polys<C>(c, B * (size_t)s.polys), "fs leaf kernel", [&](const LaunchCfg& cfg) {
+    return launch_fs_leaves(cfg, m, (c->q - 1) / 2, c->trusted ? 0 : 1, dig, ok, c->d_bad, B, sizeof(C));
   });
   if (rc != RZK_OK) return rc;
   return run_profiled(c, (uint64_t)B * r.leaves * 32, "fs root kernel",
-                      [&](const LaunchCfg& cfg) { return launch_fs_roots(cfg, r, dig, d, digest, B, width); });
+                      [&](const LaunchCfg& cfg) { return launch_fs_roots(cfg, r, dig, launch_addr(d), digest, B, sizeof(C)); });
 }
+RZK_BOTH_WIDTHS(fs_challenge_dev)
 
-int fs_challenge_host(rzk_ctx* c, int kind, uint32_t V, const int64_t* const* fields, const uint8_t* aux32, int64_t* d,
-                      uint8_t* digest, uint8_t* ok, size_t B, uint32_t width) {
+}  // namespace rzk::api
+
+namespace {
+
+template <class C>
+int fs_challenge_host(rzk_ctx* c, int kind, uint32_t V, const C* const* fields, const uint8_t* aux32, C* d, uint8_t* digest, uint8_t* ok,
+                      size_t B) {
   WireSchema s;
   if (!c) return RZK_E_ARG;
   if (!fs_kind_ok(kind) || !wire_schema_of(c, kind, V, 8, &s)) return fail(c, RZK_E_ARG, "fs challenge: bad kind or V");
@@ -189,30 +196,30 @@ int fs_challenge_host(rzk_ctx* c, int kind, uint32_t V, const int64_t* const* fi
   WireSlabs sl;
   if (!d || !wire_slabs(s, kind, fields, false, &sl)) return fail(c, RZK_E_ARG, "fs challenge: NULL pointer");
   HostCall h(c);
-  const auto dd = h.out(d, width_bytes(c, B, width));
+  const auto dd = h.pout(d, B);
   const auto ddigest = h.out(digest, B * 32), dok = h.out(ok, B);
-  const int64_t* dev_fields[kWireMaxFields] = {};
-  for (uint32_t f = 0; f < s.nfields; ++f) h.in_to(&dev_fields[f], fields[f], wire_field_bytes(c, s, f, B) / 8 * width);
-  return h.run([&] { return fs_challenge_dev(c, kind, V, dev_fields, aux32, dd, ddigest, dok, B, width); });
+  const C* dev_fields[kWireMaxFields] = {};
+  for (uint32_t f = 0; f < s.nfields; ++f) h.in_to(&dev_fields[f], fields[f], wire_field_bytes<C>(c, s, f, B));
+  return h.run([&] { return fs_challenge_dev<C>(c, kind, V, dev_fields, aux32, dd, ddigest, dok, B); });
 }
 
 }  // namespace
 
 int rzk_fs_challenge_batch_dev(rzk_ctx* c, int kind, uint32_t V, const int64_t* const* fields, const uint8_t* aux32,
                                int64_t* d, uint8_t* digest, uint8_t* ok, size_t B) {
-  return fs_challenge_dev(c, kind, V, fields, aux32, d, digest, ok, B, 8);
+  return fs_challenge_dev(c, kind, V, fields, aux32, d, digest, ok, B);
 }
 int rzk_fs_challenge_batch(rzk_ctx* c, int kind, uint32_t V, const int64_t* const* fields, const uint8_t* aux32,
                            int64_t* d, uint8_t* digest, uint8_t* ok, size_t B) {
-  return fs_challenge_host(c, kind, V, fields, aux32, d, digest, ok, B, 8);
+  return fs_challenge_host(c, kind, V, fields, aux32, d, digest, ok, B);
 }
 int rzk_fs_challenge32_batch_dev(rzk_ctx* c, int kind, uint32_t V, const int32_t* const* fields, const uint8_t* aux32,
                                  int32_t* d, uint8_t* digest, uint8_t* ok, size_t B) {
-  return fs_challenge_dev(c, kind, V, as64(fields), aux32, as64(d), digest, ok, B, 4);
+  return fs_challenge_dev(c, kind, V, fields, aux32, d, digest, ok, B);
 }
 int rzk_fs_challenge32_batch(rzk_ctx* c, int kind, uint32_t V, const int32_t* const* fields, const uint8_t* aux32,
                              int32_t* d, uint8_t* digest, uint8_t* ok, size_t B) {
-  return fs_challenge_host(c, kind, V, as64(fields), aux32, as64(d), digest, ok, B, 4);
+  return fs_challenge_host(c, kind, V, fields, aux32, d, digest, ok, B);
 }
 
 // ---- v7: the prover's rejection-sampling step (rzk_reject_dev.hip, rzk_reject.h) --------------------------------------
@@ -343,34 +350,45 @@ const char* const kResponseRejectNull = "response reject: non-NULL y, r, d, coin
 
 }  // namespace
 
-int rzk_open_response_reject_batch_dev(rzk_ctx* c, const int64_t* y, const int64_t* r, const int64_t* d, const int64_t* coin,
-                                       uint64_t R, double lnM, int64_t* z, uint8_t* accept, int64_t* E, size_t B) {
+// The Open form at either width (v14, slab32 prover).  The partials, the decision kernel, coin, accept and
+// E do not see the width; reject_args and RejectParts only carry the addresses of z and y.  32-bit slabs run natively
+// where the fused rows do, and convert everywhere else.
+namespace rzk::api {
+
+template <class C>
+int open_response_reject_dev(rzk_ctx* c, const C* y, const C* r, const C* d, const int64_t* coin, uint64_t R, double lnM, C* z,
+                             uint8_t* accept, int64_t* E, size_t B) {
   if (!c) return RZK_E_ARG;
   if (B == 0) return RZK_OK;
   if (!y || !r || !d || !coin || !z || !accept) return fail(c, RZK_E_ARG, kResponseRejectNull);
   const uint32_t k = c->k;
-  const int64_t *zs[1] = {z}, *ys[1] = {y};
+  if constexpr (sizeof(C) == 4) {
+    if (misaligned({y, r, d, z})) return align_fail(c);
+    if (!(program_native32(c, PG_RESPONSE, 1) && response_stat_fused(c)))
+      return convert_call(c, {{y, nullptr, B * k}, {r, nullptr, B * k}, {d, nullptr, B}, {nullptr, z, B * k}}, [&](int64_t* const* w) {
+        return open_response_reject_dev<int64_t>(c, w[0], w[1], w[2], coin, R, lnM, w[3], accept, E, B);
+      });
+  }
+  const int64_t *zs[1] = {launch_addr(z)}, *ys[1] = {launch_addr(y)};
   const uint32_t rows[1] = {k};
   return response_reject(c, 1, zs, ys, rows, coin, R, lnM, accept, E, B, [&](const ResponseStat* st) {
-    return run_program(c, PG_RESPONSE, 1, {{d, 1, 0}, {y, k, 0}, {r, k, 0}, {z, k, 0}}, nullptr, 1, B, 0, true, 0, 0, st);
+    if constexpr (sizeof(C) == 4) {
+      if (!st) return fail(c, RZK_E_STATE, "response reject on 32-bit slabs needs the fused rows");
+    }
+    return run_program<C>(c, PG_RESPONSE, 1, {{d, 1, 0}, {y, k, 0}, {r, k, 0}, {z, k, 0}}, nullptr, 1, B, 0, true, 0, 0, st);
   });
 }
+RZK_BOTH_WIDTHS(open_response_reject_dev)
 
-// v14, slab32 prover (rzk_slab32.cpp routes here): the same call with width 4.  The partials, the decision
-// kernel, coin, accept and E do not see the width; reject_args and RejectParts only carry the addresses of z and y.
-int rzk::api::open_response_reject_native32(rzk_ctx* c, const int32_t* y, const int32_t* r, const int32_t* d, const int64_t* coin,
-                                            uint64_t R, double lnM, int32_t* z, uint8_t* accept, int64_t* E, size_t B) {
-  const uint32_t k = c->k;
-  const int64_t* y64 = reinterpret_cast<const int64_t*>(y);
-  const int64_t* r64 = reinterpret_cast<const int64_t*>(r);
-  const int64_t* d64 = reinterpret_cast<const int64_t*>(d);
-  const int64_t* z64 = reinterpret_cast<const int64_t*>(z);
-  const int64_t *zs[1] = {z64}, *ys[1] = {y64};
-  const uint32_t rows[1] = {k};
-  return response_reject(c, 1, zs, ys, rows, coin, R, lnM, accept, E, B, [&](const ResponseStat* st) {
-    if (!st) return fail(c, RZK_E_STATE, "response reject on 32-bit slabs needs the fused rows");
-    return run_program(c, PG_RESPONSE, 1, {{d64, 1, 0}, {y64, k, 0}, {r64, k, 0}, {z64, k, 0}}, nullptr, 1, B, 0, true, 0, 0, st, 4);
-  });
+}  // namespace rzk::api
+
+int rzk_open_response_reject_batch_dev(rzk_ctx* c, const int64_t* y, const int64_t* r, const int64_t* d, const int64_t* coin,
+                                       uint64_t R, double lnM, int64_t* z, uint8_t* accept, int64_t* E, size_t B) {
+  return open_response_reject_dev(c, y, r, d, coin, R, lnM, z, accept, E, B);
+}
+int rzk_open_response_reject32_batch_dev(rzk_ctx* c, const int32_t* y, const int32_t* r, const int32_t* d, const int64_t* coin,
+                                         uint64_t R, double lnM, int32_t* z, uint8_t* accept, int64_t* E, size_t B) {
+  return open_response_reject_dev(c, y, r, d, coin, R, lnM, z, accept, E, B);
 }
 
 int rzk_linear_response_reject_batch_dev(rzk_ctx* c, const int64_t* y, const int64_t* yp, const int64_t* r, const int64_t* rp,
@@ -410,8 +428,10 @@ int rzk_sum_response_reject_batch_dev(rzk_ctx* c, uint32_t V, const int64_t* ys,
   });
 }
 
-int rzk_open_response_reject_batch(rzk_ctx* c, const int64_t* y, const int64_t* r, const int64_t* d, const int64_t* coin, uint64_t R,
-                                   double lnM, int64_t* z, uint8_t* accept, int64_t* E, size_t B) {
+namespace {
+template <class C>
+int open_response_reject_host(rzk_ctx* c, const C* y, const C* r, const C* d, const int64_t* coin, uint64_t R, double lnM, C* z,
+                              uint8_t* accept, int64_t* E, size_t B) {
   if (!c) return RZK_E_ARG;
   if (B == 0) return RZK_OK;
   if (!y || !r || !d || !coin || !z || !accept) return fail(c, RZK_E_ARG, kResponseRejectNull);
@@ -422,7 +442,17 @@ int rzk_open_response_reject_batch(rzk_ctx* c, const int64_t* y, const int64_t* 
   const auto dz = h.pout(z, kb);
   const auto daccept = h.out(accept, B);
   const auto dE = h.out(E, B * sizeof(int64_t));
-  return h.run([&] { return rzk_open_response_reject_batch_dev(c, dy, dr, dd, dcoin, R, lnM, dz, daccept, dE, B); });
+  return h.run([&] { return open_response_reject_dev<C>(c, dy, dr, dd, dcoin, R, lnM, dz, daccept, dE, B); });
+}
+}  // namespace
+
+int rzk_open_response_reject_batch(rzk_ctx* c, const int64_t* y, const int64_t* r, const int64_t* d, const int64_t* coin, uint64_t R,
+                                   double lnM, int64_t* z, uint8_t* accept, int64_t* E, size_t B) {
+  return open_response_reject_host(c, y, r, d, coin, R, lnM, z, accept, E, B);
+}
+int rzk_open_response_reject32_batch(rzk_ctx* c, const int32_t* y, const int32_t* r, const int32_t* d, const int64_t* coin, uint64_t R,
+                                     double lnM, int32_t* z, uint8_t* accept, int64_t* E, size_t B) {
+  return open_response_reject_host(c, y, r, d, coin, R, lnM, z, accept, E, B);
 }
 
 int rzk_linear_response_reject_batch(rzk_ctx* c, const int64_t* y, const int64_t* yp, const int64_t* r, const int64_t* rp,
@@ -470,91 +500,89 @@ bool packed_schema_of(const rzk_ctx* c, int kind, uint32_t V, PackedSchema* s) {
   return c && packed_schema(kind, c->N, c->n, c->k, c->l, V, c->q, c->verify_bound, s);
 }
 
-// argument rules shared by the four entry points; on RZK_OK *s and *sl are filled
-int packed_args(rzk_ctx* c, int kind, uint32_t V, const int64_t* const* fields, const uint8_t* records, const uint8_t* ok,
-                size_t B, PackedSchema* s, PackedSlabs* sl) {
+// argument rules shared by the entry points; on RZK_OK *s and *sl are filled
+template <class C>
+int packed_args(rzk_ctx* c, int kind, uint32_t V, const C* const* fields, const uint8_t* records, const uint8_t* ok, size_t B,
+                PackedSchema* s, PackedSlabs* sl) {
   if (!packed_schema_of(c, kind, V, s)) return fail(c, RZK_E_ARG, "packed codec: bad kind or V");
   if (B == 0) return RZK_OK;   // a no-op, whatever the pointers
   if (!fields || !records || !ok) return fail(c, RZK_E_ARG, "packed codec: NULL pointer");
   for (int f = 0; f < kPackedMaxFields; ++f) sl->ptr[f] = nullptr;
   for (uint32_t f = 0; f < s->nfields; ++f) {
     if (!fields[f]) return fail(c, RZK_E_ARG, "packed codec: NULL slab");
-    sl->ptr[f] = const_cast<int64_t*>(fields[f]);
+    sl->ptr[f] = launch_addr(const_cast<C*>(fields[f]));   // (PackedSlabs serves both directions, so its pointers are not const)
   }
   if ((uintptr_t)records % 8) return fail(c, RZK_E_ARG, "packed codec: records must be 8-byte aligned");
   return RZK_OK;
 }
 
-size_t packed_field_bytes(const rzk_ctx* c, const PackedSchema& s, uint32_t f, size_t B, uint32_t width = 8) {
-  return polys(c, B * (size_t)s.f[f].rows) / 8 * width;
+template <class C>
+size_t packed_field_bytes(const rzk_ctx* c, const PackedSchema& s, uint32_t f, size_t B) {
+  return polys<C>(c, B * (size_t)s.f[f].rows);
 }
 
-// one launch between preset and profile bookkeeping; decode != 0: records -> slabs
-int packed_run(rzk_ctx* c, const PackedSchema& s, const PackedSlabs& sl, uint8_t* records, uint8_t* ok, size_t B, int decode,
-               uint32_t width) {
+// one launch between preset and profile bookkeeping, on slabs of C; decode: records -> slabs
+template <class C>
+int packed_run(rzk_ctx* c, const PackedSchema& s, const PackedSlabs& sl, uint8_t* records, uint8_t* ok, size_t B, bool decode) {
   for (uint32_t f = 0; f < s.nfields; ++f)
     if ((uintptr_t)sl.ptr[f] % 16) return fail(c, RZK_E_ARG, "packed codec: device slabs must be 16-byte aligned");
   HIPCHK(c, hipSetDevice(c->device));   // the memset below comes before the first cfg_of
   HIPCHK(c, hipMemsetAsync(ok, 1, B, c->stream));
   uint64_t slab_bytes = 0;
-  for (uint32_t f = 0; f < s.nfields; ++f) slab_bytes += packed_field_bytes(c, s, f, B, width);
+  for (uint32_t f = 0; f < s.nfields; ++f) slab_bytes += packed_field_bytes<C>(c, s, f, B);
   return run_profiled(c, slab_bytes + (uint64_t)B * packed_record_bytes(s), decode ? "packed decode kernel" : "packed encode kernel",
                       [&](const LaunchCfg& cfg) {
-                        return decode ? launch_packed_decode(cfg, s, sl, (const uint64_t*)records, ok, B, width)
-                                      : launch_packed_encode(cfg, s, sl, (uint64_t*)records, ok, B, width);
+                        return decode ? launch_packed_decode(cfg, s, sl, (const uint64_t*)records, ok, B, sizeof(C))
+                                      : launch_packed_encode(cfg, s, sl, (uint64_t*)records, ok, B, sizeof(C));
                       });
 }
 
-int packed_encode_dev(rzk_ctx* c, int kind, uint32_t V, const int64_t* const* fields, uint8_t* records, uint8_t* ok, size_t B,
-                      uint32_t width) {
+// encode reads the slabs of `fields` and writes `records`; decode the reverse
+template <class C>
+int packed_dev(rzk_ctx* c, int kind, uint32_t V, const C* const* fields, uint8_t* records, uint8_t* ok, size_t B, bool decode) {
   PackedSchema s;
   PackedSlabs sl;
   if (!c) return RZK_E_ARG;
   const int rc = packed_args(c, kind, V, fields, records, ok, B, &s, &sl);
   if (rc != RZK_OK || B == 0) return rc;
-  return packed_run(c, s, sl, records, ok, B, 0, width);
+  return packed_run<C>(c, s, sl, records, ok, B, decode);
 }
 
-int packed_decode_dev(rzk_ctx* c, int kind, uint32_t V, const uint8_t* records, const int64_t* const* fields, uint8_t* ok, size_t B,
-                      uint32_t width) {
+// the host forms stage the slabs on 256-byte boundaries; sl, checked on the host pointers, then names the staged copies
+template <class C>
+int packed_encode_host(rzk_ctx* c, int kind, uint32_t V, const C* const* fields, uint8_t* records, uint8_t* ok, size_t B) {
   PackedSchema s;
   PackedSlabs sl;
   if (!c) return RZK_E_ARG;
-  const int rc = packed_args(c, kind, V, fields, records, ok, B, &s, &sl);
-  if (rc != RZK_OK || B == 0) return rc;
-  return packed_run(c, s, sl, const_cast<uint8_t*>(records), ok, B, 1, width);
-}
-
-int packed_encode_host(rzk_ctx* c, int kind, uint32_t V, const int64_t* const* fields, uint8_t* records, uint8_t* ok, size_t B,
-                       uint32_t width) {
-  PackedSchema s;
-  PackedSlabs sl;
-  if (!c) return RZK_E_ARG;
-  const int rc = packed_args(c, kind, V, fields, records, ok, B, &s, &sl);
+  int rc = packed_args(c, kind, V, fields, records, ok, B, &s, &sl);
   if (rc != RZK_OK || B == 0) return rc;
   HostCall h(c);
   const auto drecords = h.out(records, B * (size_t)packed_record_bytes(s));
   const auto dok = h.out(ok, B);
-  // sl.ptr: the staged slabs, on 256-byte boundaries (PackedSlabs serves both directions, so its pointers are not const)
-  for (uint32_t f = 0; f < s.nfields; ++f)
-    h.in_to(const_cast<const int64_t**>(&sl.ptr[f]), fields[f], packed_field_bytes(c, s, f, B, width));
-  return h.run([&] { return packed_run(c, s, sl, drecords, dok, B, 0, width); });
+  const C* dev_fields[kPackedMaxFields] = {};
+  for (uint32_t f = 0; f < s.nfields; ++f) h.in_to(&dev_fields[f], fields[f], packed_field_bytes<C>(c, s, f, B));
+  return h.run([&] {
+    for (uint32_t f = 0; f < s.nfields; ++f) sl.ptr[f] = launch_addr(const_cast<C*>(dev_fields[f]));
+    return packed_run<C>(c, s, sl, drecords, dok, B, false);
+  });
 }
 
-int packed_decode_host(rzk_ctx* c, int kind, uint32_t V, const uint8_t* records, const int64_t* const* fields, uint8_t* ok, size_t B,
-                       uint32_t width) {
+template <class C>
+int packed_decode_host(rzk_ctx* c, int kind, uint32_t V, const uint8_t* records, C* const* fields, uint8_t* ok, size_t B) {
   PackedSchema s;
   PackedSlabs sl;
   if (!c) return RZK_E_ARG;
-  const int rc = packed_args(c, kind, V, fields, records, ok, B, &s, &sl);
+  const int rc = packed_args<C>(c, kind, V, fields, records, ok, B, &s, &sl);
   if (rc != RZK_OK || B == 0) return rc;
   HostCall h(c);
   const auto drecords = h.in(records, B * (size_t)packed_record_bytes(s));
   const auto dok = h.out(ok, B);
-  for (uint32_t f = 0; f < s.nfields; ++f) h.out_to(&sl.ptr[f], const_cast<int64_t*>(fields[f]), packed_field_bytes(c, s, f, B, width));
+  C* dev_fields[kPackedMaxFields] = {};
+  for (uint32_t f = 0; f < s.nfields; ++f) h.out_to(&dev_fields[f], fields[f], packed_field_bytes<C>(c, s, f, B));
   return h.run([&] {
     const uint8_t* rec = drecords;
-    return packed_run(c, s, sl, const_cast<uint8_t*>(rec), dok, B, 1, width);
+    for (uint32_t f = 0; f < s.nfields; ++f) sl.ptr[f] = launch_addr(dev_fields[f]);
+    return packed_run<C>(c, s, sl, const_cast<uint8_t*>(rec), dok, B, true);
   });
 }
 
@@ -577,36 +605,36 @@ int rzk_packed_widths(const rzk_ctx* c, uint32_t* wq, uint32_t* wz) {
 
 int rzk_packed_encode_batch_dev(rzk_ctx* c, int kind, uint32_t V, const int64_t* const* fields, uint8_t* records, uint8_t* ok,
                                 size_t B) {
-  return packed_encode_dev(c, kind, V, fields, records, ok, B, 8);
+  return packed_dev(c, kind, V, fields, records, ok, B, false);
 }
 int rzk_packed_decode_batch_dev(rzk_ctx* c, int kind, uint32_t V, const uint8_t* records, int64_t* const* fields, uint8_t* ok,
                                 size_t B) {
-  return packed_decode_dev(c, kind, V, records, (const int64_t* const*)fields, ok, B, 8);
+  return packed_dev<int64_t>(c, kind, V, fields, const_cast<uint8_t*>(records), ok, B, true);
 }
 int rzk_packed_encode_batch(rzk_ctx* c, int kind, uint32_t V, const int64_t* const* fields, uint8_t* records, uint8_t* ok,
                             size_t B) {
-  return packed_encode_host(c, kind, V, fields, records, ok, B, 8);
+  return packed_encode_host(c, kind, V, fields, records, ok, B);
 }
 int rzk_packed_decode_batch(rzk_ctx* c, int kind, uint32_t V, const uint8_t* records, int64_t* const* fields, uint8_t* ok,
                             size_t B) {
-  return packed_decode_host(c, kind, V, records, (const int64_t* const*)fields, ok, B, 8);
+  return packed_decode_host(c, kind, V, records, fields, ok, B);
 }
 // the same four over int32_t slabs (v14, slab32 messages): records carry no width
 int rzk_packed_encode32_batch_dev(rzk_ctx* c, int kind, uint32_t V, const int32_t* const* fields, uint8_t* records, uint8_t* ok,
                                   size_t B) {
-  return packed_encode_dev(c, kind, V, as64(fields), records, ok, B, 4);
+  return packed_dev(c, kind, V, fields, records, ok, B, false);
 }
 int rzk_packed_decode32_batch_dev(rzk_ctx* c, int kind, uint32_t V, const uint8_t* records, int32_t* const* fields, uint8_t* ok,
                                   size_t B) {
-  return packed_decode_dev(c, kind, V, records, as64((const int32_t* const*)fields), ok, B, 4);
+  return packed_dev<int32_t>(c, kind, V, fields, const_cast<uint8_t*>(records), ok, B, true);
 }
 int rzk_packed_encode32_batch(rzk_ctx* c, int kind, uint32_t V, const int32_t* const* fields, uint8_t* records, uint8_t* ok,
                               size_t B) {
-  return packed_encode_host(c, kind, V, as64(fields), records, ok, B, 4);
+  return packed_encode_host(c, kind, V, fields, records, ok, B);
 }
 int rzk_packed_decode32_batch(rzk_ctx* c, int kind, uint32_t V, const uint8_t* records, int32_t* const* fields, uint8_t* ok,
                               size_t B) {
-  return packed_decode_host(c, kind, V, records, as64((const int32_t* const*)fields), ok, B, 4);
+  return packed_decode_host(c, kind, V, records, fields, ok, B);
 }
 
 // ---- v10: public polynomials expanded from 32-byte seeds, "XP1" (rzk_xof_dev.hip, rzk_xof.h; keys: rzk_key.cpp) ------------

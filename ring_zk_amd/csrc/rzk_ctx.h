@@ -1,5 +1,7 @@
 // rzk_ctx.h — internal to the C-ABI host code (rzk_ctx.cpp, rzk_key.cpp, rzk_run.cpp, rzk_protocols.cpp, rzk_host.cpp,
-// rzk_samplers.cpp, rzk_codec.cpp): the context behind include/rzk.h and the helpers those translation units share.
+// rzk_samplers.cpp, rzk_codec.cpp, rzk_slab32.cpp, rzk_prove_loop.cpp): the context behind include/rzk.h and the helpers
+// those translation units share.  An entry point that exists for int64_t and int32_t slabs is one template over the
+// coefficient type C (rzk_coef.h); its extern "C" symbols forward to it.
 // Host-only.  Everything in rzk::api has hidden visibility: the library exports the rzk_* entry points, not these.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -17,6 +19,7 @@
 
 #include "../../include/rzk.h"
 #include "rzk_chacha.h"
+#include "rzk_coef.h"
 #include "rzk_core.h"
 #include "rzk_dev.h"
 #include "rzk_dgauss.h"
@@ -47,11 +50,27 @@ struct Arena {   // grow-only device buffer
   size_t cap = 0;
 };
 
-struct OpSpec {   // one operand of a row-program launch
-  const int64_t* base;
-  uint32_t stride;
-  uint32_t outer;   // 0: indexed by the task batch index; otherwise by the proof index b / group
+using OpSpec = Op<int64_t>;
+
+struct OpList {   // an operand list as the bodies of rzk_run.cpp take it: lowered addresses and, once, what they point at
+  const int64_t* base[kMaxOperands];
+  uint32_t stride[kMaxOperands];
+  uint32_t outer[kMaxOperands];
+  size_t n;         // operands of the list; the bodies refuse more than kMaxOperands (none beyond are held)
+  uint32_t width;   // sizeof(C)
 };
+template <class C>
+inline OpList lower(const std::vector<Op<C>>& specs) {
+  OpList o;
+  o.n = specs.size();
+  o.width = sizeof(C);
+  for (size_t i = 0; i < o.n && i < (size_t)kMaxOperands; ++i) {
+    o.base[i] = launch_addr(specs[i].base);
+    o.stride[i] = specs[i].stride;
+    o.outer[i] = specs[i].outer;
+  }
+  return o;
+}
 
 }  // namespace api
 }  // namespace rzk
@@ -164,7 +183,15 @@ LaunchCfg cfg_of(rzk_ctx* c);
 int arena_reserve(rzk_ctx* c, Arena& a, size_t bytes);
 int check_launch(rzk_ctx* c, int lrc, const char* what);
 int take_input_error(rzk_ctx* c);   // synchronises and reports (then clears) the sticky input-error word
-inline size_t polys(const rzk_ctx* c, size_t count) { return count * (size_t)c->N * sizeof(int64_t); }
+template <class C = int64_t>
+inline size_t polys(const rzk_ctx* c, size_t count) { return poly_bytes<C>(c->N, count); }   // bytes of `count` polynomials
+// 32-bit device slabs are 16-byte aligned (rzk_slab32.h); the 64-bit entry points have no such rule
+inline bool misaligned(std::initializer_list<const void*> slabs) {
+  uintptr_t bits = 0;
+  for (const void* p : slabs) bits |= reinterpret_cast<uintptr_t>(p);
+  return (bits & 15u) != 0;
+}
+inline int align_fail(rzk_ctx* c) { return fail(c, RZK_E_ARG, "slab32: device slabs must be 16-byte aligned"); }
 
 // ---- rzk_run.cpp: row programs, norm kernels, the images of a call ----------------------------------------------------
 void drop_programs(rzk_ctx* c);
@@ -180,11 +207,17 @@ int run_profiled(rzk_ctx* c, uint64_t bytes, const char* what, L launch) {
 }
 bool shift_ok(const rzk_ctx* c);
 bool response_stat_fused(const rzk_ctx* c);
-int run_program(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSpec>& specs, uint8_t* flags, uint32_t group,
-                uint64_t batch, uint64_t norm_limit = 0, bool sticky = true, uint8_t preset_value = 0, uint64_t nflags = 0,
-                const ResponseStat* stat = nullptr, uint32_t width = 8);
-// width 4: the operands are int32_t slabs (their addresses travel as int64_t*) and the program must have native 32-bit
-// kernels on this context (program_native32, asked by the entry point before its first launch)
+// The operands' coefficient type says which kernels run.  C defaults to int64_t where the list is written in braces at the
+// call (a list of int32_t slabs then does not compile); a named std::vector<Op<C>> brings its own.  int32_t: the program
+// must have native 32-bit kernels on this context (program_native32, asked by the entry point before its first launch).
+int run_program_lowered(rzk_ctx* c, int id, uint32_t var, const OpList& specs, uint8_t* flags, uint32_t group, uint64_t batch,
+                        uint64_t norm_limit, bool sticky, uint8_t preset_value, uint64_t nflags, const ResponseStat* stat);
+template <class C = int64_t>
+inline int run_program(rzk_ctx* c, int id, uint32_t var, const std::vector<Op<C>>& specs, uint8_t* flags, uint32_t group,
+                       uint64_t batch, uint64_t norm_limit = 0, bool sticky = true, uint8_t preset_value = 0, uint64_t nflags = 0,
+                       const ResponseStat* stat = nullptr) {
+  return run_program_lowered(c, id, var, lower(specs), flags, group, batch, norm_limit, sticky, preset_value, nflags, stat);
+}
 bool program_native32(rzk_ctx* c, int id, uint32_t var);
 // the fused (var | 1) form of a checked program can run on this context with this bound (run_checked then takes no fallback)
 bool checked_fuses(rzk_ctx* c, int id, uint32_t var, uint64_t bound);
@@ -195,9 +228,14 @@ struct NormSpec {   // one launch of the norm kernel: flags (mode, shift) sum c^
   uint32_t rows;
   int mode, shift;   // launch_norm: 0 = overwrite, 1 = and, 2 = or (result << shift)
 };
-int run_checked(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSpec>& specs, uint8_t* flags, uint32_t group,
-                uint64_t batch, uint64_t nflags, uint64_t bound, bool preset, bool sticky, std::initializer_list<NormSpec> norms,
-                uint32_t width = 8);
+int run_checked_lowered(rzk_ctx* c, int id, uint32_t var, const OpList& specs, uint8_t* flags, uint32_t group, uint64_t batch,
+                        uint64_t nflags, uint64_t bound, bool preset, bool sticky, std::initializer_list<NormSpec> norms);
+template <class C = int64_t>
+inline int run_checked(rzk_ctx* c, int id, uint32_t var, const std::vector<Op<C>>& specs, uint8_t* flags, uint32_t group,
+                       uint64_t batch, uint64_t nflags, uint64_t bound, bool preset, bool sticky,
+                       std::initializer_list<NormSpec> norms) {
+  return run_checked_lowered(c, id, var, lower(specs), flags, group, batch, nflags, bound, preset, sticky, norms);
+}
 int prepare_dkey(rzk_ctx* c, const int64_t* g, uint64_t entries, uint32_t per_entry, uint32_t uses, uint8_t* flags, bool sticky);
 int prepare_oimg(rzk_ctx* c, uint64_t B, uint32_t V, uint32_t uses);
 bool sum_uses_d(const rzk_ctx* c, uint32_t V);
@@ -222,11 +260,46 @@ struct OimgProducer {
   ~OimgProducer() { c->oimg_producer_op = 0xffu; }
 };
 
-// ---- rzk_codec.cpp ---------------------------------------------------------------------------------------------------
-// rzk_open_response_reject_batch_dev on int32_t slabs y, r, d, z where the fused rows run natively (the caller has asked
-// program_native32(c, PG_RESPONSE, 1) && response_stat_fused(c)): the sibling's argument rules, launches and outputs
-int open_response_reject_native32(rzk_ctx* c, const int32_t* y, const int32_t* r, const int32_t* d, const int64_t* coin, uint64_t R,
-                                  double lnM, int32_t* z, uint8_t* accept, int64_t* E, size_t B);
+// ---- rzk_slab32.cpp: the convert path of a 32-bit call ----------------------------------------------------------------
+// The call's slabs as int64_t copies in ws32: convert_call reserves the arena and widens every `in`, runs body(wide) —
+// the call's own body on int64_t, wide[i] the copy of slab i (NULL for an absent one) — and narrows every `out`.
+struct Conv {   // one slab of the call, `count` polynomials: read (in), written (out), or absent (neither)
+  const int32_t* in;
+  int32_t* out;
+  size_t count;
+};
+int convert_begin(rzk_ctx* c, const Conv* slabs, size_t n, int64_t** wide);
+int convert_end(rzk_ctx* c, const Conv* slabs, size_t n, int64_t* const* wide);
+template <size_t K, class F>
+int convert_call(rzk_ctx* c, const Conv (&slabs)[K], F body) {
+  int64_t* wide[K];
+  int rc = convert_begin(c, slabs, K, wide);
+  if (rc == RZK_OK) rc = body(wide);
+  return rc != RZK_OK ? rc : convert_end(c, slabs, K, wide);
+}
+
+// ---- the *_dev entry points that exist at both widths, C = int64_t or int32_t (the siblings' extern "C" symbols forward
+// here; rzk_prove_loop.cpp calls them typed).  Defined, and instantiated for both, in the file named.
+// (an explicit instantiation takes the visibility of where it stands, not of the declaration here: hidden is said again)
+#define RZK_BOTH_WIDTHS(fn)                                                              \
+  template __attribute__((visibility("hidden"))) decltype(fn<int64_t>) fn<int64_t>; \
+  template __attribute__((visibility("hidden"))) decltype(fn<int32_t>) fn<int32_t>;
+// rzk_protocols.cpp
+template <class C> int open_commit_dev(rzk_ctx* c, const C* x, const C* r, const C* y, C* cm, C* t, uint8_t* ok, size_t B);
+template <class C> int open_response_dev(rzk_ctx* c, const C* y, const C* r, const C* d, C* z, size_t B);
+template <class C> int open_a1_relation_dev(rzk_ctx* c, const C* z, const C* t, const C* cm, const C* d, uint8_t* accept, size_t B,
+                                            bool recover);   // verify; recover: t is the output
+template <class C> int matvec_dev(rzk_ctx* c, int which, const C* v, const C* addend, C* out, size_t B);
+// rzk_samplers.cpp
+template <class C> int sample_uniform_keyed_dev(rzk_ctx* c, const uint8_t* nonce, uint32_t stream, uint64_t bound, C* out, size_t count);
+template <class C> int sample_gauss_keyed_dev(rzk_ctx* c, const uint8_t* nonce, uint32_t stream, double sigma, C* out, size_t count);
+template <class C> int sample_dgauss_keyed_dev(rzk_ctx* c, const uint8_t* nonce, uint32_t stream, uint32_t sigma, C* out, size_t count);
+template <class C> int sample_challenge_keyed_dev(rzk_ctx* c, const uint8_t* nonce, uint32_t stream, C* out, size_t count);
+// rzk_codec.cpp
+template <class C> int fs_challenge_dev(rzk_ctx* c, int kind, uint32_t V, const C* const* fields, const uint8_t* aux32, C* d,
+                                        uint8_t* digest, uint8_t* ok, size_t B);
+template <class C> int open_response_reject_dev(rzk_ctx* c, const C* y, const C* r, const C* d, const int64_t* coin, uint64_t R,
+                                                double lnM, C* z, uint8_t* accept, int64_t* E, size_t B);
 // out[b][r] = polynomial p0 + r of XP1 under seeds[b] and `domain`; seeds and out on the device
 int run_xof(rzk_ctx* c, uint32_t domain, uint32_t p0, uint32_t rows, const uint64_t* seeds, int64_t* out, size_t B);
 
@@ -254,11 +327,11 @@ class HostCall {
   template <class T> Dev<const T> in(const T* host, size_t bytes) { return {&c_->stage, add(host, nullptr, bytes, !host)}; }
   template <class T> Dev<T> out(T* host, size_t bytes) { return {&c_->stage, add(nullptr, host, bytes, !host)}; }
   template <class T> Dev<T> scratch(size_t bytes) { return {&c_->stage, add(nullptr, nullptr, bytes, false)}; }
-  Dev<const int64_t> pin(const int64_t* host, size_t count) { return in(host, polys(c_, count)); }   // count polynomials
-  Dev<int64_t> pout(int64_t* host, size_t count) { return out(host, polys(c_, count)); }
+  template <class C> Dev<const C> pin(const C* host, size_t count) { return in(host, polys<C>(c_, count)); }   // count polynomials
+  template <class C> Dev<C> pout(C* host, size_t count) { return out(host, polys<C>(c_, count)); }
   // for pointer tables (the slabs of a message's fields): *slot receives the device pointer when the arena is staged
-  void in_to(const int64_t** slot, const int64_t* host, size_t bytes) { add(host, nullptr, bytes, !host, const_cast<int64_t**>(slot)); }
-  void out_to(int64_t** slot, int64_t* host, size_t bytes) { add(nullptr, host, bytes, !host, slot); }
+  template <class C> void in_to(const C** slot, const C* host, size_t bytes) { add(host, nullptr, bytes, !host, slot, &set_slot<const C>); }
+  template <class C> void out_to(C** slot, C* host, size_t bytes) { add(nullptr, host, bytes, !host, slot, &set_slot<C>); }
   int stage();   // reserve and fill the arena only (callers without the sticky-word protocol)
   template <class F>
   int run(F dev_call) {
@@ -271,9 +344,11 @@ class HostCall {
     const void* in;   // host source (nullptr for pure outputs)
     void* out;        // host destination (nullptr for pure inputs)
     size_t bytes, off;
-    int64_t** slot;   // in_to / out_to
+    void* slot;                    // in_to / out_to: the caller's T*, written by set(slot, device pointer)
+    void (*set)(void*, void*);
   };
-  size_t add(const void* in, void* out, size_t bytes, bool null, int64_t** slot = nullptr);
+  template <class T> static void set_slot(void* slot, void* p) { *static_cast<T**>(slot) = static_cast<T*>(p); }
+  size_t add(const void* in, void* out, size_t bytes, bool null, void* slot = nullptr, void (*set)(void*, void*) = nullptr);
   int begin();
   int end(int rc);
   rzk_ctx* c_;

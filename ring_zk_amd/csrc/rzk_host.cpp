@@ -1,13 +1,14 @@
 // rzk_host.cpp — the host-pointer variants of the Mat-level operations and the three protocols (include/rzk.h): each
 // stages its operands through HostCall (rzk_ctx.h) and calls the *_dev entry point of the same name.  The variants of
-// the codecs, Fiat-Shamir, rejection and XOF entry points sit next to those in rzk_codec.cpp.
+// the codecs, Fiat-Shamir, rejection and XOF entry points sit next to those in rzk_codec.cpp.  The calls that exist for
+// int64_t and int32_t slabs are one template over the coefficient type (pin / pout stage by it).
 #include "rzk_ctx.h"
 
 namespace rzk::api {
 
-size_t HostCall::add(const void* in, void* out, size_t bytes, bool null, int64_t** slot) {
+size_t HostCall::add(const void* in, void* out, size_t bytes, bool null, void* slot, void (*set)(void*, void*)) {
   if (null) return kNull;
-  bufs_.push_back(Buf{in, out, bytes, total_, slot});
+  bufs_.push_back(Buf{in, out, bytes, total_, slot, set});
   total_ += (bytes + 255) & ~size_t(255);
   return bufs_.back().off;
 }
@@ -16,7 +17,7 @@ int HostCall::stage() {
   int rc = arena_reserve(c_, c_->stage, total_);
   if (rc != RZK_OK) return rc;
   for (const Buf& b : bufs_) {
-    if (b.slot) *b.slot = (int64_t*)((char*)c_->stage.p + b.off);
+    if (b.slot) b.set(b.slot, (char*)c_->stage.p + b.off);
     if (b.in && b.bytes)
       HIPCHK(c_, hipMemcpyAsync((char*)c_->stage.p + b.off, b.in, b.bytes, hipMemcpyHostToDevice, c_->stream));
   }
@@ -67,6 +68,59 @@ int host_ntt(rzk_ctx* c, int prime, const uint32_t* in, uint32_t* out, size_t co
   return h.run([&] { return dev(c, prime, din, dout, count); });
 }
 
+template <class C>
+int matvec_host(rzk_ctx* c, int which, const C* v, const C* addend, C* out, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !v || !out || which < 0 || which > 2) return RZK_E_ARG;
+  const uint32_t rows = which == RZK_KEY_A1 ? c->n : (which == RZK_KEY_A2 ? c->l : c->n + c->l);
+  HostCall h(c);
+  const auto dv = h.pin(v, B * c->k), dadd = h.pin(addend, B * rows);
+  const auto dout = h.pout(out, B * rows);
+  return h.run([&] { return matvec_dev<C>(c, which, dv, dadd, dout, B); });
+}
+
+template <class C>
+int open_commit_host(rzk_ctx* c, const C* x, const C* r, const C* y, C* cm, C* t, uint8_t* ok, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !x || !r || !y || !cm || !t) return RZK_E_ARG;
+  HostCall h(c);
+  const auto dx = h.pin(x, B * c->l), dr = h.pin(r, B * c->k), dy = h.pin(y, B * c->k);
+  const auto dcm = h.pout(cm, B * (c->n + c->l)), dt = h.pout(t, B * c->n);
+  const auto dok = h.out(ok, B);
+  return h.run([&] { return open_commit_dev<C>(c, dx, dr, dy, dcm, dt, dok, B); });
+}
+
+template <class C>
+int open_response_host(rzk_ctx* c, const C* y, const C* r, const C* d, C* z, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !y || !r || !d || !z) return RZK_E_ARG;
+  HostCall h(c);
+  const auto dy = h.pin(y, B * c->k), dr = h.pin(r, B * c->k), dd = h.pin(d, B);
+  const auto dz = h.pout(z, B * c->k);
+  return h.run([&] { return open_response_dev<C>(c, dy, dr, dd, dz, B); });
+}
+
+template <class C>
+int open_verify_host(rzk_ctx* c, const C* z, const C* t, const C* cm, const C* d, uint8_t* accept, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !z || !t || !cm || !d || !accept) return RZK_E_ARG;
+  HostCall h(c);
+  const auto dz = h.pin(z, B * c->k), dt = h.pin(t, B * c->n), dcm = h.pin(cm, B * (c->n + c->l)), dd = h.pin(d, B);
+  const auto dacc = h.out(accept, B);
+  return h.run([&] { return open_a1_relation_dev<C>(c, dz, dt, dcm, dd, dacc, B, false); });
+}
+
+template <class C>
+int open_recover_host(rzk_ctx* c, const C* z, const C* cm, const C* d, C* t_out, uint8_t* accept, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !z || !cm || !d || !t_out || !accept) return RZK_E_ARG;
+  HostCall h(c);
+  const auto dz = h.pin(z, B * c->k), dcm = h.pin(cm, B * (c->n + c->l)), dd = h.pin(d, B);
+  const auto dt = h.pout(t_out, B * c->n);
+  const auto dacc = h.out(accept, B);
+  return h.run([&] { return open_a1_relation_dev<C>(c, dz, dt, dcm, dd, dacc, B, true); });
+}
+
 }  // namespace
 
 extern "C" {
@@ -88,13 +142,10 @@ int rzk_ntt_inverse_batch(rzk_ctx* c, int prime, const uint32_t* in, uint32_t* o
 }
 
 int rzk_matvec_batch(rzk_ctx* c, int which, const int64_t* v, const int64_t* addend, int64_t* out, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !v || !out || which < 0 || which > 2) return RZK_E_ARG;
-  const uint32_t rows = which == RZK_KEY_A1 ? c->n : (which == RZK_KEY_A2 ? c->l : c->n + c->l);
-  HostCall h(c);
-  const auto dv = h.pin(v, B * c->k), dadd = h.pin(addend, B * rows);
-  const auto dout = h.pout(out, B * rows);
-  return h.run([&] { return rzk_matvec_batch_dev(c, which, dv, dadd, dout, B); });
+  return matvec_host(c, which, v, addend, out, B);
+}
+int rzk_matvec32_batch(rzk_ctx* c, int which, const int32_t* v, const int32_t* addend, int32_t* out, size_t B) {
+  return matvec_host(c, which, v, addend, out, B);
 }
 
 int rzk_cmul_batch(rzk_ctx* c, const int64_t* m, uint32_t rows, const int64_t* p, int64_t* out, size_t B) {
@@ -153,34 +204,36 @@ int rzk_commitment_verify_batch(rzk_ctx* c, const int64_t* cm, const int64_t* x,
   return h.run([&] { return rzk_commitment_verify_batch_dev(c, dcm, dx, dr, df, dok, B); });
 }
 
-int rzk_open_commit_batch(rzk_ctx* c, const int64_t* x, const int64_t* r, const int64_t* y, int64_t* cm, int64_t* t,
-                          uint8_t* ok, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !x || !r || !y || !cm || !t) return RZK_E_ARG;
-  HostCall h(c);
-  const auto dx = h.pin(x, B * c->l), dr = h.pin(r, B * c->k), dy = h.pin(y, B * c->k);
-  const auto dcm = h.pout(cm, B * (c->n + c->l)), dt = h.pout(t, B * c->n);
-  const auto dok = h.out(ok, B);
-  return h.run([&] { return rzk_open_commit_batch_dev(c, dx, dr, dy, dcm, dt, dok, B); });
+// ---- OpenProof and its recompute step, at either width ---------------------------------------------------------------
+int rzk_open_commit_batch(rzk_ctx* c, const int64_t* x, const int64_t* r, const int64_t* y, int64_t* cm, int64_t* t, uint8_t* ok,
+                          size_t B) {
+  return open_commit_host(c, x, r, y, cm, t, ok, B);
 }
-
+int rzk_open_commit32_batch(rzk_ctx* c, const int32_t* x, const int32_t* r, const int32_t* y, int32_t* cm, int32_t* t, uint8_t* ok,
+                            size_t B) {
+  return open_commit_host(c, x, r, y, cm, t, ok, B);
+}
 int rzk_open_response_batch(rzk_ctx* c, const int64_t* y, const int64_t* r, const int64_t* d, int64_t* z, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !y || !r || !d || !z) return RZK_E_ARG;
-  HostCall h(c);
-  const auto dy = h.pin(y, B * c->k), dr = h.pin(r, B * c->k), dd = h.pin(d, B);
-  const auto dz = h.pout(z, B * c->k);
-  return h.run([&] { return rzk_open_response_batch_dev(c, dy, dr, dd, dz, B); });
+  return open_response_host(c, y, r, d, z, B);
 }
-
-int rzk_open_verify_batch(rzk_ctx* c, const int64_t* z, const int64_t* t, const int64_t* cm, const int64_t* d,
-                          uint8_t* accept, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !z || !t || !cm || !d || !accept) return RZK_E_ARG;
-  HostCall h(c);
-  const auto dz = h.pin(z, B * c->k), dt = h.pin(t, B * c->n), dcm = h.pin(cm, B * (c->n + c->l)), dd = h.pin(d, B);
-  const auto dacc = h.out(accept, B);
-  return h.run([&] { return rzk_open_verify_batch_dev(c, dz, dt, dcm, dd, dacc, B); });
+int rzk_open_response32_batch(rzk_ctx* c, const int32_t* y, const int32_t* r, const int32_t* d, int32_t* z, size_t B) {
+  return open_response_host(c, y, r, d, z, B);
+}
+int rzk_open_verify_batch(rzk_ctx* c, const int64_t* z, const int64_t* t, const int64_t* cm, const int64_t* d, uint8_t* accept,
+                          size_t B) {
+  return open_verify_host(c, z, t, cm, d, accept, B);
+}
+int rzk_open_verify32_batch(rzk_ctx* c, const int32_t* z, const int32_t* t, const int32_t* cm, const int32_t* d, uint8_t* accept,
+                            size_t B) {
+  return open_verify_host(c, z, t, cm, d, accept, B);
+}
+int rzk_open_recover_batch(rzk_ctx* c, const int64_t* z, const int64_t* cm, const int64_t* d, int64_t* t_out, uint8_t* accept,
+                           size_t B) {
+  return open_recover_host(c, z, cm, d, t_out, accept, B);
+}
+int rzk_open_recover32_batch(rzk_ctx* c, const int32_t* z, const int32_t* cm, const int32_t* d, int32_t* t_out, uint8_t* accept,
+                             size_t B) {
+  return open_recover_host(c, z, cm, d, t_out, accept, B);
 }
 
 int rzk_linear_commit_batch(rzk_ctx* c, const int64_t* g, const int64_t* x, const int64_t* r, const int64_t* rp,
@@ -264,17 +317,6 @@ int rzk_sum_verify_batch(rzk_ctx* c, uint32_t V, const int64_t* zs, const int64_
 }
 
 // ---- recompute steps of the short proofs ---------------------------------------------------------------------------
-int rzk_open_recover_batch(rzk_ctx* c, const int64_t* z, const int64_t* cm, const int64_t* d, int64_t* t_out,
-                           uint8_t* accept, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !z || !cm || !d || !t_out || !accept) return RZK_E_ARG;
-  HostCall h(c);
-  const auto dz = h.pin(z, B * c->k), dcm = h.pin(cm, B * (c->n + c->l)), dd = h.pin(d, B);
-  const auto dt = h.pout(t_out, B * c->n);
-  const auto dacc = h.out(accept, B);
-  return h.run([&] { return rzk_open_recover_batch_dev(c, dz, dcm, dd, dt, dacc, B); });
-}
-
 int rzk_linear_recover_batch(rzk_ctx* c, const int64_t* z, const int64_t* zp, const int64_t* cm, const int64_t* cpm,
                              const int64_t* g, const int64_t* d, int64_t* t_out, int64_t* tp_out, int64_t* u_out,
                              uint8_t* accept, size_t B) {

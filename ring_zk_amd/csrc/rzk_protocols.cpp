@@ -92,7 +92,96 @@ int sum_relations(rzk_ctx* c, uint32_t V, const int64_t* zs, const int64_t* zp, 
                      1, B, 0, false);
 }
 
+// a checked program (run_checked) runs natively on 32-bit slabs: its fused form when the call has flags, its plain form otherwise
+bool native_checked(rzk_ctx* c, int id, uint32_t var, uint64_t bound, const uint8_t* flags) {
+  if (!flags) return program_native32(c, id, var);
+  return checked_fuses(c, id, var, bound) && program_native32(c, id, var | 1);
+}
+
 }  // namespace
+
+namespace rzk::api {
+
+template <class C>
+int matvec_dev(rzk_ctx* c, int which, const C* v, const C* addend, C* out, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !v || !out || which < 0 || which > 2) return RZK_E_ARG;
+  const uint32_t rows = which == RZK_KEY_A1 ? c->n : (which == RZK_KEY_A2 ? c->l : c->n + c->l);
+  const uint32_t var = (uint32_t)which * 2 + (addend ? 1 : 0);
+  if constexpr (sizeof(C) == 4) {
+    if (misaligned({v, addend, out})) return align_fail(c);
+    if (!program_native32(c, PG_MATVEC, var))
+      return convert_call(c, {{v, nullptr, B * c->k}, {nullptr, out, B * rows}, {addend, nullptr, B * rows}},
+                          [&](int64_t* const* w) { return matvec_dev<int64_t>(c, which, w[0], w[2], w[1], B); });
+  }
+  return run_program<C>(c, PG_MATVEC, var, {{v, c->k, 0}, {addend, rows, 0}, {out, rows, 0}}, nullptr, 1, B);
+}
+RZK_BOTH_WIDTHS(matvec_dev)
+
+template <class C>
+int open_commit_dev(rzk_ctx* c, const C* x, const C* r, const C* y, C* cm, C* t, uint8_t* ok, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !x || !r || !y || !cm || !t) return RZK_E_ARG;
+  auto specs = [&] {   // of the launching branches
+    return std::vector<Op<C>>{{x, c->l, 0}, {r, c->k, 0}, {y, c->k, 0}, {cm, c->n + c->l, 0}, {t, c->n, 0}};
+  };
+  if constexpr (sizeof(C) == 4) {
+    if (misaligned({x, r, y, cm, t})) return align_fail(c);
+    if (native_checked(c, PG_OPEN_COMMIT, 0, c->commit_bound, ok))   // fused, or no flags: no norm kernel (they read 64-bit slabs)
+      return run_checked(c, PG_OPEN_COMMIT, 0, specs(), ok, 1, B, B, c->commit_bound, true, true, {});
+    return convert_call(c, {{x, nullptr, B * c->l}, {r, nullptr, B * c->k}, {y, nullptr, B * c->k}, {nullptr, cm, B * (c->n + c->l)},
+                            {nullptr, t, B * c->n}},
+                        [&](int64_t* const* w) { return open_commit_dev<int64_t>(c, w[0], w[1], w[2], w[3], w[4], ok, B); });
+  } else {
+    // check_commit_constraint(r) (params.rs:102-108) rides on the loads of r the commit rows do anyway
+    return run_checked(c, PG_OPEN_COMMIT, 0, specs(), ok, 1, B, B, c->commit_bound, true, true, {{r, c->k, 0, 0}});
+  }
+}
+RZK_BOTH_WIDTHS(open_commit_dev)
+
+template <class C>
+int open_response_dev(rzk_ctx* c, const C* y, const C* r, const C* d, C* z, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !y || !r || !d || !z) return RZK_E_ARG;
+  if constexpr (sizeof(C) == 4) {
+    if (misaligned({y, r, d, z})) return align_fail(c);
+    if (!program_native32(c, PG_RESPONSE, 1))
+      return convert_call(c, {{y, nullptr, B * c->k}, {r, nullptr, B * c->k}, {d, nullptr, B}, {nullptr, z, B * c->k}},
+                          [&](int64_t* const* w) { return open_response_dev<int64_t>(c, w[0], w[1], w[2], w[3], B); });
+  }
+  return run_program<C>(c, PG_RESPONSE, 1, {{d, 1, 0}, {y, c->k, 0}, {r, c->k, 0}, {z, c->k, 0}}, nullptr, 1, B);
+}
+RZK_BOTH_WIDTHS(open_response_dev)
+
+// open.rs:167-173 behind rzk_open_verify and, with recover, rzk_open_recover: the recompute step of the short proof, the
+// verifier's launches with the commitment message t = a1.z - c1 (.) d as output (t is written).  64-bit slabs take
+// run_a1_relation with its workspace; 32-bit slabs the one-launch relation at n = 1 where it runs natively (never the
+// split: program_native32 is false wherever that would apply), the convert path otherwise.
+template <class C>
+int open_a1_relation_dev(rzk_ctx* c, const C* z, const C* t, const C* cm, const C* d, uint8_t* accept, size_t B, bool recover) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !z || !t || !cm || !d || !accept) return RZK_E_ARG;
+  if (c->n != c->l) return fail(c, RZK_E_ARG, "c1_c2 split needs n == l (reference panics in Mat::add)");
+  auto specs = [&] { return std::vector<Op<C>>{{z, c->k, 0}, {t, c->n, 0}, {cm, c->n + c->l, 0}, {d, 1, 0}}; };   // of the launching branches
+  if constexpr (sizeof(C) == 4) {
+    if (misaligned({z, t, cm, d})) return align_fail(c);
+    const uint32_t rv = recover ? kRecoverVar : 0u;
+    if (native_checked(c, PG_A1_RELATION, rv, c->verify_bound, accept))
+      return run_checked(c, PG_A1_RELATION, rv, specs(), accept, 1, B, B, c->verify_bound, true, false, {});
+    C* const t_out = const_cast<C*>(t);
+    return convert_call(c, {{z, nullptr, B * c->k}, {cm, nullptr, B * (c->n + c->l)}, {d, nullptr, B},
+                            {recover ? nullptr : t, recover ? t_out : nullptr, B * c->n}},
+                        [&](int64_t* const* w) { return open_a1_relation_dev<int64_t>(c, w[0], w[3], w[1], w[2], accept, B, recover); });
+  } else {
+    int rc = arena_reserve(c, c->ws, polys(c, B * c->n));
+    if (rc != RZK_OK) return rc;
+    // the norm predicate on z rides on the rows that load z
+    return run_a1_relation(c, specs(), (int64_t*)c->ws.p, accept, 1, B, B, true, recover);
+  }
+}
+RZK_BOTH_WIDTHS(open_a1_relation_dev)
+
+}  // namespace rzk::api
 
 extern "C" {
 
@@ -104,11 +193,10 @@ int rzk_polymul_batch_dev(rzk_ctx* c, const int64_t* a, const int64_t* b, int64_
 }
 
 int rzk_matvec_batch_dev(rzk_ctx* c, int which, const int64_t* v, const int64_t* addend, int64_t* out, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !v || !out || which < 0 || which > 2) return RZK_E_ARG;
-  const uint32_t rows = which == RZK_KEY_A1 ? c->n : (which == RZK_KEY_A2 ? c->l : c->n + c->l);
-  return run_program(c, PG_MATVEC, (uint32_t)which * 2 + (addend ? 1 : 0),
-                     {{v, c->k, 0}, {addend, rows, 0}, {out, rows, 0}}, nullptr, 1, B);
+  return matvec_dev(c, which, v, addend, out, B);
+}
+int rzk_matvec32_batch_dev(rzk_ctx* c, int which, const int32_t* v, const int32_t* addend, int32_t* out, size_t B) {
+  return matvec_dev(c, which, v, addend, out, B);
 }
 
 int rzk_cmul_batch_dev(rzk_ctx* c, const int64_t* m, uint32_t rows, const int64_t* p, int64_t* out, size_t B) {
@@ -198,33 +286,36 @@ int rzk_commitment_verify_batch_dev(rzk_ctx* c, const int64_t* cm, const int64_t
                      c->commit_bound, true, false, {{r, c->k, 0, 0}});
 }
 
-// ---- OpenProof -----------------------------------------------------------------------------------------------------
-int rzk_open_commit_batch_dev(rzk_ctx* c, const int64_t* x, const int64_t* r, const int64_t* y, int64_t* cm,
-                              int64_t* t, uint8_t* ok, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !x || !r || !y || !cm || !t) return RZK_E_ARG;
-  const std::vector<OpSpec> specs = {{x, c->l, 0}, {r, c->k, 0}, {y, c->k, 0}, {cm, c->n + c->l, 0}, {t, c->n, 0}};
-  // check_commit_constraint(r) (params.rs:102-108) rides on the loads of r the commit rows do anyway
-  return run_checked(c, PG_OPEN_COMMIT, 0, specs, ok, 1, B, B, c->commit_bound, true, true, {{r, c->k, 0, 0}});
+// ---- OpenProof and its recompute step, at either width (the templates above) ---------------------------------------
+int rzk_open_commit_batch_dev(rzk_ctx* c, const int64_t* x, const int64_t* r, const int64_t* y, int64_t* cm, int64_t* t, uint8_t* ok,
+                              size_t B) {
+  return open_commit_dev(c, x, r, y, cm, t, ok, B);
 }
-
-int rzk_open_response_batch_dev(rzk_ctx* c, const int64_t* y, const int64_t* r, const int64_t* d, int64_t* z,
+int rzk_open_commit32_batch_dev(rzk_ctx* c, const int32_t* x, const int32_t* r, const int32_t* y, int32_t* cm, int32_t* t, uint8_t* ok,
                                 size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !y || !r || !d || !z) return RZK_E_ARG;
-  return run_program(c, PG_RESPONSE, 1, {{d, 1, 0}, {y, c->k, 0}, {r, c->k, 0}, {z, c->k, 0}}, nullptr, 1, B);
+  return open_commit_dev(c, x, r, y, cm, t, ok, B);
 }
-
-int rzk_open_verify_batch_dev(rzk_ctx* c, const int64_t* z, const int64_t* t, const int64_t* cm, const int64_t* d,
-                              uint8_t* accept, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !z || !t || !cm || !d || !accept) return RZK_E_ARG;
-  if (c->n != c->l) return fail(c, RZK_E_ARG, "c1_c2 split needs n == l (reference panics in Mat::add)");
-  const std::vector<OpSpec> specs = {{z, c->k, 0}, {t, c->n, 0}, {cm, c->n + c->l, 0}, {d, 1, 0}};
-  int rc = arena_reserve(c, c->ws, polys(c, B * c->n));
-  if (rc != RZK_OK) return rc;
-  // open.rs:167-173: the norm predicate on z rides on the rows that load z
-  return run_a1_relation(c, specs, (int64_t*)c->ws.p, accept, 1, B, B, true);
+int rzk_open_response_batch_dev(rzk_ctx* c, const int64_t* y, const int64_t* r, const int64_t* d, int64_t* z, size_t B) {
+  return open_response_dev(c, y, r, d, z, B);
+}
+int rzk_open_response32_batch_dev(rzk_ctx* c, const int32_t* y, const int32_t* r, const int32_t* d, int32_t* z, size_t B) {
+  return open_response_dev(c, y, r, d, z, B);
+}
+int rzk_open_verify_batch_dev(rzk_ctx* c, const int64_t* z, const int64_t* t, const int64_t* cm, const int64_t* d, uint8_t* accept,
+                              size_t B) {
+  return open_a1_relation_dev(c, z, t, cm, d, accept, B, false);
+}
+int rzk_open_verify32_batch_dev(rzk_ctx* c, const int32_t* z, const int32_t* t, const int32_t* cm, const int32_t* d, uint8_t* accept,
+                                size_t B) {
+  return open_a1_relation_dev(c, z, t, cm, d, accept, B, false);
+}
+int rzk_open_recover_batch_dev(rzk_ctx* c, const int64_t* z, const int64_t* cm, const int64_t* d, int64_t* t_out, uint8_t* accept,
+                               size_t B) {
+  return open_a1_relation_dev(c, z, t_out, cm, d, accept, B, true);
+}
+int rzk_open_recover32_batch_dev(rzk_ctx* c, const int32_t* z, const int32_t* cm, const int32_t* d, int32_t* t_out, uint8_t* accept,
+                                 size_t B) {
+  return open_a1_relation_dev(c, z, t_out, cm, d, accept, B, true);
 }
 
 // ---- LinearProof ---------------------------------------------------------------------------------------------------
@@ -364,18 +455,6 @@ int rzk_sum_verify_batch_dev(rzk_ctx* c, uint32_t V, const int64_t* zs, const in
 }
 
 // ---- recompute steps of the short proofs: the verifiers' launches with the commitment message as output --------------
-int rzk_open_recover_batch_dev(rzk_ctx* c, const int64_t* z, const int64_t* cm, const int64_t* d, int64_t* t_out,
-                               uint8_t* accept, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !z || !cm || !d || !t_out || !accept) return RZK_E_ARG;
-  if (c->n != c->l) return fail(c, RZK_E_ARG, "c1_c2 split needs n == l (reference panics in Mat::add)");
-  const std::vector<OpSpec> specs = {{z, c->k, 0}, {t_out, c->n, 0}, {cm, c->n + c->l, 0}, {d, 1, 0}};
-  int rc = arena_reserve(c, c->ws, polys(c, B * c->n));
-  if (rc != RZK_OK) return rc;
-  // open.rs:171-173 solved for t: t = a1.z - c1 (.) d
-  return run_a1_relation(c, specs, (int64_t*)c->ws.p, accept, 1, B, B, true, true);
-}
-
 int rzk_linear_recover_batch_dev(rzk_ctx* c, const int64_t* z, const int64_t* zp, const int64_t* cm, const int64_t* cpm,
                                  const int64_t* g, const int64_t* d, int64_t* t_out, int64_t* tp_out, int64_t* u_out,
                                  uint8_t* accept, size_t B) {

@@ -9,63 +9,13 @@
 //             the dense sub-batch: y and the coin draws under the next three nonces, r and c gathered, t = a1.y, the hash,
 //             the response with its test, and the accepted (t, z) scattered to the caller's slabs
 //   end       t, z of every proof that never passed are zeroed, ok = done; the secret parts of the workspace are wiped
-// One body for both slab widths: `width` is the bytes per coefficient, as in fs_challenge_dev (rzk_codec.cpp).
+// One body for both slab widths, over the coefficient type C of the caller's slabs: it calls the typed
+// forms of the entry points (rzk_ctx.h); the 32-bit ones convert inside themselves where the context has no native 32-bit
+// kernels (ws32 is theirs, within the same call: the loop does not touch it).
 #include "rzk_ctx.h"
 #include "rzk_prove_loop.h"
 
 namespace {
-
-bool misaligned(std::initializer_list<const void*> slabs) {
-  uintptr_t bits = 0;
-  for (const void* p : slabs) bits |= reinterpret_cast<uintptr_t>(p);
-  return (bits & 15u) != 0;
-}
-
-// The library calls of the loop at one width.  Slabs travel as void*; the 32-bit calls convert inside themselves where the
-// context has no native 32-bit kernels (ws32 is theirs, within the same call: the loop does not touch it).
-struct Calls {
-  rzk_ctx* c;
-  uint32_t width;
-  static const int64_t* i64(const void* p) { return static_cast<const int64_t*>(p); }
-  static int64_t* i64(void* p) { return static_cast<int64_t*>(p); }
-  static const int32_t* i32(const void* p) { return static_cast<const int32_t*>(p); }
-  static int32_t* i32(void* p) { return static_cast<int32_t*>(p); }
-
-  int uniform(const uint8_t* nonce, uint32_t stream, uint64_t bound, void* out, size_t count) const {
-    return width == 4 ? rzk_sample_uniform_keyed32_dev(c, nonce, stream, bound, i32(out), count)
-                      : rzk_sample_uniform_keyed_dev(c, nonce, stream, bound, i64(out), count);
-  }
-  // y: count polynomials at rzk_sigma(ctx), Box-Muller (0) or the exact discrete Gaussian (1)
-  int gauss(int kind, const uint8_t* nonce, uint32_t stream, void* out, size_t count) const {
-    if (kind == 0)
-      return width == 4 ? rzk_sample_gauss_keyed32_dev(c, nonce, stream, (double)c->sigma, i32(out), count)
-                        : rzk_sample_gauss_keyed_dev(c, nonce, stream, (double)c->sigma, i64(out), count);
-    const uint32_t sg = c->sigma > 0xffffffffull ? 0xffffffffu : (uint32_t)c->sigma;   // (out of range: the sampler says so)
-    return width == 4 ? rzk_sample_dgauss_keyed32_dev(c, nonce, stream, sg, i32(out), count * c->N)
-                      : rzk_sample_dgauss_keyed_dev(c, nonce, stream, sg, i64(out), count * c->N);
-  }
-  int commit(const void* x, const void* r, const void* y, void* cm, void* t, uint8_t* ok, size_t B) const {
-    return width == 4 ? rzk_open_commit32_batch_dev(c, i32(x), i32(r), i32(y), i32(cm), i32(t), ok, B)
-                      : rzk_open_commit_batch_dev(c, i64(x), i64(r), i64(y), i64(cm), i64(t), ok, B);
-  }
-  int a1y(const void* y, void* t, size_t B) const {
-    return width == 4 ? rzk_matvec32_batch_dev(c, RZK_KEY_A1, i32(y), nullptr, i32(t), B)
-                      : rzk_matvec_batch_dev(c, RZK_KEY_A1, i64(y), nullptr, i64(t), B);
-  }
-  int challenge(const void* cm, const void* t, const uint8_t* aux32, void* d, uint8_t* ok, size_t B) const {
-    if (width == 4) {
-      const int32_t* fields[2] = {i32(cm), i32(t)};
-      return rzk_fs_challenge32_batch_dev(c, RZK_MSG_OPEN_COMMITMENT, 0, fields, aux32, i32(d), nullptr, ok, B);
-    }
-    const int64_t* fields[2] = {i64(cm), i64(t)};
-    return rzk_fs_challenge_batch_dev(c, RZK_MSG_OPEN_COMMITMENT, 0, fields, aux32, i64(d), nullptr, ok, B);
-  }
-  int response_reject(const void* y, const void* r, const void* d, const int64_t* coin, double lnM, void* z, uint8_t* accept,
-                      size_t B) const {
-    return width == 4 ? rzk_open_response_reject32_batch_dev(c, i32(y), i32(r), i32(d), coin, kCoinR, lnM, i32(z), accept, nullptr, B)
-                      : rzk_open_response_reject_batch_dev(c, i64(y), i64(r), i64(d), coin, kCoinR, lnM, i64(z), accept, nullptr, B);
-  }
-};
 
 // ws_prove of one call: every part starts on a 256-byte boundary
 struct Workspace {
@@ -101,9 +51,9 @@ int prove_args(rzk_ctx* c, const uint8_t* nonce0, int gauss_kind, uint32_t max_r
   return RZK_OK;
 }
 
-int open_prove_zk_dev(rzk_ctx* c, const void* x, const uint8_t* nonce0, uint32_t stream, int gauss_kind, const uint8_t* aux32,
-                      uint32_t max_rounds, void* cm, void* t, void* z, void* r, uint8_t* ok, uint8_t* rounds, uint32_t* rounds_run,
-                      size_t B, uint32_t width) {
+template <class C>
+int open_prove_zk_dev(rzk_ctx* c, const C* x, const uint8_t* nonce0, uint32_t stream, int gauss_kind, const uint8_t* aux32,
+                      uint32_t max_rounds, C* cm, C* t, C* z, C* r, uint8_t* ok, uint8_t* rounds, uint32_t* rounds_run, size_t B) {
   if (!c) return RZK_E_ARG;
   if (rounds_run) *rounds_run = 0;
   int rc = prove_args(c, nonce0, gauss_kind, max_rounds, B);
@@ -117,7 +67,7 @@ int open_prove_zk_dev(rzk_ctx* c, const void* x, const uint8_t* nonce0, uint32_t
   if (rc != RZK_OK) return rc;
 
   const uint32_t N = c->N, n = c->n, k = c->k, l = c->l;
-  const size_t poly = (size_t)N * width;
+  const size_t poly = polys<C>(c, 1);
   // Reserved once, for the full batch, before round 0.  The arenas of the calls below (ws_fs, ws_reject, ws, and ws32 on
   // the convert path) are sized by the batch of the call, which is largest in round 0: nothing grows in mid-loop.
   Workspace w;
@@ -129,14 +79,15 @@ int open_prove_zk_dev(rzk_ctx* c, const void* x, const uint8_t* nonce0, uint32_t
   rc = arena_reserve(c, c->ws_prove, w.total);
   if (rc != RZK_OK) return rc;
   char* const base = (char*)c->ws_prove.p;
-  void *const wy = base + o_y, *const wt = base + o_t, *const wz = base + o_z, *const wd = base + o_d;
-  void *const wrg = base + o_rg, *const wcg = base + o_cg, *const wca = base + o_ca, *const wcb = base + o_cb;
+  auto slab = [&](size_t off) { return (C*)(base + off); };
+  C *const wy = slab(o_y), *const wt = slab(o_t), *const wz = slab(o_z), *const wd = slab(o_d);
+  C *const wrg = slab(o_rg), *const wcg = slab(o_cg), *const wca = slab(o_ca), *const wcb = slab(o_cb);
   int64_t* const coin = (int64_t*)(base + o_coin);
   uint8_t *const accept = (uint8_t*)(base + o_accept), *const okc = (uint8_t*)(base + o_okc), *const okf = (uint8_t*)(base + o_okf);
   uint8_t *const live = (uint8_t*)(base + o_live), *const done = (uint8_t*)(base + o_done);
   uint32_t *const idx = (uint32_t*)(base + o_idx), *const d_count = (uint32_t*)(base + o_count);
 
-  const Calls call{c, width};
+  constexpr uint32_t width = sizeof(C);   // for the loop's own kernels, which take untyped slabs
   const double lnM = reject_lnm(11.0);   // one response vector: alpha = 11 (fiat_shamir.zk_lnm(1))
   uint64_t used = 0;                      // nonces consumed
   uint8_t nonce[16];
@@ -144,11 +95,21 @@ int open_prove_zk_dev(rzk_ctx* c, const void* x, const uint8_t* nonce0, uint32_t
     (void)nonce_add(nonce0, used++, nonce);   // inside the span prove_args accepted
     return nonce;
   };
+  // y: `count` polynomials at rzk_sigma(ctx), Box-Muller (0) or the exact discrete Gaussian (1)
+  auto gauss = [&](const uint8_t* nc, size_t count) -> int {
+    if (gauss_kind == 0) return sample_gauss_keyed_dev(c, nc, stream, (double)c->sigma, wy, count);
+    const uint32_t sg = c->sigma > 0xffffffffull ? 0xffffffffu : (uint32_t)c->sigma;   // (out of range: the sampler says so)
+    return sample_dgauss_keyed_dev(c, nc, stream, sg, wy, count * N);
+  };
+  auto challenge = [&](const C* cmsg, const C* tmsg, size_t nb) -> int {
+    const C* fields[2] = {cmsg, tmsg};
+    return fs_challenge_dev(c, RZK_MSG_OPEN_COMMITMENT, 0, fields, aux32, wd, nullptr, okf, nb);
+  };
   // y and the coins of a round on `nb` proofs: three nonces, in the order of open_prove_zk's attempt()
   auto draw = [&](size_t nb) -> int {
-    int st = call.gauss(gauss_kind, next_nonce(), stream, wy, nb * k);
-    if (st == RZK_OK) st = call.uniform(next_nonce(), stream, (uint64_t)kCoinHalf, wca, nb);
-    if (st == RZK_OK) st = call.uniform(next_nonce(), stream, (uint64_t)kCoinHalf, wcb, nb);
+    int st = gauss(next_nonce(), nb * k);
+    if (st == RZK_OK) st = sample_uniform_keyed_dev(c, next_nonce(), stream, (uint64_t)kCoinHalf, wca, nb);
+    if (st == RZK_OK) st = sample_uniform_keyed_dev(c, next_nonce(), stream, (uint64_t)kCoinHalf, wcb, nb);
     if (st != RZK_OK) return st;
     return run_profiled(c, (uint64_t)nb * 24, "coin kernel",
                         [&](const LaunchCfg& cfg) { return launch_prove_coins(cfg, wca, wcb, N, coin, nb, width); });
@@ -158,11 +119,11 @@ int open_prove_zk_dev(rzk_ctx* c, const void* x, const uint8_t* nonce0, uint32_t
   uint32_t ran = 0;
   auto loop = [&]() -> int {
     // ---- round 0: the dense batch, into the caller's slabs
-    int st = call.uniform(next_nonce(), stream, c->b, r, B * k);
+    int st = sample_uniform_keyed_dev(c, next_nonce(), stream, c->b, r, B * k);
     if (st == RZK_OK) st = draw(B);
-    if (st == RZK_OK) st = call.commit(x, r, wy, cm, t, okc, B);
-    if (st == RZK_OK) st = call.challenge(cm, t, aux32, wd, okf, B);
-    if (st == RZK_OK) st = call.response_reject(wy, r, wd, coin, lnM, z, accept, B);
+    if (st == RZK_OK) st = open_commit_dev<C>(c, x, r, wy, cm, t, okc, B);
+    if (st == RZK_OK) st = challenge(cm, t, B);
+    if (st == RZK_OK) st = open_response_reject_dev<C>(c, wy, r, wd, coin, kCoinR, lnM, z, accept, nullptr, B);
     if (st == RZK_OK)
       st = run_profiled(c, (uint64_t)B * 6, "prove first kernel",
                         [&](const LaunchCfg& cfg) { return launch_prove_first(cfg, okc, okf, accept, live, done, rounds, B); });
@@ -184,9 +145,10 @@ int open_prove_zk_dev(rzk_ctx* c, const void* x, const uint8_t* nonce0, uint32_t
         st = run_profiled(c, (uint64_t)nb * (2 * k + 2 * (n + l)) * poly, "gather rows kernel", [&](const LaunchCfg& cfg) {
           return launch_gather_rows(cfg, r, wrg, k, cm, wcg, n + l, N, idx, (uint32_t)nb, width);
         });
-      if (st == RZK_OK) st = call.a1y(wy, wt, nb);   // c = commit(x; r) does not depend on y: a retry computes t = a1.y alone
-      if (st == RZK_OK) st = call.challenge(wcg, wt, aux32, wd, okf, nb);   // (its ok is not used: c and t are this library's)
-      if (st == RZK_OK) st = call.response_reject(wy, wrg, wd, coin, lnM, wz, accept, nb);
+      // c = commit(x; r) does not depend on y: a retry computes t = a1.y alone
+      if (st == RZK_OK) st = matvec_dev<C>(c, RZK_KEY_A1, wy, nullptr, wt, nb);
+      if (st == RZK_OK) st = challenge(wcg, wt, nb);   // (its ok is not used: c and t are this library's)
+      if (st == RZK_OK) st = open_response_reject_dev<C>(c, wy, wrg, wd, coin, kCoinR, lnM, wz, accept, nullptr, nb);
       if (st == RZK_OK)
         st = run_profiled(c, (uint64_t)nb * 2 * (n + k) * poly, "accept scatter kernel", [&](const LaunchCfg& cfg) {
           return launch_accept_scatter(cfg, wt, wz, t, z, n, k, N, accept, idx, (uint32_t)nb, (uint8_t)rnd, rounds, done, width);
@@ -222,24 +184,21 @@ int open_prove_zk_dev(rzk_ctx* c, const void* x, const uint8_t* nonce0, uint32_t
   return RZK_OK;
 }
 
-int open_prove_zk_host(rzk_ctx* c, const void* x, const uint8_t* nonce0, uint32_t stream, int gauss_kind, const uint8_t* aux32,
-                       uint32_t max_rounds, void* cm, void* t, void* z, void* r, uint8_t* ok, uint8_t* rounds, uint32_t* rounds_run,
-                       size_t B, uint32_t width) {
+template <class C>
+int open_prove_zk_host(rzk_ctx* c, const C* x, const uint8_t* nonce0, uint32_t stream, int gauss_kind, const uint8_t* aux32,
+                       uint32_t max_rounds, C* cm, C* t, C* z, C* r, uint8_t* ok, uint8_t* rounds, uint32_t* rounds_run, size_t B) {
   if (!c) return RZK_E_ARG;
   if (rounds_run) *rounds_run = 0;
   const int rc = prove_args(c, nonce0, gauss_kind, max_rounds, B);
   if (rc != RZK_OK) return rc;
   if (B == 0) return RZK_OK;
   if (!x || !cm || !t || !z || !r || !ok || !rounds) return fail(c, RZK_E_ARG, "open prove zk: non-NULL x, c, t, z, r, ok, rounds expected");
-  const size_t poly = (size_t)c->N * width;
   HostCall h(c);
-  const auto dx = h.in((const char*)x, B * c->l * poly);
-  const auto dcm = h.out((char*)cm, B * (c->n + c->l) * poly), dt = h.out((char*)t, B * c->n * poly);
-  const auto dz = h.out((char*)z, B * c->k * poly), dr = h.out((char*)r, B * c->k * poly);
+  const auto dx = h.pin(x, B * c->l);
+  const auto dcm = h.pout(cm, B * (c->n + c->l)), dt = h.pout(t, B * c->n), dz = h.pout(z, B * c->k), dr = h.pout(r, B * c->k);
   const auto dok = h.out(ok, B), drounds = h.out(rounds, B);
   return h.run([&] {
-    return open_prove_zk_dev(c, (const char*)dx, nonce0, stream, gauss_kind, aux32, max_rounds, (char*)dcm, (char*)dt, (char*)dz, (char*)dr, dok,
-                             drounds, rounds_run, B, width);
+    return open_prove_zk_dev<C>(c, dx, nonce0, stream, gauss_kind, aux32, max_rounds, dcm, dt, dz, dr, dok, drounds, rounds_run, B);
   });
 }
 
@@ -250,22 +209,22 @@ extern "C" {
 int rzk_open_prove_zk_batch_dev(rzk_ctx* c, const int64_t* x, const uint8_t nonce0[16], uint32_t stream, int gauss_kind,
                                 const uint8_t* aux32, uint32_t max_rounds, int64_t* cm, int64_t* t, int64_t* z, int64_t* r, uint8_t* ok,
                                 uint8_t* rounds, uint32_t* rounds_run, size_t B) {
-  return open_prove_zk_dev(c, x, nonce0, stream, gauss_kind, aux32, max_rounds, cm, t, z, r, ok, rounds, rounds_run, B, 8);
+  return open_prove_zk_dev(c, x, nonce0, stream, gauss_kind, aux32, max_rounds, cm, t, z, r, ok, rounds, rounds_run, B);
 }
 int rzk_open_prove_zk32_batch_dev(rzk_ctx* c, const int32_t* x, const uint8_t nonce0[16], uint32_t stream, int gauss_kind,
                                   const uint8_t* aux32, uint32_t max_rounds, int32_t* cm, int32_t* t, int32_t* z, int32_t* r, uint8_t* ok,
                                   uint8_t* rounds, uint32_t* rounds_run, size_t B) {
-  return open_prove_zk_dev(c, x, nonce0, stream, gauss_kind, aux32, max_rounds, cm, t, z, r, ok, rounds, rounds_run, B, 4);
+  return open_prove_zk_dev(c, x, nonce0, stream, gauss_kind, aux32, max_rounds, cm, t, z, r, ok, rounds, rounds_run, B);
 }
 int rzk_open_prove_zk_batch(rzk_ctx* c, const int64_t* x, const uint8_t nonce0[16], uint32_t stream, int gauss_kind,
                             const uint8_t* aux32, uint32_t max_rounds, int64_t* cm, int64_t* t, int64_t* z, int64_t* r, uint8_t* ok,
                             uint8_t* rounds, uint32_t* rounds_run, size_t B) {
-  return open_prove_zk_host(c, x, nonce0, stream, gauss_kind, aux32, max_rounds, cm, t, z, r, ok, rounds, rounds_run, B, 8);
+  return open_prove_zk_host(c, x, nonce0, stream, gauss_kind, aux32, max_rounds, cm, t, z, r, ok, rounds, rounds_run, B);
 }
 int rzk_open_prove_zk32_batch(rzk_ctx* c, const int32_t* x, const uint8_t nonce0[16], uint32_t stream, int gauss_kind,
                               const uint8_t* aux32, uint32_t max_rounds, int32_t* cm, int32_t* t, int32_t* z, int32_t* r, uint8_t* ok,
                               uint8_t* rounds, uint32_t* rounds_run, size_t B) {
-  return open_prove_zk_host(c, x, nonce0, stream, gauss_kind, aux32, max_rounds, cm, t, z, r, ok, rounds, rounds_run, B, 4);
+  return open_prove_zk_host(c, x, nonce0, stream, gauss_kind, aux32, max_rounds, cm, t, z, r, ok, rounds, rounds_run, B);
 }
 
 // diagnostic: pending_compact_kernel on the caller's flags, so that its edges are tested without a prover around it

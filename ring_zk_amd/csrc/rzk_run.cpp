@@ -128,14 +128,15 @@ int prof_end(rzk_ctx* c) {
 // programs pass false — there the offending proof's verdict flag is cleared and the call succeeds.
 // preset_value != 0: every verdict flag (nflags of them) starts at that value — written by the launch itself when one
 // team evaluates all rows of a batch entry (no 5-us fill launch in front of a 75-us kernel), by a fill launch otherwise.
-int run_program(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSpec>& specs, uint8_t* flags, uint32_t group,
-                uint64_t batch, uint64_t norm_limit, bool sticky, uint8_t preset_value, uint64_t nflags, const ResponseStat* stat,
-                uint32_t width) {
+// specs: the list run_program<C> (rzk_ctx.h) lowered; its width is sizeof(C).
+int run_program_lowered(rzk_ctx* c, int id, uint32_t var, const OpList& specs, uint8_t* flags, uint32_t group, uint64_t batch,
+                        uint64_t norm_limit, bool sticky, uint8_t preset_value, uint64_t nflags, const ResponseStat* stat) {
+  const uint32_t width = specs.width;
   DevProg dp;
   int rc = get_program(c, id, var, dp);
   if (rc != RZK_OK) return rc;
   if (width != 8 && (width != 4 || !native32(c, dp))) return fail(c, RZK_E_STATE, "no 32-bit kernels for this program");
-  if (specs.size() > (size_t)kMaxOperands) return fail(c, RZK_E_ARG, "too many operands");
+  if (specs.n > (size_t)kMaxOperands) return fail(c, RZK_E_ARG, "too many operands");
   // units of one batch entry per task: all of them (one team per entry: equal-cost tasks, no tail) once the batch alone
   // fills the chip's wave slots; one unit per task below that
   uint32_t upt = batch >= (uint64_t)c->num_cus * 16 ? dp.nunits : 1;
@@ -151,10 +152,10 @@ int run_program(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSpec>& spe
   // the operand images of the call in progress, if any (all zero otherwise): this launch stores (producer op) and / or reads them
   Operands ops = c->oimg_state;
   ops.oimg_op = ops.oimg ? c->oimg_producer_op : 0xffu;
-  for (size_t i = 0; i < specs.size(); ++i) {
-    ops.base[i] = const_cast<int64_t*>(specs[i].base);
-    ops.stride[i] = specs[i].stride;
-    ops.outer[i] = specs[i].outer ? 1 : 0;
+  for (size_t i = 0; i < specs.n; ++i) {
+    ops.base[i] = const_cast<int64_t*>(specs.base[i]);
+    ops.stride[i] = specs.stride[i];
+    ops.outer[i] = specs.outer[i] ? 1 : 0;
   }
   ops.group = group ? group : 1;
   ops.pad = dp.two_bit ? 1 : 0;
@@ -169,8 +170,8 @@ int run_program(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSpec>& spe
     ops.dkey_n = c->dkey_n;
   }
   uint64_t bytes = 0;   // what the launch has to move at least: its operands in, its results out
-  for (size_t i = 0; i < specs.size(); ++i)
-    bytes += (uint64_t)dp.polys_in[i] * (specs[i].outer ? batch / (group ? group : 1) : batch);
+  for (size_t i = 0; i < specs.n; ++i)
+    bytes += (uint64_t)dp.polys_in[i] * (specs.outer[i] ? batch / (group ? group : 1) : batch);
   bytes = (bytes + (uint64_t)dp.polys_out * batch) * (uint64_t)width * c->N;
   LaunchCfg cfg;
   rc = prof_begin(c, bytes, cfg);
@@ -216,7 +217,7 @@ int run_program(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSpec>& spe
       for (uint64_t b0 = 0; b0 < batch && lrc == 0; b0 += chunk) {
         const uint64_t nb = batch - b0 < chunk ? batch - b0 : chunk;
         Operands o2 = ops;
-        for (size_t i = 0; i < specs.size(); ++i) {
+        for (size_t i = 0; i < specs.n; ++i) {
           if (!o2.base[i]) continue;
           const uint64_t first = o2.outer[i] ? b0 / grp : b0;
           o2.base[i] += first * o2.stride[i] * c->N;
@@ -257,8 +258,8 @@ uint64_t fused_limit(const rzk_ctx* c, uint64_t bound) {
 
 // Runs the checked variant (var | 1) of a program with the norm predicate fused into it: flags are
 // preset to 1 and cleared by failing rows.  Returns RZK_E_UNSUPPORTED when fusion is not possible.
-int run_program_checked(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSpec>& specs, uint8_t* flags,
-                        uint32_t group, uint64_t batch, uint64_t nflags, uint64_t bound, bool preset, bool sticky, uint32_t width) {
+int run_program_checked(rzk_ctx* c, int id, uint32_t var, const OpList& specs, uint8_t* flags, uint32_t group, uint64_t batch,
+                        uint64_t nflags, uint64_t bound, bool preset, bool sticky) {
   const uint64_t lim = fused_limit(c, bound);
   if (!lim || !flags) return RZK_E_UNSUPPORTED;
   DevProg dp;
@@ -267,7 +268,7 @@ int run_program_checked(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSp
   // two-bit verdicts are cleared with word atomics: the flag array must be made of whole aligned words
   if (dp.two_bit && ((reinterpret_cast<uintptr_t>(flags) & 3u) || (nflags & 3u))) return RZK_E_UNSUPPORTED;
   const uint8_t all_ok = dp.two_bit ? 3 : 1;
-  return run_program(c, id, var | 1, specs, flags, group, batch, lim, sticky, preset ? all_ok : (uint8_t)0, nflags, nullptr, width);
+  return run_program_lowered(c, id, var | 1, specs, flags, group, batch, lim, sticky, preset ? all_ok : (uint8_t)0, nflags, nullptr);
 }
 
 }  // namespace
@@ -288,18 +289,17 @@ bool checked_fuses(rzk_ctx* c, int id, uint32_t var, uint64_t bound) {
 // order, and then the plain program, which clears the verdicts of proofs with non-canonical inputs.  Without flags
 // (a prover that does not ask) the norms are skipped.  preset: the fused launch initialises the flags; the first of
 // `norms` does so in the fallback (mode 0), or the caller has (mode 1 throughout).
-int run_checked(rzk_ctx* c, int id, uint32_t var, const std::vector<OpSpec>& specs, uint8_t* flags, uint32_t group,
-                uint64_t batch, uint64_t nflags, uint64_t bound, bool preset, bool sticky, std::initializer_list<NormSpec> norms,
-                uint32_t width) {
-  int rc = run_program_checked(c, id, var, specs, flags, group, batch, nflags, bound, preset, sticky, width);
+int run_checked_lowered(rzk_ctx* c, int id, uint32_t var, const OpList& specs, uint8_t* flags, uint32_t group, uint64_t batch,
+                        uint64_t nflags, uint64_t bound, bool preset, bool sticky, std::initializer_list<NormSpec> norms) {
+  int rc = run_program_checked(c, id, var, specs, flags, group, batch, nflags, bound, preset, sticky);
   if (rc != RZK_E_UNSUPPORTED) return rc;
-  if (width != 8 && flags) return fail(c, RZK_E_STATE, "the norm kernels read 64-bit slabs");   // (the 32-bit entry points ask checked_fuses first)
+  if (specs.width != 8 && flags) return fail(c, RZK_E_STATE, "the norm kernels read 64-bit slabs");   // (the 32-bit entry points ask checked_fuses first)
   for (const NormSpec& n : norms) {
     if (!flags) break;
     rc = run_norm(c, n.v, n.rows, bound, flags, nflags, n.mode, n.shift, sticky);
     if (rc != RZK_OK) return rc;
   }
-  return run_program(c, id, var, specs, flags, group, batch, 0, sticky, 0, 0, nullptr, width);
+  return run_program_lowered(c, id, var, specs, flags, group, batch, 0, sticky, 0, 0, nullptr);
 }
 
 // The scalar multipliers of a Linear / Sum call (g: one per proof; g_i: V per proof) transformed once into the form of the

@@ -4,28 +4,23 @@
 
 namespace {
 
-// One keyed draw of `npoly` polynomials: subkey = HChaCha20(key, nonce), the launch in a profiling slot (so that
-// rzk_prof_read_kernels names the form that ran); the launch has copied the subkey into its kernel arguments, so the
-// host copy is wiped whichever way the call ends.  launch(cfg, subkey) returns the launcher's status.
-// width: bytes per coefficient of `out` (8, or 4 for the slab32 forms)
-template <class L>
-int keyed_sample(rzk_ctx* c, const uint8_t* nonce, size_t npoly, L launch, uint32_t width = 8) {
+// One keyed draw of `npoly` polynomials into the device slab `out` (int32_t: 16-byte aligned, the slab32 rule, tested
+// first): subkey = HChaCha20(key, nonce), the launch in a profiling slot (so that rzk_prof_read_kernels names the form that
+// ran); the launch has copied the subkey into its kernel arguments, so the host copy is wiped whichever way the call
+// ends.  launch(cfg, subkey) returns the launcher's status.
+template <class C, class L>
+int keyed_sample(rzk_ctx* c, const uint8_t* nonce, const C* out, size_t npoly, L launch) {
+  if constexpr (sizeof(C) == 4) {
+    if (misaligned({out})) return align_fail(c);
+  }
   if (!c->sampler_key_set) return fail(c, RZK_E_ARG, "keyed sampler: no key set (rzk_sampler_set_key)");
   if (!nonce) return fail(c, RZK_E_ARG, "keyed sampler: NULL nonce");
   uint32_t sk[8];
   chacha_sampler_subkey(c->sampler_key, nonce, sk);
-  const int rc = run_profiled(c, (uint64_t)npoly * c->N * width, "keyed sampler",
-                              [&](const LaunchCfg& cfg) { return launch(cfg, sk); });
+  const int rc = run_profiled(c, (uint64_t)polys<C>(c, npoly), "keyed sampler", [&](const LaunchCfg& cfg) { return launch(cfg, sk); });
   wipe(sk, sizeof(sk));
   return rc;
 }
-
-// the slab32 rule for a device slab (rzk_slab32.h)
-int out32_misaligned(rzk_ctx* c, const int32_t* out) {
-  if ((reinterpret_cast<uintptr_t>(out) & 15u) == 0) return RZK_OK;
-  return fail(c, RZK_E_ARG, "slab32: device slabs must be 16-byte aligned");
-}
-int64_t* as64(int32_t* p) { return reinterpret_cast<int64_t*>(p); }   // the launchers carry addresses; `width` says what they point at
 
 }  // namespace
 
@@ -60,78 +55,82 @@ int rzk_sampler_set_key(rzk_ctx* c, const uint8_t key[32]) {
   return RZK_OK;
 }
 
-int rzk_sample_uniform_keyed_dev(rzk_ctx* c, const uint8_t nonce[16], uint32_t stream, uint64_t bound, int64_t* out,
-                                 size_t count) {
+}  // extern "C"
+
+// The four draws write int64_t or int32_t slabs (v14, slab32 prover): the same argument rules, streams and
+// launches; every value an accepted argument can produce fits int32_t (tests/test_prove32_host.py), so the narrow form
+// has no further range rule.
+namespace rzk::api {
+
+template <class C>
+int sample_uniform_keyed_dev(rzk_ctx* c, const uint8_t* nonce, uint32_t stream, uint64_t bound, C* out, size_t count) {
   if (c && count == 0) return RZK_OK;
   if (!c || !out || bound == 0 || bound > (uint64_t)(c->q - 1) / 2) return RZK_E_ARG;
-  return keyed_sample(c, nonce, count, [&](const LaunchCfg& cfg, const uint32_t* sk) {
-    return launch_sample_uniform_chacha(cfg, out, count, c->N, sk, stream, (uint32_t)bound);
+  return keyed_sample(c, nonce, out, count, [&](const LaunchCfg& cfg, const uint32_t* sk) {
+    return launch_sample_uniform_chacha(cfg, launch_addr(out), count, c->N, sk, stream, (uint32_t)bound, sizeof(C));
   });
 }
-int rzk_sample_gauss_keyed_dev(rzk_ctx* c, const uint8_t nonce[16], uint32_t stream, double sigma, int64_t* out,
-                               size_t count) {
+RZK_BOTH_WIDTHS(sample_uniform_keyed_dev)
+
+template <class C>
+int sample_gauss_keyed_dev(rzk_ctx* c, const uint8_t* nonce, uint32_t stream, double sigma, C* out, size_t count) {
   if (c && count == 0) return RZK_OK;
   if (!c || !out || !(sigma > 0.0) || sigma > 67108864.0) return RZK_E_ARG;   // as rzk_sample_gauss_dev
-  return keyed_sample(c, nonce, count, [&](const LaunchCfg& cfg, const uint32_t* sk) {
-    return launch_sample_gauss_chacha(cfg, out, count, c->N, sk, stream, sigma);
+  return keyed_sample(c, nonce, out, count, [&](const LaunchCfg& cfg, const uint32_t* sk) {
+    return launch_sample_gauss_chacha(cfg, launch_addr(out), count, c->N, sk, stream, sigma, sizeof(C));
   });
 }
+RZK_BOTH_WIDTHS(sample_gauss_keyed_dev)
+
 // v11: the exact discrete Gaussian D_sigma (rzk_dgauss.h); count is in coefficients here
-int rzk_sample_dgauss_keyed_dev(rzk_ctx* c, const uint8_t nonce[16], uint32_t stream, uint32_t sigma, int64_t* out,
-                                size_t count) {
+template <class C>
+int sample_dgauss_keyed_dev(rzk_ctx* c, const uint8_t* nonce, uint32_t stream, uint32_t sigma, C* out, size_t count) {
   if (c && count == 0) return RZK_OK;
   if (!c || !out || sigma == 0 || sigma > kDgaussSigmaMax || count % c->N != 0) return RZK_E_ARG;
   const size_t npoly = count / c->N;
-  return keyed_sample(c, nonce, npoly, [&](const LaunchCfg& cfg, const uint32_t* sk) {
-    return launch_sample_dgauss_chacha(cfg, out, npoly, c->N, sk, stream, sigma);
+  return keyed_sample(c, nonce, out, npoly, [&](const LaunchCfg& cfg, const uint32_t* sk) {
+    return launch_sample_dgauss_chacha(cfg, launch_addr(out), npoly, c->N, sk, stream, sigma, sizeof(C));
   });
+}
+RZK_BOTH_WIDTHS(sample_dgauss_keyed_dev)
+
+template <class C>
+int sample_challenge_keyed_dev(rzk_ctx* c, const uint8_t* nonce, uint32_t stream, C* out, size_t count) {
+  if (c && count == 0) return RZK_OK;
+  if (!c || !out) return RZK_E_ARG;
+  return keyed_sample(c, nonce, out, count, [&](const LaunchCfg& cfg, const uint32_t* sk) {
+    return launch_sample_challenge_chacha(cfg, launch_addr(out), count, c->N, sk, stream, c->kappa, sizeof(C));
+  });
+}
+RZK_BOTH_WIDTHS(sample_challenge_keyed_dev)
+
+}  // namespace rzk::api
+
+extern "C" {
+
+int rzk_sample_uniform_keyed_dev(rzk_ctx* c, const uint8_t nonce[16], uint32_t stream, uint64_t bound, int64_t* out, size_t count) {
+  return sample_uniform_keyed_dev(c, nonce, stream, bound, out, count);
+}
+int rzk_sample_uniform_keyed32_dev(rzk_ctx* c, const uint8_t nonce[16], uint32_t stream, uint64_t bound, int32_t* out, size_t count) {
+  return sample_uniform_keyed_dev(c, nonce, stream, bound, out, count);
+}
+int rzk_sample_gauss_keyed_dev(rzk_ctx* c, const uint8_t nonce[16], uint32_t stream, double sigma, int64_t* out, size_t count) {
+  return sample_gauss_keyed_dev(c, nonce, stream, sigma, out, count);
+}
+int rzk_sample_gauss_keyed32_dev(rzk_ctx* c, const uint8_t nonce[16], uint32_t stream, double sigma, int32_t* out, size_t count) {
+  return sample_gauss_keyed_dev(c, nonce, stream, sigma, out, count);
+}
+int rzk_sample_dgauss_keyed_dev(rzk_ctx* c, const uint8_t nonce[16], uint32_t stream, uint32_t sigma, int64_t* out, size_t count) {
+  return sample_dgauss_keyed_dev(c, nonce, stream, sigma, out, count);
+}
+int rzk_sample_dgauss_keyed32_dev(rzk_ctx* c, const uint8_t nonce[16], uint32_t stream, uint32_t sigma, int32_t* out, size_t count) {
+  return sample_dgauss_keyed_dev(c, nonce, stream, sigma, out, count);
 }
 int rzk_sample_challenge_keyed_dev(rzk_ctx* c, const uint8_t nonce[16], uint32_t stream, int64_t* out, size_t count) {
-  if (c && count == 0) return RZK_OK;
-  if (!c || !out) return RZK_E_ARG;
-  return keyed_sample(c, nonce, count, [&](const LaunchCfg& cfg, const uint32_t* sk) {
-    return launch_sample_challenge_chacha(cfg, out, count, c->N, sk, stream, c->kappa);
-  });
-}
-
-// ---- v14, slab32 prover: the keyed samplers writing int32_t slabs ---------------------------------------
-// The siblings' argument rules, streams and launches; every value an accepted argument can produce fits int32_t
-// (tests/test_prove32_host.py), so there is no further range rule.  out is 16-byte aligned, the slab32 rule.
-int rzk_sample_uniform_keyed32_dev(rzk_ctx* c, const uint8_t nonce[16], uint32_t stream, uint64_t bound, int32_t* out,
-                                   size_t count) {
-  if (c && count == 0) return RZK_OK;
-  if (!c || !out || bound == 0 || bound > (uint64_t)(c->q - 1) / 2) return RZK_E_ARG;
-  if (const int rc = out32_misaligned(c, out)) return rc;
-  return keyed_sample(c, nonce, count, [&](const LaunchCfg& cfg, const uint32_t* sk) {
-    return launch_sample_uniform_chacha(cfg, as64(out), count, c->N, sk, stream, (uint32_t)bound, 4);
-  }, 4);
-}
-int rzk_sample_gauss_keyed32_dev(rzk_ctx* c, const uint8_t nonce[16], uint32_t stream, double sigma, int32_t* out,
-                                 size_t count) {
-  if (c && count == 0) return RZK_OK;
-  if (!c || !out || !(sigma > 0.0) || sigma > 67108864.0) return RZK_E_ARG;   // as rzk_sample_gauss_keyed_dev
-  if (const int rc = out32_misaligned(c, out)) return rc;
-  return keyed_sample(c, nonce, count, [&](const LaunchCfg& cfg, const uint32_t* sk) {
-    return launch_sample_gauss_chacha(cfg, as64(out), count, c->N, sk, stream, sigma, 4);
-  }, 4);
-}
-int rzk_sample_dgauss_keyed32_dev(rzk_ctx* c, const uint8_t nonce[16], uint32_t stream, uint32_t sigma, int32_t* out,
-                                  size_t count) {
-  if (c && count == 0) return RZK_OK;
-  if (!c || !out || sigma == 0 || sigma > kDgaussSigmaMax || count % c->N != 0) return RZK_E_ARG;
-  if (const int rc = out32_misaligned(c, out)) return rc;
-  const size_t npoly = count / c->N;
-  return keyed_sample(c, nonce, npoly, [&](const LaunchCfg& cfg, const uint32_t* sk) {
-    return launch_sample_dgauss_chacha(cfg, as64(out), npoly, c->N, sk, stream, sigma, 4);
-  }, 4);
+  return sample_challenge_keyed_dev(c, nonce, stream, out, count);
 }
 int rzk_sample_challenge_keyed32_dev(rzk_ctx* c, const uint8_t nonce[16], uint32_t stream, int32_t* out, size_t count) {
-  if (c && count == 0) return RZK_OK;
-  if (!c || !out) return RZK_E_ARG;
-  if (const int rc = out32_misaligned(c, out)) return rc;
-  return keyed_sample(c, nonce, count, [&](const LaunchCfg& cfg, const uint32_t* sk) {
-    return launch_sample_challenge_chacha(cfg, as64(out), count, c->N, sk, stream, c->kappa, 4);
-  }, 4);
+  return sample_challenge_keyed_dev(c, nonce, stream, out, count);
 }
 
 }  // extern "C"

@@ -34,6 +34,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+from collections import namedtuple
 from typing import Optional
 
 import numpy as np
@@ -139,19 +140,85 @@ def _flag(cond):
 
 
 # ---- OpenProof (src/prove/open.rs) -------------------------------------------------------------------------------------
+# The Open functions exist for int64 and for int32 slabs and are written once, over the record of the
+# operations they use at one width.  On int32 slabs every slab is int32 (numpy or torch CUDA): no 64-bit slab and no convert
+# launch appears between record and verdict at N = 512 and 1024, n = 1.
+def _method(name):
+    return lambda ctx, *args: getattr(ctx, name)(*args)
+
+
+def _same_challenge32(ctx, d2, d):
+    """_same_challenge on int32 slabs, word for word (Context.eq32): a canonical d is its own canonical copy, and a
+    non-canonical one has already cleared the verdict of open_recover32, so the canonicalize launch of the 64-bit form has
+    nothing to do here."""
+    return ctx.eq32(d2.reshape(-1, 1, ctx.N), d.reshape(-1, 1, ctx.N))
+
+
+def draw_coins32(sampler, lead):
+    """draw_coins from a sampler that returns int32 tensors: the same two draws and coefficients; the two [*lead] vectors
+    are converted to int64 before (a + half) R0 + (b + half) is formed (the product overflows int32).  That is a gather of
+    one value per proof, not a pass over a slab.  The coin is int64, as Context.open_response_reject32 takes it."""
+    import torch
+
+    half = (COIN_R0 - 1) // 2
+    a = sampler.uniform(half, tuple(lead))[..., 0].to(torch.int64)
+    b = sampler.uniform(half, tuple(lead))[..., 1].to(torch.int64)
+    return ((a + half) * COIN_R0 + (b + half)).contiguous(), COIN_R0 * COIN_R0
+
+
+# suffix: of the public names ("" on int64 slabs, "32" on int32 slabs); decode: packed records -> slabs; same_challenge: the
+# short verifier's final compare; coins: the coin draw of a zero-knowledge round; the others: the Context methods
+_OpenOps = namedtuple("_OpenOps", "suffix challenge decode same_challenge coins commit matvec response response_reject verify recover")
+
+
+def _open_ops(suffix, challenge_, decode, same_challenge, coins):
+    names = ("open_commit", "matvec", "open_response", "open_response_reject", "open_verify", "open_recover")
+    return _OpenOps(suffix, challenge_, decode, same_challenge, coins, *[_method(m + suffix) for m in names])
+
+
+def _open_prove(w, ctx, x, r, y, aux):
+    c, t, ok = w.commit(ctx, x, r, y)
+    d, _, okf = w.challenge(ctx, MSG_OPEN_COMMITMENT, c, t, aux=aux)
+    z = w.response(ctx, y, r, d)
+    return c, t, z, ok & okf
+
+
+def _open_verify(w, ctx, c, t, z, aux):
+    d, _, okf = w.challenge(ctx, MSG_OPEN_COMMITMENT, c, t, aux=aux)
+    return w.verify(ctx, z, t, c, d) & okf
+
+
+def _open_verify_packed(w, ctx, commitment_records, response_records, aux):
+    c, t, ok1 = w.decode(ctx, MSG_OPEN_COMMITMENT, commitment_records)
+    (z, ok2) = w.decode(ctx, MSG_OPEN_RESPONSE, response_records)
+    return _open_verify(w, ctx, c, t, z, aux) & ok1 & ok2
+
+
+def _open_short(w, ctx, c, t, z, aux):
+    d, _, _ = w.challenge(ctx, MSG_OPEN_COMMITMENT, c, t, aux=aux)
+    return d
+
+
+def _open_verify_short(w, ctx, c, d, z, aux):
+    t, acc = w.recover(ctx, z, c, d)
+    d2, _, okf = w.challenge(ctx, MSG_OPEN_COMMITMENT, c, t, aux=aux)   # the caller's c: a non-canonical one clears okf
+    return acc & okf & w.same_challenge(ctx, d2, d)
+
+
+def _open_verify_short_packed(w, ctx, records, aux):
+    c, d, z, ok = w.decode(ctx, MSG_OPEN_SHORT, records)
+    return _open_verify_short(w, ctx, c, d, z, aux) & ok
+
+
 def open_prove(ctx, x, r, y, aux=None):
     """commit (open.rs:80-103), d = challenge(c, t), response (open.rs:107-117): (c, t, z, ok); ok[b] = 0 where r fails
     the commit constraint (the caller resamples) or an output is not canonical."""
-    c, t, ok = ctx.open_commit(x, r, y)
-    d, _, okf = challenge(ctx, MSG_OPEN_COMMITMENT, c, t, aux=aux)
-    z = ctx.open_response(y, r, d)
-    return c, t, z, ok & okf
+    return _open_prove(_OPEN64, ctx, x, r, y, aux)
 
 
 def open_verify(ctx, c, t, z, aux=None):
     """OpenProofVerifier::verify (open.rs:162-174) with the recomputed challenge."""
-    d, _, okf = challenge(ctx, MSG_OPEN_COMMITMENT, c, t, aux=aux)
-    return ctx.open_verify(z, t, c, d) & okf
+    return _open_verify(_OPEN64, ctx, c, t, z, aux)
 
 
 def verify_open_wire(ctx, commitment_msgs, response_msgs, aux=None, coef_bytes: int = 8):
@@ -165,16 +232,13 @@ def verify_open_wire(ctx, commitment_msgs, response_msgs, aux=None, coef_bytes: 
 def open_verify_packed(ctx, commitment_records, response_records, aux=None):
     """open_verify from packed MSG_OPEN_COMMITMENT and MSG_OPEN_RESPONSE records (packed.encode_batch): decode,
     recompute d, verify; a record that does not decode rejects its own proof."""
-    c, t, ok1 = packed.decode_batch(ctx, MSG_OPEN_COMMITMENT, commitment_records)
-    (z, ok2) = packed.decode_batch(ctx, MSG_OPEN_RESPONSE, response_records)
-    return open_verify(ctx, c, t, z, aux=aux) & ok1 & ok2
+    return _open_verify_packed(_OPEN64, ctx, commitment_records, response_records, aux)
 
 
 def open_short(ctx, c, t, z, aux=None):
     """The short form of the Open proof (c, t, z): (c, d, z) with d = challenge(c, t), as a Fiat-Shamir signature sends
     it.  Returns d; t is dropped, the verifier recomputes it (open_verify_short).  z is left as it is."""
-    d, _, _ = challenge(ctx, MSG_OPEN_COMMITMENT, c, t, aux=aux)
-    return d
+    return _open_short(_OPEN64, ctx, c, t, z, aux)
 
 
 def open_verify_short(ctx, c, d, z, aux=None):
@@ -182,59 +246,43 @@ def open_verify_short(ctx, c, d, z, aux=None):
     (open.rs:171-173) for (c, d, z), computed by Context.open_recover together with the norm rule on z; accept iff the
     transcript of (c, t') gives d again, z passes the norm rule and neither step met a non-canonical coefficient
     (foreign data rejects its proof instead of failing the call).  An honest proof has t' = t."""
-    t, acc = ctx.open_recover(z, c, d)
-    d2, _, okf = challenge(ctx, MSG_OPEN_COMMITMENT, c, t, aux=aux)   # the caller's c: a non-canonical one clears okf
-    return acc & okf & _same_challenge(ctx, d2, d)
+    return _open_verify_short(_OPEN64, ctx, c, d, z, aux)
 
 
 def open_verify_short_packed(ctx, records, aux=None):
     """open_verify_short from packed MSG_OPEN_SHORT records; a record that does not decode rejects its own proof."""
-    c, d, z, ok = packed.decode_batch(ctx, MSG_OPEN_SHORT, records)
-    return open_verify_short(ctx, c, d, z, aux=aux) & ok
+    return _open_verify_short_packed(_OPEN64, ctx, records, aux)
 
 
-# ---- OpenProof on 32-bit slabs (DESIGN.md §19): the functions above restated on open_*32, challenge32, decode_batch32 and
-# eq32.  Every slab is int32 (numpy or torch CUDA); no 64-bit slab and no convert launch appears between record and verdict.
 def open_prove32(ctx, x, r, y, aux=None):
     """open_prove on int32 slabs: (c, t, z, ok), each the int32 of open_prove's."""
-    c, t, ok = ctx.open_commit32(x, r, y)
-    d, _, okf = challenge32(ctx, MSG_OPEN_COMMITMENT, c, t, aux=aux)
-    z = ctx.open_response32(y, r, d)
-    return c, t, z, ok & okf
+    return _open_prove(_OPEN32, ctx, x, r, y, aux)
 
 
 def open_verify32(ctx, c, t, z, aux=None):
     """open_verify on int32 slabs."""
-    d, _, okf = challenge32(ctx, MSG_OPEN_COMMITMENT, c, t, aux=aux)
-    return ctx.open_verify32(z, t, c, d) & okf
+    return _open_verify(_OPEN32, ctx, c, t, z, aux)
 
 
 def open_verify_packed32(ctx, commitment_records, response_records, aux=None):
     """open_verify_packed through int32 slabs: the records are those of packed.encode_batch or encode_batch32."""
-    c, t, ok1 = packed.decode_batch32(ctx, MSG_OPEN_COMMITMENT, commitment_records)
-    (z, ok2) = packed.decode_batch32(ctx, MSG_OPEN_RESPONSE, response_records)
-    return open_verify32(ctx, c, t, z, aux=aux) & ok1 & ok2
+    return _open_verify_packed(_OPEN32, ctx, commitment_records, response_records, aux)
 
 
 def open_short32(ctx, c, t, z, aux=None):
     """open_short on int32 slabs: d = challenge32(c, t) as int32."""
-    d, _, _ = challenge32(ctx, MSG_OPEN_COMMITMENT, c, t, aux=aux)
-    return d
+    return _open_short(_OPEN32, ctx, c, t, z, aux)
 
 
 def open_verify_short32(ctx, c, d, z, aux=None):
     """open_verify_short on int32 slabs.  The recomputed challenge is compared with the caller's d word for word
-    (Context.eq32): a canonical d is its own canonical copy, and a non-canonical one has already cleared the verdict of
-    open_recover32, so the canonicalize launch of the 64-bit form has nothing to do here."""
-    t, acc = ctx.open_recover32(z, c, d)
-    d2, _, okf = challenge32(ctx, MSG_OPEN_COMMITMENT, c, t, aux=aux)
-    return acc & okf & ctx.eq32(d2.reshape(-1, 1, ctx.N), d.reshape(-1, 1, ctx.N))
+    (_same_challenge32)."""
+    return _open_verify_short(_OPEN32, ctx, c, d, z, aux)
 
 
 def open_verify_short_packed32(ctx, records, aux=None):
     """open_verify_short_packed through int32 slabs: packed MSG_OPEN_SHORT records -> verdicts."""
-    c, d, z, ok = packed.decode_batch32(ctx, MSG_OPEN_SHORT, records)
-    return open_verify_short32(ctx, c, d, z, aux=aux) & ok
+    return _open_verify_short_packed(_OPEN32, ctx, records, aux)
 
 
 # ---- LinearProof (src/prove/linear.rs) ---------------------------------------------------------------------------------
@@ -337,12 +385,21 @@ def _lead(x, tail: int):
     return tuple(x.shape[:-tail])
 
 
-def open_prove_sampled(ctx, x, sampler, aux=None):
-    """open_prove with r, y from `sampler`: (c, t, z, ok, r)."""
+def _open_prove_sampled(w, ctx, x, sampler, aux):
     lead = _lead(x, 2)
     r = sampler.uniform(ctx.b, lead + (ctx.k,))
     y = sampler.gauss(ctx.sigma, lead + (ctx.k,))
-    return open_prove(ctx, x, r, y, aux=aux) + (r,)
+    return _open_prove(w, ctx, x, r, y, aux) + (r,)
+
+
+def open_prove_sampled(ctx, x, sampler, aux=None):
+    """open_prove with r, y from `sampler`: (c, t, z, ok, r)."""
+    return _open_prove_sampled(_OPEN64, ctx, x, sampler, aux)
+
+
+def open_prove_sampled32(ctx, x, sampler, aux=None):
+    """open_prove_sampled on int32 slabs, r and y from a KeyedSampler32: (c, t, z, ok, r)."""
+    return _open_prove_sampled(_OPEN32, ctx, x, sampler, aux)
 
 
 def linear_prove_sampled(ctx, g, x, sampler, aux=None):
@@ -428,66 +485,11 @@ def _batch3(x, tail: int, name: str):
     return int(x.shape[0])
 
 
-def open_prove_zk(ctx, x, sampler, aux=None, max_rounds: int = 64):
-    """open_prove_sampled with the rejection step: (c, t, z, ok, r, rounds).  Round 0 is open_prove_sampled; each later
-    round proves the pending proofs again with the same r and a fresh y.  ok[b] = 1 iff r passed the commit constraint
-    and the proof was accepted within max_rounds, in round rounds[b]; t and z of the other proofs are zero."""
-    B = _batch3(x, 2, "open_prove_zk")
-    r = sampler.uniform(ctx.b, (B, ctx.k))
-
-    first = {}
-
-    def attempt(idx, lnM):
-        xs, rs = (x, r) if idx is None else (x[idx], r[idx])
-        nb = int(xs.shape[0])
-        y = sampler.gauss(ctx.sigma, (nb, ctx.k))
-        coin, R = draw_coins(sampler, (nb,))
-        if idx is None:
-            c, t, ok = ctx.open_commit(xs, rs, y)
-            first["c"] = c
-        else:               # c = commit(x; r) does not depend on y: a retry computes t = a1.y alone
-            c, ok = first["c"][idx], None
-            t = ctx.matvec(KEY_A1, y)
-        d, _, okf = challenge(ctx, MSG_OPEN_COMMITMENT, c, t, aux=aux)
-        z, acc, _ = ctx.open_response_reject(y, rs, d, coin, R, lnM)
-        return (c, t, z), (okf if ok is None else ok & okf), acc
-
-    (c, t, z), ok, rounds = _zk_rounds(ctx, sampler, 1, max_rounds, attempt, fresh=(1, 2))
-    return c, t, z, ok, r, rounds
-
-
-# ---- the zero-knowledge Open prover on 32-bit slabs (DESIGN.md §20): the two provers above restated on open_commit32,
-# matvec32, challenge32 and open_response_reject32 with a backend.KeyedSampler32 / ExactKeyedSampler32.  The draw order is the
-# same (r; then per round y and the two coin draws), so with the same key and nonce0 the outputs are the int32 of
-# open_prove_zk's; no 64-bit slab and no convert launch appears at N = 512 and 1024, n = 1.
-def open_prove_sampled32(ctx, x, sampler, aux=None):
-    """open_prove_sampled on int32 slabs, r and y from a KeyedSampler32: (c, t, z, ok, r)."""
-    lead = _lead(x, 2)
-    r = sampler.uniform(ctx.b, lead + (ctx.k,))
-    y = sampler.gauss(ctx.sigma, lead + (ctx.k,))
-    return open_prove32(ctx, x, r, y, aux=aux) + (r,)
-
-
-def draw_coins32(sampler, lead):
-    """draw_coins from a sampler that returns int32 tensors: the same two draws and coefficients; the two [*lead] vectors
-    are converted to int64 before (a + half) R0 + (b + half) is formed (the product overflows int32).  That is a gather of
-    one value per proof, not a pass over a slab.  The coin is int64, as Context.open_response_reject32 takes it."""
+def _open_prove_zk(w, ctx, x, sampler, aux, max_rounds):
     import torch
 
-    half = (COIN_R0 - 1) // 2
-    a = sampler.uniform(half, tuple(lead))[..., 0].to(torch.int64)
-    b = sampler.uniform(half, tuple(lead))[..., 1].to(torch.int64)
-    return ((a + half) * COIN_R0 + (b + half)).contiguous(), COIN_R0 * COIN_R0
-
-
-def open_prove_zk32(ctx, x, sampler, aux=None, max_rounds: int = 64):
-    """open_prove_zk on int32 slabs: x int32 [B, l, N] (torch CUDA), sampler a KeyedSampler32 / ExactKeyedSampler32 ->
-    (c, t, z, ok, r, rounds) with c, t, z, r int32.  Bit-identical to narrow() of open_prove_zk's outputs under the same
-    key and nonces; ok and rounds are the same."""
-    import torch
-
-    B = _batch3(x, 2, "open_prove_zk32")
-    if x.dtype != torch.int32:
+    B = _batch3(x, 2, "open_prove_zk" + w.suffix)
+    if w is _OPEN32 and x.dtype != torch.int32:
         raise ValueError("open_prove_zk32: x must be an int32 tensor")
     r = sampler.uniform(ctx.b, (B, ctx.k))
 
@@ -497,19 +499,38 @@ def open_prove_zk32(ctx, x, sampler, aux=None, max_rounds: int = 64):
         xs, rs = (x, r) if idx is None else (x[idx], r[idx])
         nb = int(xs.shape[0])
         y = sampler.gauss(ctx.sigma, (nb, ctx.k))
-        coin, R = draw_coins32(sampler, (nb,))
+        coin, R = w.coins(sampler, (nb,))
         if idx is None:
-            c, t, ok = ctx.open_commit32(xs, rs, y)
+            c, t, ok = w.commit(ctx, xs, rs, y)
             first["c"] = c
         else:               # c = commit(x; r) does not depend on y: a retry computes t = a1.y alone
             c, ok = first["c"][idx], None
-            t = ctx.matvec32(KEY_A1, y)
-        d, _, okf = challenge32(ctx, MSG_OPEN_COMMITMENT, c, t, aux=aux)
-        z, acc, _ = ctx.open_response_reject32(y, rs, d, coin, R, lnM)
+            t = w.matvec(ctx, KEY_A1, y)
+        d, _, okf = w.challenge(ctx, MSG_OPEN_COMMITMENT, c, t, aux=aux)
+        z, acc, _ = w.response_reject(ctx, y, rs, d, coin, R, lnM)
         return (c, t, z), (okf if ok is None else ok & okf), acc
 
     (c, t, z), ok, rounds = _zk_rounds(ctx, sampler, 1, max_rounds, attempt, fresh=(1, 2))
     return c, t, z, ok, r, rounds
+
+
+def open_prove_zk(ctx, x, sampler, aux=None, max_rounds: int = 64):
+    """open_prove_sampled with the rejection step: (c, t, z, ok, r, rounds).  Round 0 is open_prove_sampled; each later
+    round proves the pending proofs again with the same r and a fresh y.  ok[b] = 1 iff r passed the commit constraint
+    and the proof was accepted within max_rounds, in round rounds[b]; t and z of the other proofs are zero."""
+    return _open_prove_zk(_OPEN64, ctx, x, sampler, aux, max_rounds)
+
+
+def open_prove_zk32(ctx, x, sampler, aux=None, max_rounds: int = 64):
+    """open_prove_zk on int32 slabs: x int32 [B, l, N] (torch CUDA), sampler a KeyedSampler32 /
+    ExactKeyedSampler32 -> (c, t, z, ok, r, rounds) with c, t, z, r int32.  The draw order is the same (r; then per round y
+    and the two coin draws), so the outputs are bit-identical to narrow() of open_prove_zk's under the same key and nonces;
+    ok and rounds are the same."""
+    return _open_prove_zk(_OPEN32, ctx, x, sampler, aux, max_rounds)
+
+
+_OPEN64 = _open_ops("", challenge, packed.decode_batch, _same_challenge, draw_coins)
+_OPEN32 = _open_ops("32", challenge32, packed.decode_batch32, _same_challenge32, draw_coins32)
 
 
 # ---- the same prover with the loop inside the library (include/rzk.h "prover loop", DESIGN.md §21) ----------------------

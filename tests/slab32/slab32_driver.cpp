@@ -3,6 +3,8 @@
 //                               canon32 widen test_word (else "-")
 //   slab32_driver route CASES   per line "n k l logn small rot shift_bytes pair_poly id var key": the planner's status,
 //                               the launch path of the plan and slab32_native for it (key as in plan_driver, "-" = none)
+//   slab32_driver coef CASES    per line "N count": the typed byte count of `count` polynomials (rzk_coef.h) for int64_t and
+//                               int32_t slabs, and whether launch_addr kept the address of a slab of each type (1 1)
 #include <cstdio>
 #include <fstream>
 #include <limits>
@@ -11,12 +13,45 @@
 #include <string>
 #include <vector>
 
+#include "../../ring_zk_amd/csrc/rzk_coef.h"
 #include "../../ring_zk_amd/csrc/rzk_plan.h"
 #include "../../ring_zk_amd/csrc/rzk_slab32.h"
 
 using namespace rzk;
 
 namespace {
+
+// An operand list has the type of its slabs: Op<C>{p, stride, outer} exists for a const C* only, so a 32-bit list cannot
+// be filled from 64-bit slabs or the reverse (the mistake a runtime width argument let through).
+template <class O, class P, class = void>
+struct OpFrom : std::false_type {};
+template <class O, class P>
+struct OpFrom<O, P, std::void_t<decltype(O{std::declval<P>(), 0u, 0u})>> : std::true_type {};
+static_assert(OpFrom<Op<int32_t>, const int32_t*>::value && OpFrom<Op<int64_t>, const int64_t*>::value, "the detector sees a good list");
+static_assert(OpFrom<Op<int32_t>, int32_t*>::value && OpFrom<Op<int64_t>, int64_t*>::value, "output slabs are operands too");
+static_assert(!OpFrom<Op<int32_t>, const int64_t*>::value, "no Op<int32_t> from a 64-bit slab");
+static_assert(!OpFrom<Op<int64_t>, const int32_t*>::value, "no Op<int64_t> from a 32-bit slab");
+static_assert(!OpFrom<Op<int32_t>, const void*>::value && !OpFrom<Op<int64_t>, const void*>::value, "nor from an untyped address");
+static_assert(poly_bytes<int64_t>(4, 1) == 32 && poly_bytes<int32_t>(4, 1) == 16, "constexpr byte counts");
+
+int run_coef(const char* path) {
+  std::ifstream in(path);
+  if (!in) return 2;
+  std::string line;
+  int64_t wide[2] = {1, 2};
+  int32_t narrow[2] = {3, 4};
+  while (std::getline(in, line)) {
+    if (line.empty()) continue;
+    std::istringstream ss(line);
+    uint32_t N;
+    unsigned long long count;
+    if (!(ss >> N >> count)) return 2;
+    const bool same64 = (const void*)launch_addr(&wide[1]) == (const void*)&wide[1] && launch_addr(&wide[1])[0] == 2;
+    const bool same32 = (const void*)launch_addr(&narrow[1]) == (const void*)&narrow[1];
+    std::printf("%zu %zu %d %d\n", poly_bytes<int64_t>(N, (size_t)count), poly_bytes<int32_t>(N, (size_t)count), (int)same64, (int)same32);
+  }
+  return 0;
+}
 
 int run_rules(const char* path) {
   std::ifstream in(path);
@@ -95,6 +130,7 @@ int main(int argc, char** argv) {
   const std::string mode = argc > 1 ? argv[1] : "";
   if (mode == "rules" && argc == 3) return run_rules(argv[2]);
   if (mode == "route" && argc == 3) return run_route(argv[2]);
-  std::fprintf(stderr, "usage: slab32_driver rules CASES | slab32_driver route CASES\n");
+  if (mode == "coef" && argc == 3) return run_coef(argv[2]);
+  std::fprintf(stderr, "usage: slab32_driver rules CASES | slab32_driver route CASES | slab32_driver coef CASES\n");
   return 2;
 }

@@ -1,6 +1,7 @@
 """CPU tier of the 32-bit slab format: ring_zk_amd/csrc/rzk_slab32.h (the scalar narrow / widen / canonical rules and the
-routing predicate of the 32-bit entry points), compiled with g++ under -fsanitize=address,undefined into
-tests/slab32/slab32_driver.cpp and run as a process, against Python integers."""
+routing predicate of the 32-bit entry points) and ring_zk_amd/csrc/rzk_coef.h (the coefficient type that carries a slab's
+width through the host layer), compiled with g++ under -fsanitize=address,undefined into tests/slab32/slab32_driver.cpp
+and run as a process, against Python integers."""
 import os
 import shutil
 import subprocess
@@ -150,3 +151,13 @@ def test_routing_native(driver, tmp_path, N):
 def test_routing_convert(driver, tmp_path, N, nkl, knobs):
     got = route(driver, tmp_path, N, nkl, **knobs)
     assert [g[2] for g in got] == [0] * 4, "every program of such a context takes the convert path"
+
+
+@pytest.mark.parametrize("N", [4, 512])
+def test_typed_byte_count(driver, tmp_path, N):
+    """poly_bytes<C>(N, count) = count * N * sizeof(C): the one byte count of the host layer, for both slab types (the
+    driver's static_asserts hold that an Op<int32_t> takes no 64-bit slab and an Op<int64_t> no 32-bit one)."""
+    counts = [0, 1, 3, 9, 4096 * 9, 2 ** 33 + 5]     # the last: a count whose bytes need more than 32 bits at either width
+    got = run_driver(driver, tmp_path, "coef", ["%d %d" % (N, k) for k in counts])
+    for k, g in zip(counts, got):
+        assert [int(v) for v in g] == [k * N * 8, k * N * 4, 1, 1], (N, k)
