@@ -174,11 +174,11 @@ int fs_challenge_dev(rzk_ctx* c, int kind, uint32_t V, const C* const* fields, c
   if (ok) HIPCHK(c, hipMemsetAsync(ok, 1, B, c->stream));
   HIPCHK(c, hipMemsetAsync(d, 0, polys<C>(c, B), c->stream));   // the sampler writes the kappa non-zero coefficients only
   rc = run_profiled(c, polys<C>(c, B * (size_t)s.polys), "fs leaf kernel", [&](const LaunchCfg& cfg) {
-    return launch_fs_leaves(cfg, m, (c->q - 1) / 2, c->trusted ? 0 : 1, dig, ok, c->d_bad, B, sizeof(C));
+    return launch_fs_leaves<C>(cfg, m, (c->q - 1) / 2, c->trusted ? 0 : 1, dig, ok, c->d_bad, B);
   });
   if (rc != RZK_OK) return rc;
   return run_profiled(c, (uint64_t)B * r.leaves * 32, "fs root kernel",
-                      [&](const LaunchCfg& cfg) { return launch_fs_roots(cfg, r, dig, launch_addr(d), digest, B, sizeof(C)); });
+                      [&](const LaunchCfg& cfg) { return launch_fs_roots(cfg, r, dig, d, digest, B); });
 }
 RZK_BOTH_WIDTHS(fs_challenge_dev)
 
@@ -532,8 +532,8 @@ int packed_run(rzk_ctx* c, const PackedSchema& s, const PackedSlabs& sl, uint8_t
   for (uint32_t f = 0; f < s.nfields; ++f) slab_bytes += packed_field_bytes<C>(c, s, f, B);
   return run_profiled(c, slab_bytes + (uint64_t)B * packed_record_bytes(s), decode ? "packed decode kernel" : "packed encode kernel",
                       [&](const LaunchCfg& cfg) {
-                        return decode ? launch_packed_decode(cfg, s, sl, (const uint64_t*)records, ok, B, sizeof(C))
-                                      : launch_packed_encode(cfg, s, sl, (uint64_t*)records, ok, B, sizeof(C));
+                        return decode ? launch_packed_decode<C>(cfg, s, sl, (const uint64_t*)records, ok, B)
+                                      : launch_packed_encode<C>(cfg, s, sl, (uint64_t*)records, ok, B);
                       });
 }
 

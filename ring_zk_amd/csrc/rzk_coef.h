@@ -1,8 +1,11 @@
 // rzk_coef.h — the coefficient type of a slab, as the host layer carries it.  A slab of the C ABI holds
 // int64_t coefficients or, in the "slab32" format (rzk_slab32.h), int32_t ones.  The host code is written once per entry
 // point over that type C: sizeof(C) is the only source of a slab's width, and an operand list has one type, so a launch
-// cannot be told a width its operands do not have.  The kernels' argument structs (rzk_dev.h) still carry addresses as
-// int64_t* beside a width; launch_addr is the one place where a typed pointer becomes such an address.
+// cannot be told a width its operands do not have.  The launchers that take a slab take it typed (rzk_dev.h, DESIGN.md
+// §23); what still carries addresses as int64_t* are the kernels' argument structs — Operands::base (filled by `lower`,
+// rzk_ctx.h), FsMsg::ptr, PackedSlabs::ptr — and the zs / ys arrays of the reject launch.  launch_addr is the one place where
+// a typed pointer becomes such an address; the launcher that reads the struct is named its type (launch_fs_leaves<C>) or,
+// below run_program_lowered, a width.
 // Plain C++ (tests/test_slab32_host.py compiles it with g++).
 #pragma once
 #include <stddef.h>
@@ -30,7 +33,7 @@ struct __attribute__((visibility("hidden"))) Op {   // one operand of a row-prog
   uint32_t outer;   // 0: indexed by the task batch index; otherwise by the proof index b / group
 };
 
-// the address of a slab as the launchers take it; its width, sizeof(C), goes beside it
+// the address of a slab as the kernels' argument structs carry it
 template <class C>
 inline const int64_t* launch_addr(const C* p) {
   static_assert(is_coef<C>, "a slab holds int64_t or int32_t coefficients");

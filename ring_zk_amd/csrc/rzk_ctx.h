@@ -280,10 +280,7 @@ int convert_call(rzk_ctx* c, const Conv (&slabs)[K], F body) {
 
 // ---- the *_dev entry points that exist at both widths, C = int64_t or int32_t (the siblings' extern "C" symbols forward
 // here; rzk_prove_loop.cpp calls them typed).  Defined, and instantiated for both, in the file named.
-// (an explicit instantiation takes the visibility of where it stands, not of the declaration here: hidden is said again)
-#define RZK_BOTH_WIDTHS(fn)                                                              \
-  template __attribute__((visibility("hidden"))) decltype(fn<int64_t>) fn<int64_t>; \
-  template __attribute__((visibility("hidden"))) decltype(fn<int32_t>) fn<int32_t>;
+// (RZK_BOTH_WIDTHS(fn), rzk_dev.h: the typed launchers are instantiated the same way)
 // rzk_protocols.cpp
 template <class C> int open_commit_dev(rzk_ctx* c, const C* x, const C* r, const C* y, C* cm, C* t, uint8_t* ok, size_t B);
 template <class C> int open_response_dev(rzk_ctx* c, const C* y, const C* r, const C* d, C* z, size_t B);

@@ -218,6 +218,21 @@ struct Operands {
 };
 
 // ---- launchers (defined in rzk_kernels.hip; their shared launch rules: rzk_launch.h) ----------------------------
+// Behind every launch of every .hip file: the launcher returns the HIP error of a launch that did not start.
+#define RZK_LAUNCH_CHECK()                      \
+  do {                                          \
+    hipError_t e_ = hipGetLastError();          \
+    if (e_ != hipSuccess) return (int)e_;       \
+  } while (0)
+// A launcher that exists for both coefficient types of a slab (C = int64_t, int32_t; rzk_coef.h) is declared below as a
+// template over C, and defined and instantiated for both in its .hip file: RZK_BOTH_WIDTHS(launch_x) behind the definition.
+// The host layer's typed entry points (rzk_ctx.h) use the same macro.
+// (an explicit instantiation takes the visibility of where it stands, not of its declaration: hidden is said here, so
+// that the library's export list holds none of them)
+#define RZK_BOTH_WIDTHS(fn)                                                              \
+  template __attribute__((visibility("hidden"))) decltype(fn<int64_t>) fn<int64_t>; \
+  template __attribute__((visibility("hidden"))) decltype(fn<int32_t>) fn<int32_t>;
+
 struct LaunchCfg {
   void* stream;   // hipStream_t
   int num_cus;
@@ -334,26 +349,32 @@ struct FsRoot {
 // leaf digests of B proofs: word w of leaf j = p * C + c of proof b at dig[(j * 4 + w) * B + b].  check != 0: every
 // coefficient is range-tested while it is loaded; a violation clears ok[b], or with ok == NULL sets *bad_word (the
 // context's sticky bad-input word), so that a non-canonical coefficient is never hashed silently as its low 32 bits.
-// width 4: the slabs of m hold int32_t coefficients (32-bit slabs; the addresses travel as int64_t*), fs_leaf_kernel<i32>
+// C: what the slabs of m hold (FsMsg carries addresses, so the caller names it: launch_fs_leaves<C>); int32_t is reported
+// as fs_leaf_kernel<i32>
+template <class C>
 int launch_fs_leaves(const LaunchCfg& cfg, const FsMsg& m, int64_t half, int check, uint64_t* dig, uint8_t* ok,
-                     uint32_t* bad_word, uint64_t B, uint32_t width = 8);
-// root of every proof: digest [B][32] (may be NULL) and, with d != NULL, the challenge into d [B][N] (zeroed before)
-// width 4: d addresses an int32_t slab, fs_root_kernel<i32>
-int launch_fs_roots(const LaunchCfg& cfg, const FsRoot& r, const uint64_t* dig, int64_t* d, uint8_t* digest,
-                    uint64_t B, uint32_t width = 8);
+                     uint32_t* bad_word, uint64_t B);
+// root of every proof: digest [B][32] (may be NULL) and, with d != NULL, the challenge into d [B][N] (zeroed before);
+// an int32_t slab d is reported as fs_root_kernel<i32>
+template <class C>
+int launch_fs_roots(const LaunchCfg& cfg, const FsRoot& r, const uint64_t* dig, C* d, uint8_t* digest, uint64_t B);
 // ---- keyed samplers (rzk_csprng_dev.hip; stream and maps in rzk_chacha.h): the distributions of launch_sample_*,
 // drawn from ChaCha20 blocks under the call's subkey = HChaCha20(key, nonce)
-// width 4: out addresses an int32_t slab (16-byte aligned), sample_*_chacha_kernel_i32: the same streams, narrowed at the store
-int launch_sample_uniform_chacha(const LaunchCfg& cfg, int64_t* out, uint64_t npoly, uint32_t n_ring, const uint32_t subkey[8],
-                                 uint32_t stream, uint32_t bound, uint32_t width = 8);
-int launch_sample_gauss_chacha(const LaunchCfg& cfg, int64_t* out, uint64_t npoly, uint32_t n_ring, const uint32_t subkey[8],
-                               uint32_t stream, double sigma, uint32_t width = 8);
-int launch_sample_challenge_chacha(const LaunchCfg& cfg, int64_t* out, uint64_t npoly, uint32_t n_ring, const uint32_t subkey[8],
-                                   uint32_t stream, uint32_t kappa, uint32_t width = 8);
+// an int32_t slab `out` (16-byte aligned) is reported as sample_*_chacha_kernel_i32: the same streams, narrowed at the store
+template <class C>
+int launch_sample_uniform_chacha(const LaunchCfg& cfg, C* out, uint64_t npoly, uint32_t n_ring, const uint32_t subkey[8],
+                                 uint32_t stream, uint32_t bound);
+template <class C>
+int launch_sample_gauss_chacha(const LaunchCfg& cfg, C* out, uint64_t npoly, uint32_t n_ring, const uint32_t subkey[8],
+                               uint32_t stream, double sigma);
+template <class C>
+int launch_sample_challenge_chacha(const LaunchCfg& cfg, C* out, uint64_t npoly, uint32_t n_ring, const uint32_t subkey[8],
+                                   uint32_t stream, uint32_t kappa);
 // the exact discrete Gaussian D_sigma, integer sigma in [1, 2^26] (definition and stream: rzk_dgauss.h), and its trial
 // on chosen words: words [trials][8] -> out [trials][2] = (accepted, value)
-int launch_sample_dgauss_chacha(const LaunchCfg& cfg, int64_t* out, uint64_t npoly, uint32_t n_ring, const uint32_t subkey[8],
-                                uint32_t stream, uint32_t sigma, uint32_t width = 8);
+template <class C>
+int launch_sample_dgauss_chacha(const LaunchCfg& cfg, C* out, uint64_t npoly, uint32_t n_ring, const uint32_t subkey[8],
+                                uint32_t stream, uint32_t sigma);
 int launch_debug_dgauss_trial(const LaunchCfg& cfg, uint32_t sigma, const uint32_t* words, int64_t* out, uint64_t trials);
 // ---- rejection sampling of the provers (rzk_reject_dev.hip; definition in rzk_reject.h) --------------------------------
 struct RejectPartial;
@@ -399,35 +420,39 @@ int launch_widen(const LaunchCfg& cfg, const int32_t* in, int64_t* out, uint64_t
 // slabs 16-byte aligned
 int launch_eq32(const LaunchCfg& cfg, const int32_t* a, const int32_t* b, uint64_t words, uint8_t* eq, uint64_t B);
 // ---- the in-library Open prover loop (rzk_prove_loop_dev.hip; arithmetic in rzk_prove_loop.h) ------------
-// width: bytes per coefficient of the slabs (8 or 4); every slab 16-byte aligned.  count == 0 launches nothing.
+// C: the coefficient type of the slabs; every slab 16-byte aligned.  count == 0 launches nothing.
 // idx[0 .. *count) = the ascending b < B with live[b] && !done[b]; entries from *count on are not written.  -2: B >= 2^32
 int launch_pending_compact(const LaunchCfg& cfg, const uint8_t* live, const uint8_t* done, uint64_t B, uint32_t* idx, uint32_t* count);
 // coin[i] = prove_coin(a[i][0], b[i][1]); a, b: [count][N]
-int launch_prove_coins(const LaunchCfg& cfg, const void* a, const void* b, uint32_t N, int64_t* coin, uint64_t count, uint32_t width);
+template <class C>
+int launch_prove_coins(const LaunchCfg& cfg, const C* a, const C* b, uint32_t N, int64_t* coin, uint64_t count);
 // dst0[i] = src0[idx[i]] ([rows0][N] each) and, with src1 != NULL, dst1[i] = src1[idx[i]] ([rows1][N]), i < count
-int launch_gather_rows(const LaunchCfg& cfg, const void* src0, void* dst0, uint32_t rows0, const void* src1, void* dst1, uint32_t rows1,
-                       uint32_t N, const uint32_t* idx, uint32_t count, uint32_t width);
+template <class C>
+int launch_gather_rows(const LaunchCfg& cfg, const C* src0, C* dst0, uint32_t rows0, const C* src1, C* dst1, uint32_t rows1, uint32_t N,
+                       const uint32_t* idx, uint32_t count);
 // accept[i] != 0: t[i] -> t_out[idx[i]], z[i] -> z_out[idx[i]], rounds[idx[i]] = rnd, done[idx[i]] = 1, i < count
-int launch_accept_scatter(const LaunchCfg& cfg, const void* t, const void* z, void* t_out, void* z_out, uint32_t t_rows, uint32_t z_rows,
-                          uint32_t N, const uint8_t* accept, const uint32_t* idx, uint32_t count, uint8_t rnd, uint8_t* rounds,
-                          uint8_t* done, uint32_t width);
+template <class C>
+int launch_accept_scatter(const LaunchCfg& cfg, const C* t, const C* z, C* t_out, C* z_out, uint32_t t_rows, uint32_t z_rows, uint32_t N,
+                          const uint8_t* accept, const uint32_t* idx, uint32_t count, uint8_t rnd, uint8_t* rounds, uint8_t* done);
 // after round 0: live = (ok_commit & ok_hash) != 0, done = live && accept, rounds = 0
 int launch_prove_first(const LaunchCfg& cfg, const uint8_t* ok_commit, const uint8_t* ok_hash, const uint8_t* accept, uint8_t* live,
                        uint8_t* done, uint8_t* rounds, uint64_t B);
 // after the last round: rows of t_out, z_out of every proof with done == 0 zeroed; ok = done
-int launch_prove_last(const LaunchCfg& cfg, const uint8_t* done, void* t_out, void* z_out, uint32_t t_rows, uint32_t z_rows, uint32_t N,
-                      uint8_t* ok, uint64_t B, uint32_t width);
+template <class C>
+int launch_prove_last(const LaunchCfg& cfg, const uint8_t* done, C* t_out, C* z_out, uint32_t t_rows, uint32_t z_rows, uint32_t N,
+                      uint8_t* ok, uint64_t B);
 // ---- fixed-width packed records (rzk_packed_dev.hip; format in rzk_packed.h) -------------------------------------------
 struct PackedSlabs {
   int64_t* ptr[kPackedMaxFields];   // dense slab of every field ([B][rows of the field][N]), 16-byte aligned
 };
 // rec: [B][s.rec_words] 64-bit words.  ok[b] must hold 1 before the launch; it is cleared for a message with a coefficient
 // outside its class's range (encode: the marker is written in its place) / a record that does not decode
-// width 4: the slabs hold int32_t coefficients (their addresses travel as int64_t*), packed_*_kernel<i32>
-int launch_packed_encode(const LaunchCfg& cfg, const PackedSchema& s, const PackedSlabs& sl, uint64_t* rec, uint8_t* ok, uint64_t B,
-                         uint32_t width = 8);
-int launch_packed_decode(const LaunchCfg& cfg, const PackedSchema& s, const PackedSlabs& sl, const uint64_t* rec, uint8_t* ok,
-                         uint64_t B, uint32_t width = 8);
+// C: what the slabs hold (PackedSlabs carries addresses, so the caller names it: launch_packed_encode<C>); int32_t is
+// reported as packed_*_kernel<i32>
+template <class C>
+int launch_packed_encode(const LaunchCfg& cfg, const PackedSchema& s, const PackedSlabs& sl, uint64_t* rec, uint8_t* ok, uint64_t B);
+template <class C>
+int launch_packed_decode(const LaunchCfg& cfg, const PackedSchema& s, const PackedSlabs& sl, const uint64_t* rec, uint8_t* ok, uint64_t B);
 // ---- seed expansion "XP1" (rzk_xof_dev.hip; format in rzk_xof.h) ---------------------------------------------------------
 struct XofJob {
   uint64_t q;

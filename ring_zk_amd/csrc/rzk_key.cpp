@@ -94,7 +94,7 @@ int fs_key_digest_dev(rzk_ctx* c, const int64_t* a_host, const int64_t* a_dev) {
   m.ptr[0] = a_dev;
   const LaunchCfg cfg = cfg_of(c);
   // (the host loop of the load has range-tested every coefficient)
-  rc = check_launch(c, launch_fs_leaves(cfg, m, (c->q - 1) / 2, 0, dig, nullptr, nullptr, 1), "key leaf hash");
+  rc = check_launch(c, launch_fs_leaves<int64_t>(cfg, m, (c->q - 1) / 2, 0, dig, nullptr, nullptr, 1), "key leaf hash");
   if (rc != RZK_OK) return rc;
   FsRoot r{};
   fs_key_header(c->q, c->N, c->n, c->k, c->l, c->kappa, c->b, r.hdr);
@@ -102,7 +102,7 @@ int fs_key_digest_dev(rzk_ctx* c, const int64_t* a_host, const int64_t* a_dev) {
   r.leaves = leaves;
   r.N = c->N;
   r.kappa = c->kappa;
-  rc = check_launch(c, launch_fs_roots(cfg, r, dig, nullptr, out, 1), "key root hash");
+  rc = check_launch(c, launch_fs_roots<int64_t>(cfg, r, dig, nullptr, out, 1), "key root hash");
   if (rc != RZK_OK) return rc;
   HIPCHK(c, hipMemcpyAsync(c->key_digest, out, sizeof c->key_digest, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -13,12 +13,6 @@
 
 namespace rzk {
 
-#define RZK_LAUNCH_CHECK()                      \
-  do {                                          \
-    hipError_t e_ = hipGetLastError();          \
-    if (e_ != hipSuccess) return (int)e_;       \
-  } while (0)
-
 static inline unsigned grid_for(uint64_t tasks, int num_cus, int waves_per_block = 4, int blocks_per_cu = 8) {
   uint64_t blocks = (tasks + waves_per_block - 1) / waves_per_block;
   const uint64_t cap = (uint64_t)num_cus * blocks_per_cu;

@@ -14,9 +14,9 @@
 //                          one 16-byte piece.  The lane that loaded the last word tests the padding bits.
 // The wavefront of a record's first polynomial also writes / checks the header word.  ok[] is preset to 1 by the entry
 // point; a wavefront that meets a fault stores 0 (every writer stores the same value).  No scratch memory.
-// Both kernels exist for int64_t slabs and for 32-bit slabs (reported as packed_encode_kernel<i32>, packed_decode_kernel<i32>;
-// DESIGN.md §19) from one text (rzk_packed_kernels.inc): there a lane's piece of two coefficients is one 8-byte access (int2) and the raw rule
-// runs in 32-bit arithmetic (packed_raw32).  Records carry no width.
+// Both kernels are templates over the coefficient type of the slabs, int64_t or the 32-bit slabs' int32_t (reported as
+// packed_encode_kernel<i32>, packed_decode_kernel<i32>): there a lane's piece of two coefficients is one
+// 8-byte access (int2) and the raw rule runs in 32-bit arithmetic (packed_raw32).  Records carry no width.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -26,12 +26,6 @@
 #include "rzk_wave.h"
 
 namespace rzk {
-
-#define RZK_LAUNCH_CHECK()                      \
-  do {                                          \
-    hipError_t e_ = hipGetLastError();          \
-    if (e_ != hipSuccess) return (int)e_;       \
-  } while (0)
 
 namespace {
 
@@ -65,29 +59,132 @@ __device__ __forceinline__ PolyTask poly_task(const PackedSchema& s, uint64_t p)
   return t;
 }
 
-// The kernels' text, once per coefficient width (see the head of rzk_packed_kernels.inc).
-#define RZK_PK_KERNEL(name) name
-#define RZK_PK_COEF int64_t
-#define RZK_PK_PAIR v2l
-#define RZK_PK_RAW packed_raw
-#define RZK_PK_UNBIAS(r, b) ((long)(r) - (long)(b))
-#include "rzk_packed_kernels.inc"
-#undef RZK_PK_KERNEL
-#undef RZK_PK_COEF
-#undef RZK_PK_PAIR
-#undef RZK_PK_RAW
-#undef RZK_PK_UNBIAS
-#define RZK_PK_KERNEL(name) name##_i32
-#define RZK_PK_COEF int32_t
-#define RZK_PK_PAIR int2
-#define RZK_PK_RAW packed_raw32
-#define RZK_PK_UNBIAS(r, b) ((int)((r) - (b)))
-#include "rzk_packed_kernels.inc"
-#undef RZK_PK_KERNEL
-#undef RZK_PK_COEF
-#undef RZK_PK_PAIR
-#undef RZK_PK_RAW
-#undef RZK_PK_UNBIAS
+// What the kernels take from the coefficient type C of the slabs (PackedSlabs carries addresses):
+//   Pair           a lane's piece of two coefficients: v2l, one 16-byte access / int2, one 8-byte access.  Slabs are 16-byte
+//                  aligned and a piece starts at an even coefficient, so both are naturally aligned
+//   raw            packed_raw / packed_raw32 (rzk_packed.h)
+//   unbias(r, b)   the decoded coefficient r - b in the slab's type (a valid r is at most 2 b, so it fits an int32_t; the
+//                  value of a rejected record is unspecified at either width)
+template <class C>
+struct PackedCoef;
+template <>
+struct PackedCoef<int64_t> {
+  using Pair = v2l;
+  static __device__ __forceinline__ bool raw(int64_t v, const PackedWidth& w, uint32_t* r) { return packed_raw(v, w, r); }
+  static __device__ __forceinline__ long unbias(uint32_t r, uint32_t b) { return ((long)(r) - (long)(b)); }
+};
+template <>
+struct PackedCoef<int32_t> {
+  using Pair = int2;
+  static __device__ __forceinline__ bool raw(int32_t v, const PackedWidth& w, uint32_t* r) { return packed_raw32(v, w, r); }
+  static __device__ __forceinline__ int unbias(uint32_t r, uint32_t b) { return ((int)((r) - (b))); }
+};
+template <class C>
+using PackedPair = typename PackedCoef<C>::Pair;
+
+template <class C>
+__global__ void __launch_bounds__(64 * kWavesPerBlock) packed_encode_kernel(PackedSchema s, PackedSlabs sl, uint64_t* __restrict__ rec,
+                                                                            uint8_t* __restrict__ ok, uint64_t npolys) {
+  __shared__ uint32_t tile_all[kWavesPerBlock][kTripCoefs];
+  const uint32_t lane = threadIdx.x & 63u;
+  uint32_t* tile = tile_all[wave_index()];
+  const uint32_t trips = (s.N + kTripCoefs - 1) / kTripCoefs;
+  const uint32_t ncoef = s.N < kTripCoefs ? s.N : kTripCoefs;   // coefficients per trip (N is a power of two)
+  for (uint64_t p = (uint64_t)blockIdx.x * kWavesPerBlock + wave_index(); p < npolys;
+       p += (uint64_t)gridDim.x * kWavesPerBlock) {
+    const PolyTask t = poly_task(s, p);
+    const PackedWidth w = s.w[s.f[t.f].cls];
+    const C* src = reinterpret_cast<const C*>(sl.ptr[t.f]) + t.coef;
+    uint64_t* dst = rec + t.word;
+    if (t.j == 0 && lane == 0) rec[t.b * s.rec_words] = packed_header(s.kind, s.V);
+    bool bad = false;
+    const bool active = 2u * lane < ncoef;   // (N >= 4 is even: a piece never straddles the end)
+    const uint32_t nw = (ncoef * w.W + 63u) / 64u;   // words of one trip, at most 2 W <= 64
+    // Loads are unconditional, so that the next trip's piece stays in flight while this one is packed (a load under a
+    // branch makes the compiler wait for everything outstanding): an idle lane (N < 128) re-reads the polynomial's first
+    // piece and the last trip re-reads itself; both stay inside the polynomial and their values are not used (the indices
+    // count coefficients, so this holds at either width).
+    const uint32_t at = active ? 2u * lane : 0u;
+    PackedPair<C> cc = *reinterpret_cast<const PackedPair<C>*>(src + at);
+    for (uint32_t tr = 0; tr < trips; ++tr) {
+      const uint32_t tn = tr + 1 < trips ? tr + 1 : tr;
+      const PackedPair<C> next = *reinterpret_cast<const PackedPair<C>*>(src + tn * kTripCoefs + at);
+      uint32_t r0 = 0, r1 = 0;
+      if (active) {
+        bad |= !PackedCoef<C>::raw((C)cc.x, w, &r0);
+        bad |= !PackedCoef<C>::raw((C)cc.y, w, &r1);
+      }
+      wave_sync();   // the previous trip's reads of the tile are over
+      *reinterpret_cast<uint2*>(tile + 2u * lane) = make_uint2(r0, r1);   // lanes past the end store zeros: the padding
+      wave_sync();
+      if (lane < nw) {
+        const uint32_t bit0 = 64u * lane;
+        uint64_t word = 0;
+        for (uint32_t i = packed_div(bit0, w); i < kTripCoefs && i * w.W < bit0 + 64u; ++i) {
+          const int32_t sh = (int32_t)(i * w.W) - (int32_t)bit0;   // -W < sh < 64
+          const uint64_t v = tile[i];
+          word |= sh >= 0 ? v << sh : v >> (-sh);
+        }
+        dst[(uint64_t)tr * 2u * w.W + lane] = word;
+      }
+      cc = next;
+    }
+    if (wave_any(bad) && lane == 0) ok[t.b] = 0;
+  }
+}
+
+template <class C>
+__global__ void __launch_bounds__(64 * kWavesPerBlock) packed_decode_kernel(PackedSchema s, PackedSlabs sl, const uint64_t* __restrict__ rec,
+                                                                            uint8_t* __restrict__ ok, uint64_t npolys) {
+  __shared__ uint64_t tile_all[kWavesPerBlock][64];
+  const uint32_t lane = threadIdx.x & 63u;
+  uint64_t* tile = tile_all[wave_index()];
+  const uint32_t trips = (s.N + kTripCoefs - 1) / kTripCoefs;
+  const uint32_t ncoef = s.N < kTripCoefs ? s.N : kTripCoefs;   // coefficients per trip (N is a power of two)
+  for (uint64_t p = (uint64_t)blockIdx.x * kWavesPerBlock + wave_index(); p < npolys;
+       p += (uint64_t)gridDim.x * kWavesPerBlock) {
+    const PolyTask t = poly_task(s, p);
+    const PackedWidth w = s.w[s.f[t.f].cls];
+    const uint64_t* src = rec + t.word;
+    C* dst = reinterpret_cast<C*>(sl.ptr[t.f]) + t.coef;
+    const uint64_t mask = (1ull << w.W) - 1;
+    bool bad = false;
+    if (t.j == 0 && lane == 0) bad = rec[t.b * s.rec_words] != packed_header(s.kind, s.V);
+    const uint32_t bits = ncoef * w.W;
+    const uint32_t nw = (bits + 63u) / 64u;   // words of one trip, at most 2 W <= 64
+    // unconditional loads, as in the encoder: a lane past the trip's words re-reads word 0, the last trip itself
+    const uint32_t at = lane < nw ? lane : 0u;
+    uint64_t word = src[at];
+    for (uint32_t tr = 0; tr < trips; ++tr) {
+      const uint32_t tn = tr + 1 < trips ? tr + 1 : tr;
+      const uint64_t next = src[(uint64_t)tn * 2u * w.W + at];
+      wave_sync();   // the previous trip's reads of the tile are over
+      if (lane < nw) {
+        tile[lane] = word;
+        if (lane == nw - 1 && (bits & 63u)) bad |= (word >> (bits & 63u)) != 0;   // padding bits
+      }
+      wave_sync();
+      if (2u * lane < ncoef) {
+        uint32_t raw[2];
+#pragma unroll
+        for (uint32_t e = 0; e < 2; ++e) {
+          const uint32_t bit = (2u * lane + e) * w.W;
+          const uint32_t sh = bit & 63u;
+          uint64_t v = tile[bit >> 6] >> sh;
+          if (sh + w.W > 64u) v |= tile[(bit >> 6) + 1] << (64u - sh);   // the next word exists: the coefficient ends inside the trip
+          raw[e] = (uint32_t)(v & mask);
+          bad |= raw[e] > w.limit;
+        }
+        PackedPair<C> out;
+        out.x = PackedCoef<C>::unbias(raw[0], w.bias);
+        out.y = PackedCoef<C>::unbias(raw[1], w.bias);
+        *reinterpret_cast<PackedPair<C>*>(dst + tr * kTripCoefs + 2u * lane) = out;
+      }
+      word = next;
+    }
+    if (wave_any(bad) && lane == 0) ok[t.b] = 0;
+  }
+}
 
 uint64_t capped(uint64_t tasks, int num_cus) {   // workgroups of kWavesPerBlock tasks under the grid cap
   uint64_t blocks = (tasks + kWavesPerBlock - 1) / kWavesPerBlock;
@@ -97,26 +194,28 @@ uint64_t capped(uint64_t tasks, int num_cus) {   // workgroups of kWavesPerBlock
 
 }  // namespace
 
-int launch_packed_encode(const LaunchCfg& cfg, const PackedSchema& s, const PackedSlabs& sl, uint64_t* rec, uint8_t* ok, uint64_t B,
-                         uint32_t width) {
+template <class C>
+int launch_packed_encode(const LaunchCfg& cfg, const PackedSchema& s, const PackedSlabs& sl, uint64_t* rec, uint8_t* ok, uint64_t B) {
   const uint64_t npolys = B * s.polys;
   if (npolys == 0) return 0;
-  hipLaunchKernelGGL(width == 4 ? packed_encode_kernel_i32 : packed_encode_kernel, dim3((unsigned)capped(npolys, cfg.num_cus)), dim3(64 * kWavesPerBlock), 0,
+  hipLaunchKernelGGL(packed_encode_kernel<C>, dim3((unsigned)capped(npolys, cfg.num_cus)), dim3(64 * kWavesPerBlock), 0,
                      (hipStream_t)cfg.stream, s, sl, rec, ok, npolys);
   RZK_LAUNCH_CHECK();
-  if (cfg.launched) *cfg.launched = width == 4 ? "packed_encode_kernel<i32>" : "packed_encode_kernel";
+  if (cfg.launched) *cfg.launched = sizeof(C) == 4 ? "packed_encode_kernel<i32>" : "packed_encode_kernel";
   return 0;
 }
+RZK_BOTH_WIDTHS(launch_packed_encode)
 
-int launch_packed_decode(const LaunchCfg& cfg, const PackedSchema& s, const PackedSlabs& sl, const uint64_t* rec, uint8_t* ok,
-                         uint64_t B, uint32_t width) {
+template <class C>
+int launch_packed_decode(const LaunchCfg& cfg, const PackedSchema& s, const PackedSlabs& sl, const uint64_t* rec, uint8_t* ok, uint64_t B) {
   const uint64_t npolys = B * s.polys;
   if (npolys == 0) return 0;
-  hipLaunchKernelGGL(width == 4 ? packed_decode_kernel_i32 : packed_decode_kernel, dim3((unsigned)capped(npolys, cfg.num_cus)), dim3(64 * kWavesPerBlock), 0,
+  hipLaunchKernelGGL(packed_decode_kernel<C>, dim3((unsigned)capped(npolys, cfg.num_cus)), dim3(64 * kWavesPerBlock), 0,
                      (hipStream_t)cfg.stream, s, sl, rec, ok, npolys);
   RZK_LAUNCH_CHECK();
-  if (cfg.launched) *cfg.launched = width == 4 ? "packed_decode_kernel<i32>" : "packed_decode_kernel";
+  if (cfg.launched) *cfg.launched = sizeof(C) == 4 ? "packed_decode_kernel<i32>" : "packed_decode_kernel";
   return 0;
 }
+RZK_BOTH_WIDTHS(launch_packed_decode)
 
 }  // namespace rzk

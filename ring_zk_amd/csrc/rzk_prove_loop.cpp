@@ -87,7 +87,6 @@ int open_prove_zk_dev(rzk_ctx* c, const C* x, const uint8_t* nonce0, uint32_t st
   uint8_t *const live = (uint8_t*)(base + o_live), *const done = (uint8_t*)(base + o_done);
   uint32_t *const idx = (uint32_t*)(base + o_idx), *const d_count = (uint32_t*)(base + o_count);
 
-  constexpr uint32_t width = sizeof(C);   // for the loop's own kernels, which take untyped slabs
   const double lnM = reject_lnm(11.0);   // one response vector: alpha = 11 (fiat_shamir.zk_lnm(1))
   uint64_t used = 0;                      // nonces consumed
   uint8_t nonce[16];
@@ -112,7 +111,7 @@ int open_prove_zk_dev(rzk_ctx* c, const C* x, const uint8_t* nonce0, uint32_t st
     if (st == RZK_OK) st = sample_uniform_keyed_dev(c, next_nonce(), stream, (uint64_t)kCoinHalf, wcb, nb);
     if (st != RZK_OK) return st;
     return run_profiled(c, (uint64_t)nb * 24, "coin kernel",
-                        [&](const LaunchCfg& cfg) { return launch_prove_coins(cfg, wca, wcb, N, coin, nb, width); });
+                        [&](const LaunchCfg& cfg) { return launch_prove_coins(cfg, wca, wcb, N, coin, nb); });
   };
 
   size_t retry_max = 0;   // the largest sub-batch: how much of the workspace's t and z was written
@@ -143,7 +142,7 @@ int open_prove_zk_dev(rzk_ctx* c, const C* x, const uint8_t* nonce0, uint32_t st
       st = draw(nb);
       if (st == RZK_OK)
         st = run_profiled(c, (uint64_t)nb * (2 * k + 2 * (n + l)) * poly, "gather rows kernel", [&](const LaunchCfg& cfg) {
-          return launch_gather_rows(cfg, r, wrg, k, cm, wcg, n + l, N, idx, (uint32_t)nb, width);
+          return launch_gather_rows(cfg, r, wrg, k, cm, wcg, n + l, N, idx, (uint32_t)nb);
         });
       // c = commit(x; r) does not depend on y: a retry computes t = a1.y alone
       if (st == RZK_OK) st = matvec_dev<C>(c, RZK_KEY_A1, wy, nullptr, wt, nb);
@@ -151,14 +150,14 @@ int open_prove_zk_dev(rzk_ctx* c, const C* x, const uint8_t* nonce0, uint32_t st
       if (st == RZK_OK) st = open_response_reject_dev<C>(c, wy, wrg, wd, coin, kCoinR, lnM, wz, accept, nullptr, nb);
       if (st == RZK_OK)
         st = run_profiled(c, (uint64_t)nb * 2 * (n + k) * poly, "accept scatter kernel", [&](const LaunchCfg& cfg) {
-          return launch_accept_scatter(cfg, wt, wz, t, z, n, k, N, accept, idx, (uint32_t)nb, (uint8_t)rnd, rounds, done, width);
+          return launch_accept_scatter(cfg, wt, wz, t, z, n, k, N, accept, idx, (uint32_t)nb, (uint8_t)rnd, rounds, done);
         });
       if (st != RZK_OK) return st;
       ++ran;
     }
     // ---- a rejected attempt never leaves: what is left of round 0 in the caller's t and z is overwritten
     return run_profiled(c, (uint64_t)B * (n + k) * poly, "prove last kernel",
-                        [&](const LaunchCfg& cfg) { return launch_prove_last(cfg, done, t, z, n, k, N, ok, B, width); });
+                        [&](const LaunchCfg& cfg) { return launch_prove_last(cfg, done, t, z, n, k, N, ok, B); });
   };
   rc = loop();
   // Rejected responses, and the y and coins behind them, are exactly what must not be released: the y, t, z and coin parts of

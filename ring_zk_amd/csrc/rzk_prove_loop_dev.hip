@@ -23,12 +23,6 @@
 
 namespace rzk {
 
-#define RZK_LAUNCH_CHECK()                      \
-  do {                                          \
-    hipError_t e_ = hipGetLastError();          \
-    if (e_ != hipSuccess) return (int)e_;       \
-  } while (0)
-
 namespace {
 
 __global__ void __launch_bounds__(kCompactTile) pending_compact_kernel(const uint8_t* __restrict__ live, const uint8_t* __restrict__ done,
@@ -139,13 +133,8 @@ template <class T>
 const char* width_mark() {
   return std::is_same<T, int32_t>::value ? "<i32>" : "<i64>";
 }
-uint32_t quads_of(uint32_t rows, uint32_t N, uint32_t width) { return rows * N * width / 16; }   // N >= 4: a whole number
-
-// f(T{}) for the coefficient type of a width
-template <class F>
-int with_width(uint32_t width, F&& f) {
-  return width == 4 ? f(int32_t{}) : f(int64_t{});
-}
+template <class C>
+uint32_t quads_of(uint32_t rows, uint32_t N) { return rows * N * sizeof(C) / 16; }   // N >= 4: a whole number
 
 }  // namespace
 
@@ -157,47 +146,42 @@ int launch_pending_compact(const LaunchCfg& cfg, const uint8_t* live, const uint
   return 0;
 }
 
-int launch_prove_coins(const LaunchCfg& cfg, const void* a, const void* b, uint32_t N, int64_t* coin, uint64_t count, uint32_t width) {
+template <class C>
+int launch_prove_coins(const LaunchCfg& cfg, const C* a, const C* b, uint32_t N, int64_t* coin, uint64_t count) {
   if (count == 0) return 0;
-  return with_width(width, [&](auto t) -> int {
-    using T = decltype(t);
-    hipLaunchKernelGGL(coin_kernel<T>, dim3(flat_grid(count, cfg.num_cus)), dim3(256), 0, (hipStream_t)cfg.stream, (const T*)a, (const T*)b, N,
-                       coin, count);
-    RZK_LAUNCH_CHECK();
-    if (cfg.launched) *cfg.launched = std::string("coin_kernel") + width_mark<T>();
-    return 0;
-  });
+  hipLaunchKernelGGL(coin_kernel<C>, dim3(flat_grid(count, cfg.num_cus)), dim3(256), 0, (hipStream_t)cfg.stream, a, b, N, coin, count);
+  RZK_LAUNCH_CHECK();
+  if (cfg.launched) *cfg.launched = std::string("coin_kernel") + width_mark<C>();
+  return 0;
 }
+RZK_BOTH_WIDTHS(launch_prove_coins)
 
-int launch_gather_rows(const LaunchCfg& cfg, const void* src0, void* dst0, uint32_t rows0, const void* src1, void* dst1, uint32_t rows1,
-                       uint32_t N, const uint32_t* idx, uint32_t count, uint32_t width) {
+template <class C>
+int launch_gather_rows(const LaunchCfg& cfg, const C* src0, C* dst0, uint32_t rows0, const C* src1, C* dst1, uint32_t rows1, uint32_t N,
+                       const uint32_t* idx, uint32_t count) {
   if (count == 0) return 0;
   GatherJob job{};
-  job.src[0] = (const int4*)src0, job.dst[0] = (int4*)dst0, job.quads[0] = quads_of(rows0, N, width);
-  job.src[1] = (const int4*)src1, job.dst[1] = (int4*)dst1, job.quads[1] = src1 ? quads_of(rows1, N, width) : 0;
-  return with_width(width, [&](auto t) -> int {
-    using T = decltype(t);
-    hipLaunchKernelGGL(gather_rows_kernel<T>, dim3(entry_grid(count, cfg.num_cus)), dim3(256), 0, (hipStream_t)cfg.stream, job, idx, count);
-    RZK_LAUNCH_CHECK();
-    if (cfg.launched) *cfg.launched = std::string("gather_rows_kernel") + width_mark<T>();
-    return 0;
-  });
+  job.src[0] = (const int4*)src0, job.dst[0] = (int4*)dst0, job.quads[0] = quads_of<C>(rows0, N);
+  job.src[1] = (const int4*)src1, job.dst[1] = (int4*)dst1, job.quads[1] = src1 ? quads_of<C>(rows1, N) : 0;
+  hipLaunchKernelGGL(gather_rows_kernel<C>, dim3(entry_grid(count, cfg.num_cus)), dim3(256), 0, (hipStream_t)cfg.stream, job, idx, count);
+  RZK_LAUNCH_CHECK();
+  if (cfg.launched) *cfg.launched = std::string("gather_rows_kernel") + width_mark<C>();
+  return 0;
 }
+RZK_BOTH_WIDTHS(launch_gather_rows)
 
-int launch_accept_scatter(const LaunchCfg& cfg, const void* t, const void* z, void* t_out, void* z_out, uint32_t t_rows, uint32_t z_rows,
-                          uint32_t N, const uint8_t* accept, const uint32_t* idx, uint32_t count, uint8_t rnd, uint8_t* rounds,
-                          uint8_t* done, uint32_t width) {
+template <class C>
+int launch_accept_scatter(const LaunchCfg& cfg, const C* t, const C* z, C* t_out, C* z_out, uint32_t t_rows, uint32_t z_rows, uint32_t N,
+                          const uint8_t* accept, const uint32_t* idx, uint32_t count, uint8_t rnd, uint8_t* rounds, uint8_t* done) {
   if (count == 0) return 0;
-  const ScatterJob job{(const int4*)t, (const int4*)z, (int4*)t_out, (int4*)z_out, quads_of(t_rows, N, width), quads_of(z_rows, N, width)};
-  return with_width(width, [&](auto tt) -> int {
-    using T = decltype(tt);
-    hipLaunchKernelGGL(accept_scatter_kernel<T>, dim3(entry_grid(count, cfg.num_cus)), dim3(256), 0, (hipStream_t)cfg.stream, job, accept, idx,
-                       count, rnd, rounds, done);
-    RZK_LAUNCH_CHECK();
-    if (cfg.launched) *cfg.launched = std::string("accept_scatter_kernel") + width_mark<T>();
-    return 0;
-  });
+  const ScatterJob job{(const int4*)t, (const int4*)z, (int4*)t_out, (int4*)z_out, quads_of<C>(t_rows, N), quads_of<C>(z_rows, N)};
+  hipLaunchKernelGGL(accept_scatter_kernel<C>, dim3(entry_grid(count, cfg.num_cus)), dim3(256), 0, (hipStream_t)cfg.stream, job, accept, idx,
+                     count, rnd, rounds, done);
+  RZK_LAUNCH_CHECK();
+  if (cfg.launched) *cfg.launched = std::string("accept_scatter_kernel") + width_mark<C>();
+  return 0;
 }
+RZK_BOTH_WIDTHS(launch_accept_scatter)
 
 int launch_prove_first(const LaunchCfg& cfg, const uint8_t* ok_commit, const uint8_t* ok_hash, const uint8_t* accept, uint8_t* live,
                        uint8_t* done, uint8_t* rounds, uint64_t B) {
@@ -209,17 +193,16 @@ int launch_prove_first(const LaunchCfg& cfg, const uint8_t* ok_commit, const uin
   return 0;
 }
 
-int launch_prove_last(const LaunchCfg& cfg, const uint8_t* done, void* t_out, void* z_out, uint32_t t_rows, uint32_t z_rows, uint32_t N,
-                      uint8_t* ok, uint64_t B, uint32_t width) {
+template <class C>
+int launch_prove_last(const LaunchCfg& cfg, const uint8_t* done, C* t_out, C* z_out, uint32_t t_rows, uint32_t z_rows, uint32_t N,
+                      uint8_t* ok, uint64_t B) {
   if (B == 0) return 0;
-  return with_width(width, [&](auto t) -> int {
-    using T = decltype(t);
-    hipLaunchKernelGGL(prove_last_kernel<T>, dim3(entry_grid(B, cfg.num_cus)), dim3(256), 0, (hipStream_t)cfg.stream, done, (int4*)t_out,
-                       (int4*)z_out, quads_of(t_rows, N, width), quads_of(z_rows, N, width), ok, B);
-    RZK_LAUNCH_CHECK();
-    if (cfg.launched) *cfg.launched = std::string("prove_last_kernel") + width_mark<T>();
-    return 0;
-  });
+  hipLaunchKernelGGL(prove_last_kernel<C>, dim3(entry_grid(B, cfg.num_cus)), dim3(256), 0, (hipStream_t)cfg.stream, done, (int4*)t_out,
+                     (int4*)z_out, quads_of<C>(t_rows, N), quads_of<C>(z_rows, N), ok, B);
+  RZK_LAUNCH_CHECK();
+  if (cfg.launched) *cfg.launched = std::string("prove_last_kernel") + width_mark<C>();
+  return 0;
 }
+RZK_BOTH_WIDTHS(launch_prove_last)
 
 }  // namespace rzk

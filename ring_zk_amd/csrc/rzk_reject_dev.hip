@@ -19,12 +19,6 @@
 
 namespace rzk {
 
-#define RZK_LAUNCH_CHECK()                      \
-  do {                                          \
-    hipError_t e_ = hipGetLastError();          \
-    if (e_ != hipSuccess) return (int)e_;       \
-  } while (0)
-
 namespace {
 
 constexpr uint32_t kWavesPerBlock = 4;

@@ -67,7 +67,7 @@ int sample_uniform_keyed_dev(rzk_ctx* c, const uint8_t* nonce, uint32_t stream, 
   if (c && count == 0) return RZK_OK;
   if (!c || !out || bound == 0 || bound > (uint64_t)(c->q - 1) / 2) return RZK_E_ARG;
   return keyed_sample(c, nonce, out, count, [&](const LaunchCfg& cfg, const uint32_t* sk) {
-    return launch_sample_uniform_chacha(cfg, launch_addr(out), count, c->N, sk, stream, (uint32_t)bound, sizeof(C));
+    return launch_sample_uniform_chacha(cfg, out, count, c->N, sk, stream, (uint32_t)bound);
   });
 }
 RZK_BOTH_WIDTHS(sample_uniform_keyed_dev)
@@ -77,7 +77,7 @@ int sample_gauss_keyed_dev(rzk_ctx* c, const uint8_t* nonce, uint32_t stream, do
   if (c && count == 0) return RZK_OK;
   if (!c || !out || !(sigma > 0.0) || sigma > 67108864.0) return RZK_E_ARG;   // as rzk_sample_gauss_dev
   return keyed_sample(c, nonce, out, count, [&](const LaunchCfg& cfg, const uint32_t* sk) {
-    return launch_sample_gauss_chacha(cfg, launch_addr(out), count, c->N, sk, stream, sigma, sizeof(C));
+    return launch_sample_gauss_chacha(cfg, out, count, c->N, sk, stream, sigma);
   });
 }
 RZK_BOTH_WIDTHS(sample_gauss_keyed_dev)
@@ -89,7 +89,7 @@ int sample_dgauss_keyed_dev(rzk_ctx* c, const uint8_t* nonce, uint32_t stream, u
   if (!c || !out || sigma == 0 || sigma > kDgaussSigmaMax || count % c->N != 0) return RZK_E_ARG;
   const size_t npoly = count / c->N;
   return keyed_sample(c, nonce, out, npoly, [&](const LaunchCfg& cfg, const uint32_t* sk) {
-    return launch_sample_dgauss_chacha(cfg, launch_addr(out), npoly, c->N, sk, stream, sigma, sizeof(C));
+    return launch_sample_dgauss_chacha(cfg, out, npoly, c->N, sk, stream, sigma);
   });
 }
 RZK_BOTH_WIDTHS(sample_dgauss_keyed_dev)
@@ -99,7 +99,7 @@ int sample_challenge_keyed_dev(rzk_ctx* c, const uint8_t* nonce, uint32_t stream
   if (c && count == 0) return RZK_OK;
   if (!c || !out) return RZK_E_ARG;
   return keyed_sample(c, nonce, out, count, [&](const LaunchCfg& cfg, const uint32_t* sk) {
-    return launch_sample_challenge_chacha(cfg, launch_addr(out), count, c->N, sk, stream, c->kappa, sizeof(C));
+    return launch_sample_challenge_chacha(cfg, out, count, c->N, sk, stream, c->kappa);
   });
 }
 RZK_BOTH_WIDTHS(sample_challenge_keyed_dev)

@@ -25,12 +25,6 @@
 
 namespace rzk {
 
-#define RZK_LAUNCH_CHECK()                      \
-  do {                                          \
-    hipError_t e_ = hipGetLastError();          \
-    if (e_ != hipSuccess) return (int)e_;       \
-  } while (0)
-
 namespace {
 
 constexpr int kWaves = 4;   // wavefronts per workgroup of the per-polynomial kernels

@@ -20,12 +20,6 @@
 
 namespace rzk {
 
-#define RZK_LAUNCH_CHECK()                      \
-  do {                                          \
-    hipError_t e_ = hipGetLastError();          \
-    if (e_ != hipSuccess) return (int)e_;       \
-  } while (0)
-
 namespace {
 
 constexpr uint32_t kRing = 64;               // ring entries per row (power of two, >= 15 + 34)
