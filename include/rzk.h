@@ -819,12 +819,21 @@ int rzk_prof_read_kernels(rzk_ctx* ctx, char* buf, size_t cap, size_t* needed);
  *                          teams, N <= 1024)
  *   RZK_CRT2_SHORT=0       unit kernels: the two-prime reconstruction with two reductions mod q and a 64-bit sign test
  *                          (default 1: digit compares and one reduction, crt2_zq_short)
- *   RZK_TW_LDS=0           unit_kernel at N = 1024 (one-wavefront teams, 64- and 32-bit slabs): phase 2 of every transform reads its
- *                          per-lane twiddles from the global tables (default 1 at N = 1024: from an LDS image the workgroup's 256
- *                          threads copy once at kernel entry, entries 16 .. 255 of the 3 x 2 tables in 256 words each, 6 144 bytes
- *                          behind the four teams' 4 x 8 320: 39 424 bytes per workgroup, four workgroups = 4 waves per SIMD in
- *                          157 696 of a CU's 163 840 bytes; the table is neither requested nor filled with 0).  No effect at other
- *                          ring degrees or on the other kernels; see DESIGN.md §6
+ *   RZK_TW_LDS=0|1|2       unit_kernel at N = 1024 (one-wavefront teams, 64- and 32-bit slabs): where the per-lane (vector) twiddles of
+ *                          every transform come from.  All three report the same kernel names and give the same bytes.
+ *                          0: the global tables.
+ *                          1 (default at N = 1024): phase 2 from an LDS image the workgroup's 256 threads copy once at kernel
+ *                          entry, entries 16 .. 255 of the 3 x 2 tables in 256 words each, 6 144 bytes behind the four teams'
+ *                          4 x 8 320: 39 424 bytes per workgroup, four workgroups = 4 waves per SIMD in 157 696 of a CU's
+ *                          163 840 bytes; phase 3 from the global tables, the forward transform asking for them where its
+ *                          phase 2 begins.
+ *                          2: phases 2 and 3 from LDS.  Sixteen teams per workgroup, one workgroup per CU under the grid cap;
+ *                          its 1024 threads copy entries 16 .. 1023 of the six tables once (1024 words each, 24 576 bytes
+ *                          behind 16 x 8 320): the same 157 696 bytes per CU and 4 waves per SIMD.  The teams stay independent
+ *                          after the one barrier behind the fill.  Measured slower than 1 (the workgroup shape costs more
+ *                          than the image gains), so not the default.
+ *                          Values above 2 read as 2, negative ones as 0.  No effect at other ring degrees or on the other
+ *                          kernels; see DESIGN.md §6
  *   RZK_GRID_CUS=<c>       testing: size every grid cap, and the scratch behind it, for c CUs instead of the device's count
  *                          (clamped to 1 .. multiProcessorCount; 0 or a non-number gives 1), so that small batches make
  *                          several grid-stride trips.  The batch at which RZK_UPT's default switches to all units per

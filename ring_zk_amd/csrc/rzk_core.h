@@ -245,9 +245,63 @@ struct Tw2Img {
   }
 };
 
+// ---- phase-3 twiddles as an LDS image (N = 1024, one-wavefront teams) ----------------------------------------------
+// Phase 3 of either direction reads the rest of the vector twiddles, entries [2^(2 LE), N) of a prime's table: stage sq
+// takes the E >> (R3 - sq) entries 2^(2 LE + sq) + lane (E >> (R3 - sq)) + k.  At LE = 4, R3 = 2 these are the 768 entries
+// 256 .. 1023, and a lane needs 4 + 8 = 12 of them.  Re-ordered so that ONE per-lane base (16 bytes x lane) plus
+// compile-time offsets addresses all of them with three 16-byte reads:
+//     block 0 (words   0 .. 255): [lane][4] = stage 0 k = 0 .. 3      (table order: entry 256 + w)
+//     block 1 (words 256 .. 511): [lane][4] = stage 1 k = 0 .. 3
+//     block 2 (words 512 .. 767): [lane][4] = stage 1 k = 4 .. 7
+// 768 words per table, no pads.  Bank picture (ds_read_b128: banks (addr / 4) mod 64, four groups of 16 lanes): the 16
+// lanes of a group read 16 consecutive 16-byte slots = 64 consecutive words: every bank once, conflict-free.  (Stage 1 in
+// table order, 8 lane + k, would put lane and lane + 8 on the same banks: 2-way.)
+template <int LOGN, int LL = 6>
+struct Tw3Img {
+  using G = Geo<LOGN, LL>;
+  static constexpr bool kFits = LL == 6 && G::LE == 4 && G::R3 == 2;   // the layout above
+  static constexpr int FIRST = 1 << (2 * G::LE), END = 1 << LOGN;      // table entries phase 3 may touch: [FIRST, END)
+  static constexpr int WORDS = 768;                                    // per table
+  RZK_HD static int base(int lane) { return lane << 2; }
+  // register slot (= word inside the lane's three quads, in block order) of twiddle k of stage sq
+  static constexpr int slot(int sq, int k) { return sq == 0 ? k : 4 + k; }
+  // table entry that image word w holds
+  RZK_HD static int src(int w) {
+    const int blk = w >> 8, lane = (w >> 2) & 63, c = w & 3;
+    if (blk == 0) return (1 << (2 * G::LE)) + (lane << 2) + c;
+    return (1 << (2 * G::LE + 1)) + (lane << 3) + ((blk - 1) << 2) + c;
+  }
+  // the lane's 12 twiddles: three 16-byte reads at compile-time offsets from one base
+  RZK_HD static void load(uint32_t* w, const uint32_t* img, int lane) {
+    const uint32_t* row = img + base(lane);
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+      const uint4 v = *reinterpret_cast<const uint4*>(row + 256 * b);
+      w[4 * b] = v.x, w[4 * b + 1] = v.y, w[4 * b + 2] = v.z, w[4 * b + 3] = v.w;
+#else
+      for (int c = 0; c < 4; ++c) w[4 * b + c] = row[256 * b + c];
+#endif
+    }
+  }
+};
+// The complete vector-twiddle set of a table, one image of 1024 words: the phase-2 image, then the phase-3 image.  One
+// workgroup of 1024 threads (sixteen one-wavefront teams) copies one word per thread and table.
+template <int LOGN, int LL = 6>
+struct TwAllImg {
+  using I2 = Tw2Img<LOGN, LL>;
+  using I3 = Tw3Img<LOGN, LL>;
+  static constexpr bool kFits = I2::kFits && I3::kFits;
+  static constexpr int P3 = I2::WORDS;                 // where the phase-3 image begins
+  static constexpr int WORDS = I2::WORDS + I3::WORDS;  // per table
+  static constexpr int TABLES = I2::TABLES;
+  RZK_HD static int src(int w) { return w < P3 ? I2::src(w) : I3::src(w - P3); }
+};
+
 // ---- forward transform, register phases ----------------------------------------------------------------
 // tw: Montgomery-form table, tw[m + i] = psi^{bitrev(m+i)} * R mod p (first N entries used).
-// Phase 2 takes its table through a pointer of its own: the global table (IMG = false), or the prime's Tw2Img image.
+// Phases 2 and 3 take their tables through pointers of their own: the global table (IMG = false), or the prime's Tw2Img /
+// Tw3Img image.
 template <int LOGN, int LL = 6>
 RZK_HD void fwd_phase1(uint32_t* x, const uint32_t* tw, const PrimeConsts& pc) {
   using G = Geo<LOGN, LL>;
@@ -281,9 +335,13 @@ RZK_HD void fwd_phase2(uint32_t* x, int lane, const uint32_t* tw, const PrimeCon
     }
   }
 }
-template <int LOGN, int LL = 6>
+template <int LOGN, int LL = 6, bool IMG = false>
 RZK_HD void fwd_phase3(uint32_t* x, int lane, const uint32_t* tw, const PrimeConsts& pc) {
   using G = Geo<LOGN, LL>;
+  using I = Tw3Img<LOGN, LL>;
+  static_assert(!IMG || I::kFits, "the LDS image is laid out for N = 1024 on one wavefront");
+  uint32_t wi[16];
+  if (IMG) I::load(wi, tw, lane);
 #pragma unroll
   for (int sq = 0; sq < G::R3; ++sq) {
     const int sh = G::R3 - sq;            // idx = 2^s + (j >> sh)
@@ -292,15 +350,50 @@ RZK_HD void fwd_phase3(uint32_t* x, int lane, const uint32_t* tw, const PrimeCon
 #pragma unroll
     for (int c = 0; c < G::E; ++c) {
       if (c & half) continue;
-      bfly_fwd(x[c], x[c + half], twl[c >> sh], pc);
+      bfly_fwd(x[c], x[c + half], IMG ? wi[I::slot(sq, c >> sh) & 15] : twl[c >> sh], pc);
+    }
+  }
+}
+
+// Phase 3 with the lane's twiddles already in registers, in Tw3Img slot order (which is table order: stage 0's four
+// entries, then stage 1's eight): fwd_phase3_request asks the global table for them, three 16-byte loads that the caller
+// may issue long before the butterflies (wave_fwd, RZK_FWD3_EARLY).
+template <int LOGN, int LL = 6>
+RZK_HD void fwd_phase3_request(uint32_t* wi, int lane, const uint32_t* tw) {
+  using G = Geo<LOGN, LL>;
+  using I = Tw3Img<LOGN, LL>;
+  static_assert(I::kFits, "N = 1024 on one wavefront");
+#pragma unroll
+  for (int sq = 0; sq < G::R3; ++sq) {
+    const int n = G::E >> (G::R3 - sq);
+#pragma unroll
+    for (int k = 0; k < n; ++k) wi[I::slot(sq, k)] = tw[(1 << (2 * G::LE + sq)) + lane * n + k];
+  }
+}
+template <int LOGN, int LL = 6>
+RZK_HD void fwd_phase3_regs(uint32_t* x, const uint32_t* wi, const PrimeConsts& pc) {
+  using G = Geo<LOGN, LL>;
+  using I = Tw3Img<LOGN, LL>;
+#pragma unroll
+  for (int sq = 0; sq < G::R3; ++sq) {
+    const int sh = G::R3 - sq;
+    const int half = 1 << (sh - 1);
+#pragma unroll
+    for (int c = 0; c < G::E; ++c) {
+      if (c & half) continue;
+      bfly_fwd(x[c], x[c + half], wi[I::slot(sq, c >> sh) & 15], pc);
     }
   }
 }
 
 // ---- inverse transform, register phases (mirror image; tw = psi^{-bitrev} * R) -------------------------------
-template <int LOGN, int LL = 6>
+template <int LOGN, int LL = 6, bool IMG = false>
 RZK_HD void inv_phase3(uint32_t* x, int lane, const uint32_t* tw, const PrimeConsts& pc) {
   using G = Geo<LOGN, LL>;
+  using I = Tw3Img<LOGN, LL>;
+  static_assert(!IMG || I::kFits, "the LDS image is laid out for N = 1024 on one wavefront");
+  uint32_t wi[16];
+  if (IMG) I::load(wi, tw, lane);
 #pragma unroll
   for (int sq = G::R3 - 1; sq >= 0; --sq) {
     const int sh = G::R3 - sq;
@@ -309,7 +402,7 @@ RZK_HD void inv_phase3(uint32_t* x, int lane, const uint32_t* tw, const PrimeCon
 #pragma unroll
     for (int c = 0; c < G::E; ++c) {
       if (c & half) continue;
-      bfly_inv(x[c], x[c + half], twl[c >> sh], pc);
+      bfly_inv(x[c], x[c + half], IMG ? wi[I::slot(sq, c >> sh) & 15] : twl[c >> sh], pc);
     }
   }
 }

@@ -18,7 +18,7 @@ int fail(rzk_ctx* c, int code, const char* msg) {
 
 LaunchCfg cfg_of(rzk_ctx* c) {
   (void)hipSetDevice(c->device);   // the calling thread may have another current device
-  return LaunchCfg{(void*)c->stream, c->num_cus, c->pair_poly ? 1 : 0, c->unit_io ? 1 : 0, c->shift_bytes ? 1 : 0, c->tw_lds ? 1 : 0};
+  return LaunchCfg{(void*)c->stream, c->num_cus, c->pair_poly ? 1 : 0, c->unit_io ? 1 : 0, c->shift_bytes ? 1 : 0, c->tw_lds};
 }
 
 int arena_reserve(rzk_ctx* c, Arena& a, size_t bytes) {
@@ -108,9 +108,11 @@ const Knob kKnobs[] = {
     {"RZK_BLOCK_MIN_LOGN", &rzk_ctx::block_min_logn, "row blocks from this log2 N on (12: never)"},
     {"RZK_ROT_LAST", &rzk_ctx::rot_last, "0: unit_kernel evaluates every row's rotation terms first, through its scratch line"},
     {"RZK_DOT2", &rzk_ctx::dot2, "0: unit_kernel reduces each of a two-product row's products on its own"},
-    {"RZK_TW_LDS", &rzk_ctx::tw_lds, "0: unit_kernel at N = 1024 reads its phase-2 twiddles from the global tables, not from an LDS image per workgroup"},
+    {"RZK_TW_LDS", Knob::Int, &rzk_ctx::tw_lds, "unit_kernel at N = 1024: 0 twiddles from the global tables, 1 phase 2 from an LDS image, 2 phases 2 and 3 (16-team workgroups)"},
     {"RZK_CRT2_SHORT", &rzk_ctx::crt2_short, "0: two-prime reconstruction with two reductions mod q (crt2_zq)"},
 };
+
+constexpr int kTwLdsDefault = 1;   // RZK_TW_LDS at N = 1024 (2 did not pass its A/B — commit gains, verify loses more)
 
 // needs num_cus, group_max, unit_io and tw_lds at their defaults
 void read_knobs(rzk_ctx* c) {
@@ -185,8 +187,9 @@ int rzk_ctx_create(rzk_ctx** out, int64_t q, uint32_t N, uint32_t n, uint32_t k,
   // that small batches make several grid-stride trips; read before the first allocation sized by num_cus (the row scratch)
   c->group_max = group_max_for((int)c->logn);
   c->unit_io = c->logn == 9;
-  c->tw_lds = c->logn == 10;
+  c->tw_lds = c->logn == 10 ? kTwLdsDefault : 0;
   read_knobs(c);
+  c->tw_lds = c->tw_lds < 0 ? 0 : (c->tw_lds > 2 ? 2 : c->tw_lds);
   c->hT.diet = (c->rot_last ? DIET_ROT_LAST : 0u) | (c->crt2_short ? DIET_CRT2 : 0u);   // (RZK_DOT2 goes into the plans: plan_env)
   if ((de = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking)) != hipSuccess) {
     delete c;

@@ -105,8 +105,9 @@ struct rzk_ctx {
   bool rot_last = true;                // unit_kernel: rotation terms of single-row units after the transforms, sums in registers (RZK_ROT_LAST=0: first, through the scratch line)
   bool dot2 = true;                    // unit_kernel: two-product key rows park the transform and reduce once (RZK_DOT2=0: one reduction per product)
   bool crt2_short = true;              // two-prime reconstruction with one reduction mod q (RZK_CRT2_SHORT=0: crt2_zq)
-  bool tw_lds = false;                 // unit_kernel, one-wavefront teams: phase-2 twiddles from an LDS image per workgroup (on at N = 1024, the
-                                       // only size with the image; RZK_TW_LDS=0: from the global tables)
+  int tw_lds = 0;                      // unit_kernel, one-wavefront teams at N = 1024 (the only size with the images; RZK_TW_LDS): 0 = twiddles from the
+                                       // global tables, 1 = phase 2 from an LDS image per four-team workgroup, 2 = phases 2 and 3 from one image per
+                                       // sixteen-team workgroup
   int group_max = 1;                   // rows per group of row_group_kernel (group_max_for; RZK_GROUP_MAX overrides, tuning)
   bool use_shift = true;               // challenge products as signed rotations (shift_row_kernel) instead of transforms
   bool shift_bytes = true;             // ... of short operands as packed bytes (shift_row_kernel, N <= 1024; RZK_SHIFT_BYTES=0: words only)

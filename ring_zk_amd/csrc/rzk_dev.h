@@ -239,7 +239,7 @@ struct LaunchCfg {
   int pair_poly;  // N = 2048: two wavefronts per polynomial (PairTeam) in unit_kernel / row_kernel / row_block_kernel
   int unit_io;    // key-product programs through unit_io_kernel (operands read once) instead of unit_kernel
   int shift_bytes;   // shift_row_kernel at N <= 1024: short operands rotate as packed bytes (RZK_SHIFT_BYTES)
-  int tw_lds;     // unit_kernel at N = 1024: phase-2 twiddles from an LDS image per workgroup (RZK_TW_LDS)
+  int tw_lds;     // unit_kernel at N = 1024: 1 = phase-2 twiddles from an LDS image per workgroup, 2 = phase 3 too, sixteen teams per workgroup (RZK_TW_LDS)
   std::string* launched = nullptr;   // out: the row-program launchers write the name of the instantiation they started here
 };
 

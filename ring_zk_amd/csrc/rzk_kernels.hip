@@ -91,7 +91,8 @@ int launch_units(int logn, const LaunchCfg& cfg, const RowArgs& a, const Operand
       constexpr bool kVec = decltype(V)::value;
       switch (logn) {
         case 9: return launch_units_t<9, kVec, S>(cfg, a, ops, t);
-        case 10:   // phase-2 twiddles from LDS (RZK_TW_LDS): N = 1024, one-wavefront teams
+        case 10:   // twiddles from LDS (RZK_TW_LDS): N = 1024, one-wavefront teams; 1: phase 2, 2: phases 2 and 3 on sixteen-team workgroups
+          if (cfg.tw_lds >= 2) return launch_units_t<10, kVec, S, WaveTeamTw3>(cfg, a, ops, t);
           return cfg.tw_lds ? launch_units_t<10, kVec, S, WaveTeamTw>(cfg, a, ops, t) : launch_units_t<10, kVec, S>(cfg, a, ops, t);
         case 11:
           if (pair) return launch_units_t<11, kVec, S, PairTeam>(cfg, a, ops, t);

@@ -64,7 +64,9 @@ static int with_flag(bool v, F&& f) {
 static inline const char* tf(bool v) { return v ? "true" : "false"; }
 template <class TM>
 static std::string team_arg() {   // (the teams with the twiddle image report as the teams they derive from)
-  return std::is_same<TM, WaveTeam>::value || std::is_same<TM, WaveTeamTw>::value ? std::string() : std::string(", ") + TM::kName;
+  return std::is_same<TM, WaveTeam>::value || std::is_same<TM, WaveTeamTw>::value || std::is_same<TM, WaveTeamTw3>::value
+             ? std::string()
+             : std::string(", ") + TM::kName;
 }
 
 // ---- unit kernels ------------------------------------------------------------------------------------------------------
@@ -81,7 +83,8 @@ constexpr size_t team_lds_words() {
 }
 template <int LOGN, class TM>
 constexpr size_t block_tw_words() {
-  return TeamTwLds<TM>::value ? (size_t)Tw2Img<LOGN, TM::LL>::TABLES * Tw2Img<LOGN, TM::LL>::WORDS : 0;
+  using I = typename TeamTwImg<LOGN, TM>::type;
+  return TeamTwLds<TM>::value ? (size_t)I::TABLES * I::WORDS : 0;
 }
 // bytes per workgroup of unit_kernel (and, for the teams without the image, row_kernel) / of unit_io_kernel
 template <int LOGN, class TM, bool HAS_SHIFT>
@@ -92,11 +95,16 @@ template <int LOGN, class TM>
 constexpr size_t unit_io_lds_bytes() {   // per team: slab + parking buffers
   return TM::kTeamsPerBlock * (size_t)IoCfg<LOGN, TM::LL>::WORDS * sizeof(uint32_t);
 }
-// workgroups per CU under the grid cap: at most num_cus * 32 team lines of scratch; every team walks its tasks with a grid stride
+// workgroups per CU under the grid cap: at most num_cus * 32 team lines of scratch; every team walks its tasks with a grid stride.
+// A sixteen-team workgroup is all a CU holds (LDS), and a second one would only start when all sixteen teams of the first
+// are done: one per CU, so that every team fills its image once and walks on.
 template <class TM>
 constexpr int unit_blocks_per_cu() {
-  return TM::LL == 6 ? 32 / TM::kTeamsPerBlock : 8;
+  return TM::LL == 6 ? (TM::kTeamsPerBlock >= 16 ? 1 : 32 / TM::kTeamsPerBlock) : 8;
 }
+static_assert(unit_blocks_per_cu<WaveTeam>() * WaveTeam::kTeamsPerBlock <= 32 && unit_blocks_per_cu<WaveTeamTw3>() * WaveTeamTw3::kTeamsPerBlock <= 32 &&
+                  unit_blocks_per_cu<WaveTeam32Tw3>() * WaveTeam32Tw3::kTeamsPerBlock <= 32,
+              "row_scratch_words: 32 team lines per CU");
 
 template <int LOGN, bool HAS_VEC, bool HAS_SHIFT, class TM = WaveTeam>
 static int launch_units_t(const LaunchCfg& cfg, const RowArgs& a, const Operands& ops, const UnitTasks& t) {
@@ -193,6 +201,8 @@ static_assert(unit_lds_bytes<10, WaveTeam, false>() == 33280 && unit_lds_bytes<1
 static_assert(unit_lds_bytes<10, WaveTeam32, false>() == 33280 && unit_lds_bytes<10, WaveTeam32, true>() == 33280, "");
 static_assert(unit_lds_bytes<10, WaveTeamTw, false>() == 39424 && unit_lds_bytes<10, WaveTeamTw, true>() == 39424, "");   // 4 x 8 320 + 6 144
 static_assert(unit_lds_bytes<10, WaveTeam32Tw, false>() == 39424 && unit_lds_bytes<10, WaveTeam32Tw, true>() == 39424, "");
+static_assert(unit_lds_bytes<10, WaveTeamTw3, false>() == 157696 && unit_lds_bytes<10, WaveTeamTw3, true>() == 157696, "");   // 16 x 8 320 + 24 576
+static_assert(unit_lds_bytes<10, WaveTeam32Tw3, false>() == 157696 && unit_lds_bytes<10, WaveTeam32Tw3, true>() == 157696, "");
 static_assert(unit_lds_bytes<11, WaveTeam, false>() == 66560, "");   // (above 48 KiB: the opt-in branch; no rotation terms on one wavefront)
 static_assert(unit_lds_bytes<11, PairTeam, false>() == 16640 && unit_lds_bytes<11, PairTeam, true>() == 18448, "");
 // unit_io_kernel
@@ -214,5 +224,8 @@ RZK_PIN_SHIFT(11, PairTeam, false, 18448, 64);
 #undef RZK_PIN_SHIFT
 // N = 1024, four one-wavefront teams with the twiddle image: four workgroups (4 waves per SIMD) in 157 696 of the CU's 163 840
 static_assert(4 * unit_lds_bytes<10, WaveTeamTw, true>() <= 160 * 1024, "the twiddle images must leave room for four workgroups per CU");
+// ... and sixteen teams with every vector twiddle in LDS: one workgroup, the same 4 waves per SIMD in the same 157 696 B
+static_assert(unit_lds_bytes<10, WaveTeamTw3, true>() == 4 * unit_lds_bytes<10, WaveTeamTw, true>() && (WaveTeamTw3::kTeamsPerBlock << 6) == 1024,
+              "the full image: one 1024-thread workgroup in the LDS of four 256-thread ones");
 
 }  // namespace rzk

@@ -84,7 +84,7 @@ unsigned stream_grid(uint64_t npairs, int num_cus) {
 // caller takes the convert path).
 static_assert(unit_lds_bytes<10, WaveTeam32Tw, true>() <= 48 * 1024 && unit_io_lds_bytes<10, WaveTeam32>() <= 48 * 1024 &&
                   unit_io_lds_bytes<9, WaveTeam32>() <= 48 * 1024 && shift_launch<10, WaveTeam32, true>().lds <= 48 * 1024,
-              "the 32-bit instantiations stay below the opt-in for large dynamic LDS");
+              "the 32-bit instantiations with four teams per workgroup stay below the opt-in for large dynamic LDS");
 
 int launch_units32(int logn, const LaunchCfg& cfg, const RowArgs& a, const Operands& ops, const UnitShape& u, uint64_t batch) {
   UnitTasks t;
@@ -101,6 +101,7 @@ int launch_units32(int logn, const LaunchCfg& cfg, const RowArgs& a, const Opera
     switch (logn) {
       case 9: return launch_units_t<9, false, S, WaveTeam32>(cfg, a, ops, t);
       case 10:
+        if (cfg.tw_lds >= 2) return launch_units_t<10, false, S, WaveTeam32Tw3>(cfg, a, ops, t);   // (the one instantiation here with the large-LDS opt-in)
         return cfg.tw_lds ? launch_units_t<10, false, S, WaveTeam32Tw>(cfg, a, ops, t) : launch_units_t<10, false, S, WaveTeam32>(cfg, a, ops, t);
     }
     return -1;

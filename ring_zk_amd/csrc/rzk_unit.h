@@ -127,7 +127,7 @@ __device__ __forceinline__ bool inverse_fold_global(int pi, int np, uint32_t* ac
 #pragma unroll
     for (int g = 0; g < E / 4; ++g) sb[g] = B4[G::own4(li, g)];
   }
-  wave_inv<LOGN, TM, TeamTwLds<TM>::value>(acc, li, lds, twi, pc, tw2i);
+  wave_inv<LOGN, TM, TeamTwLds<TM>::value, TeamTw3Lds<TM>::value>(acc, li, lds, twi, pc, tw2i);
   if (!EARLY && pi >= 1) {
 #pragma unroll
     for (int g = 0; g < E / 4; ++g) sa[g] = A4[G::own4(li, g)];
@@ -251,8 +251,9 @@ __device__ __forceinline__ void finish_row(uint32_t* u, const Program* __restric
 }
 
 // Workgroups: four independent one-wavefront teams (16-wave workgroups whose SIMD mates ranked each other through an LDS
-// table for exact fairness measured slower in round 2 — verify rows 90 vs 81 us — and were removed), or ONE
-// two-wavefront team (PairTeam, N = 2048).  Teams of two are compiled for 4 waves per SIMD (<= 128 VGPRs: 16
+// table for exact fairness measured slower in round 2 — verify rows 90 vs 81 us — and were removed), sixteen of them
+// around one image of every vector twiddle (WaveTeamTw3, RZK_TW_LDS=2: off by default, the shape costs more than the image
+// gains), or ONE two-wavefront team (PairTeam, N = 2048).  Teams of two are compiled for 4 waves per SIMD (<= 128 VGPRs: 16
 // coefficients per thread, the budget of the N = 1024 kernels).
 // The coefficient type of the launch's slabs comes with the team (TeamCoef, rzk_wave.h): int64_t for every team of
 // rzk_kernels.hip, int32_t for WaveTeam32, which rzk_slab32_dev.hip instantiates.
@@ -277,8 +278,9 @@ unit_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__ wp
   // Teams with the phase-2 twiddles in LDS (TeamTwLds): the images of every prime and direction lie behind the teams'
   // slabs, are copied from the global tables once per workgroup, and are read-only from the barrier on, over every
   // grid-stride trip.  Nothing else in the kernel meets at a workgroup barrier: the teams stay independent.
-  constexpr bool TWL = TeamTwLds<TM>::value;
-  using TWI = Tw2Img<LOGN, TM::LL>;
+  // Teams with every vector twiddle in LDS (TeamTw3Lds): the same, with the phase-3 entries behind each table's phase-2 words.
+  constexpr bool TWL = TeamTwLds<TM>::value, TW3 = TeamTw3Lds<TM>::value;
+  using TWI = typename TeamTwImg<LOGN, TM>::type;
   const uint32_t* tw2_img = smem + WPB * (G::LDS_WORDS + N);
   if (TWL) {
     static_assert(!TWL || (TWI::kFits && WPB * (G::LDS_WORDS + N) % 4 == 0 && (WPB << TM::LL) == TWI::WORDS),
@@ -415,7 +417,7 @@ unit_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__ wp
             }
             {
               RZK_T0();
-              wave_fwd<LOGN, TM, TWL>(x, ln, lds, twf, pc, tw2f);
+              wave_fwd<LOGN, TM, TWL, TW3>(x, ln, lds, twf, pc, tw2f);
               RZK_T1(t_fwd);
             }
             if (!EARLY && want_key) {
@@ -433,7 +435,7 @@ unit_kernel(const Program* __restrict__ prog, const WaveProgram* __restrict__ wp
               bool unused_below = true;
               load_lift<LOGN, TM, LL_FUSED, C>(x, operand_ptr<C>(ops, im.a_op, im.a_off, b, bo, N), ln, pc, first, na, false, 0, unused_below, qhalf,
                               trusted, fault);
-              wave_fwd<LOGN, TM, TWL>(x, ln, lds, twf, pc, tw2f);
+              wave_fwd<LOGN, TM, TWL, TW3>(x, ln, lds, twf, pc, tw2f);
               if (first) boundA = bound_fma(na, nb, boundA);
             } else if (first) {
               if (im.keyA != kNoKey) boundA = bound_fma((float)key_l2[im.keyA], nb, boundA);

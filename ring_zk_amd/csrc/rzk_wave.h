@@ -179,6 +179,32 @@ template <> struct TeamCoef<WaveTeam32Tw> { using type = int32_t; };
 template <class TM> struct TeamTwLds { static constexpr bool value = false; };
 template <> struct TeamTwLds<WaveTeamTw> { static constexpr bool value = true; };
 template <> struct TeamTwLds<WaveTeam32Tw> { static constexpr bool value = true; };
+// ... and with ALL vector twiddles in LDS, phase 3 included (TwAllImg, rzk_core.h; RZK_TW_LDS=2).  The 24 KiB of images do not
+// fit beside a four-team workgroup's slabs four times per CU; they fit once: sixteen teams per workgroup, one workgroup per
+// CU, the same 4 waves per SIMD and the same 157 696 B of LDS per CU as four workgroups of WaveTeamTw.  The teams are as
+// independent as ever (no rank table, no barrier after the fill).
+struct WaveTeamTw3 : WaveTeam {
+  static constexpr int kTeamsPerBlock = 16;
+};
+struct WaveTeam32Tw3 : WaveTeam32 {
+  static constexpr int kTeamsPerBlock = 16;
+};
+template <> struct TeamCoef<WaveTeam32Tw3> { using type = int32_t; };
+template <> struct TeamTwLds<WaveTeamTw3> { static constexpr bool value = true; };
+template <> struct TeamTwLds<WaveTeam32Tw3> { static constexpr bool value = true; };
+#ifndef RZK_TW3_IMAGE
+#define RZK_TW3_IMAGE 1   // 0 (tuning build): the sixteen-team workgroups fill the full image, but phase 3 reads the global tables as
+#endif                    // under RZK_TW_LDS=1: the workgroup shape alone, without the phase-3 image
+#ifndef RZK_FWD3_EARLY
+#define RZK_FWD3_EARLY 1  // under RZK_TW_LDS=1 the forward transform requests its phase-3 twiddles where phase 2 begins (0: tuning build, where
+#endif                    // phase 3 begins, seven instructions before the block ends)
+template <class TM> struct TeamTw3Lds { static constexpr bool value = false; };
+template <> struct TeamTw3Lds<WaveTeamTw3> { static constexpr bool value = RZK_TW3_IMAGE != 0; };
+template <> struct TeamTw3Lds<WaveTeam32Tw3> { static constexpr bool value = RZK_TW3_IMAGE != 0; };
+// the image a team's workgroup keeps behind its slabs (meaningful where TeamTwLds<TM>::value)
+template <int LOGN, class TM> struct TeamTwImg { using type = Tw2Img<LOGN, TM::LL>; };
+template <int LOGN> struct TeamTwImg<LOGN, WaveTeamTw3> { using type = TwAllImg<LOGN, 6>; };
+template <int LOGN> struct TeamTwImg<LOGN, WaveTeam32Tw3> { using type = TwAllImg<LOGN, 6>; };
 struct PairTeam {
   static constexpr const char* kName = "PairTeam";   // as a profiler prints it (launchers, rzk_kernels.hip)
   static constexpr int LL = 7;
@@ -275,7 +301,8 @@ struct BlockPairTeam {
 };
 
 // tw2: the table phase 2 reads.  Left out, it is the global table tw; with IMG it is the prime's LDS image (Tw2Img).
-template <int LOGN, class TM = WaveTeam, bool IMG = false>
+// IMG3: that image is a TwAllImg, and phase 3 reads its twiddles from the part behind the phase-2 words.
+template <int LOGN, class TM = WaveTeam, bool IMG = false, bool IMG3 = false>
 __device__ __forceinline__ void wave_fwd(uint32_t* x, int lane, uint32_t* lds, const uint32_t* __restrict__ tw,
                                          const PrimeConsts& pc, const uint32_t* __restrict__ tw2 = nullptr) {
   constexpr int LL = TM::LL;
@@ -284,19 +311,24 @@ __device__ __forceinline__ void wave_fwd(uint32_t* x, int lane, uint32_t* lds, c
   TM::sync();
   lds_get_p2<LOGN, LL>(x, lane, lds);
   TM::sync();
+  constexpr bool EARLY3 = RZK_FWD3_EARLY && IMG && !IMG3;   // phase 2 from LDS, phase 3 from the global table: ask for it now
+  uint32_t w3[16];
+  if constexpr (EARLY3) fwd_phase3_request<LOGN, LL>(w3, lane, tw);
   fwd_phase2<LOGN, LL, IMG>(x, lane, IMG ? tw2 : tw, pc);
   lds_put_p2<LOGN, LL>(x, lane, lds);
   TM::sync();
   lds_get_p3<LOGN, LL>(x, lane, lds);
   TM::sync();
-  fwd_phase3<LOGN, LL>(x, lane, tw, pc);
+  if constexpr (EARLY3) fwd_phase3_regs<LOGN, LL>(x, w3, pc);
+  else fwd_phase3<LOGN, LL, IMG3>(x, lane, IMG3 ? tw2 + TwAllImg<LOGN, LL>::P3 : tw, pc);
 }
 
-template <int LOGN, class TM = WaveTeam, bool IMG = false>
+template <int LOGN, class TM = WaveTeam, bool IMG = false, bool IMG3 = false>
 __device__ __forceinline__ void wave_inv(uint32_t* x, int lane, uint32_t* lds, const uint32_t* __restrict__ tw,
                                          const PrimeConsts& pc, const uint32_t* __restrict__ tw2 = nullptr) {
   constexpr int LL = TM::LL;
-  inv_phase3<LOGN, LL>(x, lane, tw, pc);
+  static_assert(!IMG3 || IMG, "the phase-3 image lies behind the phase-2 image");
+  inv_phase3<LOGN, LL, IMG3>(x, lane, IMG3 ? tw2 + TwAllImg<LOGN, LL>::P3 : tw, pc);
   lds_put_p3<LOGN, LL>(x, lane, lds);
   TM::sync();
   lds_get_p2<LOGN, LL>(x, lane, lds);
