@@ -105,7 +105,17 @@ uint64_t rzk_verify_bound(const rzk_ctx* ctx);
 /* CommitmentKey (src/commit.rs:19-25): a = [a1;a2], (n+l)*k polynomials row-major, exactly the
  * matrix commit() assembles at src/commit.rs:109-114 (identity / zero blocks included).  The key is
  * transformed once into the NTT domain of the three auxiliary primes and kept resident in HBM;
- * entries equal to 0 or 1 are recognised and skipped / turned into plain additions. */
+ * entries equal to 0 or 1 are recognised and skipped / turned into plain additions.
+ * What a failed load leaves behind (rzk_key_load, rzk_key_load_dev, and rzk_key_generate / rzk_key_expand, which load
+ * through the same path once their polynomials are drawn):
+ *   - a load that returns RZK_E_ARG (a coefficient outside [-(q-1)/2, (q-1)/2], a NULL argument) leaves the previous key
+ *     and every later result exactly as if the call had not been made: the key is tested as a whole, on the host, before
+ *     anything of the context changes;
+ *   - so does a failure before the key has been tested: selecting the device, the device-to-host copy of
+ *     rzk_key_load_dev, drawing the polynomials of rzk_key_generate / rzk_key_expand;
+ *   - any failure after the key has been accepted (allocation, transform, digest: RZK_E_HIP ...) leaves the context
+ *     without a key: every later call that needs one returns RZK_E_STATE until a load succeeds, never a mixture of two
+ *     keys. */
 int rzk_key_load(rzk_ctx* ctx, const int64_t* a_host);
 int rzk_key_load_dev(rzk_ctx* ctx, const int64_t* a_dev);
 /* CommitmentKey::new (src/commit.rs:33-60) with the device-side sampler: a1 = [I_n | U], a2 = [0 | I_l | U],

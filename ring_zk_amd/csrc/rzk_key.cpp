@@ -1,6 +1,7 @@
 // rzk_key.cpp — the resident commitment key of a context (include/rzk.h): load, generate, expand from a seed, and the
 // FS1 digest of the loaded key.
 #include "rzk_ctx.h"
+#include "rzk_keyplan.h"
 
 namespace {
 
@@ -8,41 +9,27 @@ int fs_key_digest_dev(rzk_ctx* c, const int64_t* a_host, const int64_t* a_dev);
 
 // a_dev: the same key on the device when the caller has it there (rzk_key_load_dev), else NULL
 int key_load_impl(rzk_ctx* c, const int64_t* a_host, const int64_t* a_dev = nullptr) {
-  const uint32_t N = c->N, rows = c->n + c->l, k = c->k;
-  const size_t total = (size_t)rows * k;
-  const int64_t half = (c->q - 1) / 2;
-  c->key_class.assign(total, KC_GENERAL);
-  c->key_entry.assign(total, -1);
-  std::vector<int64_t> general;
-  std::vector<double> kinf;
-  c->n_general = 0;
-  for (size_t e = 0; e < total; ++e) {
-    const int64_t* p = a_host + e * N;
-    bool tail_zero = true;
-    long double ssq = 0.0L;
-    for (uint32_t j = 0; j < N; ++j) {
-      const int64_t v = p[j];
-      if (v > half || v < -half) return fail(c, RZK_E_ARG, "key coefficient outside the centred range");
-      if (j > 0 && v != 0) tail_zero = false;
-      ssq += (long double)v * (long double)v;
-    }
-    if (tail_zero && p[0] == 0)
-      c->key_class[e] = KC_ZERO;
-    else if (tail_zero && p[0] == 1)
-      c->key_class[e] = KC_ONE;
-    else {
-      c->key_entry[e] = (int32_t)c->n_general++;
-      general.insert(general.end(), p, p + N);
-      kinf.push_back((double)(std::sqrt(ssq) * (1.0L + 1e-6L)));   // upper bound of the entry's 2-norm (prime-count bound), still one after rounding to float
-    }
-  }
+  const uint32_t N = c->N;
+  // the host part (rzk_keyplan.h) first: a key it refuses leaves the context as it was — the previous key, its images,
+  // its digest and every cached program stay in place
+  KeyPlan kp;
+  if (plan_key_tables(a_host, (size_t)(c->n + c->l) * c->k, N, c->q, c->key_class, c->key_entry, c->n_general, kp) != kPlanOk)
+    return fail(c, RZK_E_ARG, "key coefficient outside the centred range");
+  // from here on the previous key is gone: whichever step fails below, the context is left without a key
+  c->key_loaded = false;
+  const std::vector<int64_t>& general = kp.general;
+  const std::vector<double>& kinf = kp.kinf;
   drop_programs(c);   // programs depend on the classification
-  if (c->d_key_ntt) HIPCHK(c, hipFree(c->d_key_ntt));
-  if (c->d_key_l2) HIPCHK(c, hipFree(c->d_key_l2));
-  if (c->d_key_mont) HIPCHK(c, hipFree(c->d_key_mont));
+  void* const stores[] = {c->d_key_ntt, c->d_key_l2, c->d_key_mont};
   c->d_key_ntt = nullptr;
   c->d_key_l2 = nullptr;
   c->d_key_mont = nullptr;
+  hipError_t freed = hipSuccess;   // all three are released before the first error is reported
+  for (void* p : stores) {
+    const hipError_t e = p ? hipFree(p) : hipSuccess;
+    if (freed == hipSuccess) freed = e;
+  }
+  HIPCHK(c, freed);
   if (c->n_general) {
     const size_t gbytes = general.size() * sizeof(int64_t);
     int rc = arena_reserve(c, c->stage, gbytes);
@@ -63,7 +50,6 @@ int key_load_impl(rzk_ctx* c, const int64_t* a_host, const int64_t* a_dev = null
     if (rc != RZK_OK) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));   // `general` / `kinf` are host temporaries
   }
-  c->key_loaded = false;   // until the digest of the new key is in place
   int frc = fs_key_digest_dev(c, a_host, a_dev);
   if (frc != RZK_OK) return frc;
   c->key_loaded = true;

@@ -3,7 +3,9 @@
 //   plan_driver plan CASES [full]  one JSON line per case: status, facts, path, digests of the tables in use;
 //                                  with `full` also the tables themselves
 // A case is a line  "n k l logn small rot block_min_logn use_groups group_max use_pairs slot_share_min vec_rows id var key"
-// where key is the (n+l)*k KeyClass digits in row-major order, or "-" for a context without a key.
+// where key is the (n+l)*k KeyClass digits in row-major order, or "-" for a context without a key.  An optional last field
+// gives the (n+l)*k key_entry values, comma separated, for tables that no key load numbers (tests/test_keyplan_host.py:
+// what a refused load used to leave behind); without it the general entries are numbered as rzk_key_load numbers them.
 #include <cstdio>
 #include <fstream>
 #include <memory>
@@ -111,6 +113,17 @@ int run_cases(const char* path, bool full) {
       for (char ch : key) {
         key_class.push_back((uint8_t)(ch - '0'));
         key_entry.push_back(ch - '0' == KC_GENERAL ? general++ : -1);
+      }
+      std::string given;
+      if (ss >> given) {
+        std::istringstream es(given);
+        std::string tok;
+        key_entry.clear();
+        while (std::getline(es, tok, ',')) key_entry.push_back((int32_t)std::stol(tok));
+        if (key_entry.size() != key_class.size()) {
+          std::fprintf(stderr, "%zu key_entry values for %zu entries\n", key_entry.size(), key_class.size());
+          return 2;
+        }
       }
     }
     e.key_class = key_class.data();

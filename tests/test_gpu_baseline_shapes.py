@@ -137,10 +137,12 @@ def sum_inputs(rng, P, B, V):
     return gs, xs, rs, rp, ys, yp, d
 
 
-def check_sum_cycle(torch, ctx, A, B, V, seed, device_too=True, entries=None, edges=False):
+def check_sum_cycle(torch, ctx, A, B, V, seed, device_too=True, entries=None, edges=False, recover=False):
     """Every phase of the Sum cycle vs the oracle, one tampered proof; returns nothing, asserts.  `entries`: the batch
     entries compared with the oracle (default all of them).  The modulus is the context's; `edges`: plant_edges in the
-    transformed operands g_i and x_i, and (below 2^30) the rotation sums are asserted to reach the band past 4q."""
+    transformed operands g_i and x_i, and (below 2^30) the rotation sums are asserted to reach the band past 4q.
+    `recover`: sum_recover gives the oracle's t_i, t', u at `entries` and accepts every proof (with device_too: the
+    device-pointer form gives the same bytes)."""
     P = P_of(ctx)
     q = ctx.q
     rng = np.random.default_rng(seed)
@@ -160,6 +162,17 @@ def check_sum_cycle(torch, ctx, A, B, V, seed, device_too=True, entries=None, ed
         assert np.array_equal(zs[b], zr) and np.array_equal(zp[b], zpr)
         assert O.sum_verify(P, A, zs[b], zp[b], cs[b], cp[b], gs[b], ts[b], tp[b], u[b], d[b]) == 1   # sum.rs:257-320
     assert acc.tolist() == [1] * B
+    if recover:
+        rec = ctx.sum_recover(zs, zp, cs, cp, gs, d)
+        for b in range(B) if entries is None else entries:
+            ref = O.sum_commit(P, A, gs[b], xs[b], rs[b], rp[b], ys[b], yp[b])
+            for got, want, name in zip(rec[:3], ref[2:5], ("ts", "tp", "u")):
+                assert np.array_equal(got[b], want), ("recover", name, b)
+        assert rec[3].tolist() == [1] * B
+        if device_too:
+            recd = ctx.sum_recover(*[dev(torch, a) for a in (zs, zp, cs, cp, gs, d)])
+            for got, want in zip(recd, rec):
+                assert np.array_equal(got.cpu().numpy(), want)
     # tampered proofs: a response coefficient, a t coefficient of the last summand, the masked sum u
     last = B - 1
     zst = zs.copy()

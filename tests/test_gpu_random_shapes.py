@@ -14,7 +14,7 @@ import pytest
 from oracle import oracle as O
 from ring_zk_amd import synth
 
-from test_gpu_baseline_shapes import (P_of, assert_rotation_band, check_key_products_and_open, check_sum_cycle, make_ctx,  # noqa: F401
+from test_gpu_baseline_shapes import (P_of, assert_rotation_band, check_key_products_and_open, check_sum_cycle, dev, make_ctx,  # noqa: F401
                                       plant_edges, torch_mod)
 
 pytestmark = pytest.mark.gpu
@@ -61,9 +61,11 @@ def draw_case(seed):
     return dict(N=N, n=nl, k=k, l=nl, B=B, V=V, env=env, seed=seed)
 
 
-def check_linear_cycle(ctx, A, B, seed, entries=None, edges=False):
+def check_linear_cycle(ctx, A, B, seed, entries=None, edges=False, recover=False, torch=None):
     """Linear cycle vs the oracle at `entries` (default every batch entry), the last proof tampered.  The modulus and the
-    bound b of r are the context's; `edges`: plant_edges (test_gpu_baseline_shapes) in the transformed operands g and x."""
+    bound b of r are the context's; `edges`: plant_edges (test_gpu_baseline_shapes) in the transformed operands g and x.
+    `recover`: linear_recover gives the oracle's t, t', u at `entries` and accepts every proof; `torch`: the device-pointer
+    forms of commit, response, verify (and recover) give the bytes of the host-pointer forms."""
     P = P_of(ctx)
     q = ctx.q
     N, k, l = ctx.N, ctx.k, ctx.l
@@ -90,6 +92,25 @@ def check_linear_cycle(ctx, A, B, seed, entries=None, edges=False):
         assert np.array_equal(z[b], zr) and np.array_equal(zp[b], zpr)
         assert O.linear_verify(P, A, z[b], zp[b], c[b], cp[b], g[b], t[b], tp[b], u[b], d[b]) == 1   # linear.rs:213-250
     assert acc.tolist() == [1] * B and acct.tolist() == [1] * (B - 1) + [0]
+    if recover:
+        tr, tpr, ur, accr = ctx.linear_recover(z, zp, c, cp, g, d)
+        for b in range(B) if entries is None else entries:
+            ref = O.linear_commit(P, A, g[b], x[b], r[b], rp[b], y[b], yp[b])
+            assert np.array_equal(tr[b], ref[2]) and np.array_equal(tpr[b], ref[3]) and np.array_equal(ur[b], ref[4]), ("recover", b)
+        assert accr.tolist() == [1] * B
+    if torch is not None:   # the host-pointer outputs above are the oracle's at `entries`
+        D = lambda a: dev(torch, a)   # noqa: E731
+        outs = ctx.linear_commit(D(g), D(x), D(r), D(rp), D(y), D(yp))
+        for got, want in zip(outs, (c, cp, t, tp, u, ok)):
+            assert np.array_equal(got.cpu().numpy(), want)
+        zd, zpd = ctx.linear_response(D(y), D(yp), D(r), D(rp), D(d))
+        assert np.array_equal(zd.cpu().numpy(), z) and np.array_equal(zpd.cpu().numpy(), zp)
+        accd = ctx.linear_verify(D(zt), zpd, outs[0], outs[1], D(g), outs[2], outs[3], outs[4], D(d))
+        assert accd.cpu().numpy().tolist() == [1] * (B - 1) + [0]
+        if recover:
+            rec = ctx.linear_recover(zd, zpd, outs[0], outs[1], D(g), D(d))
+            for got, want in zip(rec, (tr, tpr, ur, accr)):
+                assert np.array_equal(got.cpu().numpy(), want)
 
 
 # RZK_SWEEP_CASES / RZK_SWEEP_FIRST: a longer soak over other seeds (e.g. 400 cases from seed 1000: ~10 min on the GPU box)
