@@ -694,6 +694,74 @@ int rzk_open_prove_zk32_batch(rzk_ctx* ctx, const int32_t* x, const uint8_t nonc
 int rzk_open_prove_zk32_batch_dev(rzk_ctx* ctx, const int32_t* x, const uint8_t nonce0[16], uint32_t stream, int gauss_kind,
                                   const uint8_t* aux32, uint32_t max_rounds, int32_t* c, int32_t* t, int32_t* z, int32_t* r,
                                   uint8_t* ok, uint8_t* rounds, uint32_t* rounds_run, size_t B);
+
+/* ---- the y-only half of the Linear and Sum commit steps ("mask" calls; v14, additions only) -----------------
+ * t, t', u are the part of the commitment message that depends on the fresh y alone (linear.rs:118-129, sum.rs:145-160):
+ *   Linear   t = a1.y, t' = a1.y', u = (a2.y) (.) g - a2.y'
+ *   Sum      t_i = a1.y_i, t' = a1.y', u = sum_i (a2.y_i) (.) g_i - a2.y'
+ * c, c' (c_i, c') do not depend on y, so a prover that retries with a fresh y (the rejection step) calls these in place of
+ * the commit call.  Layouts are those of rzk_linear_commit_batch / rzk_sum_commit_batch, and t, tp, u (ts, tp, u) are byte
+ * for byte what those calls write for the same g, y, yp (gs, ys, yp).  Shape limits, V == 0 (RZK_E_ARG), NULL pointers
+ * (RZK_E_ARG) and B == 0 (a no-op) are the commit calls' rules.  There is no ok output: y carries no norm rule in the
+ * commit step.  A non-canonical input coefficient is reported as by rzk_matvec_batch[_dev]: RZK_E_ARG from the host form,
+ * the sticky input-error word from _dev; trusted-producer mode skips the test as everywhere.
+ * Routing: Linear runs the "masks only" form of its commit-row program (y is transformed once for the a1 and the a2 row)
+ * and the u rows; Sum runs three or four of the commit call's key-product and multiplier programs, on the side of
+ * the a2.(sum_i g_i y_i - y') rearrangement that the commit call takes on the same context. */
+int rzk_linear_mask_batch(rzk_ctx* ctx, const int64_t* g, const int64_t* y, const int64_t* yp, int64_t* t, int64_t* tp,
+                          int64_t* u, size_t B);
+int rzk_linear_mask_batch_dev(rzk_ctx* ctx, const int64_t* g, const int64_t* y, const int64_t* yp, int64_t* t, int64_t* tp,
+                              int64_t* u, size_t B);
+int rzk_sum_mask_batch(rzk_ctx* ctx, uint32_t V, const int64_t* gs, const int64_t* ys, const int64_t* yp, int64_t* ts,
+                       int64_t* tp, int64_t* u, size_t B);
+int rzk_sum_mask_batch_dev(rzk_ctx* ctx, uint32_t V, const int64_t* gs, const int64_t* ys, const int64_t* yp, int64_t* ts,
+                           int64_t* tp, int64_t* u, size_t B);
+
+/* ---- prover loop: the zero-knowledge Linear and Sum provers in one call (v14, additions only) ---------------
+ * The contract of rzk_open_prove_zk_batch[_dev], restated for the other two proofs; 64-bit slabs only.
+ *   Linear   (g, x) -> (c, cp, t, tp, u, z, zp, r, rp, ok, rounds)
+ *   Sum      (gs, xs), V summands -> (cs, cp, ts, tp, u, zs, zp, rs, rp, ok, rounds)
+ *   round 0   r, r' = uniform(b) [B][k][N] each (Sum: rs [B][V][k][N] under ONE nonce, then r'); y, y' Gaussian (Sum: ys
+ *             [B][V][k][N] under one nonce, then y'); two coin draws; the full rzk_linear_commit / rzk_sum_commit; d = challenge
+ *             of (c, cp, g, t, tp, u) under RZK_MSG_LINEAR_COMMITMENT, of (cp, cs, gs, tp, ts, u) with V under
+ *             RZK_MSG_SUM_COMMITMENT, and aux32; rzk_linear_response_reject / rzk_sum_response_reject with R = (2^31 - 1)^2 and
+ *             lnM = rzk_reject_lnm(11 / sqrt(m)), m = 2 (Linear), V + 1 (Sum).  live = (ok_commit == 3) & ok_hash (Linear),
+ *             (ok_commit != 0) & ok_hash (Sum); done = live & accept
+ *   retry     the live proofs without an accepted response, in ascending order, as a dense sub-batch (position = polynomial
+ *             index of the samplers): fresh y, y' and coins; r, rp, c, cp, g (rs, rp, cs, cp, gs) gathered; the mask call above
+ *             in place of the commit call; the hash; the response with its test; the accepted t, tp, u, z, zp (ts, tp, u, zs,
+ *             zp) replace the proof's, rounds[b] = the round.  x is not read again.
+ *   coin      as for Open.
+ * gauss_kind, stream, max_rounds, aux32, rounds_run: as for rzk_open_prove_zk_batch.
+ * nonces      nonce i = nonce0 + i.  The call consumes 2 + 4 * rounds_run of them: r, r'; then per round y, y', coin draw a,
+ *             coin draw b.  RZK_E_ARG, before anything is launched, when nonce0 + 2 + 4 * max_rounds leaves 128 bits.
+ * outputs     c, cp, r, rp (cs, cp, rs, rp) are written for every proof.  ok[b] = 1 iff the proof was live and accepted in round
+ *             rounds[b] < max_rounds; t, tp, u, z, zp (ts, tp, u, zs, zp) of every other proof are zero.
+ * Argument rules are Open's: gauss_kind 0 or 1, max_rounds 1 .. 255, V 1 .. 2^20 and an entry size that fits (RZK_E_ARG); no
+ * sampler key: RZK_E_STATE; every device slab 16-byte aligned (RZK_E_ARG); B == 0 is a no-op; B >= 2^32 is RZK_E_ARG.  Each
+ * refusal comes before the first launch.  A non-canonical coefficient of x or g (xs, gs) clears ok[b] and raises the sticky
+ * input-error word as in the commit calls (the host form returns RZK_E_ARG).  The _dev form synchronises the stream once per
+ * retry round (the 4-byte pending count).  The workspace's y, y', coin draws and coins, and its retry copies of the five
+ * y-dependent outputs, are zeroed on the stream whichever way the loop ends; a call that fails after round 0 was started
+ * zeroes the five y-dependent outputs and ok.  Bit-identical to fiat_shamir.linear_prove_zk / sum_prove_zk of the Python layer
+ * under the same key, stream and first nonce.  Not claimed: constant time. */
+int rzk_linear_prove_zk_batch(rzk_ctx* ctx, const int64_t* g, const int64_t* x, const uint8_t nonce0[16], uint32_t stream,
+                              int gauss_kind, const uint8_t* aux32, uint32_t max_rounds, int64_t* c, int64_t* cp, int64_t* t,
+                              int64_t* tp, int64_t* u, int64_t* z, int64_t* zp, int64_t* r, int64_t* rp, uint8_t* ok,
+                              uint8_t* rounds, uint32_t* rounds_run, size_t B);
+int rzk_linear_prove_zk_batch_dev(rzk_ctx* ctx, const int64_t* g, const int64_t* x, const uint8_t nonce0[16], uint32_t stream,
+                                  int gauss_kind, const uint8_t* aux32, uint32_t max_rounds, int64_t* c, int64_t* cp, int64_t* t,
+                                  int64_t* tp, int64_t* u, int64_t* z, int64_t* zp, int64_t* r, int64_t* rp, uint8_t* ok,
+                                  uint8_t* rounds, uint32_t* rounds_run, size_t B);
+int rzk_sum_prove_zk_batch(rzk_ctx* ctx, uint32_t V, const int64_t* gs, const int64_t* xs, const uint8_t nonce0[16],
+                           uint32_t stream, int gauss_kind, const uint8_t* aux32, uint32_t max_rounds, int64_t* cs, int64_t* cp,
+                           int64_t* ts, int64_t* tp, int64_t* u, int64_t* zs, int64_t* zp, int64_t* rs, int64_t* rp, uint8_t* ok,
+                           uint8_t* rounds, uint32_t* rounds_run, size_t B);
+int rzk_sum_prove_zk_batch_dev(rzk_ctx* ctx, uint32_t V, const int64_t* gs, const int64_t* xs, const uint8_t nonce0[16],
+                               uint32_t stream, int gauss_kind, const uint8_t* aux32, uint32_t max_rounds, int64_t* cs, int64_t* cp,
+                               int64_t* ts, int64_t* tp, int64_t* u, int64_t* zs, int64_t* zp, int64_t* rs, int64_t* rp,
+                               uint8_t* ok, uint8_t* rounds, uint32_t* rounds_run, size_t B);
+
 /* diagnostic: the loop's compaction kernel on flags the caller chose.  idx[0 .. *count) = the ascending b < B with
  * live[b] != 0 && done[b] == 0; entries of idx from *count on are not written.  live, done:[B] uint8, idx:[B] uint32 and
  * count (one uint32) are device pointers; asynchronous on the context's stream.  RZK_E_ARG for NULL pointers or B >= 2^32. */

@@ -131,6 +131,15 @@ SIGNATURES = {
                                 [_U8, _U8, C.POINTER(C.c_uint32), _SZ]),
     "rzk_open_prove_zk32_batch": (C.c_int, [_CTX, _I32, _U8, C.c_uint32, C.c_int, _U8, C.c_uint32] + [_I32] * 4 +
                                   [_U8, _U8, C.POINTER(C.c_uint32), _SZ]),
+    # v14, additions: the y-only half of the Linear / Sum commit step (g, y, yp, t, tp, u, B), Sum with V in front
+    "rzk_linear_mask_batch": (C.c_int, [_CTX] + [_I64] * 6 + [_SZ]),
+    "rzk_sum_mask_batch": (C.c_int, [_CTX, C.c_uint32] + [_I64] * 6 + [_SZ]),
+    # ... and the zero-knowledge Linear / Sum provers with their rejection loop inside the library
+    # (g, x, nonce0, stream, gauss_kind, aux32, max_rounds, c, cp, t, tp, u, z, zp, r, rp, ok, rounds, rounds_run, B)
+    "rzk_linear_prove_zk_batch": (C.c_int, [_CTX, _I64, _I64, _U8, C.c_uint32, C.c_int, _U8, C.c_uint32] + [_I64] * 9 +
+                                  [_U8, _U8, C.POINTER(C.c_uint32), _SZ]),
+    "rzk_sum_prove_zk_batch": (C.c_int, [_CTX, C.c_uint32, _I64, _I64, _U8, C.c_uint32, C.c_int, _U8, C.c_uint32] + [_I64] * 9 +
+                               [_U8, _U8, C.POINTER(C.c_uint32), _SZ]),
     "rzk_debug_compact_dev": (C.c_int, [_CTX, _U8, _U8, _SZ, _U32P, _U32P]),
     # v8: fixed-width packed records
     "rzk_packed_record_bytes": (C.c_size_t, [_CTX, C.c_int, C.c_uint32]),

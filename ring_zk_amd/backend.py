@@ -685,6 +685,83 @@ class Context:
         """open_prove_zk on int32 slabs (rzk_open_prove_zk32_batch[_dev]): c, t, z, r are int32."""
         return self._open_prove_zk("rzk_open_prove_zk32_batch", np.int32, x, nonce0, stream, gauss_kind, aux, max_rounds)
 
+    # ---- Linear and Sum: the y-only half of the commit step and the prover loops (DESIGN §24) -------------------------
+    def linear_mask(self, g, y, yp):
+        """The part of linear_commit that depends on y alone (rzk_linear_mask_batch[_dev]): (t, tp, u), byte for byte what
+        linear_commit returns for the same g, y, yp."""
+        B = self._shape(y, self.k, self.N)
+        if self._shape(yp, self.k, self.N) != B or self._shape(g, self.N) != B:
+            raise ValueError("linear_mask: batch / shape mismatch")
+        lead = tuple(y.shape[:-2])
+        t = self._empty(y, lead + (self.n, self.N))
+        tp = self._empty(y, lead + (self.n, self.N))
+        u = self._empty(y, lead + (self.l, self.N))
+        dev, p = self._prep([g, y, yp, t, tp, u], [np.int64] * 6)
+        self._check(self._fn("rzk_linear_mask_batch", dev)(self._h, *p, B))
+        return t, tp, u
+
+    def sum_mask(self, gs, ys, yp):
+        """The part of sum_commit that depends on ys, yp alone (rzk_sum_mask_batch[_dev]): (ts, tp, u)."""
+        V = int(gs.shape[-2])
+        if V == 0:
+            raise ValueError("sum_mask: gs must not be empty (sum.rs:105)")
+        B = self._shape(gs, V, self.N)
+        if self._shape(ys, V, self.k, self.N) != B or self._shape(yp, self.k, self.N) != B:
+            raise ValueError("sum_mask: batch / shape mismatch")
+        lead = tuple(gs.shape[:-2])
+        ts = self._empty(gs, lead + (V, self.n, self.N))
+        tp = self._empty(gs, lead + (self.n, self.N))
+        u = self._empty(gs, lead + (self.l, self.N))
+        dev, p = self._prep([gs, ys, yp, ts, tp, u], [np.int64] * 6)
+        self._check(self._fn("rzk_sum_mask_batch", dev)(self._h, V, *p, B))
+        return ts, tp, u
+
+    def _field_prove_zk(self, name, lead_args, ins, shapes, nonce0, stream, gauss_kind, aux, max_rounds):
+        """ins: the input slabs; shapes: of the nine int64 outputs, in the C argument order."""
+        like = ins[0]
+        B = int(like.shape[0])
+        if aux is not None:
+            aux = bytes(aux)
+            if len(aux) != 32:
+                raise ValueError("aux must be 32 bytes")
+            aux = (C.c_uint8 * 32).from_buffer_copy(aux)
+        outs = [self._empty(like, (B,) + tuple(sh)) for sh in shapes]
+        ok = self._empty(like, (B,), np.uint8)
+        rounds = self._empty(like, (B,), np.uint8)
+        ran = C.c_uint32(0)
+        dev, p = self._prep(list(ins) + outs + [ok, rounds], [np.int64] * (len(ins) + 9) + [np.uint8] * 2)
+        self._check(self._fn(name, dev)(self._h, *lead_args, *p[:len(ins)], self._nonce(nonce0), int(stream), int(gauss_kind), aux,
+                                        int(max_rounds), *p[len(ins):], C.byref(ran), B))
+        return outs, ok, rounds, int(ran.value)
+
+    def linear_prove_zk(self, g, x, nonce0: bytes, stream: int = 0, gauss_kind: int = 0, aux=None, max_rounds: int = 64):
+        """The zero-knowledge Linear prover with its rejection loop inside the library (rzk_linear_prove_zk_batch[_dev]):
+        g [B, N], x [B, l, N] -> (c, cp, t, tp, u, z, zp, ok, r, rp, rounds, rounds_run).  The draws use the nonces nonce0,
+        nonce0 + 1, ... (2 + 4 rounds_run of them).  numpy in, numpy out (host form); torch CUDA in, torch out."""
+        if x.ndim != 3 or self._shape(x, self.l, self.N) != int(x.shape[0]) or tuple(g.shape) != (int(x.shape[0]), self.N):
+            raise ValueError("linear_prove_zk: x must be [B, l, N] and g [B, N]")
+        n, k, l, N = self.n, self.k, self.l, self.N
+        shapes = [(n + l, N), (n + l, N), (n, N), (n, N), (l, N), (k, N), (k, N), (k, N), (k, N)]
+        (c, cp, t, tp, u, z, zp, r, rp), ok, rounds, ran = self._field_prove_zk(
+            "rzk_linear_prove_zk_batch", (), [g, x], shapes, nonce0, stream, gauss_kind, aux, max_rounds)
+        return c, cp, t, tp, u, z, zp, ok, r, rp, rounds, ran
+
+    def sum_prove_zk(self, gs, xs, nonce0: bytes, stream: int = 0, gauss_kind: int = 0, aux=None, max_rounds: int = 64):
+        """The zero-knowledge Sum prover with its rejection loop inside the library (rzk_sum_prove_zk_batch[_dev]):
+        gs [B, V, N], xs [B, V, l, N] -> (cs, cp, ts, tp, u, zs, zp, ok, rs, rp, rounds, rounds_run)."""
+        if xs.ndim != 4 or gs.ndim != 3:
+            raise ValueError("sum_prove_zk: xs must be [B, V, l, N] and gs [B, V, N]")
+        V = int(xs.shape[1])
+        if V == 0:
+            raise ValueError("sum_prove_zk: V must be at least 1 (sum.rs:105)")
+        if self._shape(xs, V, self.l, self.N) != int(xs.shape[0]) or tuple(gs.shape) != (int(xs.shape[0]), V, self.N):
+            raise ValueError("sum_prove_zk: xs must be [B, V, l, N] and gs [B, V, N]")
+        n, k, l, N = self.n, self.k, self.l, self.N
+        shapes = [(V, n + l, N), (n + l, N), (V, n, N), (n, N), (l, N), (V, k, N), (k, N), (V, k, N), (k, N)]
+        (cs, cp, ts, tp, u, zs, zp, rs, rp), ok, rounds, ran = self._field_prove_zk(
+            "rzk_sum_prove_zk_batch", (V,), [gs, xs], shapes, nonce0, stream, gauss_kind, aux, max_rounds)
+        return cs, cp, ts, tp, u, zs, zp, ok, rs, rp, rounds, ran
+
     def debug_compact(self, live, done):
         """Diagnostic (rzk_debug_compact_dev): live, done uint8 [B] (torch CUDA) -> (idx uint32-as-int32 [B], count [1]):
         idx[:count] are the ascending b with live[b] and not done[b]; idx[count:] is not written (it keeps the -1 fill)."""

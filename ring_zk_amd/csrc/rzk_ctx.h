@@ -140,7 +140,8 @@ struct rzk_ctx {
   Arena ws_wire;                       // message codec: position table (decode) / lengths, positions, sizes (encode)
   Arena ws_fs;                         // Fiat-Shamir transcript: leaf digests of the call (and the key while it is hashed)
   Arena ws_reject;                     // rejection sampling: one RejectPartial per response polynomial of the call
-  Arena ws_prove;                      // the prover loop (rzk_prove_loop.cpp): y, t, z, d, gathered r and c, coin draws, flags, idx, count
+  Arena ws_prove;                      // the prover loops (rzk_prove_loop.cpp): y, retry copies of the masks and responses, d, the gathered
+                                       // randomness and commitments, coin draws, flags, idx, count
   uint32_t* h_pending = nullptr;       // ... its pending count of the round, read back once per round (pinned, allocated on first use)
   uint64_t key_digest[kFsDigestWords] = {};   // FS1 digest of the loaded key and the context's parameters (rzk_fs_key_digest)
   bool sampler_key_set = false;                // rzk_sampler_set_key: the key of the keyed (ChaCha20) samplers, host memory only;

@@ -441,6 +441,20 @@ int launch_prove_first(const LaunchCfg& cfg, const uint8_t* ok_commit, const uin
 template <class C>
 int launch_prove_last(const LaunchCfg& cfg, const uint8_t* done, C* t_out, C* z_out, uint32_t t_rows, uint32_t z_rows, uint32_t N,
                       uint8_t* ok, uint64_t B);
+// The same moves over a field list (rzk_prove_loop.h: up to kMaxFields slabs, quads per entry of each), for the Linear and
+// Sum loops; 64-bit slabs only.  -2: a list the kernels cannot walk (no field, too many, a NULL or
+// misaligned slab, an empty entry).
+struct FieldList;
+// dst[f][i] = src[f][idx[i]] for every field f, i < count
+int launch_gather_fields(const LaunchCfg& cfg, const FieldList& fl, const uint32_t* idx, uint32_t count);
+// accept[i] != 0: src[f][i] -> dst[f][idx[i]] for every field, rounds[idx[i]] = rnd, done[idx[i]] = 1, i < count
+int launch_accept_scatter_fields(const LaunchCfg& cfg, const FieldList& fl, const uint8_t* accept, const uint32_t* idx, uint32_t count,
+                                 uint8_t rnd, uint8_t* rounds, uint8_t* done);
+// launch_prove_first with live = prove_live(ok_commit, wanted, ok_hash)
+int launch_prove_first_want(const LaunchCfg& cfg, const uint8_t* ok_commit, uint8_t wanted, const uint8_t* ok_hash, const uint8_t* accept,
+                            uint8_t* live, uint8_t* done, uint8_t* rounds, uint64_t B);
+// after the last round: dst[f][b] zeroed for every field of every proof with done == 0; ok = done
+int launch_prove_last_fields(const LaunchCfg& cfg, const FieldList& fl, const uint8_t* done, uint8_t* ok, uint64_t B);
 // ---- fixed-width packed records (rzk_packed_dev.hip; format in rzk_packed.h) -------------------------------------------
 struct PackedSlabs {
   int64_t* ptr[kPackedMaxFields];   // dense slab of every field ([B][rows of the field][N]), 16-byte aligned

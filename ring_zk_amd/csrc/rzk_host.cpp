@@ -251,6 +251,28 @@ int rzk_linear_commit_batch(rzk_ctx* c, const int64_t* g, const int64_t* x, cons
   return h.run([&] { return rzk_linear_commit_batch_dev(c, dg, dx, dr, drp, dy, dyp, dcm, dcpm, dt, dtp, du, dok, B); });
 }
 
+int rzk_linear_mask_batch(rzk_ctx* c, const int64_t* g, const int64_t* y, const int64_t* yp, int64_t* t, int64_t* tp, int64_t* u,
+                          size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !g || !y || !yp || !t || !tp || !u) return RZK_E_ARG;
+  const size_t k = c->k, n = c->n, l = c->l;
+  HostCall h(c);
+  const auto dg = h.pin(g, B), dy = h.pin(y, B * k), dyp = h.pin(yp, B * k);
+  const auto dt = h.pout(t, B * n), dtp = h.pout(tp, B * n), du = h.pout(u, B * l);
+  return h.run([&] { return rzk_linear_mask_batch_dev(c, dg, dy, dyp, dt, dtp, du, B); });
+}
+
+int rzk_sum_mask_batch(rzk_ctx* c, uint32_t V, const int64_t* gs, const int64_t* ys, const int64_t* yp, int64_t* ts, int64_t* tp,
+                       int64_t* u, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || V == 0 || !gs || !ys || !yp || !ts || !tp || !u) return RZK_E_ARG;
+  const size_t k = c->k, n = c->n, l = c->l;
+  HostCall h(c);
+  const auto dgs = h.pin(gs, B * V), dys = h.pin(ys, B * V * k), dyp = h.pin(yp, B * k);
+  const auto dts = h.pout(ts, B * V * n), dtp = h.pout(tp, B * n), du = h.pout(u, B * l);
+  return h.run([&] { return rzk_sum_mask_batch_dev(c, V, dgs, dys, dyp, dts, dtp, du, B); });
+}
+
 int rzk_linear_response_batch(rzk_ctx* c, const int64_t* y, const int64_t* yp, const int64_t* r, const int64_t* rp,
                               const int64_t* d, int64_t* z, int64_t* zp, size_t B) {
   if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)

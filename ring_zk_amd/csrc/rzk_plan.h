@@ -27,7 +27,7 @@ enum ProgId : int {
   PG_OPEN_COMMIT,
   PG_RESPONSE,        // variant = number of (y,r,z) triples sharing d (1 = open, 2 = linear)
   PG_A1_RELATION,     // a1.z - c1(.)d - t == 0   (open / linear / sum verify)
-  PG_LIN_COMMIT2,
+  PG_LIN_COMMIT2,     // variant bit 1 (kMaskVar): the rows that depend on y alone (t, a2.y, t'), no commitment rows
   PG_LIN_U,
   PG_LIN_V1,
   PG_LIN_V2,
@@ -57,6 +57,11 @@ constexpr uint32_t kRecoverVar = 0x40000u;
 inline bool recover_capable(int id) {
   return id == PG_A1_RELATION || id == PG_REL_ROT || id == PG_LIN_V1B || id == PG_LIN_V2B || id == PG_SUM_V3 || id == PG_SUM_V4;
 }
+
+// bit of a PG_LIN_COMMIT2 variant: "masks only".  The program keeps the rows of t = a1.y, a2.y and t' = a1.y' (operands 4, 5,
+// 8, 9, 10 at their places; 0 .. 3, 6, 7 are not read) and drops the commitment rows: what a prover's retry needs, with y
+// transformed once for the a1 and a2 rows.  It has no fused norm check (y carries no norm rule): kMaskVar | 1 is kPlanArg.
+constexpr uint32_t kMaskVar = 2u;
 
 constexpr int kPlanOk = 0, kPlanArg = -1, kPlanUnsupported = -4;   // plan_program's status: RZK_OK / RZK_E_ARG / RZK_E_UNSUPPORTED (include/rzk.h)
 
@@ -337,8 +342,11 @@ inline int build_program(int id, uint32_t var_in, PB& pb) {
     case PG_LIN_COMMIT2:
       // ops: 0 = x[l], 1 = gx[l], 2 = r[k], 3 = rp[k], 4 = y[k], 5 = yp[k],
       //      6 = c[n+l], 7 = cp[n+l], 8 = t[n], 9 = tp[n], 10 = a2y[l]
-      pb.commit_rows(6, 2, 0);     // linear.rs:97: c = commit(x; r)
-      pb.commit_rows(7, 3, 1);     // linear.rs:96: cp = commit(g*x; rp)
+      if ((var & kMaskVar) && (var & 1)) return kPlanArg;   // no norm rule on y: the masks have no fused-check form
+      if (!(var & kMaskVar)) {
+        pb.commit_rows(6, 2, 0);   // linear.rs:97: c = commit(x; r)
+        pb.commit_rows(7, 3, 1);   // linear.rs:96: cp = commit(g*x; rp)
+      }
       pb.key_rows(8, n, 0, 4);     // linear.rs:118
       pb.key_rows(10, l, n, 4);    // a2.y, reduced mod q before it meets g (linear.rs:124-127); next to t = a1.y: the two rows can share the transform of y
       pb.key_rows(9, n, 0, 5);     // linear.rs:121

@@ -345,6 +345,29 @@ int rzk_linear_commit_batch_dev(rzk_ctx* c, const int64_t* g, const int64_t* x, 
   return run_program(c, PG_LIN_U, dkv(c), {{a2y, l, 0}, {g, 1, 0}, {yp, k, 0}, {u, l, 0}}, ok, 1, B);
 }
 
+// The y-only half of rzk_linear_commit_batch_dev (linear.rs:118-129): the rows of PG_LIN_COMMIT2 that read y and y' alone
+// (its kMaskVar form: y is transformed once for the a1 and the a2 row) and PG_LIN_U as there.  The arithmetic is exact,
+// so t, tp, u are byte for byte what the commit call writes.  No verdicts: y carries no norm rule; a non-canonical
+// coefficient raises the sticky word as in rzk_matvec_batch_dev.
+int rzk_linear_mask_batch_dev(rzk_ctx* c, const int64_t* g, const int64_t* y, const int64_t* yp, int64_t* t, int64_t* tp,
+                              int64_t* u, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !g || !y || !yp || !t || !tp || !u) return RZK_E_ARG;
+  const uint32_t n = c->n, k = c->k, l = c->l;
+  int rc = arena_reserve(c, c->ws, polys(c, B * l));
+  if (rc != RZK_OK) return rc;
+  int64_t* a2y = (int64_t*)c->ws.p;
+  rc = prepare_dkey(c, g, B, 1, l, nullptr, true);   // l rows of u
+  if (rc != RZK_OK) return rc;
+  DkeyScope dkey_scope{c};
+  // (operands at the places PG_LIN_COMMIT2 gives them; the masks-only form reads none of x, gx, r, rp and writes no c, cp)
+  const std::vector<OpSpec> m2 = {{nullptr, l, 0}, {nullptr, l, 0}, {nullptr, k, 0}, {nullptr, k, 0}, {y, k, 0}, {yp, k, 0},
+                                  {nullptr, n + l, 0}, {nullptr, n + l, 0}, {t, n, 0}, {tp, n, 0}, {a2y, l, 0}};
+  rc = run_program(c, PG_LIN_COMMIT2, kMaskVar, m2, nullptr, 1, B);
+  if (rc != RZK_OK) return rc;
+  return run_program(c, PG_LIN_U, dkv(c), {{a2y, l, 0}, {g, 1, 0}, {yp, k, 0}, {u, l, 0}}, nullptr, 1, B);
+}
+
 int rzk_linear_response_batch_dev(rzk_ctx* c, const int64_t* y, const int64_t* yp, const int64_t* r,
                                   const int64_t* rp, const int64_t* d, int64_t* z, int64_t* zp, size_t B) {
   if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
@@ -431,6 +454,37 @@ int rzk_sum_commit_batch_dev(rzk_ctx* c, uint32_t V, const int64_t* gs, const in
   rc = run_program(c, PG_MATVEC, RZK_KEY_A2 * 2, {{ys, k, 0}, {nullptr, l, 0}, {w, l, 0}}, nullptr, 1, B * V);
   if (rc != RZK_OK) return rc;
   return run_program(c, PG_SUM_U, V | dkv(c), {{w, V * l, 0}, {gs, V, 0}, {yp, k, 0}, {u, l, 0}}, ok, 1, B);
+}
+
+// The y-only half of rzk_sum_commit_batch_dev (sum.rs:145-160) as a composition of its programs: t' = a1.y' and
+// t_i = a1.y_i as plain key products (the summands are batch entries), then u on the side of sum_uses_d the commit call
+// takes.  No operand images: the a1 products here are PG_MATVEC launches, which do not produce them; exact arithmetic, so
+// the bytes are the commit call's either way.
+int rzk_sum_mask_batch_dev(rzk_ctx* c, uint32_t V, const int64_t* gs, const int64_t* ys, const int64_t* yp, int64_t* ts,
+                           int64_t* tp, int64_t* u, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || V == 0 || !gs || !ys || !yp || !ts || !tp || !u) return RZK_E_ARG;
+  const uint32_t n = c->n, k = c->k, l = c->l;
+  const size_t wpolys = (size_t)B * V * l > (size_t)B * k ? (size_t)B * V * l : (size_t)B * k;   // w[B*V][l], or D[B][k]
+  int rc = arena_reserve(c, c->ws, polys(c, wpolys));
+  if (rc != RZK_OK) return rc;
+  int64_t* w = (int64_t*)c->ws.p;
+  rc = prepare_dkey(c, gs, B, V, l, nullptr, true);   // l or (columns of a2) rows of U / D
+  if (rc != RZK_OK) return rc;
+  DkeyScope dkey_scope{c};
+  rc = run_program(c, PG_MATVEC, RZK_KEY_A1 * 2, {{yp, k, 0}, {nullptr, n, 0}, {tp, n, 0}}, nullptr, 1, B);
+  if (rc != RZK_OK) return rc;
+  rc = run_program(c, PG_MATVEC, RZK_KEY_A1 * 2, {{ys, k, 0}, {nullptr, n, 0}, {ts, n, 0}}, nullptr, 1, B * V);
+  if (rc != RZK_OK) return rc;
+  if (sum_uses_d(c, V)) {
+    int64_t* D = w;
+    rc = run_program(c, PG_SUM_D, V | dkv(c), {{ys, V * k, 0}, {gs, V, 0}, {yp, k, 0}, {D, k, 0}}, nullptr, 1, B);
+    if (rc != RZK_OK) return rc;
+    return run_program(c, PG_MATVEC, RZK_KEY_A2 * 2, {{D, k, 0}, {nullptr, l, 0}, {u, l, 0}}, nullptr, 1, B);
+  }
+  rc = run_program(c, PG_MATVEC, RZK_KEY_A2 * 2, {{ys, k, 0}, {nullptr, l, 0}, {w, l, 0}}, nullptr, 1, B * V);
+  if (rc != RZK_OK) return rc;
+  return run_program(c, PG_SUM_U, V | dkv(c), {{w, V * l, 0}, {gs, V, 0}, {yp, k, 0}, {u, l, 0}}, nullptr, 1, B);
 }
 
 int rzk_sum_response_batch_dev(rzk_ctx* c, uint32_t V, const int64_t* ys, const int64_t* yp, const int64_t* rs,

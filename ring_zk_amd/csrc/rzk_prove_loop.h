@@ -1,9 +1,12 @@
-// rzk_prove_loop.h — the arithmetic of the in-library Open prover loop (include/rzk.h "prover loop") that can
-// be wrong, shared by the kernels (rzk_prove_loop_dev.hip), the host loop (rzk_prove_loop.cpp) and the CPU test
-// (tests/test_prove_loop_host.py, g++).  Plain C++.
+// rzk_prove_loop.h — the arithmetic of the in-library prover loops (include/rzk.h "prover loop") that
+// can be wrong, shared by the kernels (rzk_prove_loop_dev.hip), the host loops (rzk_prove_loop.cpp) and the CPU tests
+// (tests/test_prove_loop_host.py, tests/test_prove_loop_fields_host.py, g++).  Plain C++.
 //
 //   nonces      nonce i of a call is nonce0 + i as a 128-bit little-endian integer (backend.KeyedSampler._next_nonce); a
 //               call that may use `span` nonces is refused when nonce0 + span leaves 128 bits.
+//   flags       which proofs are worth another y after round 0 (prove_live), with the commit flag a proof must show.
+//   field lists the slabs the Linear and Sum loops move per round, with per-field entry sizes: the quad count of an entry and
+//               its range guard (field_quads), the 64-bit entry offset (field_offset), and the three moves as host loops.
 //   coins       coin = (a + half) R0 + (b + half), a = coefficient 0 of one uniform(half) polynomial, b = coefficient 1 of
 //               another, R0 = 2^31 - 1, half = 2^30 - 1: uniform in [0, R0^2) (fiat_shamir.draw_coins).
 //   compaction  idx[0 .. count) = the ascending b with live[b] && !done[b]: the order torch.nonzero gives, which the
@@ -38,6 +41,74 @@ inline bool nonce_add(const uint8_t nonce0[16], uint64_t inc, uint8_t out[16]) {
 }
 // nonces a call with this round limit may consume: r, then (y, coin draw a, coin draw b) per round
 inline uint64_t prove_nonce_span(uint32_t max_rounds) { return 1ull + 3ull * max_rounds; }
+
+// ... of the Linear and Sum loops: r, r' (rs, r'), then (y, y', coin draw a, coin draw b) per round
+inline uint64_t prove_nonce_span_lin_sum(uint32_t max_rounds) { return 2ull + 4ull * max_rounds; }
+
+// ---- flags ---------------------------------------------------------------------------------------------------------------
+// Is a proof worth another y after round 0?  Its commit flag must have every bit of `wanted` (1: the one-bit verdicts of the
+// Open and Sum commit calls; 3: both bits of rzk_linear_commit_batch, r and r') and its transcript hash must be ok.
+RZK_PL_HD uint8_t prove_live(uint8_t ok_commit, uint8_t wanted, uint8_t ok_hash) {
+  return ((ok_commit & wanted) == wanted && ok_hash != 0) ? 1 : 0;
+}
+
+// ---- field lists ---------------------------------------------------------------------------------------------------------
+// The Linear and Sum loops move up to six slabs per direction and round, each with its own entry size, in ONE launch: the
+// kernels take the list by value.  An entry of field f is quads[f] 16-byte quads; entry e starts field_offset(e, quads[f])
+// quads into the slab.  fields_*_emulate are the kernels with loops in place of workgroups and lanes, through the same
+// functions (tests/prove_loop/fields_driver.cpp).
+constexpr uint32_t kMaxFields = 6;
+struct FieldList {
+  const void* src[kMaxFields];   // gather: the caller's slab; scatter: the sub-batch's; zero: unused
+  void* dst[kMaxFields];         // gather: the sub-batch's slab; scatter, zero: the caller's
+  uint32_t quads[kMaxFields];
+  uint32_t n;
+};
+// quads per entry of a field of `rows` polynomials (V k for zs) of N coefficients of coef_bytes bytes each; false when the
+// count leaves uint32 or B entries of it leave what a 64-bit byte offset holds (rows N coef_bytes is a multiple of 16 for
+// N >= 4 at either width, N >= 2 at 8 bytes)
+inline bool field_quads(uint64_t rows, uint32_t N, uint32_t coef_bytes, uint64_t B, uint32_t* quads) {
+  const unsigned __int128 bytes = (unsigned __int128)rows * N * coef_bytes;
+  const unsigned __int128 q = bytes / 16;
+  if (bytes % 16 != 0 || q == 0 || q > 0xffffffffull) return false;
+  if ((unsigned __int128)B * q > (unsigned __int128)0x7fffffffffffffffull / 16) return false;
+  *quads = (uint32_t)q;
+  return true;
+}
+RZK_PL_HD uint64_t field_offset(uint64_t entry, uint32_t quads) { return entry * (uint64_t)quads; }
+
+struct FieldQuad { uint64_t w[2]; };   // 16 bytes, as the kernels' int4
+inline void fields_gather_emulate(const FieldList& fl, const uint32_t* idx, uint32_t count) {
+  for (uint32_t i = 0; i < count; ++i)
+    for (uint32_t f = 0; f < fl.n; ++f) {
+      const FieldQuad* src = (const FieldQuad*)fl.src[f] + field_offset(idx[i], fl.quads[f]);
+      FieldQuad* dst = (FieldQuad*)fl.dst[f] + field_offset(i, fl.quads[f]);
+      for (uint32_t q = 0; q < fl.quads[f]; ++q) dst[q] = src[q];
+    }
+}
+inline void fields_scatter_emulate(const FieldList& fl, const uint8_t* accept, const uint32_t* idx, uint32_t count, uint8_t rnd,
+                                   uint8_t* rounds, uint8_t* done) {
+  for (uint32_t i = 0; i < count; ++i) {
+    if (accept[i] == 0) continue;
+    for (uint32_t f = 0; f < fl.n; ++f) {
+      const FieldQuad* src = (const FieldQuad*)fl.src[f] + field_offset(i, fl.quads[f]);
+      FieldQuad* dst = (FieldQuad*)fl.dst[f] + field_offset(idx[i], fl.quads[f]);
+      for (uint32_t q = 0; q < fl.quads[f]; ++q) dst[q] = src[q];
+    }
+    rounds[idx[i]] = rnd;
+    done[idx[i]] = 1;
+  }
+}
+inline void fields_zero_emulate(const FieldList& fl, const uint8_t* done, uint8_t* ok, uint64_t B) {
+  for (uint64_t b = 0; b < B; ++b) {
+    ok[b] = done[b];
+    if (done[b]) continue;
+    for (uint32_t f = 0; f < fl.n; ++f) {
+      FieldQuad* dst = (FieldQuad*)fl.dst[f] + field_offset(b, fl.quads[f]);
+      for (uint32_t q = 0; q < fl.quads[f]; ++q) dst[q] = FieldQuad{{0, 0}};
+    }
+  }
+}
 
 // ---- coins ---------------------------------------------------------------------------------------------------------------
 constexpr int64_t kCoinR0 = (1ll << 31) - 1;

@@ -1,5 +1,5 @@
-// rzk_prove_loop_dev.hip — the kernels between the library calls of the in-library Open prover loop (host loop:
-// rzk_prove_loop.cpp; arithmetic: rzk_prove_loop.h; DESIGN.md §21).  All of them move flags, indices and whole rows; none
+// rzk_prove_loop_dev.hip — the kernels between the library calls of the in-library prover loops (host loops:
+// rzk_prove_loop.cpp; arithmetic: rzk_prove_loop.h; DESIGN.md §21, §24).  All of them move flags, indices and whole rows; none
 // computes on a coefficient, so T (i64 / i32) only sets how many 16-byte quads a row has.
 //   pending_compact_kernel      idx[0 .. count) = the ascending b with live[b] && !done[b], *count.  ONE workgroup of 16
 //                               wavefronts (an ordered scan, not an atomic append: the order is the oracle's): per tile of
@@ -11,6 +11,9 @@
 //                               done[idx[i]] = 1.  idx has no duplicates, so no two workgroups write one proof.
 //   prove_first_kernel          after round 0: live = ok_commit & ok_hash (as 0 / 1), done = live & accept, rounds = 0
 //   prove_last_kernel<T>        after the last round: t, z rows of every proof with done == 0 are zeroed, ok = done
+// and, for the five slabs per direction of the Linear and Sum loops, the same moves over a field list (FieldList):
+//   gather_fields_kernel, accept_scatter_fields_kernel, prove_last_fields_kernel; prove_first_want_kernel compares the
+//   commit flag against a wanted value (prove_live).  64-bit slabs only, so they are no templates.
 // Grids follow the context's cap (LaunchCfg::num_cus, RZK_GRID_CUS) with grid-stride loops.
 #include <hip/hip_runtime.h>
 
@@ -120,6 +123,74 @@ __global__ void __launch_bounds__(256) prove_last_kernel(const uint8_t* __restri
   }
 }
 
+// ---- the field-list kernels of the Linear and Sum loops: the same moves over up to kMaxFields slabs with
+// per-field entry sizes, one launch per direction and round.  The list arrives by value (kernel arguments: scalar loads);
+// the loop over it is unrolled so that no field is indexed at run time.
+__global__ void __launch_bounds__(256) gather_fields_kernel(FieldList fl, const uint32_t* __restrict__ idx, uint32_t count) {
+  for (uint32_t i = blockIdx.x; i < count; i += gridDim.x) {
+    const uint64_t from = idx[i];
+#pragma unroll
+    for (uint32_t f = 0; f < kMaxFields; ++f) {
+      if (f >= fl.n) break;
+      const uint32_t quads = fl.quads[f];
+      const int4* __restrict__ src = (const int4*)fl.src[f] + field_offset(from, quads);
+      int4* __restrict__ dst = (int4*)fl.dst[f] + field_offset(i, quads);
+      for (uint32_t q = threadIdx.x; q < quads; q += 256) dst[q] = ld_stream(src + q);
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) accept_scatter_fields_kernel(FieldList fl, const uint8_t* __restrict__ accept,
+                                                                    const uint32_t* __restrict__ idx, uint32_t count, uint8_t rnd,
+                                                                    uint8_t* __restrict__ rounds, uint8_t* __restrict__ done) {
+  for (uint32_t i = blockIdx.x; i < count; i += gridDim.x) {
+    if (accept[i] == 0) continue;   // uniform over the workgroup
+    const uint64_t to = idx[i];
+#pragma unroll
+    for (uint32_t f = 0; f < kMaxFields; ++f) {
+      if (f >= fl.n) break;
+      const uint32_t quads = fl.quads[f];
+      const int4* __restrict__ src = (const int4*)fl.src[f] + field_offset(i, quads);
+      int4* __restrict__ dst = (int4*)fl.dst[f] + field_offset(to, quads);
+      for (uint32_t q = threadIdx.x; q < quads; q += 256) st_stream(dst + q, ld_stream(src + q));
+    }
+    if (threadIdx.x == 0) {
+      rounds[to] = rnd;
+      done[to] = 1;
+    }
+  }
+}
+
+// prove_first_kernel with the commit flag compared against a wanted value (prove_live)
+__global__ void __launch_bounds__(256) prove_first_want_kernel(const uint8_t* __restrict__ ok_commit, uint8_t wanted,
+                                                               const uint8_t* __restrict__ ok_hash, const uint8_t* __restrict__ accept,
+                                                               uint8_t* __restrict__ live, uint8_t* __restrict__ done,
+                                                               uint8_t* __restrict__ rounds, uint64_t B) {
+  for (uint64_t b = (uint64_t)blockIdx.x * 256 + threadIdx.x; b < B; b += (uint64_t)gridDim.x * 256) {
+    const uint8_t l = prove_live(ok_commit[b], wanted, ok_hash[b]);
+    live[b] = l;
+    done[b] = (l && accept[b] != 0) ? 1 : 0;
+    rounds[b] = 0;
+  }
+}
+
+__global__ void __launch_bounds__(256) prove_last_fields_kernel(FieldList fl, const uint8_t* __restrict__ done, uint8_t* __restrict__ ok,
+                                                                uint64_t B) {
+  const int4 zero = make_int4(0, 0, 0, 0);
+  for (uint64_t b = blockIdx.x; b < B; b += gridDim.x) {
+    const uint8_t dn = done[b];   // uniform over the workgroup
+    if (threadIdx.x == 0) ok[b] = dn;
+    if (dn) continue;
+#pragma unroll
+    for (uint32_t f = 0; f < kMaxFields; ++f) {
+      if (f >= fl.n) break;
+      const uint32_t quads = fl.quads[f];
+      int4* __restrict__ dst = (int4*)fl.dst[f] + field_offset(b, quads);
+      for (uint32_t q = threadIdx.x; q < quads; q += 256) st_stream(dst + q, zero);
+    }
+  }
+}
+
 unsigned entry_grid(uint64_t entries, int num_cus) {   // one workgroup per entry under the cap
   const uint64_t cap = (uint64_t)num_cus * 8;
   const uint64_t blocks = entries < cap ? entries : cap;
@@ -204,5 +275,55 @@ int launch_prove_last(const LaunchCfg& cfg, const uint8_t* done, C* t_out, C* z_
   return 0;
 }
 RZK_BOTH_WIDTHS(launch_prove_last)
+
+// a list the kernels can walk: 1 .. kMaxFields fields, every slab present and 16-byte aligned, no empty entry
+static bool field_list_ok(const FieldList& fl, bool with_src) {
+  if (fl.n < 1 || fl.n > kMaxFields) return false;
+  uintptr_t bits = 0;
+  for (uint32_t f = 0; f < fl.n; ++f) {
+    if (!fl.dst[f] || (with_src && !fl.src[f]) || fl.quads[f] == 0) return false;
+    bits |= (uintptr_t)fl.dst[f] | (with_src ? (uintptr_t)fl.src[f] : 0);
+  }
+  return (bits & 15u) == 0;
+}
+
+int launch_gather_fields(const LaunchCfg& cfg, const FieldList& fl, const uint32_t* idx, uint32_t count) {
+  if (count == 0) return 0;
+  if (!field_list_ok(fl, true)) return -2;
+  hipLaunchKernelGGL(gather_fields_kernel, dim3(entry_grid(count, cfg.num_cus)), dim3(256), 0, (hipStream_t)cfg.stream, fl, idx, count);
+  RZK_LAUNCH_CHECK();
+  if (cfg.launched) *cfg.launched = "gather_fields_kernel";
+  return 0;
+}
+
+int launch_accept_scatter_fields(const LaunchCfg& cfg, const FieldList& fl, const uint8_t* accept, const uint32_t* idx, uint32_t count,
+                                 uint8_t rnd, uint8_t* rounds, uint8_t* done) {
+  if (count == 0) return 0;
+  if (!field_list_ok(fl, true)) return -2;
+  hipLaunchKernelGGL(accept_scatter_fields_kernel, dim3(entry_grid(count, cfg.num_cus)), dim3(256), 0, (hipStream_t)cfg.stream, fl, accept,
+                     idx, count, rnd, rounds, done);
+  RZK_LAUNCH_CHECK();
+  if (cfg.launched) *cfg.launched = "accept_scatter_fields_kernel";
+  return 0;
+}
+
+int launch_prove_first_want(const LaunchCfg& cfg, const uint8_t* ok_commit, uint8_t wanted, const uint8_t* ok_hash, const uint8_t* accept,
+                            uint8_t* live, uint8_t* done, uint8_t* rounds, uint64_t B) {
+  if (B == 0) return 0;
+  hipLaunchKernelGGL(prove_first_want_kernel, dim3(flat_grid(B, cfg.num_cus)), dim3(256), 0, (hipStream_t)cfg.stream, ok_commit, wanted,
+                     ok_hash, accept, live, done, rounds, B);
+  RZK_LAUNCH_CHECK();
+  if (cfg.launched) *cfg.launched = "prove_first_want_kernel";
+  return 0;
+}
+
+int launch_prove_last_fields(const LaunchCfg& cfg, const FieldList& fl, const uint8_t* done, uint8_t* ok, uint64_t B) {
+  if (B == 0) return 0;
+  if (!field_list_ok(fl, false)) return -2;
+  hipLaunchKernelGGL(prove_last_fields_kernel, dim3(entry_grid(B, cfg.num_cus)), dim3(256), 0, (hipStream_t)cfg.stream, fl, done, ok, B);
+  RZK_LAUNCH_CHECK();
+  if (cfg.launched) *cfg.launched = "prove_last_fields_kernel";
+  return 0;
+}
 
 }  // namespace rzk

@@ -24,7 +24,9 @@ rzk_fs_challenge_batch[_dev]): a proof is (commitment message, response), and an
   * `open_prove_sampled32`, `open_prove_zk32`: the sampled and the zero-knowledge Open prover on int32 slabs with a
     `backend.KeyedSampler32` (DESIGN.md §20);
   * `open_prove_zk_native`: open_prove_zk / open_prove_zk32 with the rejection loop inside the library, one call
-    (rzk_open_prove_zk[32]_batch_dev).
+    (rzk_open_prove_zk[32]_batch_dev, DESIGN.md §21);
+  * `linear_prove_zk_native`, `sum_prove_zk_native`: the same for linear_prove_zk / sum_prove_zk
+    (rzk_linear_prove_zk_batch_dev, rzk_sum_prove_zk_batch_dev).
 
 `aux` (32 bytes, default zeros) binds the proofs of a call to a session or statement; prover and verifier must agree.
 Like the rest of the package every function takes numpy arrays (host entry points) or torch CUDA tensors (device entry
@@ -560,6 +562,47 @@ def open_prove_zk_native(ctx, x, sampler, aux=None, max_rounds: int = 64):
         used = span if (ran == 0 and B) else 1 + 3 * max(ran, 1)
         sampler.counter -= span - used
     return c, t, z, ok, r, rounds
+
+
+def _field_prove_zk_native(name, prove, B, sampler, max_rounds):
+    """The nonce bookkeeping of linear_prove_zk_native / sum_prove_zk_native around prove(nonce0) -> (..., rounds_run): the
+    largest number of nonces the call may use (2 + 4 max_rounds) is taken up front, the unused ones are given back."""
+    if not hasattr(sampler, "take_nonces") or not hasattr(sampler, "GAUSS_KIND"):
+        raise ValueError(f"{name} needs a KeyedSampler: the library draws from the keyed samplers only")
+    if not 1 <= max_rounds <= 255:
+        raise ValueError("max_rounds must lie in 1 .. 255")
+    span = 2 + 4 * max_rounds
+    nonce0 = sampler.take_nonces(span)
+    ran = 0
+    try:
+        out = prove(nonce0)
+        ran = out[-1]
+    finally:
+        # the Python loop draws r, r' and round 0 even for an empty batch; a failed call keeps the nonces it may have drawn under
+        used = span if (ran == 0 and B) else 2 + 4 * max(ran, 1)
+        sampler.counter -= span - used
+    return out[:-1]
+
+
+def linear_prove_zk_native(ctx, g, x, sampler, aux=None, max_rounds: int = 64):
+    """linear_prove_zk through Context.linear_prove_zk: one library call runs every round (rzk_linear_prove_zk_batch_dev,
+    DESIGN.md §24).  Returns the tuple of linear_prove_zk, bit for bit, and leaves the sampler's counter where it would.
+    `sampler` is a KeyedSampler of any 64-bit kind; a SeededSampler is a ValueError."""
+    B = _batch3(x, 2, "linear_prove_zk_native")
+    return _field_prove_zk_native(
+        "linear_prove_zk_native",
+        lambda nonce0: ctx.linear_prove_zk(g.contiguous(), x.contiguous(), nonce0, sampler.STREAM, sampler.GAUSS_KIND, aux, max_rounds),
+        B, sampler, max_rounds)
+
+
+def sum_prove_zk_native(ctx, gs, xs, sampler, aux=None, max_rounds: int = 64):
+    """sum_prove_zk through Context.sum_prove_zk (rzk_sum_prove_zk_batch_dev): the tuple of sum_prove_zk, bit
+    for bit, and the same sampler counter afterwards."""
+    B = _batch3(xs, 3, "sum_prove_zk_native")
+    return _field_prove_zk_native(
+        "sum_prove_zk_native",
+        lambda nonce0: ctx.sum_prove_zk(gs.contiguous(), xs.contiguous(), nonce0, sampler.STREAM, sampler.GAUSS_KIND, aux, max_rounds),
+        B, sampler, max_rounds)
 
 
 def linear_prove_zk(ctx, g, x, sampler, aux=None, max_rounds: int = 64):
