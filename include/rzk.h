@@ -762,6 +762,54 @@ int rzk_sum_prove_zk_batch_dev(rzk_ctx* ctx, uint32_t V, const int64_t* gs, cons
                                int64_t* ts, int64_t* tp, int64_t* u, int64_t* zs, int64_t* zp, int64_t* rs, int64_t* rp,
                                uint8_t* ok, uint8_t* rounds, uint32_t* rounds_run, size_t B);
 
+/* ---- 32-bit slabs: the Linear proof (v14, slab32 Linear) ----------------------------------------------------
+ * The Linear cycle, its short verifier's recompute step and the stand-alone norm predicate on int32_t slabs.  Additions only:
+ * RZK_ABI_VERSION stays 14 and every earlier signature is unchanged.  Each call has the argument list of the 64-bit sibling
+ * named by dropping "32", with every coefficient slab an int32_t* (coin and E of the reject call stay int64_t, ok / accept
+ * uint8_t); argument rules, NULL rules, B == 0, verdict bytes (the two-bit ok of the commit call included), fault reporting
+ * and trusted-producer mode are the sibling's; device slabs are 16-byte aligned (RZK_E_ARG otherwise).  Every output slab is
+ * narrow() of the sibling's output on widen(inputs), bit for bit; ok, accept and E are identical.
+ * Native 32-bit kernels run at N = 512 and 1024, n = 1, one-wavefront teams and default rotation knobs, for calls that
+ * prepare no multiplier images (RZK_DKEY=2, or l >= 2, converts) and, for rzk_linear_verify32_batch, with the rearranged
+ * verifier (RZK_LIN_E=0 converts): row_kernel<., false, i32, false> runs the vector x vector programs, norm_kernel_i32 the
+ * norm predicates the commit rows cannot fuse (ok not made of whole aligned 32-bit words).  A call runs natively only when
+ * every program it launches does; otherwise the whole call widens its inputs, runs the sibling and narrows the outputs.  The
+ * native calls keep their workspace intermediates as int32_t, in half the bytes. */
+int rzk_linear_commit32_batch(rzk_ctx* ctx, const int32_t* g, const int32_t* x, const int32_t* r, const int32_t* rp,
+                              const int32_t* y, const int32_t* yp, int32_t* c, int32_t* cp, int32_t* t, int32_t* tp, int32_t* u,
+                              uint8_t* ok, size_t B);
+int rzk_linear_commit32_batch_dev(rzk_ctx* ctx, const int32_t* g, const int32_t* x, const int32_t* r, const int32_t* rp,
+                                  const int32_t* y, const int32_t* yp, int32_t* c, int32_t* cp, int32_t* t, int32_t* tp, int32_t* u,
+                                  uint8_t* ok, size_t B);
+int rzk_linear_mask32_batch(rzk_ctx* ctx, const int32_t* g, const int32_t* y, const int32_t* yp, int32_t* t, int32_t* tp,
+                            int32_t* u, size_t B);
+int rzk_linear_mask32_batch_dev(rzk_ctx* ctx, const int32_t* g, const int32_t* y, const int32_t* yp, int32_t* t, int32_t* tp,
+                                int32_t* u, size_t B);
+int rzk_linear_response32_batch(rzk_ctx* ctx, const int32_t* y, const int32_t* yp, const int32_t* r, const int32_t* rp,
+                                const int32_t* d, int32_t* z, int32_t* zp, size_t B);
+int rzk_linear_response32_batch_dev(rzk_ctx* ctx, const int32_t* y, const int32_t* yp, const int32_t* r, const int32_t* rp,
+                                    const int32_t* d, int32_t* z, int32_t* zp, size_t B);
+int rzk_linear_response_reject32_batch(rzk_ctx* ctx, const int32_t* y, const int32_t* yp, const int32_t* r, const int32_t* rp,
+                                       const int32_t* d, const int64_t* coin, uint64_t R, double lnM, int32_t* z, int32_t* zp,
+                                       uint8_t* accept, int64_t* E, size_t B);
+int rzk_linear_response_reject32_batch_dev(rzk_ctx* ctx, const int32_t* y, const int32_t* yp, const int32_t* r, const int32_t* rp,
+                                           const int32_t* d, const int64_t* coin, uint64_t R, double lnM, int32_t* z, int32_t* zp,
+                                           uint8_t* accept, int64_t* E, size_t B);
+int rzk_linear_verify32_batch(rzk_ctx* ctx, const int32_t* z, const int32_t* zp, const int32_t* c, const int32_t* cp,
+                              const int32_t* g, const int32_t* t, const int32_t* tp, const int32_t* u, const int32_t* d,
+                              uint8_t* accept, size_t B);
+int rzk_linear_verify32_batch_dev(rzk_ctx* ctx, const int32_t* z, const int32_t* zp, const int32_t* c, const int32_t* cp,
+                                  const int32_t* g, const int32_t* t, const int32_t* tp, const int32_t* u, const int32_t* d,
+                                  uint8_t* accept, size_t B);
+int rzk_linear_recover32_batch(rzk_ctx* ctx, const int32_t* z, const int32_t* zp, const int32_t* c, const int32_t* cp,
+                               const int32_t* g, const int32_t* d, int32_t* t_out, int32_t* tp_out, int32_t* u_out,
+                               uint8_t* accept, size_t B);
+int rzk_linear_recover32_batch_dev(rzk_ctx* ctx, const int32_t* z, const int32_t* zp, const int32_t* c, const int32_t* cp,
+                                   const int32_t* g, const int32_t* d, int32_t* t_out, int32_t* tp_out, int32_t* u_out,
+                                   uint8_t* accept, size_t B);
+int rzk_norm2_le32_batch(rzk_ctx* ctx, const int32_t* v, uint32_t rows, uint64_t bound, uint8_t* ok, size_t B);
+int rzk_norm2_le32_batch_dev(rzk_ctx* ctx, const int32_t* v, uint32_t rows, uint64_t bound, uint8_t* ok, size_t B);
+
 /* diagnostic: the loop's compaction kernel on flags the caller chose.  idx[0 .. *count) = the ascending b < B with
  * live[b] != 0 && done[b] == 0; entries of idx from *count on are not written.  live, done:[B] uint8, idx:[B] uint32 and
  * count (one uint32) are device pointers; asynchronous on the context's stream.  RZK_E_ARG for NULL pointers or B >= 2^32. */

@@ -140,6 +140,14 @@ SIGNATURES = {
                                   [_U8, _U8, C.POINTER(C.c_uint32), _SZ]),
     "rzk_sum_prove_zk_batch": (C.c_int, [_CTX, C.c_uint32, _I64, _I64, _U8, C.c_uint32, C.c_int, _U8, C.c_uint32] + [_I64] * 9 +
                                [_U8, _U8, C.POINTER(C.c_uint32), _SZ]),
+    # v14, slab32 Linear: the Linear cycle, its recompute step and the norm predicate on int32 slabs (arguments as the siblings')
+    "rzk_linear_commit32_batch": (C.c_int, [_CTX] + [_I32] * 11 + [_U8, _SZ]),
+    "rzk_linear_mask32_batch": (C.c_int, [_CTX] + [_I32] * 6 + [_SZ]),
+    "rzk_linear_response32_batch": (C.c_int, [_CTX] + [_I32] * 7 + [_SZ]),
+    "rzk_linear_response_reject32_batch": (C.c_int, [_CTX] + [_I32] * 5 + [_I64, C.c_uint64, C.c_double, _I32, _I32, _U8, _I64, _SZ]),
+    "rzk_linear_verify32_batch": (C.c_int, [_CTX] + [_I32] * 9 + [_U8, _SZ]),
+    "rzk_linear_recover32_batch": (C.c_int, [_CTX] + [_I32] * 9 + [_U8, _SZ]),
+    "rzk_norm2_le32_batch": (C.c_int, [_CTX, _I32, C.c_uint32, C.c_uint64, _U8, _SZ]),
     "rzk_debug_compact_dev": (C.c_int, [_CTX, _U8, _U8, _SZ, _U32P, _U32P]),
     # v8: fixed-width packed records
     "rzk_packed_record_bytes": (C.c_size_t, [_CTX, C.c_int, C.c_uint32]),

@@ -211,13 +211,16 @@ class Context:
         self._check(self._fn("rzk_canonicalize_batch", dev)(self._h, p[0], p[1], cnt))
         return out
 
-    def norm2_le(self, v, bound: int):
+    def _norm2_le(self, dt, sym, v, bound):
         rows = int(v.shape[-2])
         B = self._shape(v, rows, self.N)
         ok = self._empty(v, (B,), np.uint8)
-        dev, p = self._prep([v, ok], [np.int64, np.uint8])
-        self._check(self._fn("rzk_norm2_le_batch", dev)(self._h, p[0], rows, bound, p[1], B))
+        dev, p = self._prep([v, ok], [dt, np.uint8])
+        self._check(self._fn(sym, dev)(self._h, p[0], rows, bound, p[1], B))
         return ok
+
+    def norm2_le(self, v, bound: int):
+        return self._norm2_le(np.int64, "rzk_norm2_le_batch", v, bound)
 
     def eq(self, a, b):
         if tuple(a.shape) != tuple(b.shape):
@@ -480,15 +483,19 @@ class Context:
         """open_response and reject([(z, y)], coin, R, lnM) in one call: (z, accept, E)."""
         return self._open_response_reject("open_response_reject", np.int64, "rzk_open_response_reject_batch", y, r, d, coin, R, lnM)
 
-    def linear_response_reject(self, y, yp, r, rp, d, coin, R: int, lnM: float):
-        """linear_response and reject([(z, y), (zp, yp)], coin, R, lnM) in one call: (z, zp, accept, E)."""
+    def _linear_response_reject(self, name, dt, sym, y, yp, r, rp, d, coin, R, lnM):
         B = self._shape(y, self.k, self.N)
         if any(self._shape(a, self.k, self.N) != B for a in (yp, r, rp)) or self._shape(d, self.N) != B or int(coin.shape[0]) != B:
-            raise ValueError("linear_response_reject: batch / shape mismatch")
-        z = self._empty(y, tuple(y.shape))
-        zp = self._empty(y, tuple(y.shape))
-        accept, E = self._response_reject("rzk_linear_response_reject_batch", (), [y, yp, r, rp, d], [z, zp], coin, R, lnM)
+            raise ValueError(f"{name}: batch / shape mismatch")
+        z = self._empty(y, tuple(y.shape), dt)
+        zp = self._empty(y, tuple(y.shape), dt)
+        accept, E = self._response_reject(sym, (), [y, yp, r, rp, d], [z, zp], coin, R, lnM, dt)
         return z, zp, accept, E
+
+    def linear_response_reject(self, y, yp, r, rp, d, coin, R: int, lnM: float):
+        """linear_response and reject([(z, y), (zp, yp)], coin, R, lnM) in one call: (z, zp, accept, E)."""
+        return self._linear_response_reject("linear_response_reject", np.int64, "rzk_linear_response_reject_batch", y, yp, r, rp, d,
+                                            coin, R, lnM)
 
     def sum_response_reject(self, ys, yp, rs, rp, d, coin, R: int, lnM: float):
         """sum_response and reject([(zs, ys), (zp, yp)], coin, R, lnM) in one call: (zs, zp, accept, E)."""
@@ -686,19 +693,22 @@ class Context:
         return self._open_prove_zk("rzk_open_prove_zk32_batch", np.int32, x, nonce0, stream, gauss_kind, aux, max_rounds)
 
     # ---- Linear and Sum: the y-only half of the commit step and the prover loops -------------------------
+    def _linear_mask(self, name, dt, sym, g, y, yp):
+        B = self._shape(y, self.k, self.N)
+        if self._shape(yp, self.k, self.N) != B or self._shape(g, self.N) != B:
+            raise ValueError(f"{name}: batch / shape mismatch")
+        lead = tuple(y.shape[:-2])
+        t = self._empty(y, lead + (self.n, self.N), dt)
+        tp = self._empty(y, lead + (self.n, self.N), dt)
+        u = self._empty(y, lead + (self.l, self.N), dt)
+        dev, p = self._prep([g, y, yp, t, tp, u], [dt] * 6)
+        self._check(self._fn(sym, dev)(self._h, *p, B))
+        return t, tp, u
+
     def linear_mask(self, g, y, yp):
         """The part of linear_commit that depends on y alone (rzk_linear_mask_batch[_dev]): (t, tp, u), byte for byte what
         linear_commit returns for the same g, y, yp."""
-        B = self._shape(y, self.k, self.N)
-        if self._shape(yp, self.k, self.N) != B or self._shape(g, self.N) != B:
-            raise ValueError("linear_mask: batch / shape mismatch")
-        lead = tuple(y.shape[:-2])
-        t = self._empty(y, lead + (self.n, self.N))
-        tp = self._empty(y, lead + (self.n, self.N))
-        u = self._empty(y, lead + (self.l, self.N))
-        dev, p = self._prep([g, y, yp, t, tp, u], [np.int64] * 6)
-        self._check(self._fn("rzk_linear_mask_batch", dev)(self._h, *p, B))
-        return t, tp, u
+        return self._linear_mask("linear_mask", np.int64, "rzk_linear_mask_batch", g, y, yp)
 
     def sum_mask(self, gs, ys, yp):
         """The part of sum_commit that depends on ys, yp alone (rzk_sum_mask_batch[_dev]): (ts, tp, u)."""
@@ -777,53 +787,93 @@ class Context:
         return idx[:B], count
 
     # ---- LinearProof (src/prove/linear.rs) ------------------------------------------------------------------------
-    def linear_commit(self, g, x, r, rp, y, yp):
+    # (written once over the dtype of the slabs, as the Open methods: the int32 forms are linear_*32 below)
+    def _linear_commit(self, name, dt, sym, g, x, r, rp, y, yp):
         B = self._shape(x, self.l, self.N)
         for a, rows in ((r, self.k), (rp, self.k), (y, self.k), (yp, self.k)):
             if self._shape(a, rows, self.N) != B:
-                raise ValueError("linear_commit: batch / shape mismatch")
+                raise ValueError(f"{name}: batch / shape mismatch")
         if self._shape(g, self.N) != B:
-            raise ValueError("linear_commit: batch / shape mismatch")
+            raise ValueError(f"{name}: batch / shape mismatch")
         lead = tuple(x.shape[:-2])
-        c = self._empty(x, lead + (self.n + self.l, self.N))
-        cp = self._empty(x, lead + (self.n + self.l, self.N))
-        t = self._empty(x, lead + (self.n, self.N))
-        tp = self._empty(x, lead + (self.n, self.N))
-        u = self._empty(x, lead + (self.l, self.N))
+        c = self._empty(x, lead + (self.n + self.l, self.N), dt)
+        cp = self._empty(x, lead + (self.n + self.l, self.N), dt)
+        t = self._empty(x, lead + (self.n, self.N), dt)
+        tp = self._empty(x, lead + (self.n, self.N), dt)
+        u = self._empty(x, lead + (self.l, self.N), dt)
         ok = self._empty(x, (B,), np.uint8)
-        dev, p = self._prep([g, x, r, rp, y, yp, c, cp, t, tp, u, ok], [np.int64] * 11 + [np.uint8])
-        self._check(self._fn("rzk_linear_commit_batch", dev)(self._h, *p, B))
+        dev, p = self._prep([g, x, r, rp, y, yp, c, cp, t, tp, u, ok], [dt] * 11 + [np.uint8])
+        self._check(self._fn(sym, dev)(self._h, *p, B))
         return c, cp, t, tp, u, ok
 
-    def linear_response(self, y, yp, r, rp, d):
+    def _linear_response(self, name, dt, sym, y, yp, r, rp, d):
         B = self._shape(y, self.k, self.N)
-        z = self._empty(y, tuple(y.shape))
-        zp = self._empty(y, tuple(y.shape))
-        dev, p = self._prep([y, yp, r, rp, d, z, zp], [np.int64] * 7)
-        self._check(self._fn("rzk_linear_response_batch", dev)(self._h, *p, B))
+        z = self._empty(y, tuple(y.shape), dt)
+        zp = self._empty(y, tuple(y.shape), dt)
+        dev, p = self._prep([y, yp, r, rp, d, z, zp], [dt] * 7)
+        self._check(self._fn(sym, dev)(self._h, *p, B))
         return z, zp
 
-    def linear_verify(self, z, zp, c, cp, g, t, tp, u, d):
+    def _linear_verify(self, name, dt, sym, z, zp, c, cp, g, t, tp, u, d):
         B = self._shape(z, self.k, self.N)
         acc = self._empty(z, (B,), np.uint8)
-        dev, p = self._prep([z, zp, c, cp, g, t, tp, u, d, acc], [np.int64] * 9 + [np.uint8])
-        self._check(self._fn("rzk_linear_verify_batch", dev)(self._h, *p, B))
+        dev, p = self._prep([z, zp, c, cp, g, t, tp, u, d, acc], [dt] * 9 + [np.uint8])
+        self._check(self._fn(sym, dev)(self._h, *p, B))
         return acc
 
-    def linear_recover(self, z, zp, c, cp, g, d):
-        """The recompute step of a short Linear proof (rzk_linear_recover_batch): (t, tp, u, accept)."""
+    def _linear_recover(self, name, dt, sym, z, zp, c, cp, g, d):
         B = self._shape(z, self.k, self.N)
         if (self._shape(zp, self.k, self.N) != B or self._shape(c, self.n + self.l, self.N) != B
                 or self._shape(cp, self.n + self.l, self.N) != B or self._shape(g, self.N) != B or self._shape(d, self.N) != B):
-            raise ValueError("linear_recover: batch / shape mismatch")
+            raise ValueError(f"{name}: batch / shape mismatch")
         lead = tuple(z.shape[:-2])
-        t = self._empty(z, lead + (self.n, self.N))
-        tp = self._empty(z, lead + (self.n, self.N))
-        u = self._empty(z, lead + (self.l, self.N))
+        t = self._empty(z, lead + (self.n, self.N), dt)
+        tp = self._empty(z, lead + (self.n, self.N), dt)
+        u = self._empty(z, lead + (self.l, self.N), dt)
         acc = self._empty(z, (B,), np.uint8)
-        dev, p = self._prep([z, zp, c, cp, g, d, t, tp, u, acc], [np.int64] * 9 + [np.uint8])
-        self._check(self._fn("rzk_linear_recover_batch", dev)(self._h, *p, B))
+        dev, p = self._prep([z, zp, c, cp, g, d, t, tp, u, acc], [dt] * 9 + [np.uint8])
+        self._check(self._fn(sym, dev)(self._h, *p, B))
         return t, tp, u, acc
+
+    def linear_commit(self, g, x, r, rp, y, yp):
+        return self._linear_commit("linear_commit", np.int64, "rzk_linear_commit_batch", g, x, r, rp, y, yp)
+
+    def linear_response(self, y, yp, r, rp, d):
+        return self._linear_response("linear_response", np.int64, "rzk_linear_response_batch", y, yp, r, rp, d)
+
+    def linear_verify(self, z, zp, c, cp, g, t, tp, u, d):
+        return self._linear_verify("linear_verify", np.int64, "rzk_linear_verify_batch", z, zp, c, cp, g, t, tp, u, d)
+
+    def linear_recover(self, z, zp, c, cp, g, d):
+        """The recompute step of a short Linear proof (rzk_linear_recover_batch): (t, tp, u, accept)."""
+        return self._linear_recover("linear_recover", np.int64, "rzk_linear_recover_batch", z, zp, c, cp, g, d)
+
+    # ---- LinearProof on int32 slabs (include/rzk.h "slab32 Linear", DESIGN §25) -------------------------------------------
+    # Every slab is int32 (numpy or torch CUDA); outputs are narrow() of the 64-bit methods' on the widened inputs, ok / accept /
+    # E are identical.  The methods above keep rejecting int32.
+    def linear_commit32(self, g, x, r, rp, y, yp):
+        return self._linear_commit("linear_commit32", np.int32, "rzk_linear_commit32_batch", g, x, r, rp, y, yp)
+
+    def linear_mask32(self, g, y, yp):
+        return self._linear_mask("linear_mask32", np.int32, "rzk_linear_mask32_batch", g, y, yp)
+
+    def linear_response32(self, y, yp, r, rp, d):
+        return self._linear_response("linear_response32", np.int32, "rzk_linear_response32_batch", y, yp, r, rp, d)
+
+    def linear_response_reject32(self, y, yp, r, rp, d, coin, R: int, lnM: float):
+        """linear_response_reject on int32 slabs (coin stays int64): (z, zp int32, accept, E)."""
+        return self._linear_response_reject("linear_response_reject32", np.int32, "rzk_linear_response_reject32_batch", y, yp, r, rp,
+                                            d, coin, R, lnM)
+
+    def linear_verify32(self, z, zp, c, cp, g, t, tp, u, d):
+        return self._linear_verify("linear_verify32", np.int32, "rzk_linear_verify32_batch", z, zp, c, cp, g, t, tp, u, d)
+
+    def linear_recover32(self, z, zp, c, cp, g, d):
+        return self._linear_recover("linear_recover32", np.int32, "rzk_linear_recover32_batch", z, zp, c, cp, g, d)
+
+    def norm2_le32(self, v, bound: int):
+        """norm2_le on an int32 slab (rzk_norm2_le32_batch): the same verdicts as norm2_le on widen(v)."""
+        return self._norm2_le(np.int32, "rzk_norm2_le32_batch", v, bound)
 
     # ---- SumProof (src/prove/sum.rs) --------------------------------------------------------------------------------
     def sum_commit(self, gs, xs, rs, rp, ys, yp):

@@ -391,20 +391,49 @@ int rzk_open_response_reject32_batch_dev(rzk_ctx* c, const int32_t* y, const int
   return open_response_reject_dev(c, y, r, d, coin, R, lnM, z, accept, E, B);
 }
 
-int rzk_linear_response_reject_batch_dev(rzk_ctx* c, const int64_t* y, const int64_t* yp, const int64_t* r, const int64_t* rp,
-                                         const int64_t* d, const int64_t* coin, uint64_t R, double lnM, int64_t* z, int64_t* zp,
-                                         uint8_t* accept, int64_t* E, size_t B) {
+// The Linear form at either width: as the Open form, with two parts.
+namespace rzk::api {
+
+template <class C>
+int linear_response_reject_dev(rzk_ctx* c, const C* y, const C* yp, const C* r, const C* rp, const C* d, const int64_t* coin, uint64_t R,
+                               double lnM, C* z, C* zp, uint8_t* accept, int64_t* E, size_t B) {
   if (!c) return RZK_E_ARG;
   if (B == 0) return RZK_OK;
   if (!y || !yp || !r || !rp || !d || !coin || !z || !zp || !accept) return fail(c, RZK_E_ARG, kResponseRejectNull);
   const uint32_t k = c->k;
-  const int64_t *zs[2] = {z, zp}, *ys[2] = {y, yp};
+  if constexpr (sizeof(C) == 4) {
+    if (misaligned({y, yp, r, rp, d, z, zp})) return align_fail(c);
+    if (!(program_native32(c, PG_RESPONSE, 2) && response_stat_fused(c)))
+      return convert_call(c, {{y, nullptr, B * k}, {yp, nullptr, B * k}, {r, nullptr, B * k}, {rp, nullptr, B * k}, {d, nullptr, B},
+                              {nullptr, z, B * k}, {nullptr, zp, B * k}},
+                          [&](int64_t* const* w) {
+                            return linear_response_reject_dev<int64_t>(c, w[0], w[1], w[2], w[3], w[4], coin, R, lnM, w[5], w[6], accept, E, B);
+                          });
+  }
+  const int64_t *zs[2] = {launch_addr(z), launch_addr(zp)}, *ys[2] = {launch_addr(y), launch_addr(yp)};
   const uint32_t rows[2] = {k, k};
   return response_reject(c, 2, zs, ys, rows, coin, R, lnM, accept, E, B, [&](const ResponseStat* st) {
+    if constexpr (sizeof(C) == 4) {
+      if (!st) return fail(c, RZK_E_STATE, "response reject on 32-bit slabs needs the fused rows");
+    }
     // the 2k rows of the program are z then zp: the order of the parts
-    return run_program(c, PG_RESPONSE, 2, {{d, 1, 0}, {y, k, 0}, {r, k, 0}, {z, k, 0}, {yp, k, 0}, {rp, k, 0}, {zp, k, 0}}, nullptr, 1,
-                       B, 0, true, 0, 0, st);
+    return run_program<C>(c, PG_RESPONSE, 2, {{d, 1, 0}, {y, k, 0}, {r, k, 0}, {z, k, 0}, {yp, k, 0}, {rp, k, 0}, {zp, k, 0}}, nullptr, 1,
+                          B, 0, true, 0, 0, st);
   });
+}
+RZK_BOTH_WIDTHS(linear_response_reject_dev)
+
+}  // namespace rzk::api
+
+int rzk_linear_response_reject_batch_dev(rzk_ctx* c, const int64_t* y, const int64_t* yp, const int64_t* r, const int64_t* rp,
+                                         const int64_t* d, const int64_t* coin, uint64_t R, double lnM, int64_t* z, int64_t* zp,
+                                         uint8_t* accept, int64_t* E, size_t B) {
+  return linear_response_reject_dev(c, y, yp, r, rp, d, coin, R, lnM, z, zp, accept, E, B);
+}
+int rzk_linear_response_reject32_batch_dev(rzk_ctx* c, const int32_t* y, const int32_t* yp, const int32_t* r, const int32_t* rp,
+                                           const int32_t* d, const int64_t* coin, uint64_t R, double lnM, int32_t* z, int32_t* zp,
+                                           uint8_t* accept, int64_t* E, size_t B) {
+  return linear_response_reject_dev(c, y, yp, r, rp, d, coin, R, lnM, z, zp, accept, E, B);
 }
 
 int rzk_sum_response_reject_batch_dev(rzk_ctx* c, uint32_t V, const int64_t* ys, const int64_t* yp, const int64_t* rs,
@@ -455,9 +484,10 @@ int rzk_open_response_reject32_batch(rzk_ctx* c, const int32_t* y, const int32_t
   return open_response_reject_host(c, y, r, d, coin, R, lnM, z, accept, E, B);
 }
 
-int rzk_linear_response_reject_batch(rzk_ctx* c, const int64_t* y, const int64_t* yp, const int64_t* r, const int64_t* rp,
-                                     const int64_t* d, const int64_t* coin, uint64_t R, double lnM, int64_t* z, int64_t* zp,
-                                     uint8_t* accept, int64_t* E, size_t B) {
+namespace {
+template <class C>
+int linear_response_reject_host(rzk_ctx* c, const C* y, const C* yp, const C* r, const C* rp, const C* d, const int64_t* coin, uint64_t R,
+                                double lnM, C* z, C* zp, uint8_t* accept, int64_t* E, size_t B) {
   if (!c) return RZK_E_ARG;
   if (B == 0) return RZK_OK;
   if (!y || !yp || !r || !rp || !d || !coin || !z || !zp || !accept) return fail(c, RZK_E_ARG, kResponseRejectNull);
@@ -468,7 +498,19 @@ int rzk_linear_response_reject_batch(rzk_ctx* c, const int64_t* y, const int64_t
   const auto dz = h.pout(z, kb), dzp = h.pout(zp, kb);
   const auto daccept = h.out(accept, B);
   const auto dE = h.out(E, B * sizeof(int64_t));
-  return h.run([&] { return rzk_linear_response_reject_batch_dev(c, dy, dyp, dr, drp, dd, dcoin, R, lnM, dz, dzp, daccept, dE, B); });
+  return h.run([&] { return linear_response_reject_dev<C>(c, dy, dyp, dr, drp, dd, dcoin, R, lnM, dz, dzp, daccept, dE, B); });
+}
+}  // namespace
+
+int rzk_linear_response_reject_batch(rzk_ctx* c, const int64_t* y, const int64_t* yp, const int64_t* r, const int64_t* rp,
+                                     const int64_t* d, const int64_t* coin, uint64_t R, double lnM, int64_t* z, int64_t* zp,
+                                     uint8_t* accept, int64_t* E, size_t B) {
+  return linear_response_reject_host(c, y, yp, r, rp, d, coin, R, lnM, z, zp, accept, E, B);
+}
+int rzk_linear_response_reject32_batch(rzk_ctx* c, const int32_t* y, const int32_t* yp, const int32_t* r, const int32_t* rp,
+                                       const int32_t* d, const int64_t* coin, uint64_t R, double lnM, int32_t* z, int32_t* zp,
+                                       uint8_t* accept, int64_t* E, size_t B) {
+  return linear_response_reject_host(c, y, yp, r, rp, d, coin, R, lnM, z, zp, accept, E, B);
 }
 
 int rzk_sum_response_reject_batch(rzk_ctx* c, uint32_t V, const int64_t* ys, const int64_t* yp, const int64_t* rs, const int64_t* rp,

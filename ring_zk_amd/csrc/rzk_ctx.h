@@ -223,10 +223,14 @@ inline int run_program(rzk_ctx* c, int id, uint32_t var, const std::vector<Op<C>
 bool program_native32(rzk_ctx* c, int id, uint32_t var);
 // the fused (var | 1) form of a checked program can run on this context with this bound (run_checked then takes no fallback)
 bool checked_fuses(rzk_ctx* c, int id, uint32_t var, uint64_t bound);
-int run_norm(rzk_ctx* c, const int64_t* v, uint32_t rows, uint64_t bound, uint8_t* ok, uint64_t B, int mode, int shift,
-             bool sticky = true);
+// run_checked of this program runs natively on 32-bit slabs whichever side it takes: the plain form (the fallback, and the
+// call without flags), the stand-alone norm kernel and, where the program has one, the fused form
+bool checked_native32(rzk_ctx* c, int id, uint32_t var, uint64_t bound, bool has_flags);
+bool norm_native32(const rzk_ctx* c);   // run_norm<int32_t> has a kernel on this context (N = 512 / 1024)
+template <class C>
+int run_norm(rzk_ctx* c, const C* v, uint32_t rows, uint64_t bound, uint8_t* ok, uint64_t B, int mode, int shift, bool sticky = true);
 struct NormSpec {   // one launch of the norm kernel: flags (mode, shift) sum c^2 of v's `rows` polynomials per flag < (bound+1)^2
-  const int64_t* v;
+  const void* v;   // the slab, int64_t or int32_t coefficients: its width is that of the program's operand list
   uint32_t rows;
   int mode, shift;   // launch_norm: 0 = overwrite, 1 = and, 2 = or (result << shift)
 };
@@ -238,6 +242,7 @@ inline int run_checked(rzk_ctx* c, int id, uint32_t var, const std::vector<Op<C>
                        std::initializer_list<NormSpec> norms) {
   return run_checked_lowered(c, id, var, lower(specs), flags, group, batch, nflags, bound, preset, sticky, norms);
 }
+bool dkey_wanted(const rzk_ctx* c, uint32_t uses);   // prepare_dkey would build images for a call with `uses` rows per multiplier
 int prepare_dkey(rzk_ctx* c, const int64_t* g, uint64_t entries, uint32_t per_entry, uint32_t uses, uint8_t* flags, bool sticky);
 int prepare_oimg(rzk_ctx* c, uint64_t B, uint32_t V, uint32_t uses);
 bool sum_uses_d(const rzk_ctx* c, uint32_t V);
@@ -289,6 +294,15 @@ template <class C> int open_response_dev(rzk_ctx* c, const C* y, const C* r, con
 template <class C> int open_a1_relation_dev(rzk_ctx* c, const C* z, const C* t, const C* cm, const C* d, uint8_t* accept, size_t B,
                                             bool recover);   // verify; recover: t is the output
 template <class C> int matvec_dev(rzk_ctx* c, int which, const C* v, const C* addend, C* out, size_t B);
+template <class C> int norm2_le_dev(rzk_ctx* c, const C* v, uint32_t rows, uint64_t bound, uint8_t* ok, size_t B);
+template <class C> int linear_commit_dev(rzk_ctx* c, const C* g, const C* x, const C* r, const C* rp, const C* y, const C* yp, C* cm, C* cpm,
+                                         C* t, C* tp, C* u, uint8_t* ok, size_t B);
+template <class C> int linear_mask_dev(rzk_ctx* c, const C* g, const C* y, const C* yp, C* t, C* tp, C* u, size_t B);
+template <class C> int linear_response_dev(rzk_ctx* c, const C* y, const C* yp, const C* r, const C* rp, const C* d, C* z, C* zp, size_t B);
+template <class C> int linear_verify_dev(rzk_ctx* c, const C* z, const C* zp, const C* cm, const C* cpm, const C* g, const C* t,
+                                         const C* tp, const C* u, const C* d, uint8_t* accept, size_t B);
+template <class C> int linear_recover_dev(rzk_ctx* c, const C* z, const C* zp, const C* cm, const C* cpm, const C* g, const C* d, C* t_out,
+                                          C* tp_out, C* u_out, uint8_t* accept, size_t B);
 // rzk_samplers.cpp
 template <class C> int sample_uniform_keyed_dev(rzk_ctx* c, const uint8_t* nonce, uint32_t stream, uint64_t bound, C* out, size_t count);
 template <class C> int sample_gauss_keyed_dev(rzk_ctx* c, const uint8_t* nonce, uint32_t stream, double sigma, C* out, size_t count);
@@ -297,6 +311,9 @@ template <class C> int sample_challenge_keyed_dev(rzk_ctx* c, const uint8_t* non
 // rzk_codec.cpp
 template <class C> int fs_challenge_dev(rzk_ctx* c, int kind, uint32_t V, const C* const* fields, const uint8_t* aux32, C* d,
                                         uint8_t* digest, uint8_t* ok, size_t B);
+template <class C> int linear_response_reject_dev(rzk_ctx* c, const C* y, const C* yp, const C* r, const C* rp, const C* d,
+                                                  const int64_t* coin, uint64_t R, double lnM, C* z, C* zp, uint8_t* accept, int64_t* E,
+                                                  size_t B);
 template <class C> int open_response_reject_dev(rzk_ctx* c, const C* y, const C* r, const C* d, const int64_t* coin, uint64_t R,
                                                 double lnM, C* z, uint8_t* accept, int64_t* E, size_t B);
 // out[b][r] = polynomial p0 + r of XP1 under seeds[b] and `domain`; seeds and out on the device

@@ -412,6 +412,13 @@ int launch_response_stat32(int logn, const LaunchCfg& cfg, const RowArgs& a, con
 // teams, N = 512 / 1024, the packed-byte rotation kernel (-1 otherwise: the caller converts, slab32_native)
 int launch_units32(int logn, const LaunchCfg& cfg, const RowArgs& a, const Operands& ops, const UnitShape& u, uint64_t batch);
 int launch_shift_rows32(int logn, const LaunchCfg& cfg, const RowArgs& a, const Operands& ops, uint32_t nrows, uint64_t batch);
+// launch_rows for such a launch: row_kernel<., false, i32, false>, programs with vector x vector items and neither rotation
+// terms nor images, N = 512 / 1024 (-1 otherwise)
+int launch_rows32(int logn, const LaunchCfg& cfg, const RowArgs& a, const Operands& ops, uint32_t nrows, bool has_shift, uint64_t batch,
+                  bool has_dd);
+// launch_norm on an int32_t slab: norm_kernel_i32, N = 512 / 1024 (-1 otherwise)
+int launch_norm32(int logn, const LaunchCfg& cfg, const int32_t* v, uint32_t rows, uint64_t limit_hi, uint64_t limit_lo, uint8_t* ok,
+                  uint64_t B, int and_mode, int shift, uint32_t qhalf, uint32_t* bad_word);
 // out = the low words of in (bad_word != NULL: a non-canonical coefficient sets it); out = in sign-extended.  ncoef even,
 // both slabs 16-byte aligned
 int launch_narrow(const LaunchCfg& cfg, const int64_t* in, int32_t* out, uint64_t ncoef, uint32_t qhalf, uint32_t* bad_word);

@@ -121,6 +121,80 @@ int open_recover_host(rzk_ctx* c, const C* z, const C* cm, const C* d, C* t_out,
   return h.run([&] { return open_a1_relation_dev<C>(c, dz, dt, dcm, dd, dacc, B, true); });
 }
 
+template <class C>
+int norm2_le_host(rzk_ctx* c, const C* v, uint32_t rows, uint64_t bound, uint8_t* ok, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !v || !ok || rows == 0) return RZK_E_ARG;
+  HostCall h(c);
+  const auto dv = h.pin(v, B * rows);
+  const auto dok = h.out(ok, B);
+  return h.run([&] { return norm2_le_dev<C>(c, dv, rows, bound, dok, B); });
+}
+
+template <class C>
+int linear_commit_host(rzk_ctx* c, const C* g, const C* x, const C* r, const C* rp, const C* y, const C* yp, C* cm, C* cpm, C* t, C* tp,
+                       C* u, uint8_t* ok, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !g || !x || !r || !rp || !y || !yp || !cm || !cpm || !t || !tp || !u) return RZK_E_ARG;
+  const size_t k = c->k, n = c->n, l = c->l;
+  HostCall h(c);
+  const auto dg = h.pin(g, B), dx = h.pin(x, B * l), dr = h.pin(r, B * k), drp = h.pin(rp, B * k), dy = h.pin(y, B * k),
+             dyp = h.pin(yp, B * k);
+  const auto dcm = h.pout(cm, B * (n + l)), dcpm = h.pout(cpm, B * (n + l)), dt = h.pout(t, B * n), dtp = h.pout(tp, B * n),
+             du = h.pout(u, B * l);
+  const auto dok = h.out(ok, B);
+  return h.run([&] { return linear_commit_dev<C>(c, dg, dx, dr, drp, dy, dyp, dcm, dcpm, dt, dtp, du, dok, B); });
+}
+
+template <class C>
+int linear_mask_host(rzk_ctx* c, const C* g, const C* y, const C* yp, C* t, C* tp, C* u, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !g || !y || !yp || !t || !tp || !u) return RZK_E_ARG;
+  const size_t k = c->k, n = c->n, l = c->l;
+  HostCall h(c);
+  const auto dg = h.pin(g, B), dy = h.pin(y, B * k), dyp = h.pin(yp, B * k);
+  const auto dt = h.pout(t, B * n), dtp = h.pout(tp, B * n), du = h.pout(u, B * l);
+  return h.run([&] { return linear_mask_dev<C>(c, dg, dy, dyp, dt, dtp, du, B); });
+}
+
+template <class C>
+int linear_response_host(rzk_ctx* c, const C* y, const C* yp, const C* r, const C* rp, const C* d, C* z, C* zp, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !y || !yp || !r || !rp || !d || !z || !zp) return RZK_E_ARG;
+  const size_t kb = B * c->k;
+  HostCall h(c);
+  const auto dy = h.pin(y, kb), dyp = h.pin(yp, kb), dr = h.pin(r, kb), drp = h.pin(rp, kb), dd = h.pin(d, B);
+  const auto dz = h.pout(z, kb), dzp = h.pout(zp, kb);
+  return h.run([&] { return linear_response_dev<C>(c, dy, dyp, dr, drp, dd, dz, dzp, B); });
+}
+
+template <class C>
+int linear_verify_host(rzk_ctx* c, const C* z, const C* zp, const C* cm, const C* cpm, const C* g, const C* t, const C* tp, const C* u,
+                       const C* d, uint8_t* accept, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !z || !zp || !cm || !cpm || !g || !t || !tp || !u || !d || !accept) return RZK_E_ARG;
+  const size_t k = c->k, n = c->n, l = c->l;
+  HostCall h(c);
+  const auto dz = h.pin(z, B * k), dzp = h.pin(zp, B * k), dcm = h.pin(cm, B * (n + l)), dcpm = h.pin(cpm, B * (n + l)),
+             dg = h.pin(g, B), dt = h.pin(t, B * n), dtp = h.pin(tp, B * n), du = h.pin(u, B * l), dd = h.pin(d, B);
+  const auto dacc = h.out(accept, B);
+  return h.run([&] { return linear_verify_dev<C>(c, dz, dzp, dcm, dcpm, dg, dt, dtp, du, dd, dacc, B); });
+}
+
+template <class C>
+int linear_recover_host(rzk_ctx* c, const C* z, const C* zp, const C* cm, const C* cpm, const C* g, const C* d, C* t_out, C* tp_out,
+                        C* u_out, uint8_t* accept, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !z || !zp || !cm || !cpm || !g || !d || !t_out || !tp_out || !u_out || !accept) return RZK_E_ARG;
+  const size_t k = c->k, n = c->n, l = c->l;
+  HostCall h(c);
+  const auto dz = h.pin(z, B * k), dzp = h.pin(zp, B * k), dcm = h.pin(cm, B * (n + l)), dcpm = h.pin(cpm, B * (n + l)),
+             dg = h.pin(g, B), dd = h.pin(d, B);
+  const auto dt = h.pout(t_out, B * n), dtp = h.pout(tp_out, B * n), du = h.pout(u_out, B * l);
+  const auto dacc = h.out(accept, B);
+  return h.run([&] { return linear_recover_dev<C>(c, dz, dzp, dcm, dcpm, dg, dd, dt, dtp, du, dacc, B); });
+}
+
 }  // namespace
 
 extern "C" {
@@ -167,12 +241,10 @@ int rzk_canonicalize_batch(rzk_ctx* c, const int64_t* in, int64_t* out, size_t c
 }
 
 int rzk_norm2_le_batch(rzk_ctx* c, const int64_t* v, uint32_t rows, uint64_t bound, uint8_t* ok, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !v || !ok || rows == 0) return RZK_E_ARG;
-  HostCall h(c);
-  const auto dv = h.pin(v, B * rows);
-  const auto dok = h.out(ok, B);
-  return h.run([&] { return rzk_norm2_le_batch_dev(c, dv, rows, bound, dok, B); });
+  return norm2_le_host(c, v, rows, bound, ok, B);
+}
+int rzk_norm2_le32_batch(rzk_ctx* c, const int32_t* v, uint32_t rows, uint64_t bound, uint8_t* ok, size_t B) {
+  return norm2_le_host(c, v, rows, bound, ok, B);
 }
 
 int rzk_eq_batch(rzk_ctx* c, const int64_t* a, const int64_t* b, uint32_t rows, uint8_t* eq, size_t B) {
@@ -236,30 +308,24 @@ int rzk_open_recover32_batch(rzk_ctx* c, const int32_t* z, const int32_t* cm, co
   return open_recover_host(c, z, cm, d, t_out, accept, B);
 }
 
+// ---- LinearProof at either width --------------------------------------------------------------------------------------
 int rzk_linear_commit_batch(rzk_ctx* c, const int64_t* g, const int64_t* x, const int64_t* r, const int64_t* rp,
                             const int64_t* y, const int64_t* yp, int64_t* cm, int64_t* cpm, int64_t* t, int64_t* tp,
                             int64_t* u, uint8_t* ok, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !g || !x || !r || !rp || !y || !yp || !cm || !cpm || !t || !tp || !u) return RZK_E_ARG;
-  const size_t k = c->k, n = c->n, l = c->l;
-  HostCall h(c);
-  const auto dg = h.pin(g, B), dx = h.pin(x, B * l), dr = h.pin(r, B * k), drp = h.pin(rp, B * k), dy = h.pin(y, B * k),
-             dyp = h.pin(yp, B * k);
-  const auto dcm = h.pout(cm, B * (n + l)), dcpm = h.pout(cpm, B * (n + l)), dt = h.pout(t, B * n), dtp = h.pout(tp, B * n),
-             du = h.pout(u, B * l);
-  const auto dok = h.out(ok, B);
-  return h.run([&] { return rzk_linear_commit_batch_dev(c, dg, dx, dr, drp, dy, dyp, dcm, dcpm, dt, dtp, du, dok, B); });
+  return linear_commit_host(c, g, x, r, rp, y, yp, cm, cpm, t, tp, u, ok, B);
 }
-
+int rzk_linear_commit32_batch(rzk_ctx* c, const int32_t* g, const int32_t* x, const int32_t* r, const int32_t* rp,
+                              const int32_t* y, const int32_t* yp, int32_t* cm, int32_t* cpm, int32_t* t, int32_t* tp,
+                              int32_t* u, uint8_t* ok, size_t B) {
+  return linear_commit_host(c, g, x, r, rp, y, yp, cm, cpm, t, tp, u, ok, B);
+}
 int rzk_linear_mask_batch(rzk_ctx* c, const int64_t* g, const int64_t* y, const int64_t* yp, int64_t* t, int64_t* tp, int64_t* u,
                           size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !g || !y || !yp || !t || !tp || !u) return RZK_E_ARG;
-  const size_t k = c->k, n = c->n, l = c->l;
-  HostCall h(c);
-  const auto dg = h.pin(g, B), dy = h.pin(y, B * k), dyp = h.pin(yp, B * k);
-  const auto dt = h.pout(t, B * n), dtp = h.pout(tp, B * n), du = h.pout(u, B * l);
-  return h.run([&] { return rzk_linear_mask_batch_dev(c, dg, dy, dyp, dt, dtp, du, B); });
+  return linear_mask_host(c, g, y, yp, t, tp, u, B);
+}
+int rzk_linear_mask32_batch(rzk_ctx* c, const int32_t* g, const int32_t* y, const int32_t* yp, int32_t* t, int32_t* tp, int32_t* u,
+                            size_t B) {
+  return linear_mask_host(c, g, y, yp, t, tp, u, B);
 }
 
 int rzk_sum_mask_batch(rzk_ctx* c, uint32_t V, const int64_t* gs, const int64_t* ys, const int64_t* yp, int64_t* ts, int64_t* tp,
@@ -275,26 +341,21 @@ int rzk_sum_mask_batch(rzk_ctx* c, uint32_t V, const int64_t* gs, const int64_t*
 
 int rzk_linear_response_batch(rzk_ctx* c, const int64_t* y, const int64_t* yp, const int64_t* r, const int64_t* rp,
                               const int64_t* d, int64_t* z, int64_t* zp, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !y || !yp || !r || !rp || !d || !z || !zp) return RZK_E_ARG;
-  const size_t kb = B * c->k;
-  HostCall h(c);
-  const auto dy = h.pin(y, kb), dyp = h.pin(yp, kb), dr = h.pin(r, kb), drp = h.pin(rp, kb), dd = h.pin(d, B);
-  const auto dz = h.pout(z, kb), dzp = h.pout(zp, kb);
-  return h.run([&] { return rzk_linear_response_batch_dev(c, dy, dyp, dr, drp, dd, dz, dzp, B); });
+  return linear_response_host(c, y, yp, r, rp, d, z, zp, B);
 }
-
+int rzk_linear_response32_batch(rzk_ctx* c, const int32_t* y, const int32_t* yp, const int32_t* r, const int32_t* rp,
+                                const int32_t* d, int32_t* z, int32_t* zp, size_t B) {
+  return linear_response_host(c, y, yp, r, rp, d, z, zp, B);
+}
 int rzk_linear_verify_batch(rzk_ctx* c, const int64_t* z, const int64_t* zp, const int64_t* cm, const int64_t* cpm,
                             const int64_t* g, const int64_t* t, const int64_t* tp, const int64_t* u, const int64_t* d,
                             uint8_t* accept, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !z || !zp || !cm || !cpm || !g || !t || !tp || !u || !d || !accept) return RZK_E_ARG;
-  const size_t k = c->k, n = c->n, l = c->l;
-  HostCall h(c);
-  const auto dz = h.pin(z, B * k), dzp = h.pin(zp, B * k), dcm = h.pin(cm, B * (n + l)), dcpm = h.pin(cpm, B * (n + l)),
-             dg = h.pin(g, B), dt = h.pin(t, B * n), dtp = h.pin(tp, B * n), du = h.pin(u, B * l), dd = h.pin(d, B);
-  const auto dacc = h.out(accept, B);
-  return h.run([&] { return rzk_linear_verify_batch_dev(c, dz, dzp, dcm, dcpm, dg, dt, dtp, du, dd, dacc, B); });
+  return linear_verify_host(c, z, zp, cm, cpm, g, t, tp, u, d, accept, B);
+}
+int rzk_linear_verify32_batch(rzk_ctx* c, const int32_t* z, const int32_t* zp, const int32_t* cm, const int32_t* cpm,
+                              const int32_t* g, const int32_t* t, const int32_t* tp, const int32_t* u, const int32_t* d,
+                              uint8_t* accept, size_t B) {
+  return linear_verify_host(c, z, zp, cm, cpm, g, t, tp, u, d, accept, B);
 }
 
 int rzk_sum_commit_batch(rzk_ctx* c, uint32_t V, const int64_t* gs, const int64_t* xs, const int64_t* rs,
@@ -342,15 +403,12 @@ int rzk_sum_verify_batch(rzk_ctx* c, uint32_t V, const int64_t* zs, const int64_
 int rzk_linear_recover_batch(rzk_ctx* c, const int64_t* z, const int64_t* zp, const int64_t* cm, const int64_t* cpm,
                              const int64_t* g, const int64_t* d, int64_t* t_out, int64_t* tp_out, int64_t* u_out,
                              uint8_t* accept, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !z || !zp || !cm || !cpm || !g || !d || !t_out || !tp_out || !u_out || !accept) return RZK_E_ARG;
-  const size_t k = c->k, n = c->n, l = c->l;
-  HostCall h(c);
-  const auto dz = h.pin(z, B * k), dzp = h.pin(zp, B * k), dcm = h.pin(cm, B * (n + l)), dcpm = h.pin(cpm, B * (n + l)),
-             dg = h.pin(g, B), dd = h.pin(d, B);
-  const auto dt = h.pout(t_out, B * n), dtp = h.pout(tp_out, B * n), du = h.pout(u_out, B * l);
-  const auto dacc = h.out(accept, B);
-  return h.run([&] { return rzk_linear_recover_batch_dev(c, dz, dzp, dcm, dcpm, dg, dd, dt, dtp, du, dacc, B); });
+  return linear_recover_host(c, z, zp, cm, cpm, g, d, t_out, tp_out, u_out, accept, B);
+}
+int rzk_linear_recover32_batch(rzk_ctx* c, const int32_t* z, const int32_t* zp, const int32_t* cm, const int32_t* cpm,
+                               const int32_t* g, const int32_t* d, int32_t* t_out, int32_t* tp_out, int32_t* u_out,
+                               uint8_t* accept, size_t B) {
+  return linear_recover_host(c, z, zp, cm, cpm, g, d, t_out, tp_out, u_out, accept, B);
 }
 
 int rzk_sum_recover_batch(rzk_ctx* c, uint32_t V, const int64_t* zs, const int64_t* zp, const int64_t* cs,

@@ -31,24 +31,6 @@ namespace rzk {
 // =============================================================================================
 size_t row_scratch_words(int logn, int num_cus) { return (size_t)num_cus * 8 * 4 * (((size_t)kScratchLines << logn) + 16); }
 
-template <int LOGN, bool HAS_SHIFT, class TM = WaveTeam, bool DD = false>
-static int launch_rows_t(const LaunchCfg& cfg, const RowArgs& a, const Operands& ops, uint32_t ntasks) {
-  constexpr int TPB = TM::kTeamsPerBlock;
-  constexpr size_t lds = unit_lds_bytes<LOGN, TM, HAS_SHIFT>();   // per team: transposition slab + state word A
-  static_assert(!TeamTwLds<TM>::value, "row_kernel reads its twiddles from the global tables");
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&row_kernel<LOGN, HAS_SHIFT, TM, DD>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
-  const unsigned grid = grid_for(ntasks, cfg.num_cus, TPB, unit_blocks_per_cu<TM>());   // <= 32 team lines per CU (scratch sizing)
-  hipLaunchKernelGGL((row_kernel<LOGN, HAS_SHIFT, TM, DD>), dim3(grid), dim3(TPB << TM::LL), lds, (hipStream_t)cfg.stream, a.prog, ops,
-                     a.key_ntt, a.key_l2, a.T, a.tw, a.scratch, a.flags, ntasks);
-  RZK_LAUNCH_CHECK();
-  if (cfg.launched) *cfg.launched = "row_kernel<" + std::to_string(LOGN) + ", " + tf(HAS_SHIFT) + ", " + TM::kName + ", " + tf(DD) + ">";
-  return 0;
-}
-
 int launch_rows(int logn, const LaunchCfg& cfg, const RowArgs& a, const Operands& ops, uint32_t nrows, bool has_shift, uint64_t batch,
                 bool has_dd) {
   uint32_t ntasks;

@@ -143,6 +143,27 @@ static int launch_units_io_t(const LaunchCfg& cfg, const RowArgs& a, const Opera
   return 0;
 }
 
+// ---- row_kernel ---------------------------------------------------------------------------------------------------------
+// The LDS request, grid and scratch lines of unit_kernel's teams.  The name always carries the team: "row_kernel<9, false,
+// WaveTeam, false>", and "row_kernel<9, false, i32, false>" on 32-bit slabs.
+template <int LOGN, bool HAS_SHIFT, class TM = WaveTeam, bool DD = false>
+static int launch_rows_t(const LaunchCfg& cfg, const RowArgs& a, const Operands& ops, uint32_t ntasks) {
+  constexpr int TPB = TM::kTeamsPerBlock;
+  constexpr size_t lds = unit_lds_bytes<LOGN, TM, HAS_SHIFT>();   // per team: transposition slab + state word A
+  static_assert(!TeamTwLds<TM>::value, "row_kernel reads its twiddles from the global tables");
+  if (lds > 48 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&row_kernel<LOGN, HAS_SHIFT, TM, DD>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+  }
+  const unsigned grid = grid_for(ntasks, cfg.num_cus, TPB, unit_blocks_per_cu<TM>());   // <= 32 team lines per CU (scratch sizing)
+  hipLaunchKernelGGL((row_kernel<LOGN, HAS_SHIFT, TM, DD>), dim3(grid), dim3(TPB << TM::LL), lds, (hipStream_t)cfg.stream, a.prog, ops,
+                     a.key_ntt, a.key_l2, a.T, a.tw, a.scratch, a.flags, ntasks);
+  RZK_LAUNCH_CHECK();
+  if (cfg.launched) *cfg.launched = "row_kernel<" + std::to_string(LOGN) + ", " + tf(HAS_SHIFT) + ", " + TM::kName + ", " + tf(DD) + ">";
+  return 0;
+}
+
 // ---- rotation kernels (shift_row_kernel, response_stat_kernel) -------------------------------------------------------------
 // One team's image is 8 N bytes.  The workgroup asks for at least 40 KiB so that a CU holds four workgroups = 4 waves per
 // SIMD: with the 79 VGPRs the kernel needs, five or six would fit, and measured slower (response rows at N = 1024:
@@ -205,6 +226,7 @@ static_assert(unit_lds_bytes<10, WaveTeamTw3, false>() == 157696 && unit_lds_byt
 static_assert(unit_lds_bytes<10, WaveTeam32Tw3, false>() == 157696 && unit_lds_bytes<10, WaveTeam32Tw3, true>() == 157696, "");
 static_assert(unit_lds_bytes<11, WaveTeam, false>() == 66560, "");   // (above 48 KiB: the opt-in branch; no rotation terms on one wavefront)
 static_assert(unit_lds_bytes<11, PairTeam, false>() == 16640 && unit_lds_bytes<11, PairTeam, true>() == 18448, "");
+// row_kernel: unit_kernel's request for the same team, in either width (pinned above for WaveTeam / WaveTeam32)
 // unit_io_kernel
 static_assert(unit_io_lds_bytes<9, WaveTeam>() == 33024 && unit_io_lds_bytes<9, WaveTeam32>() == 33024, "");
 static_assert(unit_io_lds_bytes<10, WaveTeam>() == 33280 && unit_io_lds_bytes<10, WaveTeam32>() == 33280, "");

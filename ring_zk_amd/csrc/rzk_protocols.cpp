@@ -29,24 +29,42 @@ int run_a1_relation(rzk_ctx* c, const std::vector<OpSpec>& specs, int64_t* w, ui
 }
 
 // Linear's verifier, rearranged (PG_LIN_V1B / V2B): no product with g in the first program, so it runs on the unit kernel
-// (and initialises the verdicts itself where one team owns a proof); e / e' live in the workspace.
+// (and initialises the verdicts itself where one team owns a proof); e / e' live in the workspace, in the call's width.
 // recover: t, tp, u are outputs (linear.rs:224-249 solved for them).
-int linear_rearranged(rzk_ctx* c, const int64_t* z, const int64_t* zp, const int64_t* cm, const int64_t* cpm, const int64_t* g,
-                      const int64_t* t, const int64_t* tp, const int64_t* u, const int64_t* d, uint8_t* accept, size_t B,
-                      bool recover) {
+// C = int32_t: the caller has asked linear_verify_native32 — both programs have 32-bit kernels and the call prepares no
+// multiplier images (they are read from 64-bit slabs).
+template <class C>
+int linear_rearranged(rzk_ctx* c, const C* z, const C* zp, const C* cm, const C* cpm, const C* g, const C* t, const C* tp, const C* u,
+                      const C* d, uint8_t* accept, size_t B, bool recover) {
   const uint32_t n = c->n, k = c->k, l = c->l, rv = recover ? kRecoverVar : 0u;
-  int rc = arena_reserve(c, c->ws, polys(c, 2 * B * l));
+  int rc = arena_reserve(c, c->ws, polys<C>(c, 2 * B * l));
   if (rc != RZK_OK) return rc;
-  int64_t* e = (int64_t*)c->ws.p;
-  int64_t* ep = e + B * l * c->N;
-  const std::vector<OpSpec> v1b = {{z, k, 0}, {zp, k, 0}, {t, n, 0}, {tp, n, 0}, {cm, n + l, 0}, {cpm, n + l, 0},
-                                   {d, 1, 0}, {e, l, 0}, {ep, l, 0}};
-  rc = run_checked(c, PG_LIN_V1B, rv, v1b, accept, 1, B, B, c->verify_bound, true, false, {{z, k, 0, 0}, {zp, k, 1, 0}});
+  C* e = (C*)c->ws.p;
+  C* ep = e + B * l * c->N;
+  const std::vector<Op<C>> v1b = {{z, k, 0}, {zp, k, 0}, {t, n, 0}, {tp, n, 0}, {cm, n + l, 0}, {cpm, n + l, 0},
+                                  {d, 1, 0}, {e, l, 0}, {ep, l, 0}};
+  rc = run_checked(c, PG_LIN_V1B, rv, v1b, accept, 1, B, B, c->verify_bound, true, false,
+                   {{z, k, 0, 0}, {zp, k, 1, 0}});
   if (rc != RZK_OK) return rc;
-  rc = prepare_dkey(c, g, B, 1, l, accept, false);   // (after the verdicts exist; l rows multiply by g)
-  if (rc != RZK_OK) return rc;
+  if constexpr (sizeof(C) == 8) {
+    rc = prepare_dkey(c, g, B, 1, l, accept, false);   // (after the verdicts exist; l rows multiply by g)
+    if (rc != RZK_OK) return rc;
+  }
   DkeyScope dkey_scope{c};
-  return run_program(c, PG_LIN_V2B, rv | dkv(c), {{e, l, 0}, {ep, l, 0}, {g, 1, 0}, {u, l, 0}}, accept, 1, B, 0, false);
+  return run_program<C>(c, PG_LIN_V2B, rv | dkv(c), {{e, l, 0}, {ep, l, 0}, {g, 1, 0}, {u, l, 0}}, accept, 1, B, 0, false);
+}
+
+// Every program of a Linear call on 32-bit slabs has native kernels on this context and the call would prepare no
+// multiplier images (`uses` rows per multiplier, prepare_dkey): otherwise the whole call converts — one width per call.
+bool linear_native32(rzk_ctx* c, uint32_t uses, std::initializer_list<std::pair<int, uint32_t>> plain) {
+  if (dkey_wanted(c, uses)) return false;
+  for (const auto& p : plain)
+    if (!program_native32(c, p.first, p.second)) return false;
+  return true;
+}
+bool linear_verify_native32(rzk_ctx* c, bool recover) {
+  const uint32_t rv = recover ? kRecoverVar : 0u;
+  return linear_native32(c, c->l, {{PG_LIN_V2B, rv}}) && checked_native32(c, PG_LIN_V1B, rv, c->verify_bound, true);
 }
 
 // Sum's verifier (sum.rs:262-319).  recover: ts, tp, u are outputs.
@@ -181,6 +199,178 @@ int open_a1_relation_dev(rzk_ctx* c, const C* z, const C* t, const C* cm, const 
 }
 RZK_BOTH_WIDTHS(open_a1_relation_dev)
 
+template <class C>
+int norm2_le_dev(rzk_ctx* c, const C* v, uint32_t rows, uint64_t bound, uint8_t* ok, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !v || !ok || rows == 0) return RZK_E_ARG;
+  if constexpr (sizeof(C) == 4) {
+    if (misaligned({v})) return align_fail(c);
+    if (!norm_native32(c))
+      return convert_call(c, {{v, nullptr, B * rows}}, [&](int64_t* const* w) { return norm2_le_dev<int64_t>(c, w[0], rows, bound, ok, B); });
+  }
+  return run_norm(c, v, rows, bound, ok, B, 0, 0);
+}
+RZK_BOTH_WIDTHS(norm2_le_dev)
+
+// ---- LinearProof (linear.rs), at either width -------------------------------------------------------------------------
+// 32-bit slabs: a call is native when every program it launches is (linear_native32) and converts as a
+// whole otherwise; the native calls keep gx, a2y, e, e' as int32_t in the workspace.
+template <class C>
+int linear_commit_dev(rzk_ctx* c, const C* g, const C* x, const C* r, const C* rp, const C* y, const C* yp, C* cm, C* cpm, C* t, C* tp,
+                      C* u, uint8_t* ok, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !g || !x || !r || !rp || !y || !yp || !cm || !cpm || !t || !tp || !u) return RZK_E_ARG;
+  const uint32_t n = c->n, k = c->k, l = c->l;
+  if constexpr (sizeof(C) == 4) {
+    if (misaligned({g, x, r, rp, y, yp, cm, cpm, t, tp, u})) return align_fail(c);
+    if (!(linear_native32(c, 2 * l, {{PG_CMUL, l}, {PG_LIN_U, 0}}) && checked_native32(c, PG_LIN_COMMIT2, 0, c->commit_bound, ok != nullptr)))
+      return convert_call(c, {{g, nullptr, B}, {x, nullptr, B * l}, {r, nullptr, B * k}, {rp, nullptr, B * k}, {y, nullptr, B * k},
+                              {yp, nullptr, B * k}, {nullptr, cm, B * (n + l)}, {nullptr, cpm, B * (n + l)}, {nullptr, t, B * n},
+                              {nullptr, tp, B * n}, {nullptr, u, B * l}},
+                          [&](int64_t* const* w) {
+                            return linear_commit_dev<int64_t>(c, w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8], w[9], w[10], ok, B);
+                          });
+  }
+  int rc = arena_reserve(c, c->ws, polys<C>(c, 2 * B * l));
+  if (rc != RZK_OK) return rc;
+  C* gx = (C*)c->ws.p;
+  C* a2y = gx + B * l * c->N;
+  if constexpr (sizeof(C) == 8) {
+    // the multiplier g of every proof, transformed once for the rows that multiply by it (gx, u)
+    rc = prepare_dkey(c, g, B, 1, 2 * l, nullptr, true);      // l rows of gx, l rows of u
+    if (rc != RZK_OK) return rc;
+  }
+  DkeyScope dkey_scope{c};
+  // linear.rs:91-95: gx = x_i * g
+  rc = run_program<C>(c, PG_CMUL, l | dkv(c), {{x, l, 0}, {g, 1, 0}, {gx, l, 0}}, nullptr, 1, B);
+  if (rc != RZK_OK) return rc;
+  const std::vector<Op<C>> c2 = {{x, l, 0}, {gx, l, 0}, {r, k, 0}, {rp, k, 0}, {y, k, 0}, {yp, k, 0}, {cm, n + l, 0},
+                                 {cpm, n + l, 0}, {t, n, 0}, {tp, n, 0}, {a2y, l, 0}};
+  // the norm predicates on r (bit 0 of ok) and rp (bit 1) ride on the commit rows when the kernel path allows; otherwise
+  // bit 0: constraint(r), bit 1: constraint(rp), and the rows clear the byte on non-canonical inputs
+  rc = run_checked(c, PG_LIN_COMMIT2, 0, c2, ok, 1, B, B, c->commit_bound, true, true,
+                   {{r, k, 0, 0}, {rp, k, 2, 1}});
+  if (rc != RZK_OK) return rc;
+  return run_program<C>(c, PG_LIN_U, dkv(c), {{a2y, l, 0}, {g, 1, 0}, {yp, k, 0}, {u, l, 0}}, ok, 1, B);
+}
+RZK_BOTH_WIDTHS(linear_commit_dev)
+
+// The y-only half of linear_commit_dev (linear.rs:118-129): the rows of PG_LIN_COMMIT2 that read y and y' alone
+// (its kMaskVar form: y is transformed once for the a1 and the a2 row) and PG_LIN_U as there.  The arithmetic is exact,
+// so t, tp, u are byte for byte what the commit call writes.  No verdicts: y carries no norm rule; a non-canonical
+// coefficient raises the sticky word as in rzk_matvec_batch_dev.
+template <class C>
+int linear_mask_dev(rzk_ctx* c, const C* g, const C* y, const C* yp, C* t, C* tp, C* u, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !g || !y || !yp || !t || !tp || !u) return RZK_E_ARG;
+  const uint32_t n = c->n, k = c->k, l = c->l;
+  if constexpr (sizeof(C) == 4) {
+    if (misaligned({g, y, yp, t, tp, u})) return align_fail(c);
+    if (!linear_native32(c, l, {{PG_LIN_COMMIT2, kMaskVar}, {PG_LIN_U, 0}}))
+      return convert_call(c, {{g, nullptr, B}, {y, nullptr, B * k}, {yp, nullptr, B * k}, {nullptr, t, B * n}, {nullptr, tp, B * n},
+                              {nullptr, u, B * l}},
+                          [&](int64_t* const* w) { return linear_mask_dev<int64_t>(c, w[0], w[1], w[2], w[3], w[4], w[5], B); });
+  }
+  int rc = arena_reserve(c, c->ws, polys<C>(c, B * l));
+  if (rc != RZK_OK) return rc;
+  C* a2y = (C*)c->ws.p;
+  if constexpr (sizeof(C) == 8) {
+    rc = prepare_dkey(c, g, B, 1, l, nullptr, true);   // l rows of u
+    if (rc != RZK_OK) return rc;
+  }
+  DkeyScope dkey_scope{c};
+  // (operands at the places PG_LIN_COMMIT2 gives them; the masks-only form reads none of x, gx, r, rp and writes no c, cp)
+  const C* const none = nullptr;
+  const std::vector<Op<C>> m2 = {{none, l, 0}, {none, l, 0}, {none, k, 0}, {none, k, 0}, {y, k, 0}, {yp, k, 0},
+                                 {none, n + l, 0}, {none, n + l, 0}, {t, n, 0}, {tp, n, 0}, {a2y, l, 0}};
+  rc = run_program(c, PG_LIN_COMMIT2, kMaskVar, m2, nullptr, 1, B);
+  if (rc != RZK_OK) return rc;
+  return run_program<C>(c, PG_LIN_U, dkv(c), {{a2y, l, 0}, {g, 1, 0}, {yp, k, 0}, {u, l, 0}}, nullptr, 1, B);
+}
+RZK_BOTH_WIDTHS(linear_mask_dev)
+
+template <class C>
+int linear_response_dev(rzk_ctx* c, const C* y, const C* yp, const C* r, const C* rp, const C* d, C* z, C* zp, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !y || !yp || !r || !rp || !d || !z || !zp) return RZK_E_ARG;
+  const uint32_t k = c->k;
+  if constexpr (sizeof(C) == 4) {
+    if (misaligned({y, yp, r, rp, d, z, zp})) return align_fail(c);
+    if (!program_native32(c, PG_RESPONSE, 2))
+      return convert_call(c, {{y, nullptr, B * k}, {yp, nullptr, B * k}, {r, nullptr, B * k}, {rp, nullptr, B * k}, {d, nullptr, B},
+                              {nullptr, z, B * k}, {nullptr, zp, B * k}},
+                          [&](int64_t* const* w) { return linear_response_dev<int64_t>(c, w[0], w[1], w[2], w[3], w[4], w[5], w[6], B); });
+  }
+  return run_program<C>(c, PG_RESPONSE, 2, {{d, 1, 0}, {y, k, 0}, {r, k, 0}, {z, k, 0}, {yp, k, 0}, {rp, k, 0}, {zp, k, 0}},
+                        nullptr, 1, B);
+}
+RZK_BOTH_WIDTHS(linear_response_dev)
+
+template <class C>
+int linear_verify_dev(rzk_ctx* c, const C* z, const C* zp, const C* cm, const C* cpm, const C* g, const C* t, const C* tp, const C* u,
+                      const C* d, uint8_t* accept, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !z || !zp || !cm || !cpm || !g || !t || !tp || !u || !d || !accept) return RZK_E_ARG;
+  if (c->n != c->l) return fail(c, RZK_E_ARG, "c1_c2 split needs n == l (reference panics in Mat::add)");
+  const uint32_t n = c->n, k = c->k, l = c->l;
+  const bool rearranged = c->lin_e && !c->small;
+  if constexpr (sizeof(C) == 4) {
+    if (misaligned({z, zp, cm, cpm, g, t, tp, u, d})) return align_fail(c);
+    // (RZK_LIN_E=0: the relation rows carry rotation terms inside row_kernel, which has no 32-bit form)
+    if (!(rearranged && linear_verify_native32(c, false)))
+      return convert_call(c, {{z, nullptr, B * k}, {zp, nullptr, B * k}, {cm, nullptr, B * (n + l)}, {cpm, nullptr, B * (n + l)},
+                              {g, nullptr, B}, {t, nullptr, B * n}, {tp, nullptr, B * n}, {u, nullptr, B * l}, {d, nullptr, B}},
+                          [&](int64_t* const* w) {
+                            return linear_verify_dev<int64_t>(c, w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8], accept, B);
+                          });
+    return linear_rearranged<C>(c, z, zp, cm, cpm, g, t, tp, u, d, accept, B, false);
+  } else {
+    if (rearranged) return linear_rearranged<C>(c, z, zp, cm, cpm, g, t, tp, u, d, accept, B, false);
+    int rc = arena_reserve(c, c->ws, polys(c, 2 * B * l));
+    if (rc != RZK_OK) return rc;
+    int64_t* w1 = (int64_t*)c->ws.p;
+    int64_t* w2 = w1 + B * l * c->N;
+    const std::vector<OpSpec> v1 = {{z, k, 0}, {zp, k, 0}, {t, n, 0}, {tp, n, 0}, {cm, n + l, 0}, {cpm, n + l, 0},
+                                    {d, 1, 0}, {g, 1, 0}, {w1, l, 0}, {w2, l, 0}};
+    // The verdicts are initialised first, then the multiplier's images are prepared (a non-canonical g clears its proof's
+    // verdict: nothing may preset the flags after that), then the rows.
+    rc = check_launch(c, launch_fill_u8(cfg_of(c), accept, 1, B), "flag preset");
+    if (rc != RZK_OK) return rc;
+    rc = prepare_dkey(c, g, B, 1, 2 * l, accept, false);
+    if (rc != RZK_OK) return rc;
+    DkeyScope dkey_scope{c};
+    // linear.rs:218-223: norm predicates on z and zp, fused into the rows that load them when possible (both AND into the
+    // verdicts the fill above has set)
+    rc = run_checked(c, PG_LIN_V1, dkv(c), v1, accept, 1, B, B, c->verify_bound, false, false, {{z, k, 1, 0}, {zp, k, 1, 0}});
+    if (rc != RZK_OK) return rc;
+    return run_program(c, PG_LIN_V2, dkv(c), {{w1, l, 0}, {w2, l, 0}, {g, 1, 0}, {d, 1, 0}, {zp, k, 0}, {u, l, 0}}, accept, 1, B, 0,
+                       false);
+  }
+}
+RZK_BOTH_WIDTHS(linear_verify_dev)
+
+// The recompute step of the short proof: the verifier's launches with the commitment message as output.
+template <class C>
+int linear_recover_dev(rzk_ctx* c, const C* z, const C* zp, const C* cm, const C* cpm, const C* g, const C* d, C* t_out, C* tp_out,
+                       C* u_out, uint8_t* accept, size_t B) {
+  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
+  if (!c || !z || !zp || !cm || !cpm || !g || !d || !t_out || !tp_out || !u_out || !accept) return RZK_E_ARG;
+  if (c->n != c->l) return fail(c, RZK_E_ARG, "c1_c2 split needs n == l (reference panics in Mat::add)");
+  if constexpr (sizeof(C) == 4) {
+    const uint32_t n = c->n, k = c->k, l = c->l;
+    if (misaligned({z, zp, cm, cpm, g, d, t_out, tp_out, u_out})) return align_fail(c);
+    if (!linear_verify_native32(c, true))
+      return convert_call(c, {{z, nullptr, B * k}, {zp, nullptr, B * k}, {cm, nullptr, B * (n + l)}, {cpm, nullptr, B * (n + l)},
+                              {g, nullptr, B}, {d, nullptr, B}, {nullptr, t_out, B * n}, {nullptr, tp_out, B * n}, {nullptr, u_out, B * l}},
+                          [&](int64_t* const* w) {
+                            return linear_recover_dev<int64_t>(c, w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8], accept, B);
+                          });
+  }
+  // on every context (small rings and RZK_LIN_E=0 included): the non-rearranged pair has no recover form
+  return linear_rearranged<C>(c, z, zp, cm, cpm, g, t_out, tp_out, u_out, d, accept, B, true);
+}
+RZK_BOTH_WIDTHS(linear_recover_dev)
+
 }  // namespace rzk::api
 
 extern "C" {
@@ -228,9 +418,10 @@ int rzk_sub_batch_dev(rzk_ctx* c, const int64_t* a, const int64_t* b, int64_t* o
 }
 
 int rzk_norm2_le_batch_dev(rzk_ctx* c, const int64_t* v, uint32_t rows, uint64_t bound, uint8_t* ok, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !v || !ok || rows == 0) return RZK_E_ARG;
-  return run_norm(c, v, rows, bound, ok, B, 0, 0);
+  return norm2_le_dev(c, v, rows, bound, ok, B);
+}
+int rzk_norm2_le32_batch_dev(rzk_ctx* c, const int32_t* v, uint32_t rows, uint64_t bound, uint8_t* ok, size_t B) {
+  return norm2_le_dev(c, v, rows, bound, ok, B);
 }
 
 int rzk_eq_batch_dev(rzk_ctx* c, const int64_t* a, const int64_t* b, uint32_t rows, uint8_t* eq, size_t B) {
@@ -318,92 +509,42 @@ int rzk_open_recover32_batch_dev(rzk_ctx* c, const int32_t* z, const int32_t* cm
   return open_a1_relation_dev(c, z, t_out, cm, d, accept, B, true);
 }
 
-// ---- LinearProof ---------------------------------------------------------------------------------------------------
+// ---- LinearProof, at either width (the templates above) -------------------------------------------------------------
 int rzk_linear_commit_batch_dev(rzk_ctx* c, const int64_t* g, const int64_t* x, const int64_t* r, const int64_t* rp,
                                 const int64_t* y, const int64_t* yp, int64_t* cm, int64_t* cpm, int64_t* t,
                                 int64_t* tp, int64_t* u, uint8_t* ok, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !g || !x || !r || !rp || !y || !yp || !cm || !cpm || !t || !tp || !u) return RZK_E_ARG;
-  const uint32_t n = c->n, k = c->k, l = c->l;
-  int rc = arena_reserve(c, c->ws, polys(c, 2 * B * l));
-  if (rc != RZK_OK) return rc;
-  int64_t* gx = (int64_t*)c->ws.p;
-  int64_t* a2y = gx + B * l * c->N;
-  // the multiplier g of every proof, transformed once for the rows that multiply by it (gx, u)
-  rc = prepare_dkey(c, g, B, 1, 2 * l, nullptr, true);      // l rows of gx, l rows of u
-  if (rc != RZK_OK) return rc;
-  DkeyScope dkey_scope{c};
-  // linear.rs:91-95: gx = x_i * g
-  rc = run_program(c, PG_CMUL, l | dkv(c), {{x, l, 0}, {g, 1, 0}, {gx, l, 0}}, nullptr, 1, B);
-  if (rc != RZK_OK) return rc;
-  const std::vector<OpSpec> c2 = {{x, l, 0}, {gx, l, 0}, {r, k, 0}, {rp, k, 0}, {y, k, 0}, {yp, k, 0}, {cm, n + l, 0},
-                                  {cpm, n + l, 0}, {t, n, 0}, {tp, n, 0}, {a2y, l, 0}};
-  // the norm predicates on r (bit 0 of ok) and rp (bit 1) ride on the commit rows when the kernel path allows; otherwise
-  // bit 0: constraint(r), bit 1: constraint(rp), and the rows clear the byte on non-canonical inputs
-  rc = run_checked(c, PG_LIN_COMMIT2, 0, c2, ok, 1, B, B, c->commit_bound, true, true, {{r, k, 0, 0}, {rp, k, 2, 1}});
-  if (rc != RZK_OK) return rc;
-  return run_program(c, PG_LIN_U, dkv(c), {{a2y, l, 0}, {g, 1, 0}, {yp, k, 0}, {u, l, 0}}, ok, 1, B);
+  return linear_commit_dev(c, g, x, r, rp, y, yp, cm, cpm, t, tp, u, ok, B);
 }
-
-// The y-only half of rzk_linear_commit_batch_dev (linear.rs:118-129): the rows of PG_LIN_COMMIT2 that read y and y' alone
-// (its kMaskVar form: y is transformed once for the a1 and the a2 row) and PG_LIN_U as there.  The arithmetic is exact,
-// so t, tp, u are byte for byte what the commit call writes.  No verdicts: y carries no norm rule; a non-canonical
-// coefficient raises the sticky word as in rzk_matvec_batch_dev.
+int rzk_linear_commit32_batch_dev(rzk_ctx* c, const int32_t* g, const int32_t* x, const int32_t* r, const int32_t* rp,
+                                  const int32_t* y, const int32_t* yp, int32_t* cm, int32_t* cpm, int32_t* t,
+                                  int32_t* tp, int32_t* u, uint8_t* ok, size_t B) {
+  return linear_commit_dev(c, g, x, r, rp, y, yp, cm, cpm, t, tp, u, ok, B);
+}
 int rzk_linear_mask_batch_dev(rzk_ctx* c, const int64_t* g, const int64_t* y, const int64_t* yp, int64_t* t, int64_t* tp,
                               int64_t* u, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !g || !y || !yp || !t || !tp || !u) return RZK_E_ARG;
-  const uint32_t n = c->n, k = c->k, l = c->l;
-  int rc = arena_reserve(c, c->ws, polys(c, B * l));
-  if (rc != RZK_OK) return rc;
-  int64_t* a2y = (int64_t*)c->ws.p;
-  rc = prepare_dkey(c, g, B, 1, l, nullptr, true);   // l rows of u
-  if (rc != RZK_OK) return rc;
-  DkeyScope dkey_scope{c};
-  // (operands at the places PG_LIN_COMMIT2 gives them; the masks-only form reads none of x, gx, r, rp and writes no c, cp)
-  const std::vector<OpSpec> m2 = {{nullptr, l, 0}, {nullptr, l, 0}, {nullptr, k, 0}, {nullptr, k, 0}, {y, k, 0}, {yp, k, 0},
-                                  {nullptr, n + l, 0}, {nullptr, n + l, 0}, {t, n, 0}, {tp, n, 0}, {a2y, l, 0}};
-  rc = run_program(c, PG_LIN_COMMIT2, kMaskVar, m2, nullptr, 1, B);
-  if (rc != RZK_OK) return rc;
-  return run_program(c, PG_LIN_U, dkv(c), {{a2y, l, 0}, {g, 1, 0}, {yp, k, 0}, {u, l, 0}}, nullptr, 1, B);
+  return linear_mask_dev(c, g, y, yp, t, tp, u, B);
 }
-
+int rzk_linear_mask32_batch_dev(rzk_ctx* c, const int32_t* g, const int32_t* y, const int32_t* yp, int32_t* t, int32_t* tp,
+                                int32_t* u, size_t B) {
+  return linear_mask_dev(c, g, y, yp, t, tp, u, B);
+}
 int rzk_linear_response_batch_dev(rzk_ctx* c, const int64_t* y, const int64_t* yp, const int64_t* r,
                                   const int64_t* rp, const int64_t* d, int64_t* z, int64_t* zp, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !y || !yp || !r || !rp || !d || !z || !zp) return RZK_E_ARG;
-  const uint32_t k = c->k;
-  return run_program(c, PG_RESPONSE, 2, {{d, 1, 0}, {y, k, 0}, {r, k, 0}, {z, k, 0}, {yp, k, 0}, {rp, k, 0}, {zp, k, 0}},
-                     nullptr, 1, B);
+  return linear_response_dev(c, y, yp, r, rp, d, z, zp, B);
 }
-
+int rzk_linear_response32_batch_dev(rzk_ctx* c, const int32_t* y, const int32_t* yp, const int32_t* r,
+                                    const int32_t* rp, const int32_t* d, int32_t* z, int32_t* zp, size_t B) {
+  return linear_response_dev(c, y, yp, r, rp, d, z, zp, B);
+}
 int rzk_linear_verify_batch_dev(rzk_ctx* c, const int64_t* z, const int64_t* zp, const int64_t* cm,
                                 const int64_t* cpm, const int64_t* g, const int64_t* t, const int64_t* tp,
                                 const int64_t* u, const int64_t* d, uint8_t* accept, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !z || !zp || !cm || !cpm || !g || !t || !tp || !u || !d || !accept) return RZK_E_ARG;
-  if (c->n != c->l) return fail(c, RZK_E_ARG, "c1_c2 split needs n == l (reference panics in Mat::add)");
-  const uint32_t n = c->n, k = c->k, l = c->l;
-  if (c->lin_e && !c->small) return linear_rearranged(c, z, zp, cm, cpm, g, t, tp, u, d, accept, B, false);
-  int rc = arena_reserve(c, c->ws, polys(c, 2 * B * l));
-  if (rc != RZK_OK) return rc;
-  int64_t* w1 = (int64_t*)c->ws.p;
-  int64_t* w2 = w1 + B * l * c->N;
-  const std::vector<OpSpec> v1 = {{z, k, 0}, {zp, k, 0}, {t, n, 0}, {tp, n, 0}, {cm, n + l, 0}, {cpm, n + l, 0},
-                                  {d, 1, 0}, {g, 1, 0}, {w1, l, 0}, {w2, l, 0}};
-  // The verdicts are initialised first, then the multiplier's images are prepared (a non-canonical g clears its proof's
-  // verdict: nothing may preset the flags after that), then the rows.
-  rc = check_launch(c, launch_fill_u8(cfg_of(c), accept, 1, B), "flag preset");
-  if (rc != RZK_OK) return rc;
-  rc = prepare_dkey(c, g, B, 1, 2 * l, accept, false);
-  if (rc != RZK_OK) return rc;
-  DkeyScope dkey_scope{c};
-  // linear.rs:218-223: norm predicates on z and zp, fused into the rows that load them when possible (both AND into the
-  // verdicts the fill above has set)
-  rc = run_checked(c, PG_LIN_V1, dkv(c), v1, accept, 1, B, B, c->verify_bound, false, false, {{z, k, 1, 0}, {zp, k, 1, 0}});
-  if (rc != RZK_OK) return rc;
-  return run_program(c, PG_LIN_V2, dkv(c), {{w1, l, 0}, {w2, l, 0}, {g, 1, 0}, {d, 1, 0}, {zp, k, 0}, {u, l, 0}}, accept, 1, B, 0,
-                     false);
+  return linear_verify_dev(c, z, zp, cm, cpm, g, t, tp, u, d, accept, B);
+}
+int rzk_linear_verify32_batch_dev(rzk_ctx* c, const int32_t* z, const int32_t* zp, const int32_t* cm,
+                                  const int32_t* cpm, const int32_t* g, const int32_t* t, const int32_t* tp,
+                                  const int32_t* u, const int32_t* d, uint8_t* accept, size_t B) {
+  return linear_verify_dev(c, z, zp, cm, cpm, g, t, tp, u, d, accept, B);
 }
 
 // ---- SumProof ------------------------------------------------------------------------------------------------------
@@ -512,11 +653,12 @@ int rzk_sum_verify_batch_dev(rzk_ctx* c, uint32_t V, const int64_t* zs, const in
 int rzk_linear_recover_batch_dev(rzk_ctx* c, const int64_t* z, const int64_t* zp, const int64_t* cm, const int64_t* cpm,
                                  const int64_t* g, const int64_t* d, int64_t* t_out, int64_t* tp_out, int64_t* u_out,
                                  uint8_t* accept, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !z || !zp || !cm || !cpm || !g || !d || !t_out || !tp_out || !u_out || !accept) return RZK_E_ARG;
-  if (c->n != c->l) return fail(c, RZK_E_ARG, "c1_c2 split needs n == l (reference panics in Mat::add)");
-  // on every context (small rings and RZK_LIN_E=0 included): the non-rearranged pair has no recover form
-  return linear_rearranged(c, z, zp, cm, cpm, g, t_out, tp_out, u_out, d, accept, B, true);
+  return linear_recover_dev(c, z, zp, cm, cpm, g, d, t_out, tp_out, u_out, accept, B);
+}
+int rzk_linear_recover32_batch_dev(rzk_ctx* c, const int32_t* z, const int32_t* zp, const int32_t* cm, const int32_t* cpm,
+                                   const int32_t* g, const int32_t* d, int32_t* t_out, int32_t* tp_out, int32_t* u_out,
+                                   uint8_t* accept, size_t B) {
+  return linear_recover_dev(c, z, zp, cm, cpm, g, d, t_out, tp_out, u_out, accept, B);
 }
 
 int rzk_sum_recover_batch_dev(rzk_ctx* c, uint32_t V, const int64_t* zs, const int64_t* zp, const int64_t* cs,

@@ -13,6 +13,7 @@ namespace rzk {
 // the running sum staying in registers across the terms and the Garner word A staying in LDS (measured against
 // unit_kernel's parked sums and global state lines: 1.36 vs 1.85 ms per launch for the Sum rows at (4,9,4), V = 8).
 // Primes one after the other; the first pass measures the operands (prime count, canonical test, norm marks).
+// The coefficient type of the slabs comes with the team (TeamCoef, rzk_wave.h), as in unit_kernel.
 // =============================================================================================
 template <int LOGN, bool HAS_SHIFT, class TM = WaveTeam, bool DD = false>
 __global__ void __launch_bounds__(TM::kTeamsPerBlock << TM::LL, (LOGN <= 10 || TM::LL == 7 ? 4 : 1))   // N <= 1024 and teams of two: hold the 4 waves per SIMD the LDS allows
@@ -20,6 +21,7 @@ row_kernel(const Program* __restrict__ prog, const Operands ops, const uint32_t*
            const double* __restrict__ key_l2, const DevTables* __restrict__ Tp, const uint32_t* __restrict__ tw_all,
            uint32_t* __restrict__ scratch, uint8_t* __restrict__ flags, const uint32_t ntasks) {
   using G = Geo<LOGN, TM::LL>;
+  using C = typename TeamCoef<TM>::type;   // coefficient type of the slabs
   constexpr int E = G::E;
   constexpr int N = G::N;
   constexpr bool OPQ = true;   // opaque lane ids: no hoisted address registers
@@ -61,7 +63,7 @@ row_kernel(const Program* __restrict__ prog, const Operands ops, const uint32_t*
 #pragma unroll 1
       for (uint32_t t = 0; t < row.nshift; ++t) {
         const Term tm = table_load(&prog->terms[row.term0 + row.nterms + t]);
-        const int64_t* __restrict__ pa = operand_ptr(ops, tm.a_op, tm.a_off, b, bo, N);
+        const C* __restrict__ pa = operand_ptr<C>(ops, tm.a_op, tm.a_off, b, bo, N);
         int32_t a[E];
         if (trusted) {
 #pragma unroll
@@ -72,7 +74,7 @@ row_kernel(const Program* __restrict__ prog, const Operands ops, const uint32_t*
           for (int e = 0; e < E; ++e) a[e] = canon_lo_mx(pa[G::j_p1(lane, e)], qhalf, abad, amx);
           fault = fault || canon_fail(abad, amx, qhalf);
         }
-        shift_product<LOGN, false, true, TM>(st_sh, t == 0, tm.sign < 0, a, operand_ptr(ops, tm.b_op, tm.b_off, b, bo, N), lane,
+        shift_product<LOGN, false, true, TM, kShiftH, C>(st_sh, t == 0, tm.sign < 0, a, operand_ptr<C>(ops, tm.b_op, tm.b_off, b, bo, N), lane,
                                          reinterpret_cast<int32_t*>(lds), T, fault, trusted);
       }
       if (fault) input_fault(ops, flags, bo, lane);
@@ -98,7 +100,7 @@ row_kernel(const Program* __restrict__ prog, const Operands ops, const uint32_t*
         inverse_and_fold<LOGN, OPQ, TM>(pi, np, acc, lane, lds, twf + kTableLen, pc, st_lds, st_glb, T);
       }
     }
-    row_epilogue<LOGN, TM>(prog, row, ops, b, bo, lane, has_terms, np, st_lds, T, flags, has_shift ? st_sh : nullptr);
+    row_epilogue<LOGN, TM, C>(prog, row, ops, b, bo, lane, has_terms, np, st_lds, T, flags, has_shift ? st_sh : nullptr);
   }
 }
 

@@ -574,7 +574,8 @@ __device__ __forceinline__ void store_operand_image(const uint32_t* x, const Ope
   }
 }
 
-// acc +/- (term) for prime `pi`, transforming the term's operands in the wave.
+// acc +/- (term) for prime `pi`, transforming the term's operands in the wave.  The coefficient type of the operands comes
+// with the team (TeamCoef, rzk_wave.h).
 template <int LOGN, bool HAS_VEC, bool OPQ = false, class TM = WaveTeam, bool DD = false>
 __device__ __forceinline__ void term_direct(uint32_t* acc, const Term tm, const Operands& ops, uint32_t b,
                                             uint32_t bo, int lane, uint32_t* lds, const uint32_t* __restrict__ twf,
@@ -582,6 +583,7 @@ __device__ __forceinline__ void term_direct(uint32_t* acc, const Term tm, const 
                                             const double* __restrict__ key_l2, bool first, float& bound,
                                             uint8_t* __restrict__ flags, uint32_t qhalf) {
   using G = Geo<LOGN, TM::LL>;
+  using C = typename TeamCoef<TM>::type;   // coefficient type of the slabs
   constexpr int E = G::E;
   constexpr int N = G::N;
   // optional opaque copy of the lane id (RZK_OPAQUE): stops hoisting of lane-dependent addresses
@@ -613,7 +615,7 @@ __device__ __forceinline__ void term_direct(uint32_t* acc, const Term tm, const 
     }
     nb = (float)ops.oimg_l2[oslot];
   } else {
-    load_lift<LOGN, TM, kRowLoadMode<TM>>(x, operand_ptr(ops, tm.b_op, tm.b_off, b, bo, N), ln, pc, first, nb, chk, ops.norm_limit, below, qhalf, trusted, fault);
+    load_lift<LOGN, TM, kRowLoadMode<TM>, C>(x, operand_ptr<C>(ops, tm.b_op, tm.b_off, b, bo, N), ln, pc, first, nb, chk, ops.norm_limit, below, qhalf, trusted, fault);
     if (chk && !below && (lane & 63) == 0) fail_check(flags + bo, ops.pad != 0, (tm.kind & TERM_CHECK2) != 0);
     wave_fwd<LOGN, TM>(x, ln, lds, twf, pc);
   }
@@ -624,7 +626,7 @@ __device__ __forceinline__ void term_direct(uint32_t* acc, const Term tm, const 
     for (int c = 0; c < E; ++c) xb[c] = csub(mont_lazy(x[c], pc.ninv_r2, pc.p, pc.npinv), pc.p);
     float na = 0.f;
     bool unused_below = true;
-    load_lift<LOGN, TM, kRowLoadMode<TM>>(x, operand_ptr(ops, tm.a_op, tm.a_off, b, bo, N), ln, pc, first, na, false, 0, unused_below, qhalf, trusted, fault);
+    load_lift<LOGN, TM, kRowLoadMode<TM>, C>(x, operand_ptr<C>(ops, tm.a_op, tm.a_off, b, bo, N), ln, pc, first, na, false, 0, unused_below, qhalf, trusted, fault);
     wave_fwd<LOGN, TM>(x, ln, lds, twf, pc);
     if (first) bound = bound_fma(na, nb, bound);   // |a (*) b|_inf <= |a|_2 |b|_2
     if (tm.sign >= 0) {

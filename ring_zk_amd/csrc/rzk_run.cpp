@@ -228,7 +228,8 @@ int run_program_lowered(rzk_ctx* c, int id, uint32_t var, const OpList& specs, u
       break;
     }
     case Path::Rows:
-      lrc = launch_rows(logn, cfg, a, ops, dp.nrows, dp.has_shift, batch, dp.has_dd);
+      lrc = width == 4 ? launch_rows32(logn, cfg, a, ops, dp.nrows, dp.has_shift, batch, dp.has_dd)
+                       : launch_rows(logn, cfg, a, ops, dp.nrows, dp.has_shift, batch, dp.has_dd);
       break;
     case Path::Units: {
       const UnitShape u{dp.nunits, upt, 2 * dp.work, dp.has_vec, dp.has_shift};
@@ -283,6 +284,22 @@ bool checked_fuses(rzk_ctx* c, int id, uint32_t var, uint64_t bound) {
   return !dp.two_bit;   // (two-bit verdicts depend on the flag array's alignment: not asked for here)
 }
 
+bool checked_native32(rzk_ctx* c, int id, uint32_t var, uint64_t bound, bool has_flags) {
+  if (!program_native32(c, id, var)) return false;
+  if (!has_flags) return true;
+  if (!norm_native32(c)) return false;
+  if (!fused_limit(c, bound)) return true;   // never fuses
+  DevProg dp;
+  if (get_program(c, id, var | 1, dp) != RZK_OK) {   // no fused form: the fallback runs
+    c->err.clear();
+    return true;
+  }
+  return native32(c, dp);
+}
+
+// The stand-alone norm kernel exists for 32-bit slabs where the native row kernels do (norm_kernel_i32, rzk_slab32_dev.hip)
+bool norm_native32(const rzk_ctx* c) { return !c->small && (c->logn == 9 || c->logn == 10); }
+
 // A program whose rows decide a norm predicate of `bound` into `flags` (nflags of them, one per proof): the checked
 // variant with the predicate fused into the rows that load the vector anyway; where that cannot run (small rings, a
 // bound past 2^24, no flags, a shape or flag array the fused form does not cover) the norm kernels of `norms`, in their
@@ -293,10 +310,11 @@ int run_checked_lowered(rzk_ctx* c, int id, uint32_t var, const OpList& specs, u
                         uint64_t nflags, uint64_t bound, bool preset, bool sticky, std::initializer_list<NormSpec> norms) {
   int rc = run_program_checked(c, id, var, specs, flags, group, batch, nflags, bound, preset, sticky);
   if (rc != RZK_E_UNSUPPORTED) return rc;
-  if (specs.width != 8 && flags) return fail(c, RZK_E_STATE, "the norm kernels read 64-bit slabs");   // (the 32-bit entry points ask checked_fuses first)
+  // (width 4: norm_kernel_i32, on the contexts whose 32-bit calls run natively)
   for (const NormSpec& n : norms) {
     if (!flags) break;
-    rc = run_norm(c, n.v, n.rows, bound, flags, nflags, n.mode, n.shift, sticky);
+    rc = specs.width == 4 ? run_norm(c, static_cast<const int32_t*>(n.v), n.rows, bound, flags, nflags, n.mode, n.shift, sticky)
+                          : run_norm(c, static_cast<const int64_t*>(n.v), n.rows, bound, flags, nflags, n.mode, n.shift, sticky);
     if (rc != RZK_OK) return rc;
   }
   return run_program_lowered(c, id, var, specs, flags, group, batch, 0, sticky, 0, 0, nullptr);
@@ -309,7 +327,7 @@ int run_checked_lowered(rzk_ctx* c, int id, uint32_t var, const OpList& specs, u
 // uses: rows of this call that multiply by each multiplier.  The forward launch costs three transforms per multiplier and
 // a launch of its own; measured: Linear at l = 1 (2 uses) gains nothing, the Sum shapes (9 and 17 uses) 14-15 %.
 constexpr uint32_t kDkeyMinUses = 4;
-static bool dkey_wanted(const rzk_ctx* c, uint32_t uses) {
+bool dkey_wanted(const rzk_ctx* c, uint32_t uses) {
   return !(c->use_dkey <= 0 || (c->use_dkey == 1 && uses < kDkeyMinUses) || c->small);
 }
 int prepare_dkey(rzk_ctx* c, const int64_t* g, uint64_t entries, uint32_t per_entry, uint32_t uses, uint8_t* flags, bool sticky) {
@@ -366,8 +384,8 @@ int prepare_oimg(rzk_ctx* c, uint64_t B, uint32_t V, uint32_t uses) {
   return RZK_OK;
 }
 
-int run_norm(rzk_ctx* c, const int64_t* v, uint32_t rows, uint64_t bound, uint8_t* ok, uint64_t B, int mode, int shift,
-             bool sticky) {
+template <class C>
+int run_norm(rzk_ctx* c, const C* v, uint32_t rows, uint64_t bound, uint8_t* ok, uint64_t B, int mode, int shift, bool sticky) {
   // canonical coefficients are below 2^31 in magnitude, so sum c^2 < 2^73: every bound from 2^37 on holds for
   // all inputs; clamping there keeps (bound+1)^2 inside 128 bits for any u64 bound (sigma grows with b)
   if (bound > (1ull << 40)) bound = 1ull << 40;
@@ -375,10 +393,18 @@ int run_norm(rzk_ctx* c, const int64_t* v, uint32_t rows, uint64_t bound, uint8_
   norm_limit(bound, hi, lo);
   uint32_t* bad = sticky ? c->d_bad : nullptr;
   const uint32_t qh = c->hT.crt.qhalf;
-  if (c->small)
-    return check_launch(c, launch_norm_small(c->N, cfg_of(c), v, rows, hi, lo, ok, B, mode, shift, qh, bad), "norm kernel");
-  return check_launch(c, launch_norm((int)c->logn, cfg_of(c), v, rows, hi, lo, ok, B, mode, shift, qh, bad), "norm kernel");
+  if constexpr (sizeof(C) == 4) {   // in a profiling slot of its own: the tests tell the 32-bit launch by its name
+    if (c->small) return fail(c, RZK_E_STATE, "no 32-bit norm kernel for small rings");
+    return run_profiled(c, (uint64_t)B * rows * c->N * sizeof(C), "norm kernel", [&](const LaunchCfg& cfg) {
+      return launch_norm32((int)c->logn, cfg, v, rows, hi, lo, ok, B, mode, shift, qh, bad);
+    });
+  } else {
+    if (c->small)
+      return check_launch(c, launch_norm_small(c->N, cfg_of(c), v, rows, hi, lo, ok, B, mode, shift, qh, bad), "norm kernel");
+    return check_launch(c, launch_norm((int)c->logn, cfg_of(c), v, rows, hi, lo, ok, B, mode, shift, qh, bad), "norm kernel");
+  }
 }
+RZK_BOTH_WIDTHS(run_norm)
 
 // sum_i g_i (.) (a2.v_i) - a2.v'  (sum.rs:154-160, 301-308) evaluated as a2.(sum_i g_i (.) v_i - v'): V matrix-vector
 // products (each with its inverse transforms) become one, for (columns of a2) instead of l rows of V vector x vector

@@ -35,6 +35,9 @@ RZK_S32_HD bool slab64_canonical(int64_t c, uint32_t half) { return (uint64_t)c 
 // polynomial's coefficients before the compare.
 RZK_S32_HD uint32_t slab32_test_word(int32_t c, uint32_t half) { return (uint32_t)c + half; }
 RZK_S32_HD bool slab32_canonical(int32_t c, uint32_t half) { return slab32_test_word(c, half) <= 2u * half; }
+// |c| as the 32-bit norm kernel squares it (norm_rows<., int32_t>, rzk_norm.h, behind norm_kernel_i32): below 2^31 for every canonical c; INT32_MIN
+// gives 2^31, and is not canonical for any modulus
+RZK_S32_HD uint32_t slab32_abs(int32_t c) { return c < 0 ? 0u - (uint32_t)c : (uint32_t)c; }
 
 // narrow: the low word; *fault is set (never cleared) when c is not canonical
 RZK_S32_HD int32_t slab32_narrow(int64_t c, uint32_t half, bool* fault) {
@@ -48,9 +51,12 @@ RZK_S32_HD int64_t slab32_widen(int32_t c) { return (int64_t)c; }
 // at N = 512 and N = 1024 of
 //   unit_kernel / unit_io_kernel   key-product programs (no vector x vector items), with or without rotation terms
 //   shift_row_kernel               the packed-byte form (RZK_SHIFT_BYTES, the default)
+//   row_kernel                     programs with vector x vector items and no rotation terms (Linear: gx, u, the verifier's
+//                                  last program)
 // Everything else — small rings, N = 2048 (two-wavefront teams), row groups / blocks / slots (n >= 2, the split
-// relation), row_kernel, the word-only rotation kernel, programs that multiply by prepared images — takes the convert
-// path: the call widens its inputs into the context's arena, runs the 64-bit launches and narrows the outputs.
+// relation), row_kernel with rotation terms, the word-only rotation kernel, programs that multiply by prepared images —
+// takes the convert path: the call widens its inputs into the context's arena, runs the 64-bit launches and narrows the
+// outputs.
 // The native instantiations are those of a context with its default rotation knobs at n = 1: a context with RZK_SHIFT=0
 // or RZK_SHIFT_BYTES=0, or with n >= 2, converts every 32-bit call (one rule per context, not one per program).
 enum Slab32Path : int { S32_UNITS = 0, S32_SHIFT = 1, S32_OTHER = 2 };   // what path_of (rzk_plan.h) names: Units, Shift, anything else
@@ -61,12 +67,17 @@ struct Slab32Facts {
   uint32_t n;        // rows of a1 (the context's n)
   bool rot;          // challenge products run as rotations (shift_ok, rzk_run.cpp)
   bool shift_bytes;  // ... of short operands as packed bytes (RZK_SHIFT_BYTES)
+  bool rows;         // path == S32_OTHER and it is row_kernel (none of blocks / groups / slots)
+  bool has_shift;    // rotation terms inside the rows (PlanFacts::has_shift)
 };
-// plan facts (PlanFacts, rzk_plan.h) and what path_of made of them -> Slab32Facts
+// plan facts (PlanFacts, rzk_plan.h) and what path_of made of them -> Slab32Facts.  Of the paths that are neither Units nor
+// Shift, row_kernel is the one path_of names when the plan has no blocks, groups or slots (the order of its tests); small
+// rings never get that far (slab32_native).
 template <class PlanFactsT>
 inline Slab32Facts slab32_facts(const PlanFactsT& f, bool path_units, bool path_shift, uint32_t n, bool rot, bool shift_bytes) {
+  const bool other = !path_units && !path_shift;
   return Slab32Facts{path_units ? S32_UNITS : (path_shift ? S32_SHIFT : S32_OTHER), f.has_vec, f.has_dkey || f.has_dd, n, rot,
-                     shift_bytes};
+                     shift_bytes, other && !f.nblocks && !f.ngroups && !f.nslots, f.has_shift};
 }
 // small: N < 512 (schoolbook kernels); team_ll: log2 of the threads that share a polynomial (6: one wavefront)
 RZK_S32_HD bool slab32_native(const Slab32Facts& f, uint32_t logn, bool small, int team_ll) {
@@ -74,6 +85,7 @@ RZK_S32_HD bool slab32_native(const Slab32Facts& f, uint32_t logn, bool small, i
   if (f.n != 1 || !f.rot || !f.shift_bytes) return false;
   if (f.has_images) return false;
   if (f.path == S32_SHIFT) return true;   // (its products are per-proof polynomials by definition: has_vec says nothing)
+  if (f.rows) return !f.has_shift;        // row_kernel<., false, i32, false>: vector x vector items allowed
   return f.path == S32_UNITS && !f.has_vec;
 }
 

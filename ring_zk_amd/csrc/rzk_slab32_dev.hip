@@ -8,6 +8,13 @@
 //                    (slab32_native).  Started by the launchers of the 64-bit kernels (launch_units_t, launch_units_io_t,
 //                    launch_shift_t, rzk_launch.h) with WaveTeam32 / WaveTeam32Tw as the team; only the dispatchers
 //                    launch_units32 / launch_shift_rows32 are here.  Reported as "unit_kernel<10, false, true, i32>" etc.
+//   row_kernel<LOGN, false, WaveTeam32, false>
+//                    the vector x vector programs of Linear (gx = g.x, u, the verifier's last program) on 32-bit slabs:
+//                    the kernel of rzk_row.h with the 32-bit team, without rotation terms, started by launch_rows_t
+//                    (rzk_launch.h) from launch_rows32.  Reported as "row_kernel<9, false, i32, false>".
+//   norm_kernel_i32  the stand-alone norm predicate (norm_rows, rzk_norm.h) on an int32_t slab: where a checked program's
+//                    fused form cannot run (two-bit verdicts on a flag array that is not made of whole aligned words)
+//                    and behind rzk_norm2_le32_batch.  Reported as "norm_kernel_i32<9>".
 //   narrow_kernel    int64 slab -> int32 slab (the low words), with the canonical test of the 64-bit kernels or without
 //   widen_kernel     int32 slab -> int64 slab (sign extension)
 //                    plain streaming kernels, two coefficients per thread and trip: 16-byte accesses on the wide side,
@@ -20,6 +27,7 @@
 #include <string>
 
 #include "rzk_dev.h"
+#include "rzk_norm.h"
 #include "rzk_row.h"
 #include "rzk_rowprog.h"
 #include "rzk_unit.h"
@@ -70,6 +78,13 @@ __global__ void __launch_bounds__(64 * kEqWaves) eq32_kernel(const int4* __restr
   }
 }
 
+template <int LOGN>
+__global__ void __launch_bounds__(256)
+norm_kernel_i32(const int32_t* __restrict__ v, uint32_t rows, uint64_t limit_hi, uint64_t limit_lo, uint8_t* __restrict__ ok,
+                uint64_t B, int and_mode, int shift, uint32_t qhalf, uint32_t* __restrict__ bad_word) {
+  norm_rows<LOGN, int32_t>(v, rows, limit_hi, limit_lo, ok, B, and_mode, shift, qhalf, bad_word);
+}
+
 unsigned stream_grid(uint64_t npairs, int num_cus) {
   uint64_t blocks = (npairs + 255) / 256;
   const uint64_t cap = (uint64_t)num_cus * 8;
@@ -117,6 +132,40 @@ int launch_shift_rows32(int logn, const LaunchCfg& cfg, const RowArgs& a, const 
     case 10: return launch_shift_t<10, WaveTeam32>(cfg, a, ops, ntasks);
   }
   return -1;
+}
+
+// row_kernel on 32-bit slabs: no rotation terms, no operand images (slab32_native)
+int launch_rows32(int logn, const LaunchCfg& cfg, const RowArgs& a, const Operands& ops, uint32_t nrows, bool has_shift, uint64_t batch,
+                  bool has_dd) {
+  uint32_t ntasks;
+  if (const int rc = task_count(batch, nrows, ntasks); rc <= 0) return rc;
+  if (has_shift || has_dd) return -1;
+  switch (logn) {
+    case 9: return launch_rows_t<9, false, WaveTeam32>(cfg, a, ops, ntasks);
+    case 10: return launch_rows_t<10, false, WaveTeam32>(cfg, a, ops, ntasks);
+  }
+  return -1;
+}
+
+// launch_norm (rzk_kernels.hip) on an int32_t slab: the same grid, one wavefront per proof
+int launch_norm32(int logn, const LaunchCfg& cfg, const int32_t* v, uint32_t rows, uint64_t limit_hi, uint64_t limit_lo, uint8_t* ok,
+                  uint64_t B, int and_mode, int shift, uint32_t qhalf, uint32_t* bad_word) {
+  if (B == 0) return 0;
+  const unsigned grid = grid_for(B, cfg.num_cus);
+  switch (logn) {
+    case 9:
+      hipLaunchKernelGGL(norm_kernel_i32<9>, dim3(grid), dim3(256), 0, (hipStream_t)cfg.stream, v, rows, limit_hi, limit_lo, ok, B,
+                         and_mode, shift, qhalf, bad_word);
+      break;
+    case 10:
+      hipLaunchKernelGGL(norm_kernel_i32<10>, dim3(grid), dim3(256), 0, (hipStream_t)cfg.stream, v, rows, limit_hi, limit_lo, ok, B,
+                         and_mode, shift, qhalf, bad_word);
+      break;
+    default: return -1;
+  }
+  RZK_LAUNCH_CHECK();
+  if (cfg.launched) *cfg.launched = "norm_kernel_i32<" + std::to_string(logn) + ">";
+  return 0;
 }
 
 int launch_narrow(const LaunchCfg& cfg, const int64_t* in, int32_t* out, uint64_t ncoef, uint32_t qhalf, uint32_t* bad_word) {

@@ -1,6 +1,7 @@
 // rzk_xform.h - transforms and element-wise kernels: key, dkey, ntt, addsub, norm, eq, and the small-ring (N < 512) kernels.
 // Part of the one translation unit rzk_kernels.hip (device code only; no include guards beyond #pragma once).
 #pragma once
+#include "rzk_norm.h"
 #include "rzk_rowprog.h"
 
 namespace rzk {
@@ -200,56 +201,14 @@ addsub_kernel(const int64_t* a, const int64_t* b, int64_t* out, uint64_t n2, int
   if (fault && bad_word) *bad_word = 1u;
 }
 
-// One wavefront per proof: all `rows` polynomials must satisfy sum c^2 < limit (= (bound+1)^2),
-// i.e. floor(sqrt(sum c^2)) <= bound (src/polynomial.rs:60-73, src/params.rs:105-107).
-// The sum is exact: c^2 split into 32-bit halves, accumulated in two 64-bit lane sums.
+// The norm predicate of `rows` polynomials per proof, one wavefront per proof: norm_rows (rzk_norm.h), on int64_t slabs.
+// (Its int32_t form is norm_kernel_i32, rzk_slab32_dev.hip.)
 template <int LOGN>
 __global__ void __launch_bounds__(256)
 norm_kernel(const int64_t* __restrict__ v, uint32_t rows, uint64_t limit_hi, uint64_t limit_lo,
             uint8_t* __restrict__ ok, uint64_t B, int and_mode, int shift, uint32_t qhalf,
             uint32_t* __restrict__ bad_word) {
-  using G = Geo<LOGN>;
-  constexpr int E = G::E;
-  constexpr int N = G::N;
-  const int lane = threadIdx.x & 63;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  for (uint64_t b = (uint64_t)blockIdx.x * 4 + wave; b < B; b += (uint64_t)gridDim.x * 4) {
-    int good = 1;
-    for (uint32_t r = 0; r < rows; ++r) {
-      const int64_t* __restrict__ p = v + (b * rows + r) * N;
-      uint64_t slo = 0, shi = 0;
-      int huge = 0;   // a coefficient outside the centred range: not a ZqI64 value, the predicate fails
-#pragma unroll
-      for (int e = 0; e < E; ++e) {
-        const int64_t c = p[G::j_p1(lane, e)];
-        const uint64_t a = c < 0 ? 0ull - (uint64_t)c : (uint64_t)c;
-        huge |= a > (uint64_t)qhalf;
-        const uint64_t al = a & 0xffffffffu;
-        const uint64_t ll = al * al;
-        slo += ll & 0xffffffffu;
-        shi += ll >> 32;
-      }
-      slo = wave_sum_u64(slo);
-      shi = wave_sum_u64(shi);
-      // total = shi * 2^32 + slo  (shi, slo < 2^50)
-      const uint64_t t_lo32 = slo & 0xffffffffu;
-      const uint64_t mid = shi + (slo >> 32);
-      const uint64_t tot_lo = (mid << 32) | t_lo32;
-      const uint64_t tot_hi = mid >> 32;
-      const int lt = (tot_hi < limit_hi) || (tot_hi == limit_hi && tot_lo < limit_lo);
-      const int any_huge = __any(huge);
-      good &= lt && !any_huge;
-      if (any_huge && bad_word && lane == 0) *bad_word = 1u;
-    }
-    if (lane == 0) {
-      if (and_mode == 0)
-        ok[b] = (uint8_t)good;
-      else if (and_mode == 1)
-        ok[b] = (uint8_t)(ok[b] & good);
-      else
-        ok[b] = (uint8_t)(ok[b] | (good << shift));
-    }
-  }
+  norm_rows<LOGN, int64_t>(v, rows, limit_hi, limit_lo, ok, B, and_mode, shift, qhalf, bad_word);
 }
 
 template <int LOGN>

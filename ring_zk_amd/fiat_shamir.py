@@ -23,6 +23,9 @@ rzk_fs_challenge_batch[_dev]): a proof is (commitment message, response), and an
     (Context.reject, DESIGN.md §12): a response is released only once it passed, with a fresh y per attempt;
   * `open_prove_sampled32`, `open_prove_zk32`: the sampled and the zero-knowledge Open prover on int32 slabs with a
     `backend.KeyedSampler32` (DESIGN.md §20);
+  * `linear_prove32`, `linear_verify32`, `linear_short32`, `linear_verify_short32`, `linear_verify_packed32`,
+    `linear_verify_short_packed32`, `linear_prove_sampled32`, `linear_prove_zk32`: the Linear proof on int32 slabs
+    (DESIGN.md §25);
   * `open_prove_zk_native`: open_prove_zk / open_prove_zk32 with the rejection loop inside the library, one call
     (rzk_open_prove_zk[32]_batch_dev, DESIGN.md §21);
   * `linear_prove_zk_native`, `sum_prove_zk_native`: the same for linear_prove_zk / sum_prove_zk
@@ -288,47 +291,112 @@ def open_verify_short_packed32(ctx, records, aux=None):
 
 
 # ---- LinearProof (src/prove/linear.rs) ---------------------------------------------------------------------------------
+# Written once over the record of operations at one width, as the Open functions: on int32 slabs every slab is
+# int32, and at (1, k, 1), N = 512 and 1024 no 64-bit slab and no convert launch appears between record and verdict.
+_LinearOps = namedtuple("_LinearOps", "suffix challenge decode same_challenge coins commit response response_reject verify recover")
+
+
+def _linear_ops(suffix, challenge_, decode, same_challenge, coins):
+    names = ("linear_commit", "linear_response", "linear_response_reject", "linear_verify", "linear_recover")
+    return _LinearOps(suffix, challenge_, decode, same_challenge, coins, *[_method(m + suffix) for m in names])
+
+
+def _linear_prove(w, ctx, g, x, r, rp, y, yp, aux):
+    c, cp, t, tp, u, ok = w.commit(ctx, g, x, r, rp, y, yp)
+    d, _, okf = w.challenge(ctx, MSG_LINEAR_COMMITMENT, c, cp, g, t, tp, u, aux=aux)
+    z, zp = w.response(ctx, y, yp, r, rp, d)
+    return c, cp, t, tp, u, z, zp, _flag(ok == 3) & okf
+
+
+def _linear_verify(w, ctx, c, cp, g, t, tp, u, z, zp, aux):
+    d, _, okf = w.challenge(ctx, MSG_LINEAR_COMMITMENT, c, cp, g, t, tp, u, aux=aux)
+    return w.verify(ctx, z, zp, c, cp, g, t, tp, u, d) & okf
+
+
+def _linear_verify_packed(w, ctx, commitment_records, response_records, aux):
+    c, cp, g, t, tp, u, ok1 = w.decode(ctx, MSG_LINEAR_COMMITMENT, commitment_records)
+    z, zp, ok2 = w.decode(ctx, MSG_LINEAR_RESPONSE, response_records)
+    return _linear_verify(w, ctx, c, cp, g, t, tp, u, z, zp, aux) & ok1 & ok2
+
+
+def _linear_short(w, ctx, c, cp, g, t, tp, u, z, zp, aux):
+    d, _, _ = w.challenge(ctx, MSG_LINEAR_COMMITMENT, c, cp, g, t, tp, u, aux=aux)
+    return d
+
+
+def _linear_verify_short(w, ctx, c, cp, g, d, z, zp, aux):
+    t, tp, u, acc = w.recover(ctx, z, zp, c, cp, g, d)
+    d2, _, okf = w.challenge(ctx, MSG_LINEAR_COMMITMENT, c, cp, g, t, tp, u, aux=aux)
+    return acc & okf & w.same_challenge(ctx, d2, d)
+
+
+def _linear_verify_short_packed(w, ctx, records, aux):
+    c, cp, g, d, z, zp, ok = w.decode(ctx, MSG_LINEAR_SHORT, records)
+    return _linear_verify_short(w, ctx, c, cp, g, d, z, zp, aux) & ok
+
+
 def linear_prove(ctx, g, x, r, rp, y, yp, aux=None):
     """(c, cp, t, tp, u, z, zp, ok); ok[b] = 1 iff r and rp both pass the commit constraint."""
-    c, cp, t, tp, u, ok = ctx.linear_commit(g, x, r, rp, y, yp)
-    d, _, okf = challenge(ctx, MSG_LINEAR_COMMITMENT, c, cp, g, t, tp, u, aux=aux)
-    z, zp = ctx.linear_response(y, yp, r, rp, d)
-    return c, cp, t, tp, u, z, zp, _flag(ok == 3) & okf
+    return _linear_prove(_LINEAR64, ctx, g, x, r, rp, y, yp, aux)
 
 
 def linear_verify(ctx, c, cp, g, t, tp, u, z, zp, aux=None):
     """LinearProofVerifier::verify (linear.rs:213-250) with the recomputed challenge."""
-    d, _, okf = challenge(ctx, MSG_LINEAR_COMMITMENT, c, cp, g, t, tp, u, aux=aux)
-    return ctx.linear_verify(z, zp, c, cp, g, t, tp, u, d) & okf
+    return _linear_verify(_LINEAR64, ctx, c, cp, g, t, tp, u, z, zp, aux)
 
 
 def linear_verify_packed(ctx, commitment_records, response_records, aux=None):
     """linear_verify from packed MSG_LINEAR_COMMITMENT and MSG_LINEAR_RESPONSE records."""
-    c, cp, g, t, tp, u, ok1 = packed.decode_batch(ctx, MSG_LINEAR_COMMITMENT, commitment_records)
-    z, zp, ok2 = packed.decode_batch(ctx, MSG_LINEAR_RESPONSE, response_records)
-    return linear_verify(ctx, c, cp, g, t, tp, u, z, zp, aux=aux) & ok1 & ok2
+    return _linear_verify_packed(_LINEAR64, ctx, commitment_records, response_records, aux)
 
 
 def linear_short(ctx, c, cp, g, t, tp, u, z, zp, aux=None):
     """The short form of the Linear proof: (c, cp, g, d, z, zp) with d = challenge(c, cp, g, t, tp, u).  Returns d; the
     verifier recomputes t, tp, u (linear_verify_short)."""
-    d, _, _ = challenge(ctx, MSG_LINEAR_COMMITMENT, c, cp, g, t, tp, u, aux=aux)
-    return d
+    return _linear_short(_LINEAR64, ctx, c, cp, g, t, tp, u, z, zp, aux)
 
 
 def linear_verify_short(ctx, c, cp, g, d, z, zp, aux=None):
     """Verifier of the short Linear proof: Context.linear_recover gives the only (t', tp', u') that satisfy
     linear.rs:224-249 for the rest of the proof, with the norm rule on z and zp; accept iff the transcript of the full
     commitment message with them gives d again."""
-    t, tp, u, acc = ctx.linear_recover(z, zp, c, cp, g, d)
-    d2, _, okf = challenge(ctx, MSG_LINEAR_COMMITMENT, c, cp, g, t, tp, u, aux=aux)
-    return acc & okf & _same_challenge(ctx, d2, d)
+    return _linear_verify_short(_LINEAR64, ctx, c, cp, g, d, z, zp, aux)
 
 
 def linear_verify_short_packed(ctx, records, aux=None):
     """linear_verify_short from packed MSG_LINEAR_SHORT records; a record that does not decode rejects its own proof."""
-    c, cp, g, d, z, zp, ok = packed.decode_batch(ctx, MSG_LINEAR_SHORT, records)
-    return linear_verify_short(ctx, c, cp, g, d, z, zp, aux=aux) & ok
+    return _linear_verify_short_packed(_LINEAR64, ctx, records, aux)
+
+
+def linear_prove32(ctx, g, x, r, rp, y, yp, aux=None):
+    """linear_prove on int32 slabs: every output slab the int32 of linear_prove's, ok the same."""
+    return _linear_prove(_LINEAR32, ctx, g, x, r, rp, y, yp, aux)
+
+
+def linear_verify32(ctx, c, cp, g, t, tp, u, z, zp, aux=None):
+    """linear_verify on int32 slabs.  The transcript is the 64-bit one: a proof made in either width verifies in the other
+    after narrow / widen."""
+    return _linear_verify(_LINEAR32, ctx, c, cp, g, t, tp, u, z, zp, aux)
+
+
+def linear_verify_packed32(ctx, commitment_records, response_records, aux=None):
+    """linear_verify_packed through int32 slabs: the records are those of packed.encode_batch or encode_batch32."""
+    return _linear_verify_packed(_LINEAR32, ctx, commitment_records, response_records, aux)
+
+
+def linear_short32(ctx, c, cp, g, t, tp, u, z, zp, aux=None):
+    """linear_short on int32 slabs: d as int32."""
+    return _linear_short(_LINEAR32, ctx, c, cp, g, t, tp, u, z, zp, aux)
+
+
+def linear_verify_short32(ctx, c, cp, g, d, z, zp, aux=None):
+    """linear_verify_short on int32 slabs; the recomputed challenge is compared word for word (_same_challenge32)."""
+    return _linear_verify_short(_LINEAR32, ctx, c, cp, g, d, z, zp, aux)
+
+
+def linear_verify_short_packed32(ctx, records, aux=None):
+    """linear_verify_short_packed through int32 slabs: packed MSG_LINEAR_SHORT records -> verdicts."""
+    return _linear_verify_short_packed(_LINEAR32, ctx, records, aux)
 
 
 # ---- SumProof (src/prove/sum.rs) ---------------------------------------------------------------------------------------
@@ -404,14 +472,23 @@ def open_prove_sampled32(ctx, x, sampler, aux=None):
     return _open_prove_sampled(_OPEN32, ctx, x, sampler, aux)
 
 
-def linear_prove_sampled(ctx, g, x, sampler, aux=None):
-    """linear_prove with r, r', y, y' from `sampler`: (c, cp, t, tp, u, z, zp, ok, r, rp)."""
+def _linear_prove_sampled(w, ctx, g, x, sampler, aux):
     lead = _lead(x, 2)
     r = sampler.uniform(ctx.b, lead + (ctx.k,))
     rp = sampler.uniform(ctx.b, lead + (ctx.k,))
     y = sampler.gauss(ctx.sigma, lead + (ctx.k,))
     yp = sampler.gauss(ctx.sigma, lead + (ctx.k,))
-    return linear_prove(ctx, g, x, r, rp, y, yp, aux=aux) + (r, rp)
+    return _linear_prove(w, ctx, g, x, r, rp, y, yp, aux) + (r, rp)
+
+
+def linear_prove_sampled(ctx, g, x, sampler, aux=None):
+    """linear_prove with r, r', y, y' from `sampler`: (c, cp, t, tp, u, z, zp, ok, r, rp)."""
+    return _linear_prove_sampled(_LINEAR64, ctx, g, x, sampler, aux)
+
+
+def linear_prove_sampled32(ctx, g, x, sampler, aux=None):
+    """linear_prove_sampled on int32 slabs, the draws from a KeyedSampler32: (c, cp, t, tp, u, z, zp, ok, r, rp)."""
+    return _linear_prove_sampled(_LINEAR32, ctx, g, x, sampler, aux)
 
 
 def sum_prove_sampled(ctx, gs, xs, sampler, aux=None):
@@ -533,6 +610,8 @@ def open_prove_zk32(ctx, x, sampler, aux=None, max_rounds: int = 64):
 
 _OPEN64 = _open_ops("", challenge, packed.decode_batch, _same_challenge, draw_coins)
 _OPEN32 = _open_ops("32", challenge32, packed.decode_batch32, _same_challenge32, draw_coins32)
+_LINEAR64 = _linear_ops("", challenge, packed.decode_batch, _same_challenge, draw_coins)
+_LINEAR32 = _linear_ops("32", challenge32, packed.decode_batch32, _same_challenge32, draw_coins32)
 
 
 # ---- the same prover with the loop inside the library (include/rzk.h "prover loop") ----------------------
@@ -605,9 +684,13 @@ def sum_prove_zk_native(ctx, gs, xs, sampler, aux=None, max_rounds: int = 64):
         B, sampler, max_rounds)
 
 
-def linear_prove_zk(ctx, g, x, sampler, aux=None, max_rounds: int = 64):
-    """linear_prove_sampled with the rejection step over (z, z'): (c, cp, t, tp, u, z, zp, ok, r, rp, rounds)."""
-    B = _batch3(x, 2, "linear_prove_zk")
+def _linear_prove_zk(w, ctx, g, x, sampler, aux, max_rounds):
+    B = _batch3(x, 2, "linear_prove_zk" + w.suffix)
+    if w is _LINEAR32:
+        import torch
+
+        if x.dtype != torch.int32 or g.dtype != torch.int32:
+            raise ValueError("linear_prove_zk32: g and x must be int32 tensors")
     r = sampler.uniform(ctx.b, (B, ctx.k))
     rp = sampler.uniform(ctx.b, (B, ctx.k))
 
@@ -616,14 +699,26 @@ def linear_prove_zk(ctx, g, x, sampler, aux=None, max_rounds: int = 64):
         nb = int(xs.shape[0])
         y = sampler.gauss(ctx.sigma, (nb, ctx.k))
         yp = sampler.gauss(ctx.sigma, (nb, ctx.k))
-        coin, R = draw_coins(sampler, (nb,))
-        c, cp, t, tp, u, ok = ctx.linear_commit(gs, xs, rs, rps, y, yp)
-        d, _, okf = challenge(ctx, MSG_LINEAR_COMMITMENT, c, cp, gs, t, tp, u, aux=aux)
-        z, zp, acc, _ = ctx.linear_response_reject(y, yp, rs, rps, d, coin, R, lnM)
+        coin, R = w.coins(sampler, (nb,))
+        c, cp, t, tp, u, ok = w.commit(ctx, gs, xs, rs, rps, y, yp)
+        d, _, okf = w.challenge(ctx, MSG_LINEAR_COMMITMENT, c, cp, gs, t, tp, u, aux=aux)
+        z, zp, acc, _ = w.response_reject(ctx, y, yp, rs, rps, d, coin, R, lnM)
         return (c, cp, t, tp, u, z, zp), _flag(ok == 3) & okf, acc
 
     outs, ok, rounds = _zk_rounds(ctx, sampler, 2, max_rounds, attempt, fresh=(2, 3, 4, 5, 6))
     return tuple(outs) + (ok, r, rp, rounds)
+
+
+def linear_prove_zk(ctx, g, x, sampler, aux=None, max_rounds: int = 64):
+    """linear_prove_sampled with the rejection step over (z, z'): (c, cp, t, tp, u, z, zp, ok, r, rp, rounds)."""
+    return _linear_prove_zk(_LINEAR64, ctx, g, x, sampler, aux, max_rounds)
+
+
+def linear_prove_zk32(ctx, g, x, sampler, aux=None, max_rounds: int = 64):
+    """linear_prove_zk on int32 slabs: g, x int32 (torch CUDA), sampler a KeyedSampler32 / ExactKeyedSampler32.
+    The draw order is linear_prove_zk's, so under the same key and nonces every slab is narrow() of its slab, ok and rounds are
+    the same, and the sampler's counter ends where the 64-bit loop leaves it."""
+    return _linear_prove_zk(_LINEAR32, ctx, g, x, sampler, aux, max_rounds)
 
 
 def sum_prove_zk(ctx, gs, xs, sampler, aux=None, max_rounds: int = 64):
