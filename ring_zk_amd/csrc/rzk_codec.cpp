@@ -1,6 +1,8 @@
 // rzk_codec.cpp — the entry points around the proofs' messages (include/rzk.h), device- and host-pointer variants side by
 // side: the wire codec, Fiat-Shamir challenges, the rejection step, packed records and seed expansion.  Each family
 // has its kernels in a translation unit and its format in a header of its own, named at the family's section.
+// The *_response_reject calls take their NULL test, alignment test, convert plan and staging from their slab lists
+// (rzk_slabs.h, glue in rzk_ctx.h); the wire, packed, Fiat-Shamir and reject calls are driven by a schema or the caller's rows[].
 #include "rzk_ctx.h"
 
 // ---- v4: batched codec of the serialized protocol messages (rzk_wire_dev.hip, rzk_wire_walk.h) ------------------------
@@ -246,37 +248,6 @@ int reject_args(rzk_ctx* c, uint32_t nparts, const int64_t* const* z, const int6
 }
 }  // namespace
 
-int rzk_reject_batch_dev(rzk_ctx* c, uint32_t nparts, const int64_t* const* z, const int64_t* const* y, const uint32_t* rows,
-                         const int64_t* coin, uint64_t R, double lnM, uint8_t* accept, int64_t* E, size_t B) {
-  if (!c) return RZK_E_ARG;
-  if (B == 0) return RZK_OK;
-  uint64_t total = 0;
-  int rc = reject_args(c, nparts, z, y, rows, coin, R, lnM, accept, &total);
-  if (rc != RZK_OK) return rc;
-  RejectParts m{};
-  m.nparts = nparts;
-  m.N = c->N;
-  m.rows = (uint32_t)total;
-  for (uint32_t f = 0; f < nparts; ++f) {
-    if (((uintptr_t)z[f] | (uintptr_t)y[f]) & 15u) return fail(c, RZK_E_ARG, "reject: slabs must be 16-byte aligned");
-    m.first[f + 1] = m.first[f] + rows[f];
-    m.z[f] = z[f];
-    m.y[f] = y[f];
-  }
-  rc = arena_reserve(c, c->ws_reject, (size_t)B * total * sizeof(RejectPartial));
-  if (rc != RZK_OK) return rc;
-  RejectPartial* part = (RejectPartial*)c->ws_reject.p;
-  const uint64_t limit = (c->verify_bound + 1) * (c->verify_bound + 1);   // <= 2^48 (reject_args_ok)
-  rc = run_profiled(c, (uint64_t)B * total * c->N * 2 * sizeof(int64_t), "reject stat kernel", [&](const LaunchCfg& cfg) {
-    return launch_reject_stat(cfg, m, c->q, c->b * c->kappa, limit, c->trusted, part, B);
-  });
-  if (rc != RZK_OK) return rc;
-  const double sg = (double)c->sigma;
-  return run_profiled(c, (uint64_t)B * total * sizeof(RejectPartial), "reject decide kernel", [&](const LaunchCfg& cfg) {
-    return launch_reject_decide(cfg, part, m.rows, coin, R, lnM, 2.0 * sg * sg, accept, E, c->d_bad, B);
-  });
-}
-
 int rzk_reject_batch(rzk_ctx* c, uint32_t nparts, const int64_t* const* z, const int64_t* const* y, const uint32_t* rows,
                      const int64_t* coin, uint64_t R, double lnM, uint8_t* accept, int64_t* E, size_t B) {
   if (!c) return RZK_E_ARG;
@@ -302,10 +273,11 @@ namespace {
 // One call = the response launches of `response` and the decision over the parts (z_f, y_f).  Where the rotation kernel
 // runs with one wavefront per polynomial (response_stat_fused) the response rows leave the partials themselves
 // (response(&stat)); everywhere else the chain runs inside the call: response(NULL), then reject_stat_kernel on (z, y).
-// Either way one reject_decide_kernel over ws_reject ends the call.
+// Either way one reject_decide_kernel over ws_reject ends the call.  may_fuse = false: the unfused side on every context
+// (rzk_reject_batch_dev: z exists already, there are no response rows to leave the partials).
 template <class F>
 int response_reject(rzk_ctx* c, uint32_t nparts, const int64_t* const* z, const int64_t* const* y, const uint32_t* rows,
-                    const int64_t* coin, uint64_t R, double lnM, uint8_t* accept, int64_t* E, size_t B, F response) {
+                    const int64_t* coin, uint64_t R, double lnM, uint8_t* accept, int64_t* E, size_t B, bool may_fuse, F response) {
   uint64_t total = 0;
   int rc = reject_args(c, nparts, z, y, rows, coin, R, lnM, accept, &total);
   if (rc != RZK_OK) return rc;
@@ -324,7 +296,7 @@ int response_reject(rzk_ctx* c, uint32_t nparts, const int64_t* const* z, const 
   RejectPartial* part = (RejectPartial*)c->ws_reject.p;
   const uint64_t limit = (c->verify_bound + 1) * (c->verify_bound + 1);   // <= 2^48 (reject_args_ok)
   const ResponseStat stat{part, m.rows, 0, (int64_t)(c->b * c->kappa), limit};
-  const bool fused = response_stat_fused(c);
+  const bool fused = may_fuse && response_stat_fused(c);
   rc = response(fused ? &stat : nullptr);
   if (rc != RZK_OK) return rc;
   if (!fused) {
@@ -346,9 +318,23 @@ ResponseStat stat_at(const ResponseStat& s, uint32_t off) {
   return t;
 }
 
-const char* const kResponseRejectNull = "response reject: non-NULL y, r, d, coin, z, accept expected";
+// the argument rules the response_reject calls share, both forms: kGo, or what the call returns
+template <const CallSlabs& S, class... P>
+int response_reject_args(rzk_ctx* c, size_t B, P*... p) {
+  if (!c) return RZK_E_ARG;
+  if (B == 0) return RZK_OK;
+  return slabs_null<S>(p...) ? fail(c, RZK_E_ARG, "response reject: non-NULL y, r, d, coin, z, accept expected") : kGo;
+}
 
 }  // namespace
+
+// the rejection step alone: response_reject without response launches
+int rzk_reject_batch_dev(rzk_ctx* c, uint32_t nparts, const int64_t* const* z, const int64_t* const* y, const uint32_t* rows,
+                         const int64_t* coin, uint64_t R, double lnM, uint8_t* accept, int64_t* E, size_t B) {
+  if (!c) return RZK_E_ARG;
+  if (B == 0) return RZK_OK;
+  return response_reject(c, nparts, z, y, rows, coin, R, lnM, accept, E, B, false, [](const ResponseStat*) { return RZK_OK; });
+}
 
 // The Open form at either width (v14, slab32 prover).  The partials, the decision kernel, coin, accept and
 // E do not see the width; reject_args and RejectParts only carry the addresses of z and y.  32-bit slabs run natively
@@ -358,20 +344,18 @@ namespace rzk::api {
 template <class C>
 int open_response_reject_dev(rzk_ctx* c, const C* y, const C* r, const C* d, const int64_t* coin, uint64_t R, double lnM, C* z,
                              uint8_t* accept, int64_t* E, size_t B) {
-  if (!c) return RZK_E_ARG;
-  if (B == 0) return RZK_OK;
-  if (!y || !r || !d || !coin || !z || !accept) return fail(c, RZK_E_ARG, kResponseRejectNull);
+  if (const int rc = response_reject_args<kSlabsOpenResponseReject>(c, B, y, r, d, coin, z, accept, E); rc != kGo) return rc;
   const uint32_t k = c->k;
   if constexpr (sizeof(C) == 4) {
-    if (misaligned({y, r, d, z})) return align_fail(c);
+    if (slabs_misaligned<kSlabsOpenResponseReject>(y, r, d, coin, z, accept, E)) return align_fail(c);
     if (!(program_native32(c, PG_RESPONSE, 1) && response_stat_fused(c)))
-      return convert_call(c, {{y, nullptr, B * k}, {r, nullptr, B * k}, {d, nullptr, B}, {nullptr, z, B * k}}, [&](int64_t* const* w) {
-        return open_response_reject_dev<int64_t>(c, w[0], w[1], w[2], coin, R, lnM, w[3], accept, E, B);
-      });
+      return convert_call<kSlabsOpenResponseReject>(c, {}, B, [&](auto wy, auto wr, auto wd, auto wcoin, auto... out) {
+        return open_response_reject_dev<int64_t>(c, wy, wr, wd, wcoin, R, lnM, out..., B);
+      }, y, r, d, coin, z, accept, E);
   }
   const int64_t *zs[1] = {launch_addr(z)}, *ys[1] = {launch_addr(y)};
   const uint32_t rows[1] = {k};
-  return response_reject(c, 1, zs, ys, rows, coin, R, lnM, accept, E, B, [&](const ResponseStat* st) {
+  return response_reject(c, 1, zs, ys, rows, coin, R, lnM, accept, E, B, true, [&](const ResponseStat* st) {
     if constexpr (sizeof(C) == 4) {
       if (!st) return fail(c, RZK_E_STATE, "response reject on 32-bit slabs needs the fused rows");
     }
@@ -392,27 +376,23 @@ int rzk_open_response_reject32_batch_dev(rzk_ctx* c, const int32_t* y, const int
 }
 
 // The Linear form at either width: as the Open form, with two parts.
-namespace rzk::api {
+namespace {
 
 template <class C>
 int linear_response_reject_dev(rzk_ctx* c, const C* y, const C* yp, const C* r, const C* rp, const C* d, const int64_t* coin, uint64_t R,
                                double lnM, C* z, C* zp, uint8_t* accept, int64_t* E, size_t B) {
-  if (!c) return RZK_E_ARG;
-  if (B == 0) return RZK_OK;
-  if (!y || !yp || !r || !rp || !d || !coin || !z || !zp || !accept) return fail(c, RZK_E_ARG, kResponseRejectNull);
+  if (const int rc = response_reject_args<kSlabsLinearResponseReject>(c, B, y, yp, r, rp, d, coin, z, zp, accept, E); rc != kGo) return rc;
   const uint32_t k = c->k;
   if constexpr (sizeof(C) == 4) {
-    if (misaligned({y, yp, r, rp, d, z, zp})) return align_fail(c);
+    if (slabs_misaligned<kSlabsLinearResponseReject>(y, yp, r, rp, d, coin, z, zp, accept, E)) return align_fail(c);
     if (!(program_native32(c, PG_RESPONSE, 2) && response_stat_fused(c)))
-      return convert_call(c, {{y, nullptr, B * k}, {yp, nullptr, B * k}, {r, nullptr, B * k}, {rp, nullptr, B * k}, {d, nullptr, B},
-                              {nullptr, z, B * k}, {nullptr, zp, B * k}},
-                          [&](int64_t* const* w) {
-                            return linear_response_reject_dev<int64_t>(c, w[0], w[1], w[2], w[3], w[4], coin, R, lnM, w[5], w[6], accept, E, B);
-                          });
+      return convert_call<kSlabsLinearResponseReject>(c, {}, B, [&](auto wy, auto wyp, auto wr, auto wrp, auto wd, auto wcoin, auto... out) {
+        return linear_response_reject_dev<int64_t>(c, wy, wyp, wr, wrp, wd, wcoin, R, lnM, out..., B);
+      }, y, yp, r, rp, d, coin, z, zp, accept, E);
   }
   const int64_t *zs[2] = {launch_addr(z), launch_addr(zp)}, *ys[2] = {launch_addr(y), launch_addr(yp)};
   const uint32_t rows[2] = {k, k};
-  return response_reject(c, 2, zs, ys, rows, coin, R, lnM, accept, E, B, [&](const ResponseStat* st) {
+  return response_reject(c, 2, zs, ys, rows, coin, R, lnM, accept, E, B, true, [&](const ResponseStat* st) {
     if constexpr (sizeof(C) == 4) {
       if (!st) return fail(c, RZK_E_STATE, "response reject on 32-bit slabs needs the fused rows");
     }
@@ -421,9 +401,7 @@ int linear_response_reject_dev(rzk_ctx* c, const C* y, const C* yp, const C* r, 
                           B, 0, true, 0, 0, st);
   });
 }
-RZK_BOTH_WIDTHS(linear_response_reject_dev)
-
-}  // namespace rzk::api
+}  // namespace
 
 int rzk_linear_response_reject_batch_dev(rzk_ctx* c, const int64_t* y, const int64_t* yp, const int64_t* r, const int64_t* rp,
                                          const int64_t* d, const int64_t* coin, uint64_t R, double lnM, int64_t* z, int64_t* zp,
@@ -439,14 +417,12 @@ int rzk_linear_response_reject32_batch_dev(rzk_ctx* c, const int32_t* y, const i
 int rzk_sum_response_reject_batch_dev(rzk_ctx* c, uint32_t V, const int64_t* ys, const int64_t* yp, const int64_t* rs,
                                       const int64_t* rp, const int64_t* d, const int64_t* coin, uint64_t R, double lnM, int64_t* zs,
                                       int64_t* zp, uint8_t* accept, int64_t* E, size_t B) {
-  if (!c) return RZK_E_ARG;
-  if (B == 0) return RZK_OK;
-  if (!ys || !yp || !rs || !rp || !d || !coin || !zs || !zp || !accept) return fail(c, RZK_E_ARG, kResponseRejectNull);
+  if (const int rc = response_reject_args<kSlabsSumResponseReject>(c, B, ys, yp, rs, rp, d, coin, zs, zp, accept, E); rc != kGo) return rc;
   if (V == 0 || V > (1u << 20)) return fail(c, RZK_E_ARG, "response reject: V must lie in 1 .. 2^20");
   const uint32_t k = c->k;
   const int64_t *z2[2] = {zs, zp}, *y2[2] = {ys, yp};
   const uint32_t rows[2] = {V * k, k};
-  return response_reject(c, 2, z2, y2, rows, coin, R, lnM, accept, E, B, [&](const ResponseStat* st) {
+  return response_reject(c, 2, z2, y2, rows, coin, R, lnM, accept, E, B, true, [&](const ResponseStat* st) {
     // as rzk_sum_response_batch_dev: the summands as batch entries that share d, then zp; partial (b, s k + i) and (b, V k + i)
     ResponseStat s0, s1;
     if (st) s0 = stat_at(*st, 0), s1 = stat_at(*st, V * k);
@@ -461,17 +437,10 @@ namespace {
 template <class C>
 int open_response_reject_host(rzk_ctx* c, const C* y, const C* r, const C* d, const int64_t* coin, uint64_t R, double lnM, C* z,
                               uint8_t* accept, int64_t* E, size_t B) {
-  if (!c) return RZK_E_ARG;
-  if (B == 0) return RZK_OK;
-  if (!y || !r || !d || !coin || !z || !accept) return fail(c, RZK_E_ARG, kResponseRejectNull);
-  const size_t kb = B * c->k;
-  HostCall h(c);
-  const auto dy = h.pin(y, kb), dr = h.pin(r, kb), dd = h.pin(d, B);
-  const auto dcoin = h.in(coin, B * sizeof(int64_t));
-  const auto dz = h.pout(z, kb);
-  const auto daccept = h.out(accept, B);
-  const auto dE = h.out(E, B * sizeof(int64_t));
-  return h.run([&] { return open_response_reject_dev<C>(c, dy, dr, dd, dcoin, R, lnM, dz, daccept, dE, B); });
+  if (const int rc = response_reject_args<kSlabsOpenResponseReject>(c, B, y, r, d, coin, z, accept, E); rc != kGo) return rc;
+  return host_run<kSlabsOpenResponseReject>(c, {}, B, [&](auto dy, auto dr, auto dd, auto dcoin, auto... out) {
+    return open_response_reject_dev<C>(c, dy, dr, dd, dcoin, R, lnM, out..., B);
+  }, y, r, d, coin, z, accept, E);
 }
 }  // namespace
 
@@ -488,17 +457,10 @@ namespace {
 template <class C>
 int linear_response_reject_host(rzk_ctx* c, const C* y, const C* yp, const C* r, const C* rp, const C* d, const int64_t* coin, uint64_t R,
                                 double lnM, C* z, C* zp, uint8_t* accept, int64_t* E, size_t B) {
-  if (!c) return RZK_E_ARG;
-  if (B == 0) return RZK_OK;
-  if (!y || !yp || !r || !rp || !d || !coin || !z || !zp || !accept) return fail(c, RZK_E_ARG, kResponseRejectNull);
-  const size_t kb = B * c->k;
-  HostCall h(c);
-  const auto dy = h.pin(y, kb), dyp = h.pin(yp, kb), dr = h.pin(r, kb), drp = h.pin(rp, kb), dd = h.pin(d, B);
-  const auto dcoin = h.in(coin, B * sizeof(int64_t));
-  const auto dz = h.pout(z, kb), dzp = h.pout(zp, kb);
-  const auto daccept = h.out(accept, B);
-  const auto dE = h.out(E, B * sizeof(int64_t));
-  return h.run([&] { return linear_response_reject_dev<C>(c, dy, dyp, dr, drp, dd, dcoin, R, lnM, dz, dzp, daccept, dE, B); });
+  if (const int rc = response_reject_args<kSlabsLinearResponseReject>(c, B, y, yp, r, rp, d, coin, z, zp, accept, E); rc != kGo) return rc;
+  return host_run<kSlabsLinearResponseReject>(c, {}, B, [&](auto dy, auto dyp, auto dr, auto drp, auto dd, auto dcoin, auto... out) {
+    return linear_response_reject_dev<C>(c, dy, dyp, dr, drp, dd, dcoin, R, lnM, out..., B);
+  }, y, yp, r, rp, d, coin, z, zp, accept, E);
 }
 }  // namespace
 
@@ -516,18 +478,15 @@ int rzk_linear_response_reject32_batch(rzk_ctx* c, const int32_t* y, const int32
 int rzk_sum_response_reject_batch(rzk_ctx* c, uint32_t V, const int64_t* ys, const int64_t* yp, const int64_t* rs, const int64_t* rp,
                                   const int64_t* d, const int64_t* coin, uint64_t R, double lnM, int64_t* zs, int64_t* zp,
                                   uint8_t* accept, int64_t* E, size_t B) {
-  if (!c) return RZK_E_ARG;
-  if (B == 0) return RZK_OK;
-  if (!ys || !yp || !rs || !rp || !d || !coin || !zs || !zp || !accept) return fail(c, RZK_E_ARG, kResponseRejectNull);
+  if (const int rc = response_reject_args<kSlabsSumResponseReject>(c, B, ys, yp, rs, rp, d, coin, zs, zp, accept, E); rc != kGo) return rc;
   if (V == 0 || V > (1u << 20)) return fail(c, RZK_E_ARG, "response reject: V must lie in 1 .. 2^20");
-  const size_t kb = B * c->k;
-  HostCall h(c);
-  const auto dys = h.pin(ys, kb * V), dyp = h.pin(yp, kb), drs = h.pin(rs, kb * V), drp = h.pin(rp, kb), dd = h.pin(d, B);
-  const auto dcoin = h.in(coin, B * sizeof(int64_t));
-  const auto dzs = h.pout(zs, kb * V), dzp = h.pout(zp, kb);
-  const auto daccept = h.out(accept, B);
-  const auto dE = h.out(E, B * sizeof(int64_t));
-  return h.run([&] { return rzk_sum_response_reject_batch_dev(c, V, dys, dyp, drs, drp, dd, dcoin, R, lnM, dzs, dzp, daccept, dE, B); });
+  return host_run<kSlabsSumResponseReject>(
+      c, by_V(V), B,
+      [&](const int64_t* dys, const int64_t* dyp, const int64_t* drs, const int64_t* drp, const int64_t* dd, const int64_t* dcoin,
+          int64_t* dzs, int64_t* dzp, uint8_t* daccept, int64_t* dE) {
+        return rzk_sum_response_reject_batch_dev(c, V, dys, dyp, drs, drp, dd, dcoin, R, lnM, dzs, dzp, daccept, dE, B);
+      },
+      ys, yp, rs, rp, d, coin, zs, zp, accept, E);
 }
 
 // ---- v8: fixed-width packed records "RZKP1" (rzk_packed_dev.hip, rzk_packed.h) -----------------------------------------

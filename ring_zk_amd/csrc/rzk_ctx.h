@@ -14,6 +14,8 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <tuple>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -28,6 +30,7 @@
 #include "rzk_plan.h"
 #include "rzk_reject.h"
 #include "rzk_slab32.h"
+#include "rzk_slabs.h"
 #include "rzk_tables.h"
 #include "rzk_xof.h"
 
@@ -188,6 +191,7 @@ int take_input_error(rzk_ctx* c);   // synchronises and reports (then clears) th
 template <class C = int64_t>
 inline size_t polys(const rzk_ctx* c, size_t count) { return poly_bytes<C>(c->N, count); }   // bytes of `count` polynomials
 // 32-bit device slabs are 16-byte aligned (rzk_slab32.h); the 64-bit entry points have no such rule
+// (the calls with a slab list: slabs_misaligned below; this form serves the one-output samplers)
 inline bool misaligned(std::initializer_list<const void*> slabs) {
   uintptr_t bits = 0;
   for (const void* p : slabs) bits |= reinterpret_cast<uintptr_t>(p);
@@ -267,9 +271,64 @@ struct OimgProducer {
   ~OimgProducer() { c->oimg_producer_op = 0xffu; }
 };
 
+// ---- a call's slab list (rzk_slabs.h) at work -----------------------------------------------------------------------
+// Every entry point passes its pointers as it declares them, with its list S: what follows, and host_run below, are the only
+// places that turn a list into a NULL test, an alignment test, a convert plan or a staging plan.  A pointer whose constness
+// disagrees with its slab's role, or a list of another length, does not compile.
+struct SizeArgs {   // the call's own size arguments (SlabDims) and whether they obey its rule: V >= 1, rows >= 1, a key selector
+  uint64_t V = 1, rows = 0;
+  int which = -1;   // >= 0: rows = the key rows it selects
+  bool ok = true;
+};
+inline SizeArgs by_V(uint64_t V) { return {V, 0, -1, V != 0}; }
+inline SizeArgs by_rows(uint64_t rows) { return {1, rows, -1, rows != 0}; }
+inline SizeArgs by_key(int which) { return {1, 0, which, is_key_selector(which)}; }
+inline SlabDims dims_of(const rzk_ctx* c, const SizeArgs& a = {}) {
+  return {c->n, c->k, c->l, a.V, a.which >= 0 ? key_row_count(a.which, c->n, c->l) : a.rows};
+}
+template <const CallSlabs& S, class... P>
+constexpr bool slab_types_ok() {
+  if (sizeof...(P) != slab_len(S)) return false;
+  const bool reads[] = {std::is_const_v<P>...};
+  for (size_t i = 0; i < sizeof...(P); ++i)
+    if (reads[i] != slab_reads(S.s[i].role)) return false;
+  return true;
+}
+template <const CallSlabs& S, class... P>
+inline bool slabs_null(P*... p) {   // a required pointer is NULL
+  static_assert(slab_types_ok<S, P...>(), "the pointers of the call are not its slab list");
+  const void* const a[] = {p...};
+  for (size_t i = 0; i < sizeof...(P); ++i)
+    if (!a[i] && !slab_optional(S.s[i].role)) return true;
+  return false;
+}
+template <const CallSlabs& S, class... P>
+inline bool slabs_misaligned(P*... p) {   // a coefficient slab is not 16-byte aligned (the companions have no such rule)
+  static_assert(slab_types_ok<S, P...>(), "the pointers of the call are not its slab list");
+  const void* const a[] = {p...};
+  uintptr_t bits = 0;
+  for (size_t i = 0; i < sizeof...(P); ++i)
+    if (slab_is_coef(S.s[i].kind)) bits |= reinterpret_cast<uintptr_t>(a[i]);
+  return (bits & 15u) != 0;
+}
+// The argument rules every call without error texts of its own shares, in the order include/rzk.h gives them: an empty
+// batch is a no-op whatever the pointers; a NULL context, a NULL required pointer or a size argument that breaks its rule
+// (sz.ok) is RZK_E_ARG.  kGo: the call goes on; it is no status of include/rzk.h, which are RZK_OK = 0 and negative codes.
+constexpr int kGo = 1;
+static_assert(RZK_OK == 0 && RZK_E_ARG < 0 && RZK_E_UNSUPPORTED < 0 && RZK_E_STATE < 0 && RZK_E_HIP < 0, "kGo is no status code");
+template <const CallSlabs& S, class... P>
+inline int slab_args(const rzk_ctx* c, const SizeArgs& sz, size_t B, P*... p) {
+  if (c && B == 0) return RZK_OK;
+  return !c || !sz.ok || slabs_null<S>(p...) ? RZK_E_ARG : kGo;
+}
+inline int split_check(rzk_ctx* c) {   // the verifiers and recompute steps split c into c1, c2
+  return c->n == c->l ? RZK_OK : fail(c, RZK_E_ARG, "c1_c2 split needs n == l (reference panics in Mat::add)");
+}
+
 // ---- rzk_slab32.cpp: the convert path of a 32-bit call ----------------------------------------------------------------
-// The call's slabs as int64_t copies in ws32: convert_call reserves the arena and widens every `in`, runs body(wide) —
-// the call's own body on int64_t, wide[i] the copy of slab i (NULL for an absent one) — and narrows every `out`.
+// The call's coefficient slabs as int64_t copies in ws32: convert_call reserves the arena and widens every slab the list
+// reads, runs body — the call's own body on int64_t, with the pointers of the call in declaration order, every int32_t
+// slab replaced by its copy (NULL for an absent one) and every companion as it came — and narrows every slab it writes.
 struct Conv {   // one slab of the call, `count` polynomials: read (in), written (out), or absent (neither)
   const int32_t* in;
   int32_t* out;
@@ -277,32 +336,43 @@ struct Conv {   // one slab of the call, `count` polynomials: read (in), written
 };
 int convert_begin(rzk_ctx* c, const Conv* slabs, size_t n, int64_t** wide);
 int convert_end(rzk_ctx* c, const Conv* slabs, size_t n, int64_t* const* wide);
-template <size_t K, class F>
-int convert_call(rzk_ctx* c, const Conv (&slabs)[K], F body) {
+template <const CallSlabs& S, class F, class... P>
+int convert_call(rzk_ctx* c, const SizeArgs& sz, size_t B, F body, P*... p) {
+  static_assert(slab_types_ok<S, P...>(), "the pointers of the call are not its slab list");
+  constexpr size_t K = sizeof...(P);
+  const SlabDims dm = dims_of(c, sz);
+  const CallSlabs& list = S;   // (the lambdas index this, not S: hipcc of ROCm 7.2 crashes on S.s[i] inside a generic lambda)
+  size_t i = 0;
+  auto conv = [&](auto* q) -> Conv {
+    const Slab& s = list.s[i++];
+    const size_t count = B * slab_count(s.kind, dm);
+    if constexpr (std::is_same_v<decltype(q), const int32_t*>) return {q, nullptr, count};
+    else if constexpr (std::is_same_v<decltype(q), int32_t*>) return {nullptr, q, count};
+    else return {nullptr, nullptr, 0};
+  };
+  const Conv slabs[K] = {conv(p)...};   // (braces: in the order of the list)
   int64_t* wide[K];
   int rc = convert_begin(c, slabs, K, wide);
-  if (rc == RZK_OK) rc = body(wide);
+  if (rc != RZK_OK) return rc;
+  i = 0;
+  auto pick = [&](auto* q) {
+    using T = std::remove_pointer_t<decltype(q)>;
+    int64_t* const w = wide[i++];
+    if constexpr (std::is_same_v<T, const int32_t>) return static_cast<const int64_t*>(w);
+    else if constexpr (std::is_same_v<T, int32_t>) return w;
+    else return q;
+  };
+  const std::tuple<decltype(pick(p))...> args{pick(p)...};
+  rc = std::apply(body, args);
   return rc != RZK_OK ? rc : convert_end(c, slabs, K, wide);
 }
 
-// ---- the *_dev entry points that exist at both widths, C = int64_t or int32_t (the siblings' extern "C" symbols forward
-// here; rzk_prove_loop.cpp calls them typed).  Defined, and instantiated for both, in the file named.
+// ---- the typed *_dev entry points another translation unit calls (rzk_prove_loop.cpp), C = int64_t or int32_t; the
+// siblings' extern "C" symbols forward to them.  Defined, and instantiated for both, in the file named.
 // (RZK_BOTH_WIDTHS(fn), rzk_dev.h: the typed launchers are instantiated the same way)
 // rzk_protocols.cpp
 template <class C> int open_commit_dev(rzk_ctx* c, const C* x, const C* r, const C* y, C* cm, C* t, uint8_t* ok, size_t B);
-template <class C> int open_response_dev(rzk_ctx* c, const C* y, const C* r, const C* d, C* z, size_t B);
-template <class C> int open_a1_relation_dev(rzk_ctx* c, const C* z, const C* t, const C* cm, const C* d, uint8_t* accept, size_t B,
-                                            bool recover);   // verify; recover: t is the output
 template <class C> int matvec_dev(rzk_ctx* c, int which, const C* v, const C* addend, C* out, size_t B);
-template <class C> int norm2_le_dev(rzk_ctx* c, const C* v, uint32_t rows, uint64_t bound, uint8_t* ok, size_t B);
-template <class C> int linear_commit_dev(rzk_ctx* c, const C* g, const C* x, const C* r, const C* rp, const C* y, const C* yp, C* cm, C* cpm,
-                                         C* t, C* tp, C* u, uint8_t* ok, size_t B);
-template <class C> int linear_mask_dev(rzk_ctx* c, const C* g, const C* y, const C* yp, C* t, C* tp, C* u, size_t B);
-template <class C> int linear_response_dev(rzk_ctx* c, const C* y, const C* yp, const C* r, const C* rp, const C* d, C* z, C* zp, size_t B);
-template <class C> int linear_verify_dev(rzk_ctx* c, const C* z, const C* zp, const C* cm, const C* cpm, const C* g, const C* t,
-                                         const C* tp, const C* u, const C* d, uint8_t* accept, size_t B);
-template <class C> int linear_recover_dev(rzk_ctx* c, const C* z, const C* zp, const C* cm, const C* cpm, const C* g, const C* d, C* t_out,
-                                          C* tp_out, C* u_out, uint8_t* accept, size_t B);
 // rzk_samplers.cpp
 template <class C> int sample_uniform_keyed_dev(rzk_ctx* c, const uint8_t* nonce, uint32_t stream, uint64_t bound, C* out, size_t count);
 template <class C> int sample_gauss_keyed_dev(rzk_ctx* c, const uint8_t* nonce, uint32_t stream, double sigma, C* out, size_t count);
@@ -311,9 +381,6 @@ template <class C> int sample_challenge_keyed_dev(rzk_ctx* c, const uint8_t* non
 // rzk_codec.cpp
 template <class C> int fs_challenge_dev(rzk_ctx* c, int kind, uint32_t V, const C* const* fields, const uint8_t* aux32, C* d,
                                         uint8_t* digest, uint8_t* ok, size_t B);
-template <class C> int linear_response_reject_dev(rzk_ctx* c, const C* y, const C* yp, const C* r, const C* rp, const C* d,
-                                                  const int64_t* coin, uint64_t R, double lnM, C* z, C* zp, uint8_t* accept, int64_t* E,
-                                                  size_t B);
 template <class C> int open_response_reject_dev(rzk_ctx* c, const C* y, const C* r, const C* d, const int64_t* coin, uint64_t R,
                                                 double lnM, C* z, uint8_t* accept, int64_t* E, size_t B);
 // out[b][r] = polynomial p0 + r of XP1 under seeds[b] and `domain`; seeds and out on the device
@@ -371,6 +438,47 @@ class HostCall {
   std::vector<Buf> bufs_;
   size_t total_ = 0;
 };
+
+// The host form of a call with the list S: every pointer staged by its slab's role, kind and the pointer's own coefficient
+// width, then dev(the staged pointers, typed and in declaration order) under HostCall::run.  The caller has refused what
+// the call refuses: nothing here fails before the stream is touched.
+template <const CallSlabs& S, class F, class... P>
+int host_run(rzk_ctx* c, const SizeArgs& sz, size_t B, F dev, P*... p) {
+  static_assert(slab_types_ok<S, P...>(), "the pointers of the call are not its slab list");
+  const SlabDims dm = dims_of(c, sz);
+  const CallSlabs& list = S;   // (as in convert_call)
+  HostCall h(c);
+  size_t i = 0;
+  auto stage = [&](auto* q) {
+    using T = std::remove_pointer_t<decltype(q)>;
+    const Slab& s = list.s[i++];
+    size_t bytes = B * slab_count(s.kind, dm);   // of a companion; a coefficient slab: polynomials of its pointer's width
+    if constexpr (is_coef<std::remove_const_t<T>>) {
+      if (slab_is_coef(s.kind)) bytes = polys<std::remove_const_t<T>>(c, bytes);
+    }
+    if constexpr (std::is_const_v<T>) return h.in(q, bytes);
+    else return h.out(q, bytes);
+  };
+  const std::tuple<HostCall::Dev<P>...> staged{stage(p)...};   // (braces: in the order of the list)
+  return h.run([&] { return std::apply([&](const auto&... d) { return dev(static_cast<P*>(d)...); }, staged); });
+}
+// ... with the argument rules of slab_args in front
+template <const CallSlabs& S, class F, class... P>
+int host_call(rzk_ctx* c, const SizeArgs& sz, size_t B, F dev, P*... p) {
+  const int rc = slab_args<S>(c, sz, B, p...);
+  return rc != kGo ? rc : host_run<S>(c, sz, B, dev, p...);
+}
+// the two common shapes: dev(c, slabs..., B), and dev(c, lead, slabs..., B) with the call's V or key selector in front
+template <class T> struct AsGiven { using type = T; };   // (dev's type follows from the pointers: it is not deduced itself)
+template <const CallSlabs& S, class... P>
+int host_form(rzk_ctx* c, size_t B, typename AsGiven<int (*)(rzk_ctx*, P*..., size_t)>::type dev, P*... p) {
+  return host_call<S>(c, {}, B, [&](P*... d) { return dev(c, d..., B); }, p...);
+}
+template <const CallSlabs& S, class A, class... P>
+int host_form(rzk_ctx* c, const SizeArgs& sz, size_t B, A lead, typename AsGiven<int (*)(rzk_ctx*, A, P*..., size_t)>::type dev,
+              P*... p) {
+  return host_call<S>(c, sz, B, [&](P*... d) { return dev(c, lead, d..., B); }, p...);
+}
 
 }  // namespace api
 }  // namespace rzk

@@ -1,5 +1,7 @@
 // rzk_protocols.cpp — the device-pointer entry points of the ring / Mat primitives, the commitment scheme and the Open,
 // Linear and Sum proofs (include/rzk.h): each is a short sequence of row programs and norm kernels (rzk_run.cpp).
+// A call names its slab list (rzk_slabs.h): its NULL test, its alignment test and its convert plan come from the list
+// (slab_args, slabs_misaligned, convert_call; rzk_ctx.h), the body keeps its own rules, its routing predicate and its launches.
 #include "rzk_ctx.h"
 
 namespace {
@@ -122,15 +124,13 @@ namespace rzk::api {
 
 template <class C>
 int matvec_dev(rzk_ctx* c, int which, const C* v, const C* addend, C* out, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !v || !out || which < 0 || which > 2) return RZK_E_ARG;
-  const uint32_t rows = which == RZK_KEY_A1 ? c->n : (which == RZK_KEY_A2 ? c->l : c->n + c->l);
+  if (const int rc = slab_args<kSlabsMatvec>(c, by_key(which), B, v, addend, out); rc != kGo) return rc;
+  const uint32_t rows = key_row_count(which, c->n, c->l);
   const uint32_t var = (uint32_t)which * 2 + (addend ? 1 : 0);
   if constexpr (sizeof(C) == 4) {
-    if (misaligned({v, addend, out})) return align_fail(c);
+    if (slabs_misaligned<kSlabsMatvec>(v, addend, out)) return align_fail(c);
     if (!program_native32(c, PG_MATVEC, var))
-      return convert_call(c, {{v, nullptr, B * c->k}, {nullptr, out, B * rows}, {addend, nullptr, B * rows}},
-                          [&](int64_t* const* w) { return matvec_dev<int64_t>(c, which, w[0], w[2], w[1], B); });
+      return convert_call<kSlabsMatvec>(c, by_key(which), B, [&](auto... w) { return matvec_dev<int64_t>(c, which, w..., B); }, v, addend, out);
   }
   return run_program<C>(c, PG_MATVEC, var, {{v, c->k, 0}, {addend, rows, 0}, {out, rows, 0}}, nullptr, 1, B);
 }
@@ -138,18 +138,15 @@ RZK_BOTH_WIDTHS(matvec_dev)
 
 template <class C>
 int open_commit_dev(rzk_ctx* c, const C* x, const C* r, const C* y, C* cm, C* t, uint8_t* ok, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !x || !r || !y || !cm || !t) return RZK_E_ARG;
+  if (const int rc = slab_args<kSlabsOpenCommit>(c, {}, B, x, r, y, cm, t, ok); rc != kGo) return rc;
   auto specs = [&] {   // of the launching branches
     return std::vector<Op<C>>{{x, c->l, 0}, {r, c->k, 0}, {y, c->k, 0}, {cm, c->n + c->l, 0}, {t, c->n, 0}};
   };
   if constexpr (sizeof(C) == 4) {
-    if (misaligned({x, r, y, cm, t})) return align_fail(c);
+    if (slabs_misaligned<kSlabsOpenCommit>(x, r, y, cm, t, ok)) return align_fail(c);
     if (native_checked(c, PG_OPEN_COMMIT, 0, c->commit_bound, ok))   // fused, or no flags: no norm kernel (they read 64-bit slabs)
       return run_checked(c, PG_OPEN_COMMIT, 0, specs(), ok, 1, B, B, c->commit_bound, true, true, {});
-    return convert_call(c, {{x, nullptr, B * c->l}, {r, nullptr, B * c->k}, {y, nullptr, B * c->k}, {nullptr, cm, B * (c->n + c->l)},
-                            {nullptr, t, B * c->n}},
-                        [&](int64_t* const* w) { return open_commit_dev<int64_t>(c, w[0], w[1], w[2], w[3], w[4], ok, B); });
+    return convert_call<kSlabsOpenCommit>(c, {}, B, [&](auto... w) { return open_commit_dev<int64_t>(c, w..., B); }, x, r, y, cm, t, ok);
   } else {
     // check_commit_constraint(r) (params.rs:102-108) rides on the loads of r the commit rows do anyway
     return run_checked(c, PG_OPEN_COMMIT, 0, specs(), ok, 1, B, B, c->commit_bound, true, true, {{r, c->k, 0, 0}});
@@ -157,60 +154,77 @@ int open_commit_dev(rzk_ctx* c, const C* x, const C* r, const C* y, C* cm, C* t,
 }
 RZK_BOTH_WIDTHS(open_commit_dev)
 
+}  // namespace rzk::api
+
+namespace {   // the typed forms only this file's extern "C" symbols call
+
 template <class C>
 int open_response_dev(rzk_ctx* c, const C* y, const C* r, const C* d, C* z, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !y || !r || !d || !z) return RZK_E_ARG;
+  if (const int rc = slab_args<kSlabsOpenResponse>(c, {}, B, y, r, d, z); rc != kGo) return rc;
   if constexpr (sizeof(C) == 4) {
-    if (misaligned({y, r, d, z})) return align_fail(c);
+    if (slabs_misaligned<kSlabsOpenResponse>(y, r, d, z)) return align_fail(c);
     if (!program_native32(c, PG_RESPONSE, 1))
-      return convert_call(c, {{y, nullptr, B * c->k}, {r, nullptr, B * c->k}, {d, nullptr, B}, {nullptr, z, B * c->k}},
-                          [&](int64_t* const* w) { return open_response_dev<int64_t>(c, w[0], w[1], w[2], w[3], B); });
+      return convert_call<kSlabsOpenResponse>(c, {}, B, [&](auto... w) { return open_response_dev<int64_t>(c, w..., B); }, y, r, d, z);
   }
   return run_program<C>(c, PG_RESPONSE, 1, {{d, 1, 0}, {y, c->k, 0}, {r, c->k, 0}, {z, c->k, 0}}, nullptr, 1, B);
 }
-RZK_BOTH_WIDTHS(open_response_dev)
 
 // open.rs:167-173 behind rzk_open_verify and, with recover, rzk_open_recover: the recompute step of the short proof, the
 // verifier's launches with the commitment message t = a1.z - c1 (.) d as output (t is written).  64-bit slabs take
 // run_a1_relation with its workspace; 32-bit slabs the one-launch relation at n = 1 where it runs natively (never the
 // split: program_native32 is false wherever that would apply), the convert path otherwise.
 template <class C>
-int open_a1_relation_dev(rzk_ctx* c, const C* z, const C* t, const C* cm, const C* d, uint8_t* accept, size_t B, bool recover) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !z || !t || !cm || !d || !accept) return RZK_E_ARG;
-  if (c->n != c->l) return fail(c, RZK_E_ARG, "c1_c2 split needs n == l (reference panics in Mat::add)");
-  auto specs = [&] { return std::vector<Op<C>>{{z, c->k, 0}, {t, c->n, 0}, {cm, c->n + c->l, 0}, {d, 1, 0}}; };   // of the launching branches
-  if constexpr (sizeof(C) == 4) {
-    if (misaligned({z, t, cm, d})) return align_fail(c);
-    const uint32_t rv = recover ? kRecoverVar : 0u;
-    if (native_checked(c, PG_A1_RELATION, rv, c->verify_bound, accept))
-      return run_checked(c, PG_A1_RELATION, rv, specs(), accept, 1, B, B, c->verify_bound, true, false, {});
-    C* const t_out = const_cast<C*>(t);
-    return convert_call(c, {{z, nullptr, B * c->k}, {cm, nullptr, B * (c->n + c->l)}, {d, nullptr, B},
-                            {recover ? nullptr : t, recover ? t_out : nullptr, B * c->n}},
-                        [&](int64_t* const* w) { return open_a1_relation_dev<int64_t>(c, w[0], w[3], w[1], w[2], accept, B, recover); });
+int open_a1_relation(rzk_ctx* c, const C* z, const C* t, const C* cm, const C* d, uint8_t* accept, size_t B, bool recover) {
+  const std::vector<Op<C>> specs = {{z, c->k, 0}, {t, c->n, 0}, {cm, c->n + c->l, 0}, {d, 1, 0}};
+  if constexpr (sizeof(C) == 4) {   // (the caller has asked open_relation_native32)
+    return run_checked(c, PG_A1_RELATION, recover ? kRecoverVar : 0u, specs, accept, 1, B, B, c->verify_bound, true, false, {});
   } else {
     int rc = arena_reserve(c, c->ws, polys(c, B * c->n));
     if (rc != RZK_OK) return rc;
     // the norm predicate on z rides on the rows that load z
-    return run_a1_relation(c, specs(), (int64_t*)c->ws.p, accept, 1, B, B, true, recover);
+    return run_a1_relation(c, specs, (int64_t*)c->ws.p, accept, 1, B, B, true, recover);
   }
 }
-RZK_BOTH_WIDTHS(open_a1_relation_dev)
+bool open_relation_native32(rzk_ctx* c, bool recover, const uint8_t* accept) {
+  return native_checked(c, PG_A1_RELATION, recover ? kRecoverVar : 0u, c->verify_bound, accept);
+}
+
+template <class C>
+int open_verify_dev(rzk_ctx* c, const C* z, const C* t, const C* cm, const C* d, uint8_t* accept, size_t B) {
+  if (const int rc = slab_args<kSlabsOpenVerify>(c, {}, B, z, t, cm, d, accept); rc != kGo) return rc;
+  if (const int rc = split_check(c)) return rc;
+  if constexpr (sizeof(C) == 4) {
+    if (slabs_misaligned<kSlabsOpenVerify>(z, t, cm, d, accept)) return align_fail(c);
+    if (!open_relation_native32(c, false, accept))
+      return convert_call<kSlabsOpenVerify>(c, {}, B, [&](auto... w) { return open_verify_dev<int64_t>(c, w..., B); }, z, t, cm, d, accept);
+  }
+  return open_a1_relation<C>(c, z, t, cm, d, accept, B, false);
+}
+
+template <class C>
+int open_recover_dev(rzk_ctx* c, const C* z, const C* cm, const C* d, C* t_out, uint8_t* accept, size_t B) {
+  if (const int rc = slab_args<kSlabsOpenRecover>(c, {}, B, z, cm, d, t_out, accept); rc != kGo) return rc;
+  if (const int rc = split_check(c)) return rc;
+  if constexpr (sizeof(C) == 4) {
+    if (slabs_misaligned<kSlabsOpenRecover>(z, cm, d, t_out, accept)) return align_fail(c);
+    if (!open_relation_native32(c, true, accept))
+      return convert_call<kSlabsOpenRecover>(c, {}, B, [&](auto... w) { return open_recover_dev<int64_t>(c, w..., B); }, z, cm, d, t_out, accept);
+  }
+  return open_a1_relation<C>(c, z, t_out, cm, d, accept, B, true);
+}
 
 template <class C>
 int norm2_le_dev(rzk_ctx* c, const C* v, uint32_t rows, uint64_t bound, uint8_t* ok, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !v || !ok || rows == 0) return RZK_E_ARG;
+  if (const int rc = slab_args<kSlabsNorm2Le>(c, by_rows(rows), B, v, ok); rc != kGo) return rc;
   if constexpr (sizeof(C) == 4) {
-    if (misaligned({v})) return align_fail(c);
+    if (slabs_misaligned<kSlabsNorm2Le>(v, ok)) return align_fail(c);
     if (!norm_native32(c))
-      return convert_call(c, {{v, nullptr, B * rows}}, [&](int64_t* const* w) { return norm2_le_dev<int64_t>(c, w[0], rows, bound, ok, B); });
+      return convert_call<kSlabsNorm2Le>(c, by_rows(rows), B, [&](const int64_t* w, uint8_t* flags) {
+        return norm2_le_dev<int64_t>(c, w, rows, bound, flags, B);
+      }, v, ok);
   }
   return run_norm(c, v, rows, bound, ok, B, 0, 0);
 }
-RZK_BOTH_WIDTHS(norm2_le_dev)
 
 // ---- LinearProof (linear.rs), at either width -------------------------------------------------------------------------
 // 32-bit slabs: a call is native when every program it launches is (linear_native32) and converts as a
@@ -218,18 +232,13 @@ RZK_BOTH_WIDTHS(norm2_le_dev)
 template <class C>
 int linear_commit_dev(rzk_ctx* c, const C* g, const C* x, const C* r, const C* rp, const C* y, const C* yp, C* cm, C* cpm, C* t, C* tp,
                       C* u, uint8_t* ok, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !g || !x || !r || !rp || !y || !yp || !cm || !cpm || !t || !tp || !u) return RZK_E_ARG;
+  if (const int rc = slab_args<kSlabsLinearCommit>(c, {}, B, g, x, r, rp, y, yp, cm, cpm, t, tp, u, ok); rc != kGo) return rc;
   const uint32_t n = c->n, k = c->k, l = c->l;
   if constexpr (sizeof(C) == 4) {
-    if (misaligned({g, x, r, rp, y, yp, cm, cpm, t, tp, u})) return align_fail(c);
+    if (slabs_misaligned<kSlabsLinearCommit>(g, x, r, rp, y, yp, cm, cpm, t, tp, u, ok)) return align_fail(c);
     if (!(linear_native32(c, 2 * l, {{PG_CMUL, l}, {PG_LIN_U, 0}}) && checked_native32(c, PG_LIN_COMMIT2, 0, c->commit_bound, ok != nullptr)))
-      return convert_call(c, {{g, nullptr, B}, {x, nullptr, B * l}, {r, nullptr, B * k}, {rp, nullptr, B * k}, {y, nullptr, B * k},
-                              {yp, nullptr, B * k}, {nullptr, cm, B * (n + l)}, {nullptr, cpm, B * (n + l)}, {nullptr, t, B * n},
-                              {nullptr, tp, B * n}, {nullptr, u, B * l}},
-                          [&](int64_t* const* w) {
-                            return linear_commit_dev<int64_t>(c, w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8], w[9], w[10], ok, B);
-                          });
+      return convert_call<kSlabsLinearCommit>(c, {}, B, [&](auto... w) { return linear_commit_dev<int64_t>(c, w..., B); }, g, x, r, rp, y, yp,
+                                              cm, cpm, t, tp, u, ok);
   }
   int rc = arena_reserve(c, c->ws, polys<C>(c, 2 * B * l));
   if (rc != RZK_OK) return rc;
@@ -253,7 +262,6 @@ int linear_commit_dev(rzk_ctx* c, const C* g, const C* x, const C* r, const C* r
   if (rc != RZK_OK) return rc;
   return run_program<C>(c, PG_LIN_U, dkv(c), {{a2y, l, 0}, {g, 1, 0}, {yp, k, 0}, {u, l, 0}}, ok, 1, B);
 }
-RZK_BOTH_WIDTHS(linear_commit_dev)
 
 // The y-only half of linear_commit_dev (linear.rs:118-129): the rows of PG_LIN_COMMIT2 that read y and y' alone
 // (its kMaskVar form: y is transformed once for the a1 and the a2 row) and PG_LIN_U as there.  The arithmetic is exact,
@@ -261,15 +269,12 @@ RZK_BOTH_WIDTHS(linear_commit_dev)
 // coefficient raises the sticky word as in rzk_matvec_batch_dev.
 template <class C>
 int linear_mask_dev(rzk_ctx* c, const C* g, const C* y, const C* yp, C* t, C* tp, C* u, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !g || !y || !yp || !t || !tp || !u) return RZK_E_ARG;
+  if (const int rc = slab_args<kSlabsLinearMask>(c, {}, B, g, y, yp, t, tp, u); rc != kGo) return rc;
   const uint32_t n = c->n, k = c->k, l = c->l;
   if constexpr (sizeof(C) == 4) {
-    if (misaligned({g, y, yp, t, tp, u})) return align_fail(c);
+    if (slabs_misaligned<kSlabsLinearMask>(g, y, yp, t, tp, u)) return align_fail(c);
     if (!linear_native32(c, l, {{PG_LIN_COMMIT2, kMaskVar}, {PG_LIN_U, 0}}))
-      return convert_call(c, {{g, nullptr, B}, {y, nullptr, B * k}, {yp, nullptr, B * k}, {nullptr, t, B * n}, {nullptr, tp, B * n},
-                              {nullptr, u, B * l}},
-                          [&](int64_t* const* w) { return linear_mask_dev<int64_t>(c, w[0], w[1], w[2], w[3], w[4], w[5], B); });
+      return convert_call<kSlabsLinearMask>(c, {}, B, [&](auto... w) { return linear_mask_dev<int64_t>(c, w..., B); }, g, y, yp, t, tp, u);
   }
   int rc = arena_reserve(c, c->ws, polys<C>(c, B * l));
   if (rc != RZK_OK) return rc;
@@ -287,45 +292,37 @@ int linear_mask_dev(rzk_ctx* c, const C* g, const C* y, const C* yp, C* t, C* tp
   if (rc != RZK_OK) return rc;
   return run_program<C>(c, PG_LIN_U, dkv(c), {{a2y, l, 0}, {g, 1, 0}, {yp, k, 0}, {u, l, 0}}, nullptr, 1, B);
 }
-RZK_BOTH_WIDTHS(linear_mask_dev)
 
 template <class C>
 int linear_response_dev(rzk_ctx* c, const C* y, const C* yp, const C* r, const C* rp, const C* d, C* z, C* zp, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !y || !yp || !r || !rp || !d || !z || !zp) return RZK_E_ARG;
+  if (const int rc = slab_args<kSlabsLinearResponse>(c, {}, B, y, yp, r, rp, d, z, zp); rc != kGo) return rc;
   const uint32_t k = c->k;
   if constexpr (sizeof(C) == 4) {
-    if (misaligned({y, yp, r, rp, d, z, zp})) return align_fail(c);
+    if (slabs_misaligned<kSlabsLinearResponse>(y, yp, r, rp, d, z, zp)) return align_fail(c);
     if (!program_native32(c, PG_RESPONSE, 2))
-      return convert_call(c, {{y, nullptr, B * k}, {yp, nullptr, B * k}, {r, nullptr, B * k}, {rp, nullptr, B * k}, {d, nullptr, B},
-                              {nullptr, z, B * k}, {nullptr, zp, B * k}},
-                          [&](int64_t* const* w) { return linear_response_dev<int64_t>(c, w[0], w[1], w[2], w[3], w[4], w[5], w[6], B); });
+      return convert_call<kSlabsLinearResponse>(c, {}, B, [&](auto... w) { return linear_response_dev<int64_t>(c, w..., B); }, y, yp, r, rp, d,
+                                                z, zp);
   }
   return run_program<C>(c, PG_RESPONSE, 2, {{d, 1, 0}, {y, k, 0}, {r, k, 0}, {z, k, 0}, {yp, k, 0}, {rp, k, 0}, {zp, k, 0}},
                         nullptr, 1, B);
 }
-RZK_BOTH_WIDTHS(linear_response_dev)
 
 template <class C>
 int linear_verify_dev(rzk_ctx* c, const C* z, const C* zp, const C* cm, const C* cpm, const C* g, const C* t, const C* tp, const C* u,
                       const C* d, uint8_t* accept, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !z || !zp || !cm || !cpm || !g || !t || !tp || !u || !d || !accept) return RZK_E_ARG;
-  if (c->n != c->l) return fail(c, RZK_E_ARG, "c1_c2 split needs n == l (reference panics in Mat::add)");
-  const uint32_t n = c->n, k = c->k, l = c->l;
+  if (const int rc = slab_args<kSlabsLinearVerify>(c, {}, B, z, zp, cm, cpm, g, t, tp, u, d, accept); rc != kGo) return rc;
+  if (const int rc = split_check(c)) return rc;
   const bool rearranged = c->lin_e && !c->small;
   if constexpr (sizeof(C) == 4) {
-    if (misaligned({z, zp, cm, cpm, g, t, tp, u, d})) return align_fail(c);
+    if (slabs_misaligned<kSlabsLinearVerify>(z, zp, cm, cpm, g, t, tp, u, d, accept)) return align_fail(c);
     // (RZK_LIN_E=0: the relation rows carry rotation terms inside row_kernel, which has no 32-bit form)
     if (!(rearranged && linear_verify_native32(c, false)))
-      return convert_call(c, {{z, nullptr, B * k}, {zp, nullptr, B * k}, {cm, nullptr, B * (n + l)}, {cpm, nullptr, B * (n + l)},
-                              {g, nullptr, B}, {t, nullptr, B * n}, {tp, nullptr, B * n}, {u, nullptr, B * l}, {d, nullptr, B}},
-                          [&](int64_t* const* w) {
-                            return linear_verify_dev<int64_t>(c, w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8], accept, B);
-                          });
+      return convert_call<kSlabsLinearVerify>(c, {}, B, [&](auto... w) { return linear_verify_dev<int64_t>(c, w..., B); }, z, zp, cm, cpm, g, t,
+                                              tp, u, d, accept);
     return linear_rearranged<C>(c, z, zp, cm, cpm, g, t, tp, u, d, accept, B, false);
   } else {
     if (rearranged) return linear_rearranged<C>(c, z, zp, cm, cpm, g, t, tp, u, d, accept, B, false);
+    const uint32_t n = c->n, k = c->k, l = c->l;
     int rc = arena_reserve(c, c->ws, polys(c, 2 * B * l));
     if (rc != RZK_OK) return rc;
     int64_t* w1 = (int64_t*)c->ws.p;
@@ -347,38 +344,30 @@ int linear_verify_dev(rzk_ctx* c, const C* z, const C* zp, const C* cm, const C*
                        false);
   }
 }
-RZK_BOTH_WIDTHS(linear_verify_dev)
 
 // The recompute step of the short proof: the verifier's launches with the commitment message as output.
 template <class C>
 int linear_recover_dev(rzk_ctx* c, const C* z, const C* zp, const C* cm, const C* cpm, const C* g, const C* d, C* t_out, C* tp_out,
                        C* u_out, uint8_t* accept, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !z || !zp || !cm || !cpm || !g || !d || !t_out || !tp_out || !u_out || !accept) return RZK_E_ARG;
-  if (c->n != c->l) return fail(c, RZK_E_ARG, "c1_c2 split needs n == l (reference panics in Mat::add)");
+  if (const int rc = slab_args<kSlabsLinearRecover>(c, {}, B, z, zp, cm, cpm, g, d, t_out, tp_out, u_out, accept); rc != kGo) return rc;
+  if (const int rc = split_check(c)) return rc;
   if constexpr (sizeof(C) == 4) {
-    const uint32_t n = c->n, k = c->k, l = c->l;
-    if (misaligned({z, zp, cm, cpm, g, d, t_out, tp_out, u_out})) return align_fail(c);
+    if (slabs_misaligned<kSlabsLinearRecover>(z, zp, cm, cpm, g, d, t_out, tp_out, u_out, accept)) return align_fail(c);
     if (!linear_verify_native32(c, true))
-      return convert_call(c, {{z, nullptr, B * k}, {zp, nullptr, B * k}, {cm, nullptr, B * (n + l)}, {cpm, nullptr, B * (n + l)},
-                              {g, nullptr, B}, {d, nullptr, B}, {nullptr, t_out, B * n}, {nullptr, tp_out, B * n}, {nullptr, u_out, B * l}},
-                          [&](int64_t* const* w) {
-                            return linear_recover_dev<int64_t>(c, w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8], accept, B);
-                          });
+      return convert_call<kSlabsLinearRecover>(c, {}, B, [&](auto... w) { return linear_recover_dev<int64_t>(c, w..., B); }, z, zp, cm, cpm, g,
+                                               d, t_out, tp_out, u_out, accept);
   }
   // on every context (small rings and RZK_LIN_E=0 included): the non-rearranged pair has no recover form
   return linear_rearranged<C>(c, z, zp, cm, cpm, g, t_out, tp_out, u_out, d, accept, B, true);
 }
-RZK_BOTH_WIDTHS(linear_recover_dev)
 
-}  // namespace rzk::api
+}  // namespace
 
 extern "C" {
 
 // ---- ring / Mat primitives -----------------------------------------------------------------------------------------
 int rzk_polymul_batch_dev(rzk_ctx* c, const int64_t* a, const int64_t* b, int64_t* out, size_t count) {
-  if (c && count == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !a || !b || !out) return RZK_E_ARG;
+  if (const int rc = slab_args<kSlabsPolymul>(c, {}, count, a, b, out); rc != kGo) return rc;
   return run_program(c, PG_POLYMUL, 0, {{a, 1, 0}, {b, 1, 0}, {out, 1, 0}}, nullptr, 1, count);
 }
 
@@ -390,8 +379,7 @@ int rzk_matvec32_batch_dev(rzk_ctx* c, int which, const int32_t* v, const int32_
 }
 
 int rzk_cmul_batch_dev(rzk_ctx* c, const int64_t* m, uint32_t rows, const int64_t* p, int64_t* out, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !m || !p || !out || rows == 0) return RZK_E_ARG;
+  if (const int rc = slab_args<kSlabsCmul>(c, by_rows(rows), B, m, p, out); rc != kGo) return rc;
   if (rows > (uint32_t)kMaxRows) {
     // more rows than one program holds: treat every row as its own batch entry sharing p
     return run_program(c, PG_CMUL, 1, {{m, 1, 0}, {p, 1, 1}, {out, 1, 0}}, nullptr, rows, B * rows);
@@ -400,20 +388,17 @@ int rzk_cmul_batch_dev(rzk_ctx* c, const int64_t* m, uint32_t rows, const int64_
 }
 
 int rzk_canonicalize_batch_dev(rzk_ctx* c, const int64_t* in, int64_t* out, size_t count) {
-  if (c && count == 0) return RZK_OK;
-  if (!c || !in || !out) return RZK_E_ARG;
+  if (const int rc = slab_args<kSlabsCanonicalize>(c, {}, count, in, out); rc != kGo) return rc;
   return check_launch(c, launch_canonicalize(cfg_of(c), in, out, (uint64_t)count * c->N, c->q), "canonicalize kernel");
 }
 
 int rzk_add_batch_dev(rzk_ctx* c, const int64_t* a, const int64_t* b, int64_t* out, size_t count) {
-  if (c && count == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !a || !b || !out) return RZK_E_ARG;
+  if (const int rc = slab_args<kSlabsAdd>(c, {}, count, a, b, out); rc != kGo) return rc;
   return check_launch(c, launch_addsub(cfg_of(c), false, a, b, out, (uint64_t)count * c->N, c->dT, c->d_bad), "add kernel");
 }
 
 int rzk_sub_batch_dev(rzk_ctx* c, const int64_t* a, const int64_t* b, int64_t* out, size_t count) {
-  if (c && count == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !a || !b || !out) return RZK_E_ARG;
+  if (const int rc = slab_args<kSlabsSub>(c, {}, count, a, b, out); rc != kGo) return rc;
   return check_launch(c, launch_addsub(cfg_of(c), true, a, b, out, (uint64_t)count * c->N, c->dT, c->d_bad), "sub kernel");
 }
 
@@ -425,8 +410,7 @@ int rzk_norm2_le32_batch_dev(rzk_ctx* c, const int32_t* v, uint32_t rows, uint64
 }
 
 int rzk_eq_batch_dev(rzk_ctx* c, const int64_t* a, const int64_t* b, uint32_t rows, uint8_t* eq, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !a || !b || !eq || rows == 0) return RZK_E_ARG;
+  if (const int rc = slab_args<kSlabsEq>(c, by_rows(rows), B, a, b, eq); rc != kGo) return rc;
   const uint32_t qh = c->hT.crt.qhalf;
   if (c->small) return check_launch(c, launch_eq_small(c->N, cfg_of(c), a, b, rows, eq, B, qh, c->d_bad), "eq kernel");
   return check_launch(c, launch_eq((int)c->logn, cfg_of(c), a, b, rows, eq, B, qh, c->d_bad), "eq kernel");
@@ -460,8 +444,7 @@ uint32_t rzk_ntt_layout_index(uint32_t N, uint32_t j) {
 
 // ---- commitment scheme ---------------------------------------------------------------------------------------------
 int rzk_commit_batch_dev(rzk_ctx* c, const int64_t* x, const int64_t* r, int64_t* cm, uint8_t* ok, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !x || !r || !cm) return RZK_E_ARG;
+  if (const int rc = slab_args<kSlabsCommit>(c, {}, B, x, r, cm, ok); rc != kGo) return rc;
   // unfused: the exact norm kernel sets ok, then the rows clear it again for proofs with non-canonical inputs
   return run_checked(c, PG_COMMIT, 0, {{x, c->l, 0}, {r, c->k, 0}, {cm, c->n + c->l, 0}}, ok, 1, B, B, c->commit_bound, true,
                      true, {{r, c->k, 0, 0}});
@@ -469,8 +452,7 @@ int rzk_commit_batch_dev(rzk_ctx* c, const int64_t* x, const int64_t* r, int64_t
 
 int rzk_commitment_verify_batch_dev(rzk_ctx* c, const int64_t* cm, const int64_t* x, const int64_t* r,
                                     const int64_t* f, uint8_t* ok, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !cm || !x || !r || !ok) return RZK_E_ARG;
+  if (const int rc = slab_args<kSlabsCommitmentVerify>(c, {}, B, cm, x, r, f, ok); rc != kGo) return rc;
   const uint32_t var = f ? 2u : 0u;
   // commit.rs:183-185: the norm predicate on r rides on the rows that load r
   return run_checked(c, PG_COMMIT_VERIFY, var, {{x, c->l, 0}, {r, c->k, 0}, {cm, c->n + c->l, 0}, {f, 1, 0}}, ok, 1, B, B,
@@ -494,19 +476,19 @@ int rzk_open_response32_batch_dev(rzk_ctx* c, const int32_t* y, const int32_t* r
 }
 int rzk_open_verify_batch_dev(rzk_ctx* c, const int64_t* z, const int64_t* t, const int64_t* cm, const int64_t* d, uint8_t* accept,
                               size_t B) {
-  return open_a1_relation_dev(c, z, t, cm, d, accept, B, false);
+  return open_verify_dev(c, z, t, cm, d, accept, B);
 }
 int rzk_open_verify32_batch_dev(rzk_ctx* c, const int32_t* z, const int32_t* t, const int32_t* cm, const int32_t* d, uint8_t* accept,
                                 size_t B) {
-  return open_a1_relation_dev(c, z, t, cm, d, accept, B, false);
+  return open_verify_dev(c, z, t, cm, d, accept, B);
 }
 int rzk_open_recover_batch_dev(rzk_ctx* c, const int64_t* z, const int64_t* cm, const int64_t* d, int64_t* t_out, uint8_t* accept,
                                size_t B) {
-  return open_a1_relation_dev(c, z, t_out, cm, d, accept, B, true);
+  return open_recover_dev(c, z, cm, d, t_out, accept, B);
 }
 int rzk_open_recover32_batch_dev(rzk_ctx* c, const int32_t* z, const int32_t* cm, const int32_t* d, int32_t* t_out, uint8_t* accept,
                                  size_t B) {
-  return open_a1_relation_dev(c, z, t_out, cm, d, accept, B, true);
+  return open_recover_dev(c, z, cm, d, t_out, accept, B);
 }
 
 // ---- LinearProof, at either width (the templates above) -------------------------------------------------------------
@@ -551,8 +533,7 @@ int rzk_linear_verify32_batch_dev(rzk_ctx* c, const int32_t* z, const int32_t* z
 int rzk_sum_commit_batch_dev(rzk_ctx* c, uint32_t V, const int64_t* gs, const int64_t* xs, const int64_t* rs,
                              const int64_t* rp, const int64_t* ys, const int64_t* yp, int64_t* cs, int64_t* cpm,
                              int64_t* ts, int64_t* tp, int64_t* u, uint8_t* ok, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || V == 0 || !gs || !xs || !rs || !rp || !ys || !yp || !cs || !cpm || !ts || !tp || !u) return RZK_E_ARG;
+  if (const int rc = slab_args<kSlabsSumCommit>(c, by_V(V), B, gs, xs, rs, rp, ys, yp, cs, cpm, ts, tp, u, ok); rc != kGo) return rc;
   const uint32_t n = c->n, k = c->k, l = c->l;
   const size_t wpolys = (size_t)B * V * l > (size_t)B * k ? (size_t)B * V * l : (size_t)B * k;   // w[B*V][l], or D[B][k]
   int rc = arena_reserve(c, c->ws, polys(c, B * l + wpolys));
@@ -603,8 +584,7 @@ int rzk_sum_commit_batch_dev(rzk_ctx* c, uint32_t V, const int64_t* gs, const in
 // the bytes are the commit call's either way.
 int rzk_sum_mask_batch_dev(rzk_ctx* c, uint32_t V, const int64_t* gs, const int64_t* ys, const int64_t* yp, int64_t* ts,
                            int64_t* tp, int64_t* u, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || V == 0 || !gs || !ys || !yp || !ts || !tp || !u) return RZK_E_ARG;
+  if (const int rc = slab_args<kSlabsSumMask>(c, by_V(V), B, gs, ys, yp, ts, tp, u); rc != kGo) return rc;
   const uint32_t n = c->n, k = c->k, l = c->l;
   const size_t wpolys = (size_t)B * V * l > (size_t)B * k ? (size_t)B * V * l : (size_t)B * k;   // w[B*V][l], or D[B][k]
   int rc = arena_reserve(c, c->ws, polys(c, wpolys));
@@ -630,8 +610,7 @@ int rzk_sum_mask_batch_dev(rzk_ctx* c, uint32_t V, const int64_t* gs, const int6
 
 int rzk_sum_response_batch_dev(rzk_ctx* c, uint32_t V, const int64_t* ys, const int64_t* yp, const int64_t* rs,
                                const int64_t* rp, const int64_t* d, int64_t* zs, int64_t* zp, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || V == 0 || !ys || !yp || !rs || !rp || !d || !zs || !zp) return RZK_E_ARG;
+  if (const int rc = slab_args<kSlabsSumResponse>(c, by_V(V), B, ys, yp, rs, rp, d, zs, zp); rc != kGo) return rc;
   const uint32_t k = c->k;
   // sum.rs:188-193: z_i = y_i + r_i (.) d — summands as batch entries, d shared by the V entries of a proof
   int rc = run_program(c, PG_RESPONSE, 1, {{d, 1, 1}, {ys, k, 0}, {rs, k, 0}, {zs, k, 0}}, nullptr, V, B * V);
@@ -643,9 +622,8 @@ int rzk_sum_response_batch_dev(rzk_ctx* c, uint32_t V, const int64_t* ys, const 
 int rzk_sum_verify_batch_dev(rzk_ctx* c, uint32_t V, const int64_t* zs, const int64_t* zp, const int64_t* cs,
                              const int64_t* cpm, const int64_t* gs, const int64_t* ts, const int64_t* tp,
                              const int64_t* u, const int64_t* d, uint8_t* accept, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || V == 0 || !zs || !zp || !cs || !cpm || !gs || !ts || !tp || !u || !d || !accept) return RZK_E_ARG;
-  if (c->n != c->l) return fail(c, RZK_E_ARG, "c1_c2 split needs n == l (reference panics in Mat::add)");
+  if (const int rc = slab_args<kSlabsSumVerify>(c, by_V(V), B, zs, zp, cs, cpm, gs, ts, tp, u, d, accept); rc != kGo) return rc;
+  if (const int rc = split_check(c)) return rc;
   return sum_relations(c, V, zs, zp, cs, cpm, gs, ts, tp, u, d, accept, B, false);
 }
 
@@ -664,9 +642,8 @@ int rzk_linear_recover32_batch_dev(rzk_ctx* c, const int32_t* z, const int32_t* 
 int rzk_sum_recover_batch_dev(rzk_ctx* c, uint32_t V, const int64_t* zs, const int64_t* zp, const int64_t* cs,
                               const int64_t* cpm, const int64_t* gs, const int64_t* d, int64_t* ts_out, int64_t* tp_out,
                               int64_t* u_out, uint8_t* accept, size_t B) {
-  if (c && B == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || V == 0 || !zs || !zp || !cs || !cpm || !gs || !d || !ts_out || !tp_out || !u_out || !accept) return RZK_E_ARG;
-  if (c->n != c->l) return fail(c, RZK_E_ARG, "c1_c2 split needs n == l (reference panics in Mat::add)");
+  if (const int rc = slab_args<kSlabsSumRecover>(c, by_V(V), B, zs, zp, cs, cpm, gs, d, ts_out, tp_out, u_out, accept); rc != kGo) return rc;
+  if (const int rc = split_check(c)) return rc;
   return sum_relations(c, V, zs, zp, cs, cpm, gs, ts_out, tp_out, u_out, d, accept, B, true);
 }
 

@@ -18,6 +18,8 @@
 // Open: one body for both slab widths, over the coefficient type C of the caller's slabs: it calls the typed
 // forms of the entry points (rzk_ctx.h); the 32-bit ones convert inside themselves where the context has no native 32-bit
 // kernels (ws32 is theirs, within the same call: the loop does not touch it).  Linear and Sum exist on 64-bit slabs only.
+// The NULL tests, the alignment test of Open, the staging of the host forms and the row counts of the Linear / Sum fields
+// come from the calls' slab lists (rzk_slabs.h, glue in rzk_ctx.h).
 #include "rzk_ctx.h"
 #include "rzk_prove_loop.h"
 
@@ -284,8 +286,10 @@ int open_prove_zk_dev(rzk_ctx* c, const C* x, const uint8_t* nonce0, uint32_t st
                             "nonce0 + 1 + 3 max_rounds leaves 128 bits", B);
   if (rc != RZK_OK) return rc;
   if (B == 0) return RZK_OK;
-  if (!x || !cm || !t || !z || !r || !ok || !rounds) return fail(c, RZK_E_ARG, "open prove zk: non-NULL x, c, t, z, r, ok, rounds expected");
-  if (misaligned({x, cm, t, z, r})) return fail(c, RZK_E_ARG, "open prove zk: device slabs must be 16-byte aligned");
+  if (slabs_null<kSlabsOpenProveZk>(x, cm, t, z, r, ok, rounds))
+    return fail(c, RZK_E_ARG, "open prove zk: non-NULL x, c, t, z, r, ok, rounds expected");
+  if (slabs_misaligned<kSlabsOpenProveZk>(x, cm, t, z, r, ok, rounds))
+    return fail(c, RZK_E_ARG, "open prove zk: device slabs must be 16-byte aligned");
   if (!c->key_loaded) return fail(c, RZK_E_STATE, "commitment key not loaded");
   OpenLoop<C> loop(c, x, nonce0, stream, gauss_kind, aux32, cm, t, z, r, ok, rounds, B);
   return loop.run(max_rounds, rounds_run);
@@ -300,14 +304,11 @@ int open_prove_zk_host(rzk_ctx* c, const C* x, const uint8_t* nonce0, uint32_t s
                             "nonce0 + 1 + 3 max_rounds leaves 128 bits", B);
   if (rc != RZK_OK) return rc;
   if (B == 0) return RZK_OK;
-  if (!x || !cm || !t || !z || !r || !ok || !rounds) return fail(c, RZK_E_ARG, "open prove zk: non-NULL x, c, t, z, r, ok, rounds expected");
-  HostCall h(c);
-  const auto dx = h.pin(x, B * c->l);
-  const auto dcm = h.pout(cm, B * (c->n + c->l)), dt = h.pout(t, B * c->n), dz = h.pout(z, B * c->k), dr = h.pout(r, B * c->k);
-  const auto dok = h.out(ok, B), drounds = h.out(rounds, B);
-  return h.run([&] {
+  if (slabs_null<kSlabsOpenProveZk>(x, cm, t, z, r, ok, rounds))
+    return fail(c, RZK_E_ARG, "open prove zk: non-NULL x, c, t, z, r, ok, rounds expected");
+  return host_run<kSlabsOpenProveZk>(c, {}, B, [&](const C* dx, C* dcm, C* dt, C* dz, C* dr, uint8_t* dok, uint8_t* drounds) {
     return open_prove_zk_dev<C>(c, dx, nonce0, stream, gauss_kind, aux32, max_rounds, dcm, dt, dz, dr, dok, drounds, rounds_run, B);
-  });
+  }, x, cm, t, z, r, ok, rounds);
 }
 
 // ---- Linear and Sum: five slabs per direction, through the field-list kernels ----------------------------------------------
@@ -322,6 +323,8 @@ class FieldLoop : public ProveLoop<int64_t> {
     int64_t* kept[kFields];    // the caller's (g / gs is an input: never written)
     int64_t* fresh[kFields];
     uint64_t kept_rows[kFields], fresh_rows[kFields];   // polynomials per proof
+    const int64_t* x;                                   // and what is no field: the messages x (xs), read; ok and rounds, written
+    uint8_t *ok, *rounds;
   };
   // false: an entry size or the batch times it leaves its type (field_quads)
   static bool sizes_ok(const Slabs& s, uint32_t N, size_t B) {
@@ -488,74 +491,48 @@ const char* const kSpanLinSum = "nonce0 + 2 + 4 max_rounds leaves 128 bits";
 
 // the checks both forms of a Linear / Sum call make before anything is staged or launched; *go = false: return rc at once
 int field_loop_args(rzk_ctx* c, const char* name, const uint8_t* nonce0, int gauss_kind, uint32_t max_rounds, uint32_t* rounds_run,
-                    const FieldLoop::Slabs& s, const void* x, const uint8_t* ok, const uint8_t* rounds, size_t B, bool* go) {
+                    const FieldLoop::Slabs& s, size_t B, bool* go) {
   *go = false;
   if (rounds_run) *rounds_run = 0;
   const int rc = prove_args(c, name, nonce0, gauss_kind, max_rounds, prove_nonce_span_lin_sum(max_rounds), kSpanLinSum, B);
   if (rc != RZK_OK || B == 0) return rc;
-  bool null = !x || !ok || !rounds;
+  bool null = !s.x || !s.ok || !s.rounds;
   for (uint32_t f = 0; f < FieldLoop::kFields; ++f) null = null || !s.kept[f] || !s.fresh[f];
   if (null) return named_fail(c, RZK_E_ARG, name, "non-NULL slabs, ok and rounds expected");
   if (!FieldLoop::sizes_ok(s, c->N, B)) return named_fail(c, RZK_E_ARG, name, "a proof's slab entry, or the batch of them, is too large");
   *go = true;
   return RZK_OK;
 }
-int field_loop_dev_args(rzk_ctx* c, const char* name, const FieldLoop::Slabs& s, const void* x) {
-  uintptr_t bits = (uintptr_t)x;
+int field_loop_dev_args(rzk_ctx* c, const char* name, const FieldLoop::Slabs& s) {
+  uintptr_t bits = (uintptr_t)s.x;
   for (uint32_t f = 0; f < FieldLoop::kFields; ++f) bits |= (uintptr_t)s.kept[f] | (uintptr_t)s.fresh[f];
   if (bits & 15u) return named_fail(c, RZK_E_ARG, name, "device slabs must be 16-byte aligned");
   if (!c->key_loaded) return fail(c, RZK_E_STATE, "commitment key not loaded");
   return RZK_OK;
 }
-FieldLoop::Slabs linear_slabs(const rzk_ctx* c, const int64_t* g, int64_t* cm, int64_t* cpm, int64_t* t, int64_t* tp, int64_t* u, int64_t* z,
-                              int64_t* zp, int64_t* r, int64_t* rp) {
-  const uint64_t n = c->n, k = c->k, l = c->l;
-  return FieldLoop::Slabs{{r, rp, cm, cpm, const_cast<int64_t*>(g)}, {t, tp, u, z, zp}, {k, k, n + l, n + l, 1}, {n, n, l, k, k}};
-}
-FieldLoop::Slabs sum_slabs(const rzk_ctx* c, uint64_t V, const int64_t* gs, int64_t* cs, int64_t* cpm, int64_t* ts, int64_t* tp, int64_t* u,
-                           int64_t* zs, int64_t* zp, int64_t* rs, int64_t* rp) {
-  const uint64_t n = c->n, k = c->k, l = c->l;
-  return FieldLoop::Slabs{{rs, rp, cs, cpm, const_cast<int64_t*>(gs)}, {ts, tp, u, zs, zp}, {V * k, k, V * (n + l), n + l, V},
-                          {V * n, n, l, V * k, k}};
-}
-
-// a host-pointer Linear / Sum call: x (xs) and g (gs) are staged in, the ten other slabs, ok and rounds out; dev_call gets the
-// staged slabs
-template <class F>
-int field_loop_host(rzk_ctx* c, const FieldLoop::Slabs& s, const int64_t* x, uint64_t x_rows, uint8_t* ok, uint8_t* rounds, size_t B,
-                    F dev_call) {
-  HostCall h(c);
-  const auto dx = h.pin(x, B * x_rows);
-  HostCall::Dev<const int64_t> dg = h.pin((const int64_t*)s.kept[4], B * s.kept_rows[4]);
-  HostCall::Dev<int64_t> dk[FieldLoop::kFields], df[FieldLoop::kFields];
-  for (uint32_t f = 0; f < FieldLoop::kFields; ++f) {
-    if (f != 4) dk[f] = h.pout(s.kept[f], B * s.kept_rows[f]);
-    df[f] = h.pout(s.fresh[f], B * s.fresh_rows[f]);
-  }
-  const auto dok = h.out(ok, B), drounds = h.out(rounds, B);
-  return h.run([&] {
-    FieldLoop::Slabs d = s;   // (the device pointers exist once the arena is staged: inside run)
-    for (uint32_t f = 0; f < FieldLoop::kFields; ++f) {
-      d.kept[f] = f == 4 ? const_cast<int64_t*>((const int64_t*)dg) : (int64_t*)dk[f];
-      d.fresh[f] = (int64_t*)df[f];
-    }
-    return dev_call(d, (const int64_t*)dx, (uint8_t*)dok, (uint8_t*)drounds);
-  });
+// A Linear (S = kSlabsLinearProveZk) or Sum (kSlabsSumProveZk) call's pointers, in declaration order, as the loop's fields: the
+// two lists declare g (gs), x (xs), then c, cp, t, tp, u, z, zp, r, rp (cs, ..., rs, rp), ok, rounds; the rows are the list's.
+FieldLoop::Slabs field_slabs(const CallSlabs& S, const SlabDims& dm, const int64_t* g, const int64_t* x, int64_t* cm, int64_t* cpm,
+                             int64_t* t, int64_t* tp, int64_t* u, int64_t* z, int64_t* zp, int64_t* r, int64_t* rp, uint8_t* ok,
+                             uint8_t* rounds) {
+  enum { G = 0, CM = 2, CPM, T, TP, U, Z, ZP, R, RP };   // positions in the list
+  auto rows = [&](int at) { return slab_count(S.s[at].kind, dm); };
+  return FieldLoop::Slabs{{r, rp, cm, cpm, const_cast<int64_t*>(g)}, {t, tp, u, z, zp}, {rows(R), rows(RP), rows(CM), rows(CPM), rows(G)},
+                          {rows(T), rows(TP), rows(U), rows(Z), rows(ZP)}, x, ok, rounds};
 }
 
-int linear_prove_zk_slabs(rzk_ctx* c, const FieldLoop::Slabs& s, const int64_t* x, const uint8_t* nonce0, uint32_t stream, int gauss_kind,
-                          const uint8_t* aux32, uint32_t max_rounds, uint8_t* ok, uint8_t* rounds, uint32_t* rounds_run, size_t B) {
-  const int rc = field_loop_dev_args(c, "linear prove zk", s, x);
+int linear_prove_zk_slabs(rzk_ctx* c, const FieldLoop::Slabs& s, const uint8_t* nonce0, uint32_t stream, int gauss_kind, const uint8_t* aux32,
+                          uint32_t max_rounds, uint32_t* rounds_run, size_t B) {
+  const int rc = field_loop_dev_args(c, "linear prove zk", s);
   if (rc != RZK_OK) return rc;
-  LinearLoop loop(c, s, x, nonce0, stream, gauss_kind, aux32, ok, rounds, B);
+  LinearLoop loop(c, s, s.x, nonce0, stream, gauss_kind, aux32, s.ok, s.rounds, B);
   return loop.run(max_rounds, rounds_run);
 }
-int sum_prove_zk_slabs(rzk_ctx* c, uint32_t V, const FieldLoop::Slabs& s, const int64_t* xs, const uint8_t* nonce0, uint32_t stream,
-                       int gauss_kind, const uint8_t* aux32, uint32_t max_rounds, uint8_t* ok, uint8_t* rounds, uint32_t* rounds_run,
-                       size_t B) {
-  const int rc = field_loop_dev_args(c, "sum prove zk", s, xs);
+int sum_prove_zk_slabs(rzk_ctx* c, uint32_t V, const FieldLoop::Slabs& s, const uint8_t* nonce0, uint32_t stream, int gauss_kind,
+                       const uint8_t* aux32, uint32_t max_rounds, uint32_t* rounds_run, size_t B) {
+  const int rc = field_loop_dev_args(c, "sum prove zk", s);
   if (rc != RZK_OK) return rc;
-  SumLoop loop(c, V, s, xs, nonce0, stream, gauss_kind, aux32, ok, rounds, B);
+  SumLoop loop(c, V, s, s.x, nonce0, stream, gauss_kind, aux32, s.ok, s.rounds, B);
   return loop.run(max_rounds, rounds_run);
 }
 
@@ -591,24 +568,25 @@ int rzk_linear_prove_zk_batch_dev(rzk_ctx* c, const int64_t* g, const int64_t* x
                                   int64_t* tp, int64_t* u, int64_t* z, int64_t* zp, int64_t* r, int64_t* rp, uint8_t* ok, uint8_t* rounds,
                                   uint32_t* rounds_run, size_t B) {
   if (!c) return RZK_E_ARG;
-  const FieldLoop::Slabs s = linear_slabs(c, g, cm, cpm, t, tp, u, z, zp, r, rp);
+  const FieldLoop::Slabs s = field_slabs(kSlabsLinearProveZk, dims_of(c), g, x, cm, cpm, t, tp, u, z, zp, r, rp, ok, rounds);
   bool go;
-  const int rc = field_loop_args(c, "linear prove zk", nonce0, gauss_kind, max_rounds, rounds_run, s, x, ok, rounds, B, &go);
+  const int rc = field_loop_args(c, "linear prove zk", nonce0, gauss_kind, max_rounds, rounds_run, s, B, &go);
   if (!go) return rc;
-  return linear_prove_zk_slabs(c, s, x, nonce0, stream, gauss_kind, aux32, max_rounds, ok, rounds, rounds_run, B);
+  return linear_prove_zk_slabs(c, s, nonce0, stream, gauss_kind, aux32, max_rounds, rounds_run, B);
 }
 int rzk_linear_prove_zk_batch(rzk_ctx* c, const int64_t* g, const int64_t* x, const uint8_t nonce0[16], uint32_t stream, int gauss_kind,
                               const uint8_t* aux32, uint32_t max_rounds, int64_t* cm, int64_t* cpm, int64_t* t, int64_t* tp, int64_t* u,
                               int64_t* z, int64_t* zp, int64_t* r, int64_t* rp, uint8_t* ok, uint8_t* rounds, uint32_t* rounds_run,
                               size_t B) {
   if (!c) return RZK_E_ARG;
-  const FieldLoop::Slabs s = linear_slabs(c, g, cm, cpm, t, tp, u, z, zp, r, rp);
+  const FieldLoop::Slabs s = field_slabs(kSlabsLinearProveZk, dims_of(c), g, x, cm, cpm, t, tp, u, z, zp, r, rp, ok, rounds);
   bool go;
-  const int rc = field_loop_args(c, "linear prove zk", nonce0, gauss_kind, max_rounds, rounds_run, s, x, ok, rounds, B, &go);
+  const int rc = field_loop_args(c, "linear prove zk", nonce0, gauss_kind, max_rounds, rounds_run, s, B, &go);
   if (!go) return rc;
-  return field_loop_host(c, s, x, c->l, ok, rounds, B, [&](const FieldLoop::Slabs& d, const int64_t* dx, uint8_t* dok, uint8_t* drounds) {
-    return linear_prove_zk_slabs(c, d, dx, nonce0, stream, gauss_kind, aux32, max_rounds, dok, drounds, rounds_run, B);
-  });
+  return host_run<kSlabsLinearProveZk>(c, {}, B, [&](auto... d) {   // (the device pointers exist once the arena is staged: inside run)
+    const FieldLoop::Slabs staged = field_slabs(kSlabsLinearProveZk, dims_of(c), d...);
+    return linear_prove_zk_slabs(c, staged, nonce0, stream, gauss_kind, aux32, max_rounds, rounds_run, B);
+  }, g, x, cm, cpm, t, tp, u, z, zp, r, rp, ok, rounds);
 }
 
 int rzk_sum_prove_zk_batch_dev(rzk_ctx* c, uint32_t V, const int64_t* gs, const int64_t* xs, const uint8_t nonce0[16], uint32_t stream,
@@ -618,11 +596,11 @@ int rzk_sum_prove_zk_batch_dev(rzk_ctx* c, uint32_t V, const int64_t* gs, const 
   if (!c) return RZK_E_ARG;
   if (rounds_run) *rounds_run = 0;
   if (V == 0 || V > kSumMaxV) return fail(c, RZK_E_ARG, "sum prove zk: V must lie in 1 .. 2^20");
-  const FieldLoop::Slabs s = sum_slabs(c, V, gs, cs, cpm, ts, tp, u, zs, zp, rs, rp);
+  const FieldLoop::Slabs s = field_slabs(kSlabsSumProveZk, dims_of(c, by_V(V)), gs, xs, cs, cpm, ts, tp, u, zs, zp, rs, rp, ok, rounds);
   bool go;
-  const int rc = field_loop_args(c, "sum prove zk", nonce0, gauss_kind, max_rounds, rounds_run, s, xs, ok, rounds, B, &go);
+  const int rc = field_loop_args(c, "sum prove zk", nonce0, gauss_kind, max_rounds, rounds_run, s, B, &go);
   if (!go) return rc;
-  return sum_prove_zk_slabs(c, V, s, xs, nonce0, stream, gauss_kind, aux32, max_rounds, ok, rounds, rounds_run, B);
+  return sum_prove_zk_slabs(c, V, s, nonce0, stream, gauss_kind, aux32, max_rounds, rounds_run, B);
 }
 int rzk_sum_prove_zk_batch(rzk_ctx* c, uint32_t V, const int64_t* gs, const int64_t* xs, const uint8_t nonce0[16], uint32_t stream,
                            int gauss_kind, const uint8_t* aux32, uint32_t max_rounds, int64_t* cs, int64_t* cpm, int64_t* ts, int64_t* tp,
@@ -631,14 +609,14 @@ int rzk_sum_prove_zk_batch(rzk_ctx* c, uint32_t V, const int64_t* gs, const int6
   if (!c) return RZK_E_ARG;
   if (rounds_run) *rounds_run = 0;
   if (V == 0 || V > kSumMaxV) return fail(c, RZK_E_ARG, "sum prove zk: V must lie in 1 .. 2^20");
-  const FieldLoop::Slabs s = sum_slabs(c, V, gs, cs, cpm, ts, tp, u, zs, zp, rs, rp);
+  const FieldLoop::Slabs s = field_slabs(kSlabsSumProveZk, dims_of(c, by_V(V)), gs, xs, cs, cpm, ts, tp, u, zs, zp, rs, rp, ok, rounds);
   bool go;
-  const int rc = field_loop_args(c, "sum prove zk", nonce0, gauss_kind, max_rounds, rounds_run, s, xs, ok, rounds, B, &go);
+  const int rc = field_loop_args(c, "sum prove zk", nonce0, gauss_kind, max_rounds, rounds_run, s, B, &go);
   if (!go) return rc;
-  return field_loop_host(c, s, xs, (uint64_t)V * c->l, ok, rounds, B,
-                         [&](const FieldLoop::Slabs& d, const int64_t* dxs, uint8_t* dok, uint8_t* drounds) {
-                           return sum_prove_zk_slabs(c, V, d, dxs, nonce0, stream, gauss_kind, aux32, max_rounds, dok, drounds, rounds_run, B);
-                         });
+  return host_run<kSlabsSumProveZk>(c, by_V(V), B, [&](auto... d) {
+    const FieldLoop::Slabs staged = field_slabs(kSlabsSumProveZk, dims_of(c, by_V(V)), d...);
+    return sum_prove_zk_slabs(c, V, staged, nonce0, stream, gauss_kind, aux32, max_rounds, rounds_run, B);
+  }, gs, xs, cs, cpm, ts, tp, u, zs, zp, rs, rp, ok, rounds);
 }
 
 // diagnostic: pending_compact_kernel on the caller's flags, so that its edges are tested without a prover around it

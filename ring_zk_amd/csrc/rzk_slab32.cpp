@@ -5,6 +5,7 @@
 // (slab32_native) launches them on the caller's slabs; every other call converts (convert_call, rzk_ctx.h): it widens its
 // inputs into the context's grow-only arena ws32, runs its body on int64_t there and narrows the outputs — a completeness
 // path, not a performance path.  Verdicts, fault rules and the fused norm predicate are the same in both.
+// narrow, widen and eq32 name their slab lists (rzk_slabs.h) like every other call.
 #include "rzk_ctx.h"
 
 namespace {
@@ -50,26 +51,23 @@ int convert_end(rzk_ctx* c, const Conv* slabs, size_t n, int64_t* const* wide) {
 extern "C" {
 
 int rzk_narrow_batch_dev(rzk_ctx* c, const int64_t* in, int32_t* out, size_t count) {
-  if (c && count == 0) return RZK_OK;   // empty batch: nothing to do (pointers may be NULL)
-  if (!c || !in || !out) return RZK_E_ARG;
-  if (misaligned({in, out})) return align_fail(c);
+  if (const int rc = slab_args<kSlabsNarrow>(c, {}, count, in, out); rc != kGo) return rc;
+  if (slabs_misaligned<kSlabsNarrow>(in, out)) return align_fail(c);
   return narrow_polys(c, in, out, count, true);
 }
 
 int rzk_widen_batch_dev(rzk_ctx* c, const int32_t* in, int64_t* out, size_t count) {
-  if (c && count == 0) return RZK_OK;
-  if (!c || !in || !out) return RZK_E_ARG;
-  if (misaligned({in, out})) return align_fail(c);
+  if (const int rc = slab_args<kSlabsWiden>(c, {}, count, in, out); rc != kGo) return rc;
+  if (slabs_misaligned<kSlabsWiden>(in, out)) return align_fail(c);
   return widen_polys(c, in, out, count);
 }
 
 // v14, slab32 messages: the compare of the short verifier.  No range test: the verdict of the consuming
 // call (rzk_open_recover32_batch) has tested what it read.
 int rzk_eq32_batch_dev(rzk_ctx* c, const int32_t* a, const int32_t* b, uint32_t rows, uint8_t* eq, size_t B) {
-  if (c && B == 0) return RZK_OK;
-  if (!c || !a || !b || !eq) return RZK_E_ARG;
+  if (const int rc = slab_args<kSlabsEq32>(c, {}, B, a, b, eq); rc != kGo) return rc;
   if (rows == 0) return fail(c, RZK_E_ARG, "eq32: rows must be at least 1");
-  if (misaligned({a, b})) return align_fail(c);
+  if (slabs_misaligned<kSlabsEq32>(a, b, eq)) return align_fail(c);
   const uint64_t words = (uint64_t)rows * c->N;   // a multiple of 4 (N >= 4 is a power of two)
   return run_profiled(c, (uint64_t)B * words * 8ull, "eq32 kernel",
                       [&](const LaunchCfg& cfg) { return launch_eq32(cfg, a, b, words, eq, B); });
@@ -77,30 +75,17 @@ int rzk_eq32_batch_dev(rzk_ctx* c, const int32_t* a, const int32_t* b, uint32_t 
 
 // ---- host-pointer forms: staged through HostCall like every other entry point ------------------------------------------
 int rzk_narrow_batch(rzk_ctx* c, const int64_t* in, int32_t* out, size_t count) {
-  if (c && count == 0) return RZK_OK;
-  if (!c || !in || !out) return RZK_E_ARG;
-  HostCall h(c);
-  const auto din = h.pin(in, count);
-  const auto dout = h.pout(out, count);
-  return h.run([&] { return rzk_narrow_batch_dev(c, din, dout, count); });
+  return host_form<kSlabsNarrow>(c, count, rzk_narrow_batch_dev, in, out);
 }
 
 int rzk_widen_batch(rzk_ctx* c, const int32_t* in, int64_t* out, size_t count) {
-  if (c && count == 0) return RZK_OK;
-  if (!c || !in || !out) return RZK_E_ARG;
-  HostCall h(c);
-  const auto din = h.pin(in, count);
-  const auto dout = h.pout(out, count);
-  return h.run([&] { return rzk_widen_batch_dev(c, din, dout, count); });
+  return host_form<kSlabsWiden>(c, count, rzk_widen_batch_dev, in, out);
 }
 
 int rzk_eq32_batch(rzk_ctx* c, const int32_t* a, const int32_t* b, uint32_t rows, uint8_t* eq, size_t B) {
-  if (c && B == 0) return RZK_OK;
-  if (!c || !a || !b || !eq) return RZK_E_ARG;
-  HostCall h(c);
-  const auto da = h.pin(a, B * rows), db = h.pin(b, B * rows);
-  const auto deq = h.out(eq, B);
-  return h.run([&] { return rzk_eq32_batch_dev(c, da, db, rows, deq, B); });
+  return host_call<kSlabsEq32>(c, SizeArgs{1, rows}, B, [&](const int32_t* da, const int32_t* db, uint8_t* deq) {
+    return rzk_eq32_batch_dev(c, da, db, rows, deq, B);
+  }, a, b, eq);
 }
 
 }  // extern "C"
